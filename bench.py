@@ -10,13 +10,22 @@ the inverse of the reference's "Time per rollout step" (scripts/standalonePlanar
     python bench.py --gpus 8                          # starts 8 ranks itself (below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29500 bench.py --gpus 8 --steps 10 --warmup 2      # the driver's form: the same 8 ranks
+    python bench.py --full                            # + everything beside the headline (below)
+
+A plain run sets up, runs --warmup iterations, times ONE block of exactly --steps iterations (--reps K: K blocks, value = median
+block) and prints the line: `value`, `ms_per_step`, `dtype`, the configuration and the screening counters of the timed run.
+--full adds what takes runs or instrumentation of its own: HIP events around the dominant kernel inside the timed blocks and the
+`roofline` built on them, the timed fetch of all rollout tensors, the other path (`value_screened`), the other workloads and sweeps
+(`also`) and the torch-CPU baseline (`cpu_baseline`).  --dump-outputs DIR writes, after the timed steps, what the last timed
+iteration returned to its caller as float32 .npy files (dump_outputs); the inputs are seeded, so two builds given the same
+arguments can be compared file for file.
 
 What `value` is.  The PRIMARY measurement is the all-fp32 step (--path fp32, `dtype: "f32"`), the library's DEFAULT: every network
 evaluation in the reference's own arithmetic -- ascending-k fmaf chains from zero, bias last, bit for bit the oracle's -- (k_pass1 +
 k_tail), priced against the fp32 MFMA peak in `roofline`.  The OPT-IN screened step (omds_set_screening(ctx, 2, 0)) evaluates
 the N x O first-pass rows -- which only feed the sort that picks the k closest obstacles -- in f16 and re-evaluates the candidates in
 fp32; every number it returns is an fp32 number and bit-identical to the all-fp32 step's as long as a measured error bound holds
-(include/omds.h).  That step is timed in the same run and reported as `value_screened` with its own roofline block
+(include/omds.h).  With --full that step is timed in the same run and reported as `value_screened` with its own roofline block
 (`roofline.screened`: k_screen against the dense f16 MFMA peak, algorithmic `frac` and executed `frac_issued`).
 
 Ranks.  One process per GPU.  `--gpus N` without a launcher environment starts the N ranks itself: a child
@@ -171,6 +180,30 @@ def setup(wl):
     return w, W, b, obs, q0, qf, dh, qmin, qmax
 
 
+DUMP_BYTES = 64 * 10**6     # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(path, eng, K, mu_c, sg_c, al_c, mask, qd_w, q_next):
+    """--dump-outputs: what a caller of the timed iteration holds after its last step, as float32 .npy files under `path`: the policy
+    the cost-weighted update returned (policy_mu / _sigma / _alpha, update_mask), the weighted velocity and the next state, and the
+    rollout tensors of that step's propagate (rollout_*, omds_get_rollouts).  When the rollout tensors would take the total past
+    DUMP_BYTES they are written for a fixed, seeded sample of rollouts whose indices are rollout_rows.npy (float64)."""
+    os.makedirs(path, exist_ok=True)
+    out = {"policy_mu": mu_c[:K], "policy_sigma": sg_c[:K], "policy_alpha": al_c[:K], "update_mask": mask, "qdot_weighted": qd_w,
+           "q_next": q_next}
+    N, H, n = eng.N, eng.H, eng.n
+    row_bytes = 4 * (2 * H * n + H * eng.K + 3 * H + n)     # all_traj, normal, kernel_val_all, 3 x [H], qdot of one rollout
+    room = (DUMP_BYTES - 4 * sum(np.asarray(v).size for v in out.values()) - 8 * N) // row_bytes
+    if N <= room:
+        out.update(("rollout_" + k, v) for k, v in eng.get_rollouts().items())
+    else:
+        rows = np.sort(np.random.RandomState(0).choice(N, int(room), replace=False))
+        out.update(("rollout_" + k, v) for k, v in eng.get_rollout_rows(rows).items())
+        out["rollout_rows"] = rows
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), np.asarray(v, dtype=np.float64 if k == "rollout_rows" else np.float32))
+
+
 def pmc_profile(workload, kernel, fp32):
     """(HBM bytes per launch, SQ_INSTS_MFMA per launch, round) of `kernel` from the committed rocprofv3 PMC summaries of this
     workload (separate --pmc passes; FETCH_SIZE doubled per MI355X_MICROARCH.md; tools/profile_refresh.sh).  The all-fp32 step's
@@ -237,9 +270,10 @@ def cpu_baseline(w, W, b, obs, q0, qf, dh, qmin, qmax, K, H_full):
     return out
 
 
-def measure(args, L, workload, steps, warmup, time_fetch=False, prof=True, reps=1, screening=0, kernels=None, rollouts=None):
+def measure(args, L, workload, steps, warmup, time_fetch=False, prof=True, reps=1, screening=0, kernels=None, rollouts=None, dump=None):
     """Times `reps` blocks of exactly `steps` planner iterations of `workload` on this rank's GPU (each block bracketed by a
     barrier + device synchronisation on both sides, elapsed = max over ranks); returns a dict of raw numbers.
+    dump: a directory; rank 0 writes the last timed iteration's outputs there after the timed blocks (dump_outputs).
     screening: 0 = the all-fp32 step (the library's default; set explicitly), 2 = the opt-in screened step where it pays (omds_set_screening(ctx, 2, 0)),
     1 = screening forced on.
     rollouts: this rank's rollout count when it is not the workload's (strong scaling, the shard sweep)."""
@@ -315,6 +349,7 @@ def measure(args, L, workload, steps, warmup, time_fetch=False, prof=True, reps=
     Kmax = eng.Kmax
     k_trace = []          # dynamic workload: K at the end of every timed block
     pick = np.random.RandomState(99)
+    last = None           # (update mask, weighted velocity) of the latest iteration: --dump-outputs
 
     def reset_policy():   # Policy.reset_policy (policy.py:43-49) + the integrator back at q0: a timed block of the dynamic workload
         nonlocal mu_c, sg_c, al_c, q_cur, K
@@ -341,7 +376,7 @@ def measure(args, L, workload, steps, warmup, time_fetch=False, prof=True, reps=
             K += 1
 
     def iteration(it):
-        nonlocal mu_c, sg_c, al_c, q_cur
+        nonlocal mu_c, sg_c, al_c, q_cur, last
         if dyn:
             # shelf translated by a slow sinusoid (the obstacle streamer's mechanism, obstacleStreamer.py:120-142),
             # then distance/normal at the K kernel centres (MPPI.update_kernel_normal_bases, MPPI.py:284-304)
@@ -364,6 +399,7 @@ def measure(args, L, workload, steps, warmup, time_fetch=False, prof=True, reps=
         else:
             mu_c, sg_c, al_c = m2, s2, a2
         q_cur = (q_cur + 0.1 * w["dt"] * qd_w).astype(np.float32)   # drift along the weighted rollout velocity: non-degenerate states
+        last = (mask, qd_w)
         if dyn:   # Policy.check_traj_for_kernels on the device (policy.py:153-175); only candidates cross PCIe; then add_kernel
             cq, cth, total = eng.kernel_candidates(0.03 - w["dst_thr"], 0.3, -0.9, mu_c, sg_c, K, cap=256)
             chosen = choose_candidate(cq, cth) if (cq.shape[0] and rank == 0) else None
@@ -407,6 +443,8 @@ def measure(args, L, workload, steps, warmup, time_fetch=False, prof=True, reps=
             el = float(t.item())
         els.append(el)
         k_trace.append(int(K))
+    if dump and rank == 0:
+        dump_outputs(dump, eng, K, mu_c, sg_c, al_c, last[0], last[1], q_cur)
     p1_ms, p1_launches, p1_rows = eng.prof_read()
     _, _, p1_flops, p1_kernel = eng.prof_read_ex()
     fetch_ms = None
@@ -417,7 +455,7 @@ def measure(args, L, workload, steps, warmup, time_fetch=False, prof=True, reps=
             eng.get_rollouts()
         fetch_ms = (time.perf_counter() - tf) / 5 * 1e3
     scr = eng.screen_stats()
-    skip = eng.pass1_skip_stats()
+    skip = eng.pass1_skip_stats() if prof else None     # read by roofline() only
     eng.close()
     return dict(els=els, scr=scr, skip=skip, k_trace=k_trace, dh=dh, qmin=qmin, qmax=qmax, w=w, W=W, b=b, obs=obs, q0=q0, qf=qf, N=N, H=H, K=K,
                 p1_ms=p1_ms, p1_launches=p1_launches, p1_rows=p1_rows, p1_flops=p1_flops, p1_kernel=p1_kernel, fetch_ms=fetch_ms,
@@ -492,8 +530,14 @@ SCREEN_KEYS = ("active", "eps", "candidates_per_rollout_step", "fallbacks", "aud
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed planner iterations (per block, --reps)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: kernel events + roofline, the timed fetch of the rollout tensors, the "
+                         "other path, the other workloads and sweeps ('also') and the CPU baseline (--no-secondary / --no-cpu-baseline drop parts)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed iteration returned as DIR/<name>.npy (float32, <= 64 MB in all; "
+                         "rank 0's outputs in a multi-rank run)")
     ap.add_argument("--workload", default="franka_shelf_1024x32", choices=sorted(WORKLOADS))
     ap.add_argument("--kernels", type=int, default=10, help="active RBF navigation kernels K")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
@@ -501,26 +545,28 @@ def main():
     ap.add_argument("--path", choices=("fp32", "screened"), default=None,
                     help="the PRIMARY measurement (`value`): fp32 = the all-fp32 step, the reference's arithmetic throughout (default); "
                          "screened = the opt-in step (f16 screening of the first-pass rows + fp32 re-evaluation, omds_set_screening(ctx, 2, 0)).  The other one "
-                         "is reported beside it unless --no-secondary")
+                         "is reported beside it with --full, unless --no-secondary")
     ap.add_argument("--screening", type=int, default=None, choices=(-1, 0, 1, 2),
                     help="older spelling of --path: 0 = fp32, 2 (or -1) = screened where it pays, 1 = screening forced on")
     ap.add_argument("--dense-pass1", action="store_true", help="OMDS_FLAG_DENSE_PASS1: k_pass1 without its exact zero-skip (A/B runs; same bits)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the other path and the workloads / sweeps reported under 'also'")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the other path and the workloads / sweeps reported under 'also'")
     ap.add_argument("--allow-host-collectives", action="store_true",
                     help="when the RCCL communicator cannot be formed, exchange the update's sums through the launcher's gloo group instead of "
                          "exiting non-zero; the line is labelled config.collectives = gloo-host (...)")
     ap.add_argument("--try-rccl", action="store_true", help="with --share-gpu: attempt the RCCL communicator anyway (test of the failure path with OMDS_RCCL_LIB)")
-    ap.add_argument("--reps", type=int, default=10, help="timed blocks of --steps iterations each; value = median block")
+    ap.add_argument("--reps", type=int, default=1, help="timed blocks of --steps iterations each; value = median block")
     ap.add_argument("--prof-stride", type=int, default=8,
-                    help="HIP events around every n-th launch of the dominant kernel inside the timed region (an event record between two "
+                    help="with --full: HIP events around every n-th launch of the dominant kernel inside the timed region (an event record between two "
                          "launches idles the GPU for a few us: every launch costs 2.4 %% of value at 190 us per step, every 8th 0.2 %%)")
     ap.add_argument("--share-gpu", action="store_true",
                     help="test mode for a 1-GPU box: all ranks use GPU 0 and exchange through the host (gloo); never a scaling number")
-    ap.add_argument("--time-fetch", action="store_true", help="(kept for older command lines: the fetch of all rollout tensors is always timed now)")
+    ap.add_argument("--time-fetch", action="store_true", help="(kept for older command lines: --full times the fetch of all rollout tensors)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.reps < 1 or args.warmup < 0:
+        raise SystemExit("--steps and --reps must be >= 1, --warmup >= 0")
     if args.path is None:
         args.path = "fp32" if args.screening in (None, 0) else "screened"
     prim_scr = 0 if args.path == "fp32" else (args.screening if args.screening in (1, 2) else 2)
@@ -558,13 +604,14 @@ def main():
         L.dist, L.torch = dist, torch
 
     shard = n_local if args.scaling == "strong" else None
-    r = measure(args, L, args.workload, args.steps, args.warmup, time_fetch=True, reps=max(1, args.reps), screening=prim_scr, rollouts=shard)
+    r = measure(args, L, args.workload, args.steps, args.warmup, time_fetch=args.full, prof=args.full, reps=args.reps, screening=prim_scr,
+                rollouts=shard, dump=args.dump_outputs)
     w, W, b, obs, q0, qf, H, K = (r[k] for k in ("w", "W", "b", "obs", "q0", "qf", "H", "K"))
     prim_fp32 = args.path == "fp32"
 
     other = None
     also = None
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         # the same iterations on the other path (fp32 primary: the opt-in screened step; screened primary: screening off)
         ro = measure(args, L, args.workload, args.steps, 1, reps=3 if prim_fp32 is False else max(3, args.reps // 2), screening=(2 if prim_fp32 else 0), rollouts=shard)
         other = dict(rate(ro, n_total), roofline=roofline(args, ro, args.workload, not prim_fp32), screening=ro["scr"])
@@ -631,8 +678,9 @@ def main():
                        "device_of_each_process": (L.rccl or {}).get("device_of_each_process", [int(L.local_rank)]),
                        # the device is reached through the C-ABI alone; torch (when imported at all: gloo plumbing, CPU baseline) stays on the CPU
                        "pytorch_on_device": bool("torch" in sys.modules and sys.modules["torch"].cuda.is_initialized())},
-            "roofline": roofline(args, r, args.workload, prim_fp32),
         }
+        if args.full:   # the HIP events of the timed blocks (prof=args.full)
+            out["roofline"] = roofline(args, r, args.workload, prim_fp32)
         if other is not None:
             ro_f = other["roofline"]
             brief = {"kernel": ro_f["kernel"], "pipe": ro_f["pipe"], "frac": ro_f["frac"], "frac_issued": ro_f["frac_issued"], "achieved": ro_f["achieved"],
@@ -647,10 +695,11 @@ def main():
                 out["fp32_only"] = other
                 out["roofline"]["fp32_only"] = brief
         out["screening"] = r["scr"]   # of the primary run (inactive on the fp32 path)
-        out["fetch_all_rollouts_ms"] = r["fetch_ms"]
+        if args.full:
+            out["fetch_all_rollouts_ms"] = r["fetch_ms"]
         if also is not None:
             out["also"] = also
-        if not args.no_cpu_baseline and world == 1 and act == "relu":   # oracle/torch_baseline.py restates the shipped (ReLU) path
+        if args.full and not args.no_cpu_baseline and world == 1 and act == "relu":   # oracle/torch_baseline.py restates the shipped (ReLU) path
             out["cpu_baseline"] = cpu_baseline(w, W, b, obs, q0, qf, r["dh"], r["qmin"], r["qmax"], K, H)
         print(json.dumps(out))
     if L.use_dist:

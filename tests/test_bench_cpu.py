@@ -1,9 +1,11 @@
-"""bench.py's launcher logic on a box without a GPU: it must REFUSE -- never print a line for a rank count it did not run."""
+"""bench.py's launcher logic on a box without a GPU: it must REFUSE -- never print a line for a rank count it did not run.  And the
+host side of --dump-outputs."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from helpers import ROOT
@@ -70,3 +72,51 @@ def test_physical_cores_come_from_cpuinfo_not_from_psutil():
     import bench
     n = bench.physical_cores()
     assert 1 <= n <= (os.cpu_count() or 1)
+
+
+class _RolloutsOnly:
+    """The two rollout getters of optimalmodulationds_amd.engine.Engine that bench.dump_outputs calls, on constant data."""
+    def __init__(self, N, H, n, K):
+        self.N, self.H, self.n, self.K = N, H, n, K
+        self.full_fetches = 0
+
+    def _out(self, R):
+        H, n, K = self.H, self.n, self.K
+        shapes = {"all_traj": (R, H, n), "closest_dist_all": (R, H), "kernel_val_all": (R, H, K), "dot_products": (R, H),
+                  "kernel_activations": (R, H), "qdot": (R, n), "normal": (R, H, n)}
+        return {k: np.full(s, 0.5, np.float32) for k, s in shapes.items()}
+
+    def get_rollouts(self):
+        self.full_fetches += 1
+        return self._out(self.N)
+
+    def get_rollout_rows(self, t):
+        return self._out(len(t))
+
+
+def _dump(path, eng):
+    import bench
+    K, n = 50, eng.n
+    bench.dump_outputs(str(path), eng, K, np.ones((K, n), np.float32), np.ones(K, np.float32), np.ones((K, n), np.float32),
+                       np.ones(K, bool), np.ones(n, np.float32), np.ones(n, np.float32))
+    return {f[:-4]: np.load(os.path.join(path, f)) for f in sorted(os.listdir(path))}
+
+
+def test_dump_outputs_are_float_and_within_64_mb(tmp_path):
+    """--dump-outputs: float32 files (the sample's row indices float64); rollout tensors past the budget (8192 x 32 rollouts, K = 50:
+    ~70 MB) are written for a seeded sample of rollouts -- the same one every run, so two builds compare row for row."""
+    sys.path.insert(0, ROOT)
+    import bench
+    small = _RolloutsOnly(1024, 32, 7, 50)
+    got = _dump(tmp_path / "small", small)
+    assert small.full_fetches == 1 and "rollout_rows" not in got and got["rollout_all_traj"].shape == (1024, 32, 7)
+    assert all(a.dtype == np.float32 for a in got.values()) and got["update_mask"].shape == (50,)
+    big = _RolloutsOnly(8192, 32, 7, 50)
+    a, b = _dump(tmp_path / "a", big), _dump(tmp_path / "b", big)
+    assert big.full_fetches == 0
+    rows = a["rollout_rows"]
+    assert rows.dtype == np.float64 and np.array_equal(rows, b["rollout_rows"]) and 0 < rows.size < 8192
+    assert np.all(np.diff(rows) > 0) and rows[-1] < 8192 and a["rollout_all_traj"].shape == (rows.size, 32, 7)
+    assert all(v.dtype == np.float32 for k, v in a.items() if k != "rollout_rows")
+    total = sum(os.path.getsize(os.path.join(tmp_path / "a", f)) for f in os.listdir(tmp_path / "a"))
+    assert total <= bench.DUMP_BYTES, total

@@ -199,8 +199,9 @@ def test_stale_library_version_is_reported(tmp_path, lib):
 
 def test_example_driver_accepts_the_reference_config_keys():
     """examples/franka_planner_loop.py --config: the reference's YAML keys (ds_mppi/config.yaml, read at frankaPlanner.py:20-21,
-    43-88, 129).  examples/config.yaml carries every key the loop reads; in the build container the reference's own config files
-    are parsed too and must define every one of those keys (so that the loop takes them unchanged)."""
+    43-88, 129).  examples/config.yaml carries every key the loop reads; the reference's own config files (ds_mppi/config.yaml and
+    config_real.yaml, stored unchanged under tests/golden/reference_config/) are parsed too and must define every one of those keys
+    (so that the loop takes them unchanged)."""
     import importlib.util
     spec = importlib.util.spec_from_file_location("franka_planner_loop", os.path.join(ROOT, "examples", "franka_planner_loop.py"))
     mod = importlib.util.module_from_spec(spec)
@@ -212,9 +213,7 @@ def test_example_driver_accepts_the_reference_config_keys():
     assert mod.load_config(None) == {k: dict(v) for k, v in mod.DEFAULTS.items()}
     assert os.path.exists(mod.weights_file(cfg["collision_model"]["fname"]))
     for ref in ("config.yaml", "config_real.yaml"):
-        path = os.path.join("/root/reference/python_scripts/ds_mppi", ref)
-        if not os.path.exists(path):      # the GPU box has no reference tree
-            continue
+        path = os.path.join(ROOT, "tests", "golden", "reference_config", ref)
         import yaml
         raw = yaml.safe_load(open(path))
         for sec, keys in mod.DEFAULTS.items():

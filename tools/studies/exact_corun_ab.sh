@@ -16,6 +16,6 @@ for cfg in 0 1 2; do
   rocprofv3 --kernel-trace --stats -d /tmp/prof_ab -- python3 bench.py --path screened --steps 6 --warmup 2 --reps 2 --no-cpu-baseline --no-secondary > /tmp/prof_ab.log 2>&1
   echo "## round $rep OMDS_EXACT_CORUN=$cfg"
   python3 tools/rocprof_summary.py stats "$(finddb /tmp/prof_ab)" | grep -E "k_tail_sel|k_exact|k_screen" | head -3 | cut -c1-110
-  python3 bench.py --path screened --steps 10 --warmup 3 --reps 6 --no-cpu-baseline --no-secondary 2>/dev/null | python3 -c "import sys,json; d=json.loads([l for l in sys.stdin if l.startswith(chr(123))][-1]); print('value', round(d['value']), 'ms_per_iteration', round(d['ms_per_step'],3), 'per step us', round(1e3*d['ms_per_step']/32,1), 'k_screen ms', round(d['roofline']['avg_launch_ms'],4), 'cand', round(d['screening']['candidates_per_rollout_step'],2), 'fallbacks', d['screening']['fallbacks'])"
+  python3 bench.py --full --path screened --steps 10 --warmup 3 --reps 6 --no-cpu-baseline --no-secondary 2>/dev/null | python3 -c "import sys,json; d=json.loads([l for l in sys.stdin if l.startswith(chr(123))][-1]); print('value', round(d['value']), 'ms_per_iteration', round(d['ms_per_step'],3), 'per step us', round(1e3*d['ms_per_step']/32,1), 'k_screen ms', round(d['roofline']['avg_launch_ms'],4), 'cand', round(d['screening']['candidates_per_rollout_step'],2), 'fallbacks', d['screening']['fallbacks'])"
 done
 done

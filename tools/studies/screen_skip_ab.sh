@@ -16,7 +16,7 @@ for cfg in ${CFGS:-0 1}; do
   rocprofv3 --kernel-trace --stats -d /tmp/prof_ab -- python3 bench.py --workload $wl --steps 6 --warmup 2 --reps 2 --no-cpu-baseline --no-secondary > /tmp/prof_ab.log 2>&1
   echo "## $wl round $rep OMDS_SCREEN_REORDER=$cfg"
   python3 tools/rocprof_summary.py stats "$(finddb /tmp/prof_ab)" | grep -E "k_tail_sel|k_exact|k_screen" | head -3 | cut -c1-110
-  python3 bench.py --workload $wl --steps 10 --warmup 3 --reps 5 --no-cpu-baseline --no-secondary 2>/dev/null | python3 -c "import sys,json; d=json.loads([l for l in sys.stdin if l.startswith(chr(123))][-1]); print('value', round(d['value']), 'ms_per_iteration', round(d['ms_per_step'],3), 'k_screen ms', round(d['roofline']['avg_launch_ms'],4), 'frac', round(d['roofline']['frac'],3), 'cand', round(d['screening']['candidates_per_rollout_step'],2), 'eps', d['screening']['eps'], 'fallbacks', d['screening']['fallbacks'])"
+  python3 bench.py --full --workload $wl --steps 10 --warmup 3 --reps 5 --no-cpu-baseline --no-secondary 2>/dev/null | python3 -c "import sys,json; d=json.loads([l for l in sys.stdin if l.startswith(chr(123))][-1]); print('value', round(d['value']), 'ms_per_iteration', round(d['ms_per_step'],3), 'k_screen ms', round(d['roofline']['avg_launch_ms'],4), 'frac', round(d['roofline']['frac'],3), 'cand', round(d['screening']['candidates_per_rollout_step'],2), 'eps', d['screening']['eps'], 'fallbacks', d['screening']['fallbacks'])"
 done
 done
 done
