@@ -117,7 +117,9 @@ OMDS_API const char* omds_last_error(const omds_ctx* ctx);
  * Widths: hidden layers of up to 256 units (every network the reference ships: 256 and 128) run on the fused LDS-resident MFMA
  * kernels (narrower ones zero-padded).  MLPRegression itself is width-agnostic (network_macros_mod.py:96-135): a network with a
  * hidden layer of 257 .. 4096 units takes the unfused path of csrc/wide_kernels.hip -- the reference's own op sequence on exact-fp32
- * MFMA GEMMs with the activations materialised in HBM; no screening, no skip concatenations there.  Same results contract.     */
+ * MFMA GEMMs with the activations materialised in HBM; no screening, no skip concatenations there.  Same results contract.
+ * The encoding's sin / cos (csrc/trig_device.h) are the oracle's bits for |x| < 125, the range they restate; above it (and for
+ * inf / NaN) both round the double-precision sin / cos to float, which agree but are not the same code (tests/test_gpu_trig.py). */
 OMDS_API int omds_set_mlp(omds_ctx* ctx, int n_linear, const int32_t* dims, const float* const* W,
                           const float* const* b, int act, float out_div);
 /* The same for MLPRegression(..., skips=[...]) (network_macros_mod.py:113-146): behind the activations of

@@ -1,8 +1,9 @@
 /*
  * omds_test.h -- test hooks of the MI355X-native MPPI rollout path.  NOT part of the product ABI: libomds_hip.so does not export
  * them.  They exist in libomds_hip_test.so (`make test-lib`: the same objects except capi, tail_kernel and train, which are compiled
- * with -DOMDS_TEST_HOOKS), which tests/ load explicitly (optimalmodulationds_amd._lib.load_test_hooks()).  Neither library
- * reads experiment environment variables; those exist only in `make experiment` builds (csrc/omds_internal.h).
+ * with -DOMDS_TEST_HOOKS; the sin / cos hooks live beside k_encode in train.hip), which tests/ load explicitly
+ * (optimalmodulationds_amd._lib.load_test_hooks()).  Neither library reads experiment environment variables; those exist only in
+ * `make experiment` builds (csrc/omds_internal.h).
  */
 #ifndef OMDS_TEST_H
 #define OMDS_TEST_H
@@ -34,6 +35,12 @@ OMDS_API int omds_debug_trainer_general_gemm(int on);
 OMDS_API int omds_test_pack_mlp(int n_dof, int n_linear, const int32_t* in_dims, const int32_t* out_dims, const float* const* W,
                                 const float* const* b, int act, float out_div, int n_skips, const int32_t* skip_after,
                                 uint64_t* checksum, int64_t* bytes);
+/* The encoding's sin / cos (csrc/trig_device.h: omds_sinf / omds_cosf, what every feature kernel inlines) on the current device,
+ * for tests/test_gpu_trig.py.  omds_test_trig: s[i] = sin x[i], c[i] = cos x[i] for n host floats (copied to the device and back).
+ * omds_test_trig_sweep: every float whose bit pattern lies in [lo, hi) (hi <= 2^32); digests[0] / digests[1] = the sum mod 2^64
+ * of splitmix64(bits(x) << 32 | bits(f(x))) for f = sin / cos -- order-independent, the sum oracle/chain_arith.c computes.   */
+OMDS_API int omds_test_trig(const float* x, float* s, float* c, int64_t n);
+OMDS_API int omds_test_trig_sweep(uint32_t lo, uint64_t hi, uint64_t* digests);
 
 #ifdef __cplusplus
 }

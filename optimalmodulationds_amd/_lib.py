@@ -149,6 +149,8 @@ TEST_HOOK_SIGNATURES = {
     "omds_debug_trainer_general_gemm": (C.c_int, [C.c_int]),
     "omds_test_pack_mlp": (C.c_int, [C.c_int, C.c_int, I32P, I32P, C.POINTER(F32P), C.POINTER(F32P), C.c_int, C.c_float, C.c_int, I32P,
                                      C.POINTER(C.c_uint64), C.POINTER(C.c_int64)]),
+    "omds_test_trig": (C.c_int, [F32P, F32P, F32P, C.c_int64]),
+    "omds_test_trig_sweep": (C.c_int, [C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64)]),
 }
 TEST_LIB_PATH = os.path.join(_HERE, "csrc", "libomds_hip_test.so")
 
@@ -205,8 +207,9 @@ def load(path=None, extra_signatures=None):
 
 
 def load_test_hooks():
-    """libomds_hip_test.so: the product's objects plus the two hooks of include/omds_test.h (damage the screening inputs, force
-    a tile shape).  For tests only: ``Engine(..., lib=load_test_hooks())``."""
+    """libomds_hip_test.so: the product's objects plus the hooks of include/omds_test.h (damage the screening inputs, force a tile
+    shape, the trainer's general GEMM, the host half of omds_set_mlp_ex, the encoding's sin / cos).  For tests only:
+    ``Engine(..., lib=load_test_hooks())``."""
     return load(TEST_LIB_PATH, TEST_HOOK_SIGNATURES)
 
 

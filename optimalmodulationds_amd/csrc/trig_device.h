@@ -1,20 +1,23 @@
 // sin / cos of the positional encoding [x, sin x, cos x] in the REFERENCE's arithmetic.
 //
 // network_macros_mod.py:139-140 calls torch.sin / torch.cos on a contiguous fp32 CPU tensor; torch 2.10 (the version pinned in the
-// build container) evaluates them with SLEEF 3.x's 1.0-ULP kernels Sleef_sinf16_u10 / Sleef_cosf16_u10 (xsinf_u1 / xcosf_u1 of
-// sleefsimdsp.c, AVX-512 build with FMA), not with a correctly rounded sin: about 15 % of its values differ from glibc's, numpy's
-// and ocml's by one ulp, and an input feature that is one ulp off moves every unit of layer 1.  This is a restatement of the published
-// algorithm for |x| < 125 (TRIGRANGEMAX2f; the Payne-Hanek branch above it is not restated -- joint angles and obstacle coordinates
-// in metres are nowhere near -- and falls back to the device library's sinf / cosf): Cody-Waite reduction by pi in three parts with
-// the remainder kept as a double-float, a degree-3 polynomial in s^2 evaluated in double-float arithmetic, every operation written
-// out so that no compiler contraction can change a bit.  Checked bit for bit against torch.sin / torch.cos on the CPU
-// (tests/test_trig_cpu.py: the same header compiled for the host by g++) and on the device against the host build
-// (tests/test_gpu_trig.py).
+// build container) evaluates them with MKL VML's vmsSin / vmsCos (HA mode), a closed implementation, not with a correctly rounded
+// sin: an input feature that is one ulp off moves every unit of layer 1.  The nearest PUBLISHED algorithm is SLEEF 3.x's 1.0-ULP
+// xsinf_u1 / xcosf_u1 (sleefsimdsp.c, FMA form), restated here for |x| < 125 (TRIGRANGEMAX2f; the Payne-Hanek branch above it is
+// not restated -- joint angles and obstacle coordinates in metres are nowhere near -- and falls back to the double-precision sin / cos rounded to
+// float, so bit parity with the oracle holds for |x| < 125 only): Cody-Waite reduction by pi in three parts with the remainder kept as a
+// double-float, a degree-3 polynomial in s^2 evaluated in double-float arithmetic, every operation written out so that no compiler
+// contraction can change a bit.  It is within 1 ulp of torch's everywhere and identical on ~98 % of inputs; the oracle's copy is
+// oracle/chain_arith.c.  Tests: tests/test_trig_cpu.py (this header compiled for the host by g++: every float with |x| < 125 against
+// the oracle's copy through pinned digests, float64, the edges, torch.sin / torch.cos) and tests/test_gpu_trig.py (the device's
+// bits against the same digests and the host build; the feature kernels through an identity network).
 //
 // The double-float helpers are SLEEF's df.h in its FMA form (the form the AVX-512 build uses).
 #pragma once
 
-#if defined(__HIPCC__) || defined(__CUDACC__)
+#include <math.h>
+
+#if defined(__HIPCC__)
 #define OMDS_TRIG_FN __host__ __device__ __forceinline__
 #else
 #define OMDS_TRIG_FN static inline
@@ -145,6 +148,9 @@ OMDS_TRIG_FN float cos_u10(float d) {
 
 }   // namespace omds_trig
 
-// the encoding's sin / cos: the reference's arithmetic where it is restated, the platform's elsewhere (never reached by this path)
-OMDS_TRIG_FN float omds_sinf(float x) { return omds_trig::in_range(x) ? omds_trig::sin_u10(x) : __builtin_sinf(x); }
-OMDS_TRIG_FN float omds_cosf(float x) { return omds_trig::in_range(x) ? omds_trig::cos_u10(x) : __builtin_cosf(x); }
+// the encoding's sin / cos: the reference's arithmetic where it is restated; elsewhere (|x| >= 125, inf, NaN: never reached by joint
+// angles and coordinates in metres) the double-precision sin / cos rounded to float, on the device (ocml) as on the host (libm) and
+// in oracle/chain_arith.c.  Not __builtin_sinf: on the device that is the hardware's v_sin_f32, an approximation for small
+// arguments that was off by up to 2 (not ulps) above 125 (tests/test_gpu_trig.py).
+OMDS_TRIG_FN float omds_sinf(float x) { return omds_trig::in_range(x) ? omds_trig::sin_u10(x) : (float)::sin((double)x); }
+OMDS_TRIG_FN float omds_cosf(float x) { return omds_trig::in_range(x) ? omds_trig::cos_u10(x) : (float)::cos((double)x); }

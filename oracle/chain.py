@@ -1,7 +1,10 @@
 """Loader of oracle/chain_arith.c (the reference's fp32 arithmetic restated in C).  TEST INFRASTRUCTURE ONLY.
 
-``linear`` / ``matmul`` / ``sin`` / ``cos`` on numpy float32 arrays.  The library is compiled on first use with gcc (present in the
-build container and on the GPU box) into oracle/libomds_chain.so; __graft_entry__.build() compiles it too."""
+``linear`` / ``matmul`` / ``sin`` / ``cos`` on numpy float32 arrays; ``trig_digest`` over a range of float bit patterns.
+``torch_trig()`` switches ``sin`` / ``cos`` to torch.sin / torch.cos (MKL VML, the reference's own) for as long as it is active.
+The library is compiled on first use with gcc (present in the build container and on the GPU box) into oracle/libomds_chain.so;
+__graft_entry__.build() compiles it too."""
+import contextlib
 import ctypes
 import os
 import subprocess
@@ -12,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _SRC = os.path.join(_HERE, "chain_arith.c")
 _SO = os.path.join(_HERE, "libomds_chain.so")
 _lib = None
+_torch_trig = False
 F32 = np.float32
 
 
@@ -33,6 +37,7 @@ def lib():
         _lib.omds_orc_matmul.argtypes = [vp, vp, vp, lg, it, it]
         _lib.omds_orc_sin.argtypes = [vp, vp, lg]
         _lib.omds_orc_cos.argtypes = [vp, vp, lg]
+        _lib.omds_orc_trig_digest.argtypes = [ctypes.c_uint32, ctypes.c_uint64, vp]
     return _lib
 
 
@@ -69,9 +74,35 @@ def _un(fn, x):
     return y
 
 
+def _torch_un(fn, x):
+    import torch
+    return getattr(torch, fn)(torch.from_numpy(_c(x).copy())).numpy()
+
+
 def sin(x):
-    return _un("omds_orc_sin", x)
+    return _torch_un("sin", x) if _torch_trig else _un("omds_orc_sin", x)
 
 
 def cos(x):
-    return _un("omds_orc_cos", x)
+    return _torch_un("cos", x) if _torch_trig else _un("omds_orc_cos", x)
+
+
+@contextlib.contextmanager
+def torch_trig():
+    """sin / cos (and everything of the oracle built on them) evaluated by torch.sin / torch.cos instead of the restated SLEEF
+    kernels while the block runs: the reference's own sine, which the restatement matches on ~98 % of inputs and misses by one
+    ulp on the others (tests/test_trig_cpu.py)."""
+    global _torch_trig
+    old, _torch_trig = _torch_trig, True
+    try:
+        yield
+    finally:
+        _torch_trig = old
+
+
+def trig_digest(lo, hi):
+    """(sin, cos) digests of the restated kernels (never torch's) over every float whose bit pattern lies in [lo, hi): the sum mod 2^64
+    of splitmix64(bits(x) << 32 | bits(f(x))), the same sum the device's omds_test_trig_sweep computes."""
+    out = np.zeros(2, np.uint64)
+    lib().omds_orc_trig_digest(int(lo), int(hi), out.ctypes.data)
+    return int(out[0]), int(out[1])

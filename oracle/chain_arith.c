@@ -9,7 +9,7 @@
  *   - the vjp's products (g * mask) @ W are the same chains over the layer's output units -> omds_orc_matmul
  *   - torch.sin / torch.cos are MKL VML's vmsSin / vmsCos (HA mode), a closed implementation; the nearest PUBLISHED algorithm is
  *     SLEEF's 1.0-ULP xsinf_u1 / xcosf_u1 (98.0 % / 97.0 % of 1e8 inputs bit-identical to torch's, one ulp otherwise; a correctly
- *     rounded sine agrees on 95 %), restated here in its FMA form for |x| < 125                -> omds_orc_sin / omds_orc_cos
+ *     rounded sine agrees on 95 %), restated here in its FMA form for |x| < 125 (above: the double sin / cos rounded) -> omds_orc_sin / omds_orc_cos
  * Built by oracle/chain.py (and __graft_entry__.build()):  gcc -O3 -mavx2 -mfma -ffp-contract=off -fopenmp -shared -fPIC
  * (-ffp-contract=off: only the fmaf calls written below fuse). */
 #include <math.h>
@@ -76,7 +76,7 @@ static float sin_reduced(f2 t) {
     return mul_to_f(t, x);
 }
 static float sin_u10(float d) {
-    if (!(fabsf(d) < 125.0f)) return sinf(d);
+    if (!(fabsf(d) < 125.0f)) return (float)sin((double)d);   /* as csrc/trig_device.h: the double sine rounded to float */
     float u = rintf(d * M_1_PI_F);
     int q = (int)u;
     float v = fmaf(u, -PI_A2, d);
@@ -87,7 +87,7 @@ static float sin_u10(float d) {
     return (d == 0.0f && signbit(d)) ? d : r;
 }
 static float cos_u10(float d) {
-    if (!(fabsf(d) < 125.0f)) return cosf(d);
+    if (!(fabsf(d) < 125.0f)) return (float)cos((double)d);
     float dq = fmaf(rintf(fmaf(d, M_1_PI_F, -0.5f)), 2.0f, 1.0f);
     int q = (int)dq;
     f2 s = add2_ff(d, dq * (-PI_A2 * 0.5f));
@@ -99,3 +99,26 @@ static float cos_u10(float d) {
 }
 void omds_orc_sin(const float* x, float* y, long n) { for (long i = 0; i < n; ++i) y[i] = sin_u10(x[i]); }
 void omds_orc_cos(const float* x, float* y, long n) { for (long i = 0; i < n; ++i) y[i] = cos_u10(x[i]); }
+
+/* Digest of sin / cos over every float whose bit pattern lies in [lo, hi): the sum mod 2^64 of splitmix64(bits(x) << 32 | bits(f(x)))
+ * (order-independent; the device's omds_test_trig_sweep and the host build of trig_device.h in tests/ compute the same sum) */
+static unsigned long long mix64(unsigned long long z) {
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+static unsigned int fbits(float f) { unsigned int u; memcpy(&u, &f, 4); return u; }
+void omds_orc_trig_digest(unsigned int lo, unsigned long long hi, unsigned long long* out) {
+    unsigned long long ds = 0, dc = 0;
+#pragma omp parallel for schedule(static) num_threads(OMDS_ORC_THREADS) reduction(+ : ds, dc)
+    for (unsigned long long u = lo; u < hi; ++u) {
+        const unsigned int b = (unsigned int)u;
+        float x;
+        memcpy(&x, &b, 4);
+        ds += mix64((unsigned long long)b << 32 | fbits(sin_u10(x)));
+        dc += mix64((unsigned long long)b << 32 | fbits(cos_u10(x)));
+    }
+    out[0] = ds;
+    out[1] = dc;
+}

@@ -111,3 +111,76 @@ def log_plain_bar(family, what, against, counts):
             f.write(json.dumps(dict(counts, family=family, what=what, against=against)) + "\n")
     except OSError:
         pass
+
+
+_TRIG_HOST = None
+
+
+def trig_host():
+    """The encoding's sin / cos (optimalmodulationds_amd/csrc/trig_device.h) compiled for the host by g++, the way oracle/chain.py
+    builds the oracle: -ffp-contract=off -mfma, OpenMP with a fixed team of 8 (tests/trig_host.cpp).  Built once per process into a
+    temporary directory.  Returns the ctypes library: omds_host_sin / omds_host_cos (x, y, n), omds_host_trig_digest (lo, hi, out[2])."""
+    global _TRIG_HOST
+    if _TRIG_HOST is None:
+        import atexit
+        import ctypes
+        import shutil
+        import subprocess
+        import tempfile
+        tmp = tempfile.mkdtemp(prefix="omds_trig_host_")
+        atexit.register(shutil.rmtree, tmp, True)
+        so = os.path.join(tmp, "libtrig_host.so")
+        subprocess.run(["g++", "-O2", "-std=c++17", "-mfma", "-ffp-contract=off", "-fopenmp", "-shared", "-fPIC",
+                        os.path.join(ROOT, "tests", "trig_host.cpp"), "-o", so], check=True)
+        lib = ctypes.CDLL(so)
+        vp, lg = ctypes.c_void_p, ctypes.c_long
+        lib.omds_host_sin.argtypes = lib.omds_host_cos.argtypes = [vp, vp, lg]
+        lib.omds_host_trig_digest.argtypes = [ctypes.c_uint32, ctypes.c_uint64, vp]
+        _TRIG_HOST = lib
+    return _TRIG_HOST
+
+
+def host_sin(x):
+    x = np.ascontiguousarray(x, np.float32)
+    y = np.empty_like(x)
+    trig_host().omds_host_sin(x.ctypes.data, y.ctypes.data, x.size)
+    return y
+
+
+def host_cos(x):
+    x = np.ascontiguousarray(x, np.float32)
+    y = np.empty_like(x)
+    trig_host().omds_host_cos(x.ctypes.data, y.ctypes.data, x.size)
+    return y
+
+
+def host_trig_digest(lo, hi):
+    """(sin, cos) digests of the host build over every float whose bit pattern lies in [lo, hi) (oracle.chain.trig_digest's sum)."""
+    out = np.zeros(2, np.uint64)
+    trig_host().omds_host_trig_digest(int(lo), int(hi), out.ctypes.data)
+    return int(out[0]), int(out[1])
+
+
+# Inputs of the encoding's sin / cos where an implementation goes wrong (tests/test_trig_cpu.py, tests/test_gpu_trig.py)
+TRIG_B125 = int(np.float32(125.0).view(np.uint32))          # bit pattern of 125: the restated kernels cover |x| < 125
+
+
+def trig_edges_in_range():
+    """±0, subnormals, the smallest normals, tiny values where sin x = x, the last float below 125, values near 1."""
+    b = np.array([0, 1, 2, 3, 0x12345, 0x007FFFFF, 0x00800000, 0x00800001, 0x33800000, 0x39800000, 0x3F7FFFFF, 0x3F800000,
+                  0x3F800001, TRIG_B125 - 1, TRIG_B125 - 2], np.uint32)
+    x = b.view(np.float32)
+    return np.concatenate([x, -x])
+
+
+def trig_band(kmax=79, width=2000):
+    """±1..±width ulps around float32(k pi / 2), k = 1..kmax, both signs, |x| < 125: where the quadrant of the reduction changes."""
+    c = np.float32(np.arange(1, kmax + 1) * np.pi / 2).view(np.uint32).astype(np.int64)
+    x = (c[:, None] + np.arange(-width, width + 1)[None, :]).astype(np.uint32).view(np.float32).ravel()
+    x = np.concatenate([x, -x])
+    return x[np.abs(x) < 125]
+
+
+def ulp_err(y, ref):
+    """|y - ref| in units of the float32 spacing at |ref| (ref in float64)."""
+    return np.abs(np.asarray(y, np.float64) - ref) / np.spacing(np.abs(ref).astype(np.float32)).astype(np.float64)
