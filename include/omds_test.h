@@ -2,8 +2,7 @@
  * omds_test.h -- test hooks of the MI355X-native MPPI rollout path.  NOT part of the product ABI: libomds_hip.so does not export
  * them.  They exist in libomds_hip_test.so (`make test-lib`: the same objects except capi, tail_kernel and train, which are compiled
  * with -DOMDS_TEST_HOOKS; the sin / cos hooks live beside k_encode in train.hip), which tests/ load explicitly
- * (optimalmodulationds_amd._lib.load_test_hooks()).  Neither library reads experiment environment variables; those exist only in
- * `make experiment` builds (csrc/omds_internal.h).
+ * (optimalmodulationds_amd._lib.load_test_hooks()).  Neither library reads experiment environment variables.
  */
 #ifndef OMDS_TEST_H
 #define OMDS_TEST_H

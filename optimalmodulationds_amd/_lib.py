@@ -11,7 +11,7 @@ import os
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# OMDS_LIB: another build of the same library (diagnostic / experiment builds under csrc/), never a different backend
+# OMDS_LIB: another build of the same library (the test library, diagnostic builds, an A/B build under csrc/), never a different backend
 LIB_PATH = os.environ.get("OMDS_LIB") or os.path.join(_HERE, "csrc", "libomds_hip.so")
 
 OMDS_MAX_DOF = 7

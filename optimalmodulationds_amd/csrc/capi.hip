@@ -169,12 +169,6 @@ int omds_create(const omds_config* cfg, omds_ctx** out) {
     ctx->cfg = *cfg;
     ctx->dev = cfg->device;
     omds_default_params(&ctx->prm);
-    {   // experiment builds: the audit rate / sweep period of new contexts (the release library has omds_set_screening_audit / _sweep)
-        const int v = OMDS_EXP_ENV("OMDS_SCREEN_AUDIT", -1);
-        if (v >= 0 && v <= (1 << 20) && (v & (v - 1)) == 0) ctx->audit_one_in = v;
-        const int sw = OMDS_EXP_ENV("OMDS_SCREEN_SWEEP", -1);
-        if (sw >= 0) ctx->sweep_every = sw;
-    }
     auto fail = [&](const std::string& m, int code) {
         g_create_err = m;
         free_all(ctx);
@@ -1175,10 +1169,9 @@ static bool screen_wanted(omds_ctx* ctx) {
 // calibration batch is deliberately broader than the rollouts, and fewer units are silent on it (3 / 41 / 92 / 120 of the shipped
 // network's 256 per layer against 27 / 42 / 93 / 120).
 static int screen_reorder(omds_ctx* ctx, int B, bool from_rollouts) {
-    static const int enabled = OMDS_EXP_ENV("OMDS_SCREEN_REORDER", 1);   // experiment builds: 0 keeps the natural order, 2 = the calibration's order only (A/B runs)
     const MlpDev& m = ctx->mlp;
     if (from_rollouts) ctx->scr_reorder_pending = false;
-    if (!enabled || (enabled == 2 && from_rollouts) || m.act != OMDS_ACT_RELU || m.skip_mask || ctx->scr_W.empty() || !ctx->d_exMask) return OMDS_OK;
+    if (m.act != OMDS_ACT_RELU || m.skip_mask || ctx->scr_W.empty() || !ctx->d_exMask) return OMDS_OK;
     if (from_rollouts)   // layer-1 halves of the last states the propagate reached (d_Fq is rebuilt at the start of every propagate)
         omds_launch_rollout_features(ctx->stream, m, ctx->d_trajT + (size_t)(ctx->cfg.horizon - 1) * ctx->cfg.n_dof * ctx->cfg.n_traj, ctx->cfg.n_traj, B, ctx->d_Fq);
     const int nhid = m.nhh + 1, Wd = OMDS_WIDTH, O = ctx->n_obs;
@@ -1283,7 +1276,6 @@ static int calibrate_screen(omds_ctx* ctx, const float* q_center) {
     ctx->screen_audit_err_seen = 0.f;
     ctx->screen_sweep_err_seen = 0.f;
     const bool finite = worst < 3.0e38f;
-    if (!finite && OMDS_EXP_ENV("OMDS_SCREEN_NOGUARD", 0)) { ctx->screen_eps = 1e-3f; return OMDS_OK; }   // experiment builds: timing of deliberately broken screening kernels
     if (!finite) { ctx->screen_suspended = true; ctx->screen_eps = 0.f; return OMDS_OK; }   // fp16 range exceeded on this scene: the fp32 step until the next calibration
     // The largest error over the ~10^7 pairs of a propagate was seen at up to 2x the calibration batch's maximum (3.8e-3 vs
     // 1.8e-3 .. 2.3e-3 on the shelf scene, depending on the batch drawn): 6x leaves the run-time guard (fallback above
@@ -1301,9 +1293,6 @@ static bool small_step_wanted(omds_ctx* ctx) {
     if (ctx->wide.on || (ctx->cfg.flags & (OMDS_FLAG_UNFUSED_STEP | OMDS_FLAG_TWO_KERNEL_STEP))) return false;
     const int R = omds_step_small_rollouts(ctx->mlp, ctx->cfg.n_dof, ctx->n_obs, ctx->cfg.n_closest);
     if (R <= 0) return false;
-    static const int env = OMDS_EXP_ENV("OMDS_SMALL_STEP", -1);   // experiment builds: 0 / 1 overrides the rule below
-    if (env == 0) return false;
-    if (env > 0) return true;
     return (ctx->cfg.n_traj + R - 1) / R <= 768;
 }
 
@@ -1403,14 +1392,12 @@ static int enqueue_rollouts(omds_ctx* ctx, StepArgs& a, bool tail, bool screen) 
         // the ReLU step's shape -- no matrix, no k_select, no second forward in the tail.  The buffer is allocated at the first
         // screened tanh step; if that fails (an enormous batch) the step keeps the matrix route (k_exact mode 3 + k_tail)
         if (screen && !relu && !ctx->d_exDeriv) {
-            static const int handover = OMDS_EXP_ENV("OMDS_TANH_HANDOVER", 1);   // experiment builds: 0 keeps the matrix route (A/B runs)
             const size_t bytes = (size_t)(ctx->mlp.nhh + 1) * (size_t)ctx->ex_cap * OMDS_WIDTH * 4;
-            if (handover && hipMalloc(&ctx->d_exDeriv, bytes) != hipSuccess) { ctx->d_exDeriv = nullptr; (void)hipGetLastError(); }
+            if (hipMalloc(&ctx->d_exDeriv, bytes) != hipSuccess) { ctx->d_exDeriv = nullptr; (void)hipGetLastError(); }
         }
         const bool list_tail = relu || ctx->d_exDeriv != nullptr;   // k_tail_sel works from k_exact's per-entry outputs
         ex.deriv = relu ? nullptr : ctx->d_exDeriv;
-        static const int fuse_env = OMDS_EXP_ENV("OMDS_SCREEN_FUSE_SELECT", 1);   // experiment builds: 0 keeps k_select as its own launch (A/B runs)
-        const bool fuse_select = screen && list_tail && fuse_env != 0 && omds_screen_can_select(ctx->n_obs);
+        const bool fuse_select = screen && list_tail && omds_screen_can_select(ctx->n_obs);
         if (screen) {
             CK(hipMemsetAsync(ctx->d_sctotal, 0, (size_t)(H + 2) * 4, ctx->stream));
             CK(hipMemsetAsync(ctx->d_scerr, 0, 16, ctx->stream));
@@ -1454,8 +1441,7 @@ static int enqueue_rollouts(omds_ctx* ctx, StepArgs& a, bool tail, bool screen) 
         // a throughput-bound launch cannot hide (k_pass1 +18 % at 1024 x 294, the step 29.5 -> 33.3 ms: EXPERIMENTS.md B.5).
         bool emit = false;
         ExactOut ex_all{};
-        static const int emit_env = OMDS_EXP_ENV("OMDS_PASS1_EMIT", 1);   // experiment builds: 0 keeps k_tail (A/B runs)
-        if (!screen && relu && emit_env && !(ctx->cfg.flags & OMDS_FLAG_TAIL_FORWARD) && ctx->mlp.skip_mask == 0 && ctx->mlp.nhh >= 1 &&
+        if (!screen && relu && !(ctx->cfg.flags & OMDS_FLAG_TAIL_FORWARD) && ctx->mlp.skip_mask == 0 && ctx->mlp.nhh >= 1 &&
             omds_tail_sel_supported(n, a.k) && (long long)N * ctx->n_obs <= 24576) {
             const long long pairs = (long long)N * ctx->cfg.max_obs;
             const int nhid = ctx->mlp.nhh + 1;
@@ -1478,13 +1464,6 @@ static int enqueue_rollouts(omds_ctx* ctx, StepArgs& a, bool tail, bool screen) 
             }
         }
         omds_launch_rollout_features(ctx->stream, ctx->mlp, ctx->d_trajT, N, N, fq0, screen ? ctx->d_FqH : nullptr, N);
-#ifdef OMDS_EXPERIMENT
-        static const int corun = OMDS_EXP_ENV("OMDS_EXACT_CORUN", 0);
-        static hipStream_t s2 = nullptr;
-        static hipEvent_t ev = nullptr, ev_done = nullptr;
-        static ExactOut ex2{};
-        static unsigned* err2 = nullptr;
-#endif
         for (int i = 1; i <= H; ++i) {
             float* fq_i = fq0 + (size_t)(i - 1) * fq_slab;
             float* fq_next = fq0 + (size_t)std::min(i, H - 1) * fq_slab;
@@ -1493,31 +1472,6 @@ static int enqueue_rollouts(omds_ctx* ctx, StepArgs& a, bool tail, bool screen) 
                 if ((rc = prof_begin(ctx))) return rc;
                 if (screen) {
                     sink = static_cast<const SelectSink*>(ctx->h_sinks)[i - 1];
-#ifdef OMDS_EXPERIMENT
-                    // Upper-bound experiment for "k_exact under k_screen" (EXPERIMENTS.md, round 5): a REDUNDANT k_exact over the previous
-                    // step's candidate list (scratch outputs: the step's own results are untouched) on a second stream, released when
-                    // the previous step is done, so that it runs beside this step's k_screen.  What it adds to the iteration is what
-                    // k_screen pays for a co-resident k_exact -- the most a flag-driven overlap could get back is k_exact's own 36 us
-                    // minus that.
-                    if (corun && i >= 2) {
-                        if (!s2) {
-                            CK(hipStreamCreateWithFlags(&s2, hipStreamNonBlocking));
-                            CK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-                            CK(hipEventCreateWithFlags(&ev_done, hipEventDisableTiming));
-                            ex2.cap = ctx->ex_cap;
-                            CK(hipMalloc(&ex2.D, (size_t)ex2.cap * 4)); CK(hipMalloc(&ex2.dr, (size_t)ex2.cap * 4)); CK(hipMalloc(&ex2.amin, (size_t)ex2.cap * 4));
-                            CK(hipMalloc(&ex2.mask, (size_t)ex2.cap * (OMDS_MAX_HIDDEN + 1) * 8 * 4));
-                            CK(hipMalloc(&err2, 16));
-                        }
-                        CK(hipEventRecord(ev, ctx->stream));
-                        CK(hipStreamWaitEvent(s2, ev, 0));
-                        omds_launch_exact(s2, ctx->mlp, fq0 + (size_t)(i - 2) * fq_slab, ctx->d_Fp, ctx->d_radius, ctx->n_obs, N, ctx->prm.ignored_links,
-                                          ctx->d_Dmin, ctx->d_rowlist, ctx->d_sctotal + (i - 2), err2, ex2);
-                        CK(hipEventRecord(ev_done, s2));
-                        if (corun == 2 || i == H)   // 2 = control: the same redundant launch IN the main stream's order (the serial cost of one more k_exact)
-                            CK(hipStreamWaitEvent(ctx->stream, ev_done, 0));
-                    }
-#endif
                     omds_launch_screen(ctx->stream, ctx->screen, ctx->mlp, ctx->d_FqH, ctx->cfg.n_traj, ctx->d_FpH, ctx->cfg.max_obs, ctx->d_radius, ctx->n_obs, N,
                                        ctx->prm.ignored_links, ctx->d_Dmin, fuse_select ? d_sinks + (i - 1) : nullptr);
                     if ((rc = prof_end(ctx, (int64_t)N * ctx->n_obs, -1.0, "k_screen"))) return rc;
@@ -1545,13 +1499,13 @@ static int enqueue_rollouts(omds_ctx* ctx, StepArgs& a, bool tail, bool screen) 
                                      ctx->d_rowlist, ctx->d_range, ex, ctx->d_FqH, N, ctx->screen_eps, ctx->d_scerr + 1);
             else if (screen)
                 omds_launch_tail(ctx->stream, ctx->mlp, ctx->d_Fp, ctx->d_radius, ctx->d_obs, ctx->d_Dmin, fq_i,
-                                 ctx->d_dscr, ctx->n_obs, a, 0, N, ctx->d_FqH, N, fq_next, ctx->d_range, ctx->screen_eps, ctx->d_scerr + 1);
+                                 ctx->d_dscr, ctx->n_obs, a, ctx->d_FqH, N, fq_next, ctx->d_range, ctx->screen_eps, ctx->d_scerr + 1);
             else if (emit)   // top-k over the rollout's row of Dmin, masks of the k selected pairs, backward, blend, modulation, Euler step
                 omds_launch_tail_sel(ctx->stream, ctx->mlp, ctx->d_Fp, ctx->d_radius, ctx->d_obs, ctx->d_Fq, ctx->n_obs, a,
                                      nullptr, nullptr, ex_all, nullptr, 0, 0.f, nullptr);   // (no window, no slack to count: viol = NULL)
             else
                 omds_launch_tail(ctx->stream, ctx->mlp, ctx->d_Fp, ctx->d_radius, ctx->d_obs, ctx->d_Dmin, ctx->d_Fq,
-                                 ctx->d_dscr, ctx->n_obs, a, 0, N);
+                                 ctx->d_dscr, ctx->n_obs, a);
         }
         if (screen) {
             // The audit sample of this propagate in one throughput-shaped launch: k_audit on the recorded pairs against the kept
@@ -1612,9 +1566,8 @@ int omds_propagate(omds_ctx* ctx, const float* q_cur, int per_rollout) {
     a.seds = ctx->seds_G > 0 ? ctx->d_seds : nullptr;
     a.seds_G = ctx->seds_G; a.seds_lin_thr = ctx->seds_lin_thr; a.seds_thr = ctx->seds_thr;
     a.prm = ctx->prm;
-    static const int fused = OMDS_EXP_ENV("OMDS_FUSED_TAIL", 1);   // experiment builds: 0 selects the five-kernel step (the release library: OMDS_FLAG_UNFUSED_STEP)
     // a SEDS nominal DS takes the step of stand-alone kernels: only k_modulate carries that branch (step_device.h)
-    const bool tail = fused && !(ctx->cfg.flags & OMDS_FLAG_UNFUSED_STEP) && omds_tail_supported(n, a.k) && ctx->seds_G == 0 && !ctx->wide.on;
+    const bool tail = !(ctx->cfg.flags & OMDS_FLAG_UNFUSED_STEP) && omds_tail_supported(n, a.k) && ctx->seds_G == 0 && !ctx->wide.on;
     bool screen = tail && screen_wanted(ctx);
     if (screen && !ctx->screen_cal && (rc = calibrate_screen(ctx, q_cur))) return rc;
     screen = screen && ctx->screen_ok && !ctx->screen_suspended && ctx->screen_eps > 0.f;
@@ -1652,12 +1605,11 @@ static int screened_verdict(omds_ctx* ctx, StepArgs& a, bool tail) {
     for (int i = 0; i < H; ++i) { ctx->screen_rows += tot[i]; overflow = overflow || tot[i] > ctx->ex_cap; }
     ctx->screen_audit_rows += std::min<double>(tot[H + 1], ctx->audit_cap);   // entries k_audit evaluated
     ctx->screen_steps += (double)N * H;
-    static const int noguard = OMDS_EXP_ENV("OMDS_SCREEN_NOGUARD", 0);   // experiment builds only: the release library cannot switch the guard off
     const float worst = (err != err || aerr != aerr || serr != serr) ? __builtin_inff() : std::max({err, aerr, serr});
-    if ((!overflow && worst <= 0.5f * ctx->screen_eps && slack_viol == 0) || noguard) {
+    if (!overflow && worst <= 0.5f * ctx->screen_eps && slack_viol == 0) {
         // accepted.  Keep the bound at >= 4x the largest error seen, so that states drifting into regions where the fp16
         // network is less accurate widen it gradually instead of tripping the fallback
-        if (!noguard && 4.f * worst > ctx->screen_eps) ctx->screen_eps = 4.f * worst;
+        if (4.f * worst > ctx->screen_eps) ctx->screen_eps = 4.f * worst;
         ctx->screen_consec = 0;
         if (ctx->scr_reorder_pending) {   // the unit order once more, on the states the rollouts reached.  eps was measured on the
             // calibration's order: the next propagate carries a sweep (all N x O pairs of a step of the NEW pack in fp32).  The results

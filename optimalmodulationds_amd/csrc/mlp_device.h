@@ -9,7 +9,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #define LDH OMDS_LDH
 
-// Diagnostic build (-DOMDS_TAIL_TL, tools/tail_timeline.sh): thread 0 of every k_tail_sel workgroup stamps the shader clock
+// Diagnostic build (make timeline VFLAGS=-DOMDS_TAIL_TL, tools/tail_timeline.py): thread 0 of every k_tail_sel workgroup stamps the shader clock
 // at the phase boundaries; a one-thread kernel prints the table after the launch chosen by OMDS_TAIL_TL_STEP.
 #ifdef OMDS_TAIL_TL
 static __device__ unsigned long long g_tail_tl[1024][20];
@@ -1254,10 +1254,10 @@ __device__ __forceinline__ void p2_gemm(const float* Hs, const MlpDev& m, int l,
 template <int ACT, int ROWS>
 __device__ __forceinline__ void pass2_backward(const MlpDev& m, const P2Smem& sm, const float* __restrict__ xyzr, int R0,
                                                int total_rows, const float* __restrict__ qT, int ldq, float* gradx, int dbase,
-                                               float* __restrict__ dscr, size_t dlayer, int S0, int dbg = 0);
+                                               float* __restrict__ dscr, size_t dlayer, int S0);
 template <int ROWS>
 __device__ __forceinline__ void p2_backward_first(const MlpDev& m, const P2Smem& sm, const float* __restrict__ xyzr, int R0,
-                                                  int total_rows, const float* __restrict__ qT, int ldq, float* gradx, int dbase, int dbg = 0);
+                                                  int total_rows, const float* __restrict__ qT, int ldq, float* gradx, int dbase);
 
 // The last layer of pass 2 on the tile in LDS (v_mfma_f32_16x16x4, waves 0 .. ROWS / 16 - 1), the arg-min over ALL raw outputs
 // (robot_sdf.py:155) and the distance of that link: sm.rowMin[r], drow[dbase + r]; optionally the raw outputs, the arg-min per global
@@ -1329,13 +1329,13 @@ __device__ __forceinline__ void pass2_body(const MlpDev& m, const P2Smem& sm, co
                                            const float* __restrict__ xyzr, int R0, int total_rows,
                                            const float* __restrict__ qT, int ldq, float* gradx, float* drow, int dbase,
                                            float* __restrict__ yraw, int32_t* __restrict__ minidx,
-                                           float* __restrict__ dscr, size_t dlayer, int S0, int dbg = 0,
+                                           float* __restrict__ dscr, size_t dlayer, int S0,
                                            float* d1row = nullptr, uint32_t ignored = 0, int seed_col = -1) {
     // seed_col >= 0: the backward starts from that output column instead of the arg-min one (one Jacobian column,
     // robot_sdf.py:92-100); minidx / drow then describe that column
     // d1row (optional, [ROWS]): the pass-1 value of each row, min over the un-ignored links of y / out_div - radius
     // (MPPI.py:236-242), computed from the same last-layer outputs -- bit-identical to pass1_tile's Dmin for 32-row tiles
-    // dbg: timing experiments only (return after a stage).  S0 = first row of this workgroup's private slot in the tanh scratch
+    // S0 = first row of this workgroup's private slot in the tanh scratch
     using G = P2Geo<ROWS>;
     constexpr int NV = G::NV;
     float* Hs = sm.Hs;
@@ -1397,16 +1397,13 @@ __device__ __forceinline__ void pass2_body(const MlpDev& m, const P2Smem& sm, co
         }
         maskL[(l + 1) * P2_NT + tid] = (uint16_t)bits;
         __syncthreads();
-        if (dbg == 10 && l < 0) return;
         if ((m.skip_mask >> (l + 1)) & 1u) inject(l + 1);
     }
 
-    if (dbg == 11) return;
     // ---- last layer, arg-min over ALL raw outputs (robot_sdf.py:155), distance of that link -------
     p2_last_layer<ROWS>(m, Hs, rowMin, rowO, radius, R0, total_rows, drow, dbase, yraw, minidx, d1row, ignored, seed_col);
     __syncthreads();
-    if (dbg == 12) return;
-    pass2_backward<ACT, ROWS>(m, sm, xyzr, R0, total_rows, qT, ldq, gradx, dbase, dscr, dlayer, S0, dbg);
+    pass2_backward<ACT, ROWS>(m, sm, xyzr, R0, total_rows, qT, ldq, gradx, dbase, dscr, dlayer, S0);
 }
 
 // 1 - h^2 of (row, col) at one hidden level: from the workgroup's own scratch rows (pass 2 behind its own forward) or, with
@@ -1424,7 +1421,7 @@ __device__ __forceinline__ float p2_tanh_deriv(const P2Smem& sm, const float* __
 template <int ACT, int ROWS>
 __device__ __forceinline__ void pass2_backward(const MlpDev& m, const P2Smem& sm, const float* __restrict__ xyzr, int R0,
                                                int total_rows, const float* __restrict__ qT, int ldq, float* gradx, int dbase,
-                                               float* __restrict__ dscr, size_t dlayer, int S0, int dbg) {
+                                               float* __restrict__ dscr, size_t dlayer, int S0) {
     using G = P2Geo<ROWS>;
     constexpr int NV = G::NV;
     float* Hs = sm.Hs;
@@ -1457,7 +1454,6 @@ __device__ __forceinline__ void pass2_backward(const MlpDev& m, const P2Smem& sm
     }
     __syncthreads();
     OMDS_TL_STAMP(4);
-    if (dbg == 13) return;
 
     // ---- backward through the hidden -> hidden layers ------------------------------------------
     for (int l = m.nhh - 1; l >= 0; --l) {
@@ -1481,8 +1477,7 @@ __device__ __forceinline__ void pass2_backward(const MlpDev& m, const P2Smem& sm
     }
     OMDS_TL_STAMP(8);
 
-    if (dbg == 14) return;
-    p2_backward_first<ROWS>(m, sm, xyzr, R0, total_rows, qT, ldq, gradx, dbase, dbg);
+    p2_backward_first<ROWS>(m, sm, xyzr, R0, total_rows, qT, ldq, gradx, dbase);
 }
 
 // d y / d x of one input from the gradients at its three encoded features, as torch's autograd accumulates them for
@@ -1527,14 +1522,13 @@ __device__ __forceinline__ void first_layer_backward(const MlpDev& m, const floa
 // The tail of the pass-2 backward: from the gradient at the first layer's pre-activations (sm.Hs) to the input gradients.
 template <int ROWS>
 __device__ __forceinline__ void p2_backward_first(const MlpDev& m, const P2Smem& sm, const float* __restrict__ xyzr, int R0,
-                                                  int total_rows, const float* __restrict__ qT, int ldq, float* gradx, int dbase, int dbg) {
+                                                  int total_rows, const float* __restrict__ qT, int ldq, float* gradx, int dbase) {
     float* gf = sm.gf;
     int* rowT = sm.rowT;
     int* rowO = sm.rowO;
     const int tid = threadIdx.x;
     first_layer_backward<ROWS>(m, sm.Hs, gf, m.skip_mask ? gf : nullptr);
     __syncthreads();
-    if (dbg == 15) return;
     // ---- positional-encoding chain rule -------------------------------------------------------------------------------
     const int d = m.d, n = m.n_dof;
     if (tid < ROWS * d) {
@@ -1644,7 +1638,7 @@ __device__ __forceinline__ void pass2_g4_prefetch(const MlpDev& m, const float* 
 template <int NG>
 __device__ __forceinline__ void pass2_body_g4(const MlpDev& m, P2Smem& sm, P2G4Pre& pre, const float* __restrict__ Fp,
                                               const float* __restrict__ radius, const float* __restrict__ xyzr, int R0, int total_rows,
-                                              const float* __restrict__ qT, int ldq, float* gradx, float* drow, int dbase, int dbg = 0) {
+                                              const float* __restrict__ qT, int ldq, float* gradx, float* drow, int dbase) {
     using G = P2Geo<32>;
     float* Hs = sm.Hs;
     int* rowT = sm.rowT;
@@ -1673,7 +1667,6 @@ __device__ __forceinline__ void pass2_body_g4(const MlpDev& m, P2Smem& sm, P2G4P
     }
     __syncthreads();
     OMDS_TL_STAMP(3);
-    if (dbg == 16) return;
     // ---- layer 1 on the 32-row tile ---------------------------------------------------------------------------------------
     {
         float acc[G::NV];
@@ -1684,7 +1677,6 @@ __device__ __forceinline__ void pass2_body_g4(const MlpDev& m, P2Smem& sm, P2G4P
     }
     __syncthreads();
     OMDS_TL_STAMP(17);
-    if (dbg == 10) return;
     if (mine) {
         uint32_t bits = 0;
 #pragma unroll
@@ -1713,12 +1705,9 @@ __device__ __forceinline__ void pass2_body_g4(const MlpDev& m, P2Smem& sm, P2G4P
         __syncthreads();
     }
     OMDS_TL_STAMP(18);
-    if (dbg == 11) return;
     // ---- last layer, arg-min over ALL raw outputs (robot_sdf.py:155), distance of that link: pass2_body's ---------------------
     p2_last_layer<32>(m, Hs, rowMin, rowO, radius, R0, total_rows, drow, dbase, nullptr, nullptr, nullptr, 0u, -1);
     __syncthreads();
-    if (dbg == 12) return;
     pass2_backward_hidden_g4<NG>(m, sm);
-    if (dbg == 14) return;
-    p2_backward_first<32>(m, sm, xyzr, R0, total_rows, qT, ldq, gradx, dbase, dbg);
+    p2_backward_first<32>(m, sm, xyzr, R0, total_rows, qT, ldq, gradx, dbase);
 }

@@ -190,7 +190,7 @@ __global__ __launch_bounds__(P2_NT) void k_pass2(MlpDev m, const float* __restri
     }
     __syncthreads();
     pass2_body<ACT, ROWS>(m, sm, Fq, Fp, radius, xyzr, R0, total_rows, qT, ldq, gradx, drow, R0, yraw, minidx, dscr,
-                                 (size_t)gridDim.x * ROWS * OMDS_WIDTH, R0, 0, nullptr, 0, seed_col);
+                                 (size_t)gridDim.x * ROWS * OMDS_WIDTH, R0, nullptr, 0, seed_col);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -248,22 +248,32 @@ static void launch_pass1_t(hipStream_t s, const MlpDev& m, const float* Fq, cons
     else launch_pass1_a<MT, MR, NR, OMDS_ACT_TANH>(s, m, Fq, Fp, radius, O, total, ignored, Dmin);
 }
 
-// Tile choice: 64-row tiles (8 waves, each 64 rows x 32 columns, two workgroups per CU) once there are
-// enough tiles to fill 256 CUs; 32-row tiles for small batches (planar configs, dist_grad calls).
+// Size class of a pass-1 launch over B*O rows: one rule for the dense, the compacted and the emitting launch.  Measured on
+// MI355X (profiles/): 64-row tiles (8 waves, each 64 rows x 32 columns, 2 workgroups per CU) beat 128-row tiles at N*O = 301k
+// rows (129 vs 123 TFLOP/s: shorter tail) and tie at 1.2M rows (134 TFLOP/s); once there are enough tiles to fill 256 CUs,
+// ending the launch on one round of 32-row tiles shortens the drain (135 vs 133 TFLOP/s).  Tiny batches (<= 128 32-row tiles:
+// integrator tick, planar toy shapes): 16-row tiles on the 16x16x4 MFMA halve the chain of dependent GEMMs that is the whole
+// latency of such a launch.
+enum class Pass1Size { Tiny, Small, Medium, Large };
+static Pass1Size pass1_size(long long total) {
+    if (total >= 64LL * 1024) return Pass1Size::Large;   // 64-row tiles, the last round in 32-row tiles
+    if (total >= 64LL * 512) return Pass1Size::Medium;   // 64-row tiles
+    if (total > 32LL * 128) return Pass1Size::Small;     // 32-row tiles
+    return Pass1Size::Tiny;                              // 16-row tiles
+}
+// 64-row tiles of a Large launch: the rows of its last 256 64-row tiles (one round of 512 workgroups) go to 32-row tiles
+static long long pass1_big_tiles(long long total) { return std::max(total / 64 - 256, 0LL); }
+
 template <int ACT>
 static void launch_pass1_mixed(hipStream_t s, const MlpDev& m, const float* Fq, const float* Fp, const float* radius,
-                               int O, long long total, uint32_t ignored, float* Dmin, int small_rounds) {
+                               int O, long long total, uint32_t ignored, float* Dmin) {
     const size_t lds = (size_t)64 * LDH * 4 + 64 * 4;
     static std::atomic<uint64_t> configured{0};
     if (omds_first_use_on_device(configured)) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pass1_mixed<ACT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }
-    // keep `small_rounds` x 512 x 64 rows (in units of resident 64-row workgroups) for the 32-row tail tiles
-    long long tiles64 = total / 64;
-    long long keep = (long long)small_rounds * 512 / 2;   // 64-row tiles' worth of rows given to small tiles
-    long long n_big = tiles64 > keep ? tiles64 - keep : 0;
-    const long long rest = total - n_big * 64;
-    const long long n_small = (rest + 31) / 32;
+    const long long n_big = pass1_big_tiles(total);
+    const long long n_small = (total - n_big * 64 + 31) / 32;
     hipLaunchKernelGGL((k_pass1_mixed<ACT>), dim3((unsigned)(n_big + n_small)), dim3(512), lds, s, Fq, Fp, radius, Dmin,
                        total, O, ignored, (int)n_big, OmdsDivisor::make((unsigned)O), m);
 }
@@ -272,37 +282,26 @@ void omds_launch_pass1(hipStream_t s, const MlpDev& m, const float* Fq, const fl
                        int O, int B, uint32_t ignored, float* Dmin) {
     const long long total = (long long)B * O;
     if (total <= 0) return;
-    static const int forced = OMDS_EXP_ENV("OMDS_PASS1_VARIANT", 0);   // experiment builds: a tile variant instead of the rule below
-    int v = forced;
-    // measured on MI355X (profiles/): 64-row tiles (2 workgroups per CU) beat 128-row tiles at N*O = 301k rows
-    // (129 vs 123 TFLOP/s: shorter tail) and tie at 1.2M rows (134 TFLOP/s)
-    // and ending the launch on one "round" of 32-row tiles (variant 11) shortens the drain: 135 vs 133 TFLOP/s
-    // tiny batches (<= 128 32-row tiles: integrator tick, planar toy shapes): 16-row tiles on the 16x16x4 MFMA halve the
-    // chain of dependent GEMMs that is the whole latency of such a launch
-    if (v == 0) v = (total >= 64LL * 1024) ? 11 : ((total >= 64LL * 512) ? 3 : (total <= 32LL * 128 ? 6 : 5));
-    if (m.compact && v != 6) {   // per-tile compaction: 64-row tiles, the last round (or everything, for small batches) in 32-row tiles
-        static const int lds_pad = OMDS_EXP_ENV("OMDS_DYN_LDS_PAD", 0);   // experiment builds: bytes of unused LDS (one workgroup per CU: 20000)
-        const size_t lds = (size_t)64 * LDH * 4 + 64 * 4 + 32 + (size_t)OMDS_IDS * 4 + (size_t)lds_pad;
+    const Pass1Size size = pass1_size(total);
+    if (m.compact && size != Pass1Size::Tiny) {   // per-tile compaction: 64-row tiles as above, everything else in 32-row tiles
+        const size_t lds = (size_t)64 * LDH * 4 + 64 * 4 + 32 + (size_t)OMDS_IDS * 4;
         static std::atomic<uint64_t> configured{0};
         if (omds_first_use_on_device(configured))
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pass1_dyn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        const long long tiles64 = total / 64, keep = v >= 10 ? (long long)(v - 10) * 512 / 2 : (v == 5 ? tiles64 : 0);
-        const long long n_big = tiles64 > keep ? tiles64 - keep : 0;
+        const long long n_big = size == Pass1Size::Large ? pass1_big_tiles(total) : size == Pass1Size::Medium ? total / 64 : 0;
         const long long n_small = (total - n_big * 64 + 31) / 32;
         hipLaunchKernelGGL(k_pass1_dyn, dim3((unsigned)(n_big + n_small)), dim3(512), lds, s, Fq, Fp, radius, Dmin, total, O, ignored, (int)n_big,
                            OmdsDivisor::make((unsigned)O), m);
         return;
     }
-    if (v >= 10) {   // 10 + r: mixed tiles, the last r "rounds" of 512 workgroups use 32-row tiles
-        if (m.act == OMDS_ACT_RELU) launch_pass1_mixed<OMDS_ACT_RELU>(s, m, Fq, Fp, radius, O, total, ignored, Dmin, v - 10);
-        else launch_pass1_mixed<OMDS_ACT_TANH>(s, m, Fq, Fp, radius, O, total, ignored, Dmin, v - 10);
-        return;
-    }
-    switch (v) {
-        case 1: launch_pass1_t<128, 4, 1>(s, m, Fq, Fp, radius, O, total, ignored, Dmin); break;
-        case 3: launch_pass1_t<64, 2, 1>(s, m, Fq, Fp, radius, O, total, ignored, Dmin); break;
-        case 6: launch_pass1_t<16, 1, 1>(s, m, Fq, Fp, radius, O, total, ignored, Dmin); break;
-        default: launch_pass1_t<32, 1, 1>(s, m, Fq, Fp, radius, O, total, ignored, Dmin); break;
+    switch (size) {
+        case Pass1Size::Large:
+            if (m.act == OMDS_ACT_RELU) launch_pass1_mixed<OMDS_ACT_RELU>(s, m, Fq, Fp, radius, O, total, ignored, Dmin);
+            else launch_pass1_mixed<OMDS_ACT_TANH>(s, m, Fq, Fp, radius, O, total, ignored, Dmin);
+            break;
+        case Pass1Size::Medium: launch_pass1_t<64, 2, 1>(s, m, Fq, Fp, radius, O, total, ignored, Dmin); break;
+        case Pass1Size::Small: launch_pass1_t<32, 1, 1>(s, m, Fq, Fp, radius, O, total, ignored, Dmin); break;
+        case Pass1Size::Tiny: launch_pass1_t<16, 1, 1>(s, m, Fq, Fp, radius, O, total, ignored, Dmin); break;
     }
 }
 
@@ -326,21 +325,24 @@ void omds_launch_pass1_emit(hipStream_t s, const MlpDev& m, const float* Fq, con
                             int O, int B, uint32_t ignored, float* Dmin, const ExactOut& ex) {
     const long long total = (long long)B * O;
     if (total <= 0) return;
-    if (total >= 64LL * 1024) {
-        const size_t lds = (size_t)64 * LDH * 4 + 64 * 8 + (size_t)64 * (m.nhh + 1) * 32;
-        static std::atomic<uint64_t> configured{0};
-        if (omds_first_use_on_device(configured)) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pass1e_mixed<OMDS_ACT_RELU>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)((size_t)64 * LDH * 4 + 64 * 8 + (size_t)64 * (OMDS_MAX_HIDDEN + 1) * 32));
+    switch (pass1_size(total)) {
+        case Pass1Size::Large: {
+            const size_t lds = (size_t)64 * LDH * 4 + 64 * 8 + (size_t)64 * (m.nhh + 1) * 32;
+            static std::atomic<uint64_t> configured{0};
+            if (omds_first_use_on_device(configured)) {
+                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pass1e_mixed<OMDS_ACT_RELU>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          (int)((size_t)64 * LDH * 4 + 64 * 8 + (size_t)64 * (OMDS_MAX_HIDDEN + 1) * 32));
+            }
+            const long long n_big = pass1_big_tiles(total);
+            const long long n_small = (total - n_big * 64 + 31) / 32;
+            hipLaunchKernelGGL((k_pass1e_mixed<OMDS_ACT_RELU>), dim3((unsigned)(n_big + n_small)), dim3(512), lds, s, Fq, Fp, radius, Dmin,
+                               total, O, ignored, (int)n_big, OmdsDivisor::make((unsigned)O), m, ex);
+            break;
         }
-        const long long tiles64 = total / 64, keep = 512 / 2;   // one round of 32-row tiles at the end, like omds_launch_pass1
-        const long long n_big = tiles64 > keep ? tiles64 - keep : 0;
-        const long long n_small = (total - n_big * 64 + 31) / 32;
-        hipLaunchKernelGGL((k_pass1e_mixed<OMDS_ACT_RELU>), dim3((unsigned)(n_big + n_small)), dim3(512), lds, s, Fq, Fp, radius, Dmin,
-                           total, O, ignored, (int)n_big, OmdsDivisor::make((unsigned)O), m, ex);
-    } else if (total >= 64LL * 512) launch_pass1e_t<64, 2, 1>(s, m, Fq, Fp, radius, O, total, ignored, Dmin, ex);
-    else if (total <= 32LL * 128) launch_pass1e_t<16, 1, 1>(s, m, Fq, Fp, radius, O, total, ignored, Dmin, ex);
-    else launch_pass1e_t<32, 1, 1>(s, m, Fq, Fp, radius, O, total, ignored, Dmin, ex);
+        case Pass1Size::Medium: launch_pass1e_t<64, 2, 1>(s, m, Fq, Fp, radius, O, total, ignored, Dmin, ex); break;
+        case Pass1Size::Small: launch_pass1e_t<32, 1, 1>(s, m, Fq, Fp, radius, O, total, ignored, Dmin, ex); break;
+        case Pass1Size::Tiny: launch_pass1e_t<16, 1, 1>(s, m, Fq, Fp, radius, O, total, ignored, Dmin, ex); break;
+    }
 }
 
 void omds_launch_topk(hipStream_t s, const float* Dmin, int B, int O, int k, int32_t* idx) {

@@ -9,18 +9,8 @@
 
 #include "omds.h"
 
-// Experiment knobs.  Environment variables that change a kernel choice or a tile shape, switch a run-time guard off or make a
-// kernel return early (timing experiments: wrong results by design) exist only in builds with -DOMDS_EXPERIMENT (`make experiment`,
-// `make variant`, `make timeline`: libraries the package loads only when OMDS_LIB names them).  The release library reads
-// OMDS_SCREEN (0 | 1: the screening mode of contexts left on "auto"), OMDS_ROCTX and OMDS_RCCL_LIB, nothing else.
-#ifdef OMDS_EXPERIMENT
-#include <cstdlib>
-#define OMDS_EXP_ENV(name, dflt) ([&]() -> int { const char* _e = getenv(name); return _e ? atoi(_e) : (dflt); }())
-#define OMDS_DBG(x) (x)
-#else
-#define OMDS_EXP_ENV(name, dflt) (dflt)
-#define OMDS_DBG(x) 0
-#endif
+// The library reads OMDS_SCREEN (0 | 1: the screening mode of contexts left on "auto"), OMDS_ROCTX and OMDS_RCCL_LIB from the
+// environment, nothing else (tests/test_capi_cpu.py).
 
 constexpr int OMDS_WIDTH = 256;        // hidden width the MFMA kernels are specialised for
 constexpr int OMDS_LDH = 260;          // LDS row stride of the activation tile (floats): 256 + 4 pad
@@ -312,7 +302,6 @@ struct omds_ctx {
     // staging
     float* d_stage = nullptr;    // transposition staging for host copies
     size_t stage_bytes = 0;
-    float* h_stage = nullptr;
     // multi-GPU (comm.hip): RCCL communicator of the rollout shards, nullptr = single shard
     void* comm = nullptr;        // ncclComm_t
     int comm_rank = 0, comm_world = 1;
@@ -454,7 +443,7 @@ int omds_tail_rows(int N, int k, bool g4_ok = false);   // pass-2 tile height (1
 // Dmin holds exact values on the candidates and screening values elsewhere; the tail counts the rollouts whose k-th smallest
 // value is not e_bound below k_select's tau (range[4 t + 2]) into *viol
 void omds_launch_tail(hipStream_t s, const MlpDev& m, const float* Fp, const float* radius, const float* xyzr,
-                      const float* Dmin, float* Fq, float* dscr, int O, const StepArgs& st, int t_begin, int t_end,
+                      const float* Dmin, float* Fq, float* dscr, int O, const StepArgs& st,
                       uint16_t* FqH = nullptr, int ldF = 0, float* FqOut = nullptr, const int* guard_range = nullptr,
                       float e_bound = 0.f, unsigned* viol = nullptr);
 // screened step's tail: top-k over the candidates k_exact evaluated + pass-2 backward on its masks + the rest of k_tail

@@ -47,38 +47,24 @@ typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 
 // Geometry: SC_WAVES waves per workgroup, each owning SC_RB blocks of 32 pairs; every A fragment (1 KiB of weights) a wave
-// reads from the ring feeds SC_RB MFMAs.  Default 8 waves x 1 block (two waves per SIMD, 241 registers).  The alternative
-// 4 waves x 2 blocks (one wave per SIMD with the 512-register budget: half the LDS reads per MFMA; make variant V=rb2
-// VFLAGS="-DOMDS_SC_WAVES=4 -DOMDS_SC_RB=2") is bit-identical and measured 104 vs 99 us per launch: the LDS port is not the
-// limit (tools/ubench/mfma_f16_issue.hip: one fragment read per MFMA sustains 83-87 % of the fp16 MFMA peak at two waves
-// per SIMD, 63-65 % at one), a single wave per SIMD hides less.
-#ifndef OMDS_SC_WAVES
-#define OMDS_SC_WAVES 8
-#endif
-#ifndef OMDS_SC_RB
-#define OMDS_SC_RB 1
-#endif
-#ifndef OMDS_SC_RING
-#define OMDS_SC_RING 4
-#define OMDS_SC_DIST 3
-#endif
-constexpr int SC_WAVES = OMDS_SC_WAVES;
-constexpr int SC_RB = OMDS_SC_RB;             // 32-pair blocks per wave
+// reads from the ring feeds SC_RB MFMAs.  8 waves x 1 block (two waves per SIMD, 241 registers).  The alternative 4 waves x
+// 2 blocks (one wave per SIMD with the 512-register budget: half the LDS reads per MFMA) is bit-identical and measured 104 vs
+// 99 us per launch: the LDS port is not the limit (tools/ubench/mfma_f16_issue.hip: one fragment read per MFMA sustains
+// 83-87 % of the fp16 MFMA peak at two waves per SIMD, 63-65 % at one), a single wave per SIMD hides less.
+constexpr int SC_WAVES = 8;
+constexpr int SC_RB = 1;                      // 32-pair blocks per wave
 constexpr int SC_NT = SC_WAVES * 64;
 constexpr int SC_ROWS = SC_WAVES * SC_RB * 32; // pairs per workgroup
 constexpr int SC_SLICE = 16384;               // bytes: 16 k-chunks x 1 KiB fragment
-constexpr int SC_RING = OMDS_SC_RING;         // ring slots of 16 KB (a power of two)
-constexpr int SC_DIST = OMDS_SC_DIST;         // slices in flight ahead of the one being multiplied (<= RING - 1)
+constexpr int SC_RING = 4;                    // ring slots of 16 KB (a power of two)
+constexpr int SC_DIST = 3;                    // slices in flight ahead of the one being multiplied (<= RING - 1)
 constexpr int SC_PW = 16 / SC_WAVES;          // LDS-DMA pieces (1 KiB fragments) per wave and slice
 constexpr int SC_MAX_TILES = 20;              // tiles per workgroup whose results fit the LDS next to the ring
-#ifndef OMDS_SC_TEST0
-#define OMDS_SC_TEST0 10
-#endif
 // first k-chunk whose activations are tested for "all zero" before its MFMAs (ReLU networks).  Measured on the shipped network
-// (tools/studies/screen_test0_sweep.sh, 1024 x 32 / 4096 x 32): 4: 100.0 / 365.5 us, 8: 98.0 / 357.7, 9: 96.7 / 351.2, 10: 96.1 / 349.5,
+// (variant builds, EXPERIMENTS.md; 1024 x 32 / 4096 x 32): 4: 100.0 / 365.5 us, 8: 98.0 / 357.7, 9: 96.7 / 351.2, 10: 96.1 / 349.5,
 // 11: 97.0 / 351.7, 12: 97.2 / 355.3 -- its silent units begin at chunk 9-13 depending on the layer; every test and branch in front of
 // them costs issue slots
-constexpr int SC_TEST0 = OMDS_SC_TEST0;
+constexpr int SC_TEST0 = 10;
 
 struct ScreenArgs {
     const _Float16* Wh;      // [nhh*8 + 2 slices][16 fragments][64 lane][8 halfs], fragment order (packed by omds_set_mlp)
@@ -104,9 +90,6 @@ struct ScreenArgs {
     const SelectSink* sel;   // device memory, or nullptr.  Non-null: the flush phase selects each rollout's candidates instead of writing
                              // Dmin.  A pointer on purpose: as kernel arguments the sink's 20 dwords were loaded at entry and held in
                              // SGPRs across the tile loop (SGPR spills 36 -> 114)
-    unsigned long long* tl;  // diagnostic (OMDS_SCREEN_TL=1): [workgroup][8] s_memtime stamps, nullptr otherwise
-    int dbg;                 // timing experiments only (OMDS_SCREEN_DBG): 1 = no weight streaming after the prologue,
-                             // 2 = no layer-1 loads, 4 = no per-slice wait + barrier
 };
 
 // lowbias32 (an integer hash with good avalanche): which non-candidate pairs enter the audit sample
@@ -177,8 +160,6 @@ __device__ __forceinline__ AGroup read_group(const unsigned char* slot_lane, int
     for (int i = 0; i < 4; ++i) r.f[i] = *reinterpret_cast<const h8*>(slot_lane + (4 * g + i) * 1024);
     return r;
 }
-
-#define SC_TL(i) do { if (a.tl && threadIdx.x == 0 && it == 0) a.tl[(size_t)blockIdx.x * 8 + (i)] = __builtin_readcyclecounter(); } while (0)
 
 // pair (rollout t, obstacle o) of this lane in tile `tile` of the workgroup's chunk [p0, p1); rows past the end (also: the
 // prefetch of a non-existent next tile) clamp to the chunk's last pair and are not stored.  Plain scalars on purpose: a
@@ -350,7 +331,7 @@ __global__ __launch_bounds__(SC_NT, SC_WAVES == 4 ? 1 : 2) void k_screen(ScreenA
     // The weight slices keep streaming through the ring across tile boundaries (the slice sequence is periodic), the bias
     // table is loaded once, and the results wait in LDS until the end -- a store in flight would perturb the counted vmcnt
     // waits of the LDS-DMA pieces (stores and loads retire out of order with respect to each other).  Measured on the
-    // one-tile-per-workgroup form (OMDS_SCREEN_TL): of 57 kcycles per tile slot 14 were the refill gap between two
+    // one-tile-per-workgroup form (its phase timeline, EXPERIMENTS.md): of 57 kcycles per tile slot 14 were the refill gap between two
     // workgroups of a CU, 12 the layer-1 operand loads and first-slice latency, and only 29 the slice loop.
     // A chunk of WHOLE rollouts (a.sel.rowlist != nullptr) ends with every screening value of those rollouts in this
     // workgroup's LDS: the flush phase then does k_select's work from there -- k-th smallest, window, list append, audit
@@ -370,11 +351,7 @@ __global__ __launch_bounds__(SC_NT, SC_WAVES == 4 ? 1 : 2) void k_screen(ScreenA
     const long long p1e = p0 + (long long)(a.units_base + (wg < a.units_rem ? 1 : 0)) * a.unit;
     const long long p1 = p1e < a.total_rows ? p1e : a.total_rows;
     const int my_pairs = (int)(p1 - p0);
-#ifdef OMDS_SC_EXPERIMENT   // OMDS_SCREEN_DBG 16: the partial last tile of a chunk does not exist at all (neither its MFMAs nor its ring traffic)
-    const int my_tiles = (my_pairs + SC_ROWS - 1) / SC_ROWS - (((OMDS_DBG(a.dbg) & 16) && (my_pairs % SC_ROWS) != 0 && my_pairs > SC_ROWS) ? 1 : 0);
-#else
     const int my_tiles = (my_pairs + SC_ROWS - 1) / SC_ROWS;                    // >= 1: the grid never exceeds the chunks
-#endif
 
     // slice `sl` of the network -> ring slot `slot`; this wave moves fragments PW*w .. PW*w + PW-1
     const unsigned char* wbase = reinterpret_cast<const unsigned char*>(a.Wh) + (SC_PW * wave) * 1024;   // wave-uniform
@@ -387,7 +364,6 @@ __global__ __launch_bounds__(SC_NT, SC_WAVES == 4 ? 1 : 2) void k_screen(ScreenA
         if (SC_PW > 1) dma16<1024>(src, lane16, dst);
         if (SC_PW > 2) { dma16<2048>(src, lane16, dst); dma16<3072>(src, lane16, dst); }
     };
-    if (a.tl && threadIdx.x == 0) { a.tl[(size_t)blockIdx.x * 8 + 7] = __builtin_readcyclecounter(); a.tl[(size_t)blockIdx.x * 8 + 5] = wall_clock64(); }
     for (int i = tid; i < (NHH + 2) * OMDS_WIDTH; i += SC_NT) biasL[i] = a.bias[i];
     for (int i = tid; i < my_tiles * SC_ROWS; i += SC_NT) resL[i] = __builtin_inff();   // the two lane-halves of a pair min into it
     __syncthreads();   // bias table visible; nothing of the ring is in flight yet (hipcc's fence would drain it)
@@ -466,23 +442,11 @@ __global__ __launch_bounds__(SC_NT, SC_WAVES == 4 ? 1 : 2) void k_screen(ScreenA
     AGroup cur = read_group(ring_lane, 0);
     int sigma0 = 0;
     for (int it = 0; it < my_tiles; ++it, sigma0 += S) {
-        SC_TL(0);
         auto sync_and_issue = [&](int s) {
-#ifdef OMDS_SC_EXPERIMENT   // timing experiments only (variant builds): OMDS_SCREEN_DBG 4 = no wait + barrier, 1 = no weight streaming
-            if (!(OMDS_DBG(a.dbg) & 4)) wait_vm_barrier(SC_PW * (SC_DIST - 2));
-            if (!(OMDS_DBG(a.dbg) & 1)) issue((s + SC_DIST) % S, (sigma0 + s + SC_DIST) & (SC_RING - 1));
-#else
             wait_vm_barrier(SC_PW * (SC_DIST - 2));
             issue((s + SC_DIST) % S, (sigma0 + s + SC_DIST) & (SC_RING - 1));
-#endif
         };
         auto slot_ptr = [&](int s) { return ring_lane + ((sigma0 + s) & (SC_RING - 1)) * SC_SLICE; };
-#ifdef OMDS_SC_EXPERIMENT   // OMDS_SCREEN_DBG 8: the partial last tile of a chunk is not multiplied at all (what its round costs)
-        if ((OMDS_DBG(a.dbg) & 8) && it == my_tiles - 1 && (my_pairs % SC_ROWS) != 0) {
-            for (int s = 0; s < S; ++s) sync_and_issue(s);
-            continue;
-        }
-#endif
         if (it * SC_ROWS + wave * SC_RB * 32 >= my_pairs) {
             // all pairs of this wave lie past the end of the chunk (the partial last tile of a chunk of whole rollouts): it keeps
             // the ring moving -- its DMA pieces, the barriers -- and issues no MFMA.  The matrix pipe is power-limited under this
@@ -575,7 +539,6 @@ __global__ __launch_bounds__(SC_NT, SC_WAVES == 4 ? 1 : 2) void k_screen(ScreenA
             concat(0);
             find_alive();
         }
-        SC_TL(1);
         // ---- steps 1 .. S-1: hidden->hidden layers and the last layer
         h8 nxt[SC_RB][16];
         float dmin[SC_RB];
@@ -659,9 +622,7 @@ __global__ __launch_bounds__(SC_NT, SC_WAVES == 4 ? 1 : 2) void k_screen(ScreenA
             }
 #pragma unroll
             for (int rb = 0; rb < SC_RB; ++rb) acc[rb] = acc_next;
-            if (s == 8) SC_TL(2);
         }
-        SC_TL(3);
         // links 0-3, 8-11 sit in lane-half 0, the others in half 1: both min into the pair's LDS slot (ds_min_f32; a cross-lane
         // exchange would keep a lane-index VGPR alive across the whole tile loop)
 #pragma unroll
@@ -671,7 +632,6 @@ __global__ __launch_bounds__(SC_NT, SC_WAVES == 4 ? 1 : 2) void k_screen(ScreenA
             rad[rb] = a.radius[row_o[rb]];
         }
     }
-    if (a.tl && threadIdx.x == 0) a.tl[(size_t)blockIdx.x * 8 + 4] = __builtin_readcyclecounter();
     // ---- drain the ring (pieces issued past the last tile still target this workgroup's LDS), then flush the results
     wait_vm_barrier(0);
     __syncthreads();
@@ -691,7 +651,6 @@ __global__ __launch_bounds__(SC_NT, SC_WAVES == 4 ? 1 : 2) void k_screen(ScreenA
     } else {
         for (int i = tid; i < my_pairs; i += SC_NT) a.Dmin[p0 + i] = resL[i];
     }
-    if (a.tl && threadIdx.x == 0) a.tl[(size_t)blockIdx.x * 8 + 6] = wall_clock64();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -962,13 +921,9 @@ void omds_launch_screen(hipStream_t s, const ScreenDev& sd, const MlpDev& m, con
     a.nhh = m.nhh; a.C = m.C; a.out_div = m.out_div;
     a.skip_mask = m.skip_mask;
     a.sel = nullptr;
-    static const int dbg = OMDS_EXP_ENV("OMDS_SCREEN_DBG", 0);
-    a.dbg = dbg;
     // persistent: one workgroup per CU (256 on MI355X; more only when a workgroup's result buffer would overflow its LDS),
     // each with a contiguous chunk of the pair space
-    int ncu = omds_cu_count();
-    static const int cu_cap = OMDS_EXP_ENV("OMDS_SCREEN_CUS", 0);   // experiment builds: persistent workgroups on a subset of the CUs
-    if (cu_cap > 0) ncu = std::min(ncu, cu_cap);
+    const int ncu = omds_cu_count();
     long long gl;
     int tiles_per_wg;
     if (sel && omds_screen_can_select(O)) {
@@ -994,15 +949,6 @@ void omds_launch_screen(hipStream_t s, const ScreenDev& sd, const MlpDev& m, con
     const size_t lds = omds_screen_lds_bytes(m.nhh) + (size_t)tiles_per_wg * SC_ROWS * 4;
     a.res_tiles = tiles_per_wg;
     const size_t lds_max = omds_screen_lds_bytes(4) + (size_t)SC_MAX_TILES * SC_ROWS * 4;
-    // diagnostic timeline (OMDS_SCREEN_TL=1): phase stamps of every workgroup's FIRST tile, summarised on stderr
-    static const int tl_on = OMDS_EXP_ENV("OMDS_SCREEN_TL", 0);
-    static unsigned long long* tl_buf = nullptr;
-    a.tl = nullptr;
-    if (tl_on && grid.x <= 65536) {
-        if (!tl_buf) (void)hipMalloc(&tl_buf, (size_t)65536 * 8 * sizeof(unsigned long long));
-        (void)hipMemsetAsync(tl_buf, 0, (size_t)grid.x * 8 * sizeof(unsigned long long), s);
-        a.tl = tl_buf;
-    }
     const bool skip = m.skip_mask != 0;
     switch (m.nhh) {
         case 1: launch_screen_n<1>(s, grid, lds, lds_max, a, m.act, skip); break;
@@ -1010,26 +956,6 @@ void omds_launch_screen(hipStream_t s, const ScreenDev& sd, const MlpDev& m, con
         case 3: launch_screen_n<3>(s, grid, lds, lds_max, a, m.act, skip); break;
         case 4: launch_screen_n<4>(s, grid, lds, lds_max, a, m.act, skip); break;
         default: break;   // omds_screen_supported() keeps other depths on the fp32 path
-    }
-    if (a.tl) {
-        std::vector<unsigned long long> h((size_t)grid.x * 8);
-        (void)hipStreamSynchronize(s);
-        (void)hipMemcpy(h.data(), tl_buf, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-        double seg[3] = {0, 0, 0}, pro = 0, loop = 0, wall = 0;
-        unsigned long long w0 = ~0ull, w1 = 0;
-        for (unsigned w = 0; w < grid.x; ++w) {
-            const unsigned long long* r = &h[(size_t)w * 8];
-            for (int i = 0; i < 3; ++i) seg[i] += (double)(r[i + 1] - r[i]);
-            pro += (double)(r[0] - r[7]);          // kernel start -> first tile
-            loop += (double)(r[4] - r[0]);         // all tiles of the workgroup
-            wall += (double)(r[6] - r[5]);         // 100 MHz wall clock, whole workgroup
-            w0 = std::min(w0, r[5]); w1 = std::max(w1, r[6]);
-        }
-        fprintf(stderr, "[k_screen timeline] per workgroup: prologue %.0f cycles, tile loop %.0f cycles, lifetime %.2f us (first start -> last end "
-                        "%.2f us): %.2f GHz over the loop if the rest of the lifetime ran at the same clock\n", pro / grid.x, loop / grid.x,
-                wall / grid.x / 100.0, (double)(w1 - w0) / 100.0, (pro + loop) / grid.x / (wall / grid.x / 100.0) / 1000.0);
-        fprintf(stderr, "[k_screen timeline] %u workgroups x %d tiles; first tile, mean cycles: layer-1 step %.0f, first hidden layer %.0f, "
-                        "remaining layers %.0f\n", grid.x, tiles_per_wg, seg[0] / grid.x, seg[1] / grid.x, seg[2] / grid.x);
     }
 }
 
@@ -1047,17 +973,17 @@ void omds_launch_select(hipStream_t s, const float* Dmin, int B, int O, const Se
 // that k_tail_sel<..., tanh> runs the backward only (round 4; 3 KB per candidate row of HBM traffic against a second forward in
 // the tail).  Without ex.deriv (a matrix-mode step: rows too long for the selecting flush AND no derivative buffer), mode 3: the
 // exact value replaces the screening value in the matrix Dmin itself and k_tail takes its top-k from the matrix and runs its own
-// forward.
+// forward.  The grid is sized for EXACT_RESIDENT resident workgroups per CU; longer lists stride (the list length is only known
+// on the device).
+constexpr int EXACT_RESIDENT = 3;
 void omds_launch_exact(hipStream_t s, const MlpDev& m, const float* Fq, const float* Fp, const float* radius, int O,
                        int B, uint32_t ignored, float* Dmin, const int* rowlist, const int* total, unsigned* maxerr_bits,
                        const ExactOut& ex) {
     if (B <= 0) return;
     const size_t lds = (size_t)16 * LDH * 4 + 16 * 4 + 16 * 4 + (size_t)16 * (m.nhh + 1) * 8 * 4;
     const int ncu = omds_cu_count();
-    // three resident workgroups per CU; longer lists stride (the list length is only known on the device)
     const long long blocks_max = ((long long)B * O + 15) / 16;
-    static const int res = std::max(1, OMDS_EXP_ENV("OMDS_EXACT_RESIDENT", 3));   // workgroups per CU the grid is sized for (experiment builds: another count)
-    const unsigned grid = (unsigned)std::min<long long>(blocks_max, (long long)res * ncu);
+    const unsigned grid = (unsigned)std::min<long long>(blocks_max, (long long)EXACT_RESIDENT * ncu);
     const OmdsDivisor od = OmdsDivisor::make((unsigned)O);
     if (m.act == OMDS_ACT_RELU)
         hipLaunchKernelGGL((k_exact<OMDS_ACT_RELU, 1>), dim3(grid), dim3(512), lds, s, m, Fq, Fp, radius, O, ignored, Dmin, od, rowlist, total, maxerr_bits, ex);

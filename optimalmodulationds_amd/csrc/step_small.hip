@@ -47,7 +47,6 @@ struct SmallArgs {
     float* o_drow;        // [B*k]
     int32_t* o_idx;       // [B][k]
     float* o_Dmin;        // [B][O]
-    int dbg_stop;         // timing experiments only (OMDS_SMALL_STOP): return after phase 1 / 2 / 3 / 4
     StepArgs st;
 };
 
@@ -86,7 +85,6 @@ __global__ __launch_bounds__(SS_NT, TR == 16 ? 4 : 2) void k_step_small(SmallArg
         pass1_tile<TR, 1, 1, ACT, 2>(m, smem, a.Fq, a.Fp, a.radius, O, total, a.ignored, nullptr, (long long)t_base * O, a.odiv,
                                      nullptr, nullptr, &ex);
     }
-    if (OMDS_DBG(a.dbg_stop) == 1) return;
     if (tid < SS_RK) { selRow[tid] = -1; selT[tid] = 0; selO[tid] = 0; dr[tid] = 0.f; }
     // the backward's first weights (phase 3) are on their way while the closest obstacles are picked
     const int wv = __builtin_amdgcn_readfirstlane(wave);
@@ -128,7 +126,6 @@ __global__ __launch_bounds__(SS_NT, TR == 16 ? 4 : 2) void k_step_small(SmallArg
     }
     __syncthreads();
 
-    if (OMDS_DBG(a.dbg_stop) == 2) return;
     // ---- 3. backward on the selected rows: ONE 4-row group on v_mfma_f32_4x4x1 (gemm4, mlp_device.h) -----------------------
     // Four rows are no 16-row MFMA problem (a 16-row tile would run at the 16-row rate to move four useful rows) but they are
     // exactly one row group of the 4x4x1 shape: waves 0-3 multiply 64 columns each, 256 dependent MFMAs per layer (one
@@ -181,7 +178,6 @@ __global__ __launch_bounds__(SS_NT, TR == 16 ? 4 : 2) void k_step_small(SmallArg
             __syncthreads();
         }
     }
-    if (OMDS_DBG(a.dbg_stop) == 3) return;
     // first layer: g_f[r][f] = sum_c Gz1[r][c] W1[c][f], one ascending chain per element over the four gradient rows at the top of
     // the tile (first_layer_backward works on 16-row blocks: rows 4..15 hold the forward's leftovers, whose products stay in their
     // own rows of the MFMA and are not read)
@@ -200,7 +196,6 @@ __global__ __launch_bounds__(SS_NT, TR == 16 ? 4 : 2) void k_step_small(SmallArg
         }
     }
     __syncthreads();
-    if (OMDS_DBG(a.dbg_stop) == 4) return;
     if (a.o_gradx != nullptr) {   // network-only form
         const int d = m.d;
         for (int e = tid; e < R * k * d; e += SS_NT) {
@@ -236,7 +231,7 @@ __global__ __launch_bounds__(SS_NT, TR == 16 ? 4 : 2) void k_step_small(SmallArg
             }
         }
     }
-    if (a.st.step >= a.st.H || OMDS_DBG(a.dbg_stop) == 5) return;   // last step: nothing is integrated, no next network evaluation
+    if (a.st.step >= a.st.H) return;   // last step: nothing is integrated, no next network evaluation
     __syncthreads();
     {   // the encoded joint inputs of the next step (as k_rollout_features writes them)
         const int d = m.d;
@@ -264,13 +259,10 @@ int omds_step_small_rollouts(const MlpDev& m, int n_dof, int O, int k) { return 
 // Tile height: 16 rows when that costs no rollouts per workgroup (the cap of four backward rows binds, not the tile: half the
 // forward's MFMA chain for the same work); else 32.  Halving the rollouts per workgroup to get two 16-row workgroups resident
 // per CU (one's backward and modulation under the other's forward) was measured on planar 7-DoF 1024 x 32: 17.0 M against
-// 18.9 M rollout-steps/s -- twice the workgroups stream the backward's weights twice.  OMDS_SMALL_ROWS=16|32 forces one.
-static int small_tile_rows(const MlpDev& m, int n_dof, int O, int k, int B) {
-    static const int forced = OMDS_EXP_ENV("OMDS_SMALL_ROWS", 0);   // experiment builds
+// 18.9 M rollout-steps/s -- twice the workgroups stream the backward's weights twice.
+static int small_tile_rows(const MlpDev& m, int n_dof, int O, int k) {
     const int r16 = small_rollouts(m, n_dof, O, k, 16), r32 = small_rollouts(m, n_dof, O, k, 32);
     if (r16 <= 0) return 32;
-    if (forced == 16 || forced == 32) return forced;
-    (void)B;
     return r16 == r32 ? 16 : 32;
 }
 
@@ -284,7 +276,7 @@ static void launch_small_r(hipStream_t s, const SmallArgs& a) {
 }
 template <int ND>
 static void launch_small_t(hipStream_t s, SmallArgs& a, int k) {
-    const int TR = small_tile_rows(a.m, ND, a.O, k, a.B);
+    const int TR = small_tile_rows(a.m, ND, a.O, k);
     a.R = small_rollouts(a.m, ND, a.O, k, TR);
     if (a.R <= 0) return;
     if (TR == 16) launch_small_r<ND, 16>(s, a);
@@ -301,8 +293,6 @@ void omds_launch_step_small(hipStream_t s, const MlpDev& m, const float* Fp, con
     a.qT = st.trajT + (size_t)(st.step - 1) * st.n * st.N;
     a.ldq = st.N;
     a.st = st;
-    static const int stop = OMDS_EXP_ENV("OMDS_SMALL_STOP", 0);
-    a.dbg_stop = stop;
     if (omds_step_small_rollouts(m, st.n, O, st.k) <= 0) return;
     if (st.n == 7) launch_small_t<7>(s, a, st.k);
     else launch_small_t<2>(s, a, st.k);

@@ -26,10 +26,7 @@ struct TailArgs {
     int ldF;             // row capacity of FqH
     float* dscr;         // tanh derivative scratch
     int O;
-    int t_begin, t_end;  // rollout range of this launch (a group of the rollouts; the whole batch = [0, N))
-    int slot0;           // first 32-row slot of this launch in the tanh scratch
-    int n_slots;         // slots of the whole batch (scratch stride between layers)
-    int dbg_stop;        // timing experiments only (OMDS_TAIL_STOP): return after phase 1 / 2 / 3
+    int n_slots;         // workgroups of the launch (tanh scratch stride between layers)
     // screened step (k_tail_sel): the candidate list of k_select and what k_exact computed for its entries
     const int* rowlist;  // [entries] pair t*O + o
     const int* range;    // [N][4] start, length of each rollout's entries, tau of k_select (float bits)
@@ -59,20 +56,19 @@ __global__ __launch_bounds__(P2_NT) void k_tail(TailArgs a) {
     static_assert(ACT == OMDS_ACT_RELU || ROWS != 4, "the 4-row-group pass 2 works on ReLU masks");
     constexpr int G4_NG = 5, TROWS = ROWS == 4 ? 4 * G4_NG : ROWS;
     const int RW = TROWS / k;                 // rollouts per workgroup
-    const int t_base = a.t_begin + blockIdx.x * RW;
-    const int t_end = a.t_end;
+    const int t_base = blockIdx.x * RW;
 
     OMDS_TL_STAMP(0);
     OMDS_TL_STAMP(1);
     P2G4Pre pre;   // (ROWS = 4) everything of pass 2 that does not wait for the top-k is requested in front of it
     if constexpr (ROWS == 4)
-        pass2_g4_prefetch(m, a.Fq, [&](int r) { const int rl = r / k; return (rl < RW && t_base + rl < t_end) ? t_base + rl : -1; }, pre);
+        pass2_g4_prefetch(m, a.Fq, [&](int r) { const int rl = r / k; return (rl < RW && t_base + rl < N) ? t_base + rl : -1; }, pre);
     // ---- top-k of each rollout's min-distance row (ascending, ties by lower obstacle index) -------
     if (tid < P2_MT) { sm.rowT[tid] = -1; sm.rowO[tid] = 0; }
     __syncthreads();
     for (int rl = wave; rl < RW; rl += 8) {
         const int t = t_base + rl;
-        if (t >= t_end) break;
+        if (t >= N) break;
         topk_row(a.Dmin + (size_t)t * O, O, k, lane, [&](int j, int bi) {
             sm.rowT[rl * k + j] = t;
             sm.rowO[rl * k + j] = bi;
@@ -84,24 +80,22 @@ __global__ __launch_bounds__(P2_NT) void k_tail(TailArgs a) {
     }
     __syncthreads();
     OMDS_TL_STAMP(2);
-    if (OMDS_DBG(a.dbg_stop) == 1) return;
 
     // ---- forward + backward on the selected rows; gradients and distances stay in LDS ------------
     const float* qT = a.st.trajT + (size_t)(a.st.step - 1) * ND * N;
     if constexpr (ROWS == 4)
-        pass2_body_g4<G4_NG>(m, sm, pre, a.Fp, a.radius, a.xyzr, t_base * k, N * k, qT, N, gx, dr, 0, OMDS_DBG(a.dbg_stop));
+        pass2_body_g4<G4_NG>(m, sm, pre, a.Fp, a.radius, a.xyzr, t_base * k, N * k, qT, N, gx, dr, 0);
     else
         pass2_body<ACT, ROWS>(m, sm, a.Fq, a.Fp, a.radius, a.xyzr, t_base * k, N * k, qT, N, gx, dr, 0, nullptr, nullptr,
-                              a.dscr, (size_t)a.n_slots * ROWS * OMDS_WIDTH, (a.slot0 + (int)blockIdx.x) * ROWS, OMDS_DBG(a.dbg_stop));
+                              a.dscr, (size_t)a.n_slots * ROWS * OMDS_WIDTH, (int)blockIdx.x * ROWS);
     __syncthreads();
     OMDS_TL_STAMP(9);
-    if (OMDS_DBG(a.dbg_stop) == 2) return;
 
     // ---- modulation / policy / Euler step: 16 lanes per rollout -------------------------------------
     {
         const int rl = tid >> 4, sub = tid & 15;
         const int t = t_base + rl;
-        if (rl < RW && t < t_end) {
+        if (rl < RW && t < N) {
             float q[ND], qn[ND];
 #pragma unroll
             for (int j = 0; j < ND; ++j) q[j] = qT[(size_t)j * N + t];
@@ -129,7 +123,7 @@ __global__ __launch_bounds__(P2_NT) void k_tail(TailArgs a) {
         }
     }
     OMDS_TL_STAMP(10);
-    if (a.st.step >= a.st.H || OMDS_DBG(a.dbg_stop) == 3) return;   // last step: nothing is integrated, no next network evaluation
+    if (a.st.step >= a.st.H) return;   // last step: nothing is integrated, no next network evaluation
     __syncthreads();
 
     // ---- the encoded joint inputs of the next step (as k_rollout_features writes them) --------
@@ -137,7 +131,7 @@ __global__ __launch_bounds__(P2_NT) void k_tail(TailArgs a) {
         const int d = m.d;
         for (int e = tid; e < RW * 3 * ND; e += P2_NT) {
             const int rl = e / (3 * ND), cc = e - rl * (3 * ND), part = cc / ND, t = t_base + rl;
-            if (t < t_end) a.FqOut[(size_t)t * OMDS_FROW + part * d + (cc - part * ND)] = feat[e];
+            if (t < N) a.FqOut[(size_t)t * OMDS_FROW + part * d + (cc - part * ND)] = feat[e];
         }
     }
     OMDS_TL_STAMP(11);
@@ -146,9 +140,6 @@ __global__ __launch_bounds__(P2_NT) void k_tail(TailArgs a) {
 
 
 static size_t tail_lds_bytes(int nhid);
-#ifdef OMDS_TAIL_TL
-__global__ void k_tail_tl_dump(int nb);
-#endif
 
 // ------------------------------------------------------------------------------------------------
 // Screened step: k_screen -> k_select -> k_exact -> k_tail_sel.  k_exact has evaluated every candidate row in fp32 with
@@ -182,8 +173,7 @@ __global__ __launch_bounds__(P2_NT) void k_tail_sel(TailArgs a) {
     // ROWS = 4: the backward runs on 4-row groups (pass2_backward_hidden_g4): G4_ROWS network rows per workgroup
     constexpr int G4_NG = 5, TROWS = ROWS == 4 ? 4 * G4_NG : ROWS;
     const int RW = TROWS / k;                 // rollouts per workgroup
-    const int t_base = a.t_begin + blockIdx.x * RW;
-    const int t_end = a.t_end;
+    const int t_base = blockIdx.x * RW;
 
     OMDS_TL_STAMP(0);
     OMDS_TL_STAMP(1);
@@ -192,7 +182,7 @@ __global__ __launch_bounds__(P2_NT) void k_tail_sel(TailArgs a) {
     __syncthreads();
     for (int rl = wave; rl < RW; rl += 8) {
         const int t = t_base + rl;
-        if (t >= t_end) break;
+        if (t >= N) break;
         // rowlist == nullptr: EVERY pair of the rollout is an entry and the entry index is the pair index (pass1_tile mode 6: the
         // all-fp32 step); no window, no slack to check
         const bool dense = a.rowlist == nullptr;
@@ -260,7 +250,6 @@ __global__ __launch_bounds__(P2_NT) void k_tail_sel(TailArgs a) {
     }
     __syncthreads();
     OMDS_TL_STAMP(2);
-    if (OMDS_DBG(a.dbg_stop) == 1) return;   // OMDS_TAIL_SEL_STOP: timing experiments
     if constexpr (ACT == OMDS_ACT_TANH) {
         sm.rowE = sel;   // the backward gathers 1 - h^2 of row r from entry sel[r] of ExactOut::deriv (written by k_exact, mode 5)
     } else {
@@ -301,7 +290,6 @@ __global__ __launch_bounds__(P2_NT) void k_tail_sel(TailArgs a) {
     }
 
     OMDS_TL_STAMP(3);
-    if (OMDS_DBG(a.dbg_stop) == 2) return;
     // ---- backward on the selected rows; gradients stay in LDS -----------------------------------------
     const float* qT = a.st.trajT + (size_t)(a.st.step - 1) * ND * N;
     if constexpr (ROWS == 4) {
@@ -312,13 +300,12 @@ __global__ __launch_bounds__(P2_NT) void k_tail_sel(TailArgs a) {
     }
     __syncthreads();
     OMDS_TL_STAMP(9);
-    if (OMDS_DBG(a.dbg_stop) == 3) return;
 
     // ---- modulation / policy / Euler step: 16 lanes per rollout -------------------------------------
     {
         const int rl = tid >> 4, sub = tid & 15;
         const int t = t_base + rl;
-        if (rl < RW && t < t_end) {
+        if (rl < RW && t < N) {
             float q[ND], qn[ND];
 #pragma unroll
             for (int j = 0; j < ND; ++j) q[j] = qT[(size_t)j * N + t];
@@ -354,7 +341,7 @@ __global__ __launch_bounds__(P2_NT) void k_tail_sel(TailArgs a) {
         const int d = m.d;
         for (int e = tid; e < RW * 3 * ND; e += P2_NT) {
             const int rl = e / (3 * ND), cc = e - rl * (3 * ND), part = cc / ND, t = t_base + rl;
-            if (t < t_end) a.FqOut[(size_t)t * OMDS_FROW + part * d + (cc - part * ND)] = feat[e];
+            if (t < N) a.FqOut[(size_t)t * OMDS_FROW + part * d + (cc - part * ND)] = feat[e];
         }
     }
     OMDS_TL_STAMP(11);
@@ -370,6 +357,14 @@ __global__ void k_tail_tl_dump(int nb) {
         printf(" %llu\n", g_tail_tl[b][19]);
     }
 }
+// prints the stamps of the third launch at horizon step OMDS_TAIL_TL_STEP (tools/tail_timeline.py)
+static void tail_tl_dump(hipStream_t s, int step, int grid) {
+    static int seen = 0;
+    static const char* want = getenv("OMDS_TAIL_TL_STEP");
+    if (want && step == atoi(want) && ++seen == 3) hipLaunchKernelGGL(k_tail_tl_dump, dim3(1), dim3(1), 0, s, grid);
+}
+#else
+static void tail_tl_dump(hipStream_t, int, int) {}
 #endif
 
 template <int ND, int ROWS, int ACT = OMDS_ACT_RELU>
@@ -381,33 +376,28 @@ static void launch_tail_sel_t(hipStream_t s, const TailArgs& a) {
                                   (int)(tail_lds_bytes(OMDS_MAX_HIDDEN + 1) + extra));
     }
     const int RW = (ROWS == 4 ? 20 : ROWS) / a.st.k;
-    hipLaunchKernelGGL((k_tail_sel<ND, ROWS, ACT>), dim3((a.t_end - a.t_begin + RW - 1) / RW), dim3(P2_NT), tail_lds_bytes(a.m.nhh + 1) + extra, s, a);
-#ifdef OMDS_TAIL_TL
-    {
-        static int seen = 0;
-        static const int want = OMDS_EXP_ENV("OMDS_TAIL_TL_STEP", -1);
-        if (a.st.step == want && ++seen == 3) hipLaunchKernelGGL(k_tail_tl_dump, dim3(1), dim3(1), 0, s, (a.t_end - a.t_begin + RW - 1) / RW);
-    }
-#endif
+    const int grid = (a.st.N + RW - 1) / RW;
+    hipLaunchKernelGGL((k_tail_sel<ND, ROWS, ACT>), dim3(grid), dim3(P2_NT), tail_lds_bytes(a.m.nhh + 1) + extra, s, a);
+    tail_tl_dump(s, a.st.step, grid);
 }
 
 // 16-row tiles (bit-identical to 32-row ones, mlp_device.h) while their workgroups still fit the CUs two at a time: twice as
 // many, half as long, and the second resident fills the first one's top-k / gather / modulation phases
-// Tile shapes forced by the test hook omds_debug_force_tile_rows (libomds_hip_test.so, include/omds_test.h) or, in experiment
-// builds, by the environment (OMDS_TAIL_SEL_ROWS = 4 | 16 | 32, OMDS_TAIL_ROWS = 16 | 32): every shape computes the same bits, and
-// the tests say so by running them against each other.  The release library has neither: 0 = the launcher's own choice.
+// Tile shapes (4 | 16 | 32 rows) forced by the test hook omds_debug_force_tile_rows (libomds_hip_test.so, include/omds_test.h):
+// every shape computes the same bits, and the tests say so by running them against each other.  The release library has no hook:
+// 0 = the launcher's own choice.
 #ifdef OMDS_TEST_HOOKS
 static std::atomic<int> g_force_sel_rows{0}, g_force_tail_rows{0};
 void omds_force_tile_rows(int tail_sel_rows, int tail_rows) {
     g_force_sel_rows.store(tail_sel_rows);
     g_force_tail_rows.store(tail_rows);
 }
-#define OMDS_FORCED_ROWS(slot, env) ((slot).load() > 0 ? (slot).load() : OMDS_EXP_ENV(env, 0))
+#define OMDS_FORCED_ROWS(slot) (slot).load()
 #else
-#define OMDS_FORCED_ROWS(slot, env) OMDS_EXP_ENV(env, 0)
+#define OMDS_FORCED_ROWS(slot) 0
 #endif
 static int tail_sel_rows(int N, int k, bool g4_ok) {
-    const int forced = OMDS_FORCED_ROWS(g_force_sel_rows, "OMDS_TAIL_SEL_ROWS");
+    const int forced = OMDS_FORCED_ROWS(g_force_sel_rows);
     if (k > 16) return 32;
     if (forced == 4 && g4_ok && k <= 20) return 4;
     if (forced == 16 || forced == 32) return forced;
@@ -436,10 +426,7 @@ void omds_launch_tail_sel(hipStream_t s, const MlpDev& m, const float* Fp, const
     a.viol = viol;
     a.FqH = reinterpret_cast<_Float16*>(FqH);
     a.ldF = ldF;
-    a.t_begin = 0; a.t_end = st.N;
-    a.slot0 = 0; a.n_slots = 0;
-    static const int stop = OMDS_EXP_ENV("OMDS_TAIL_SEL_STOP", 0);
-    a.dbg_stop = stop;
+    a.n_slots = 0;
     a.m = m; a.Fp = Fp; a.radius = radius; a.xyzr = xyzr; a.Dmin = nullptr; a.Fq = Fq; a.FqOut = Fq; a.dscr = nullptr; a.O = O; a.st = st;
     a.rowlist = rowlist; a.range = range; a.ex = ex;
     if (m.act == OMDS_ACT_TANH) {   // derivative rows instead of masks: 16- or 32-row tiles (the 4-row-group backward is a ReLU-mask form)
@@ -466,14 +453,9 @@ static void launch_tail_a(hipStream_t s, const TailArgs& a) {
                                   (int)tail_lds_bytes(OMDS_MAX_HIDDEN + 1));
     }
     const int RW = (ROWS == 4 ? 20 : ROWS) / a.st.k;
-    hipLaunchKernelGGL((k_tail<ND, ACT, ROWS>), dim3((a.t_end - a.t_begin + RW - 1) / RW), dim3(P2_NT), tail_lds_bytes(a.m.nhh + 1), s, a);
-#ifdef OMDS_TAIL_TL
-    {
-        static int seen = 0;
-        static const int want = OMDS_EXP_ENV("OMDS_TAIL_TL_STEP", -1);
-        if (a.st.step == want && ++seen == 3) hipLaunchKernelGGL(k_tail_tl_dump, dim3(1), dim3(1), 0, s, (a.t_end - a.t_begin + RW - 1) / RW);
-    }
-#endif
+    const int grid = (a.st.N + RW - 1) / RW;
+    hipLaunchKernelGGL((k_tail<ND, ACT, ROWS>), dim3(grid), dim3(P2_NT), tail_lds_bytes(a.m.nhh + 1), s, a);
+    tail_tl_dump(s, a.st.step, grid);
 }
 
 template <int ND, int ROWS>
@@ -484,14 +466,13 @@ static void launch_tail_t(hipStream_t s, const TailArgs& a) {
 
 bool omds_tail_supported(int n_dof, int k) { return (n_dof == 7 || n_dof == 2) && k >= 1 && k <= P2_MT; }
 
-// 16-row tiles when 32-row tiles would leave most CUs without a workgroup (OMDS_TAIL_ROWS=4|16|32 forces one); g4_ok (ReLU network
-// without skip concatenations): 4-row groups, 20 rows per workgroup (k_tail<ND, ACT, 4>), while its workgroups fit the CUs in ONE
+// 16-row tiles when 32-row tiles would leave most CUs without a workgroup; g4_ok (ReLU network without skip concatenations): 4-row groups, 20 rows per workgroup (k_tail<ND, ACT, 4>), while its workgroups fit the CUs in ONE
 // round -- 5 groups x 2048 x 1.1 matrix-pipe cycles per hidden layer against 16 384 per 32-row tile.  N = 1024, k = 5: 256 workgroups,
 // one per CU, against 171 tiles of 32 rows (71.6 -> 58.4 us).  Beyond one round the 32-row tile wins: the 4-row-group kernel holds
 // the weight ring in 64 registers (134 in all: one workgroup per CU, nothing fills its top-k / modulation phases) and multiplies on
 // four of its eight waves -- N = 4096: 233 against 200 us, N = 8192: 460 against 358 (tools/tail_rows_ab.sh).
 int omds_tail_rows(int N, int k, bool g4_ok) {
-    const int forced = OMDS_FORCED_ROWS(g_force_tail_rows, "OMDS_TAIL_ROWS");
+    const int forced = OMDS_FORCED_ROWS(g_force_tail_rows);
     if (k > 16) return 32;
     if (forced == 4 && g4_ok && k <= 20) return 4;
     if (forced == 16 || forced == 32) return forced;
@@ -514,18 +495,14 @@ int omds_tail_scratch_rows(int N, int k) {
 }
 
 void omds_launch_tail(hipStream_t s, const MlpDev& m, const float* Fp, const float* radius, const float* xyzr,
-                      const float* Dmin, float* Fq, float* dscr, int O, const StepArgs& st, int t_begin, int t_end, uint16_t* FqH, int ldF,
+                      const float* Dmin, float* Fq, float* dscr, int O, const StepArgs& st, uint16_t* FqH, int ldF,
                       float* FqOut, const int* guard_range, float e_bound, unsigned* viol) {
     TailArgs a;
     a.FqH = reinterpret_cast<_Float16*>(FqH);
     a.ldF = ldF;
     const int rows = omds_tail_rows(st.N, st.k, m.act == OMDS_ACT_RELU && m.skip_mask == 0 && m.nhh >= 1);
     const int RW = (rows == 4 ? 20 : rows) / st.k;
-    a.t_begin = t_begin; a.t_end = t_end;          // t_begin must be a multiple of RW
-    a.slot0 = t_begin / RW;
     a.n_slots = (st.N + RW - 1) / RW;
-    static const int stop = OMDS_EXP_ENV("OMDS_TAIL_STOP", 0);
-    a.dbg_stop = stop;
     a.rowlist = nullptr; a.range = guard_range; a.ex = ExactOut{}; a.e_bound = e_bound; a.viol = viol;
     a.m = m; a.Fp = Fp; a.radius = radius; a.xyzr = xyzr; a.Dmin = Dmin; a.Fq = Fq; a.FqOut = FqOut ? FqOut : Fq; a.dscr = dscr; a.O = O; a.st = st;
     if (rows == 4) {

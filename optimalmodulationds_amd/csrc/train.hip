@@ -195,7 +195,7 @@ __device__ __forceinline__ void tall_wait_all() { asm volatile("s_waitcnt vmcnt(
 // what lets the HBM traffic overlap the product: vmcnt is an in-order counter per wave, so a wave that prefetches the next tile
 // and then waits for its next weight fragment (an L2 hit) waits for the prefetch too.  Every form of this kernel that streamed
 // its weights ran the traffic in series with the MFMAs and stayed at 0.60-0.65 of the peak (two workgroups per CU; persistent +
-// double-buffered; separate mover waves, which an MFMA stream starves of issue slots: EXPERIMENTS.md; tools/studies/tall_ablation.sh:
+// double-buffered; separate mover waves, which an MFMA stream starves of issue slots: EXPERIMENTS.md; profiles/r05_gemm_tall_ablation.txt:
 // the product alone 1.00 ms, with its traffic 1.33-1.53).  Per tile: the rows of tile t + 1 arrive in the other buffer by LDS-DMA
 // (8 instructions per wave, issued before the product), the parked output of tile t - 1 leaves for C (8 x (ds_read_b128 + 16-byte
 // store) per thread, masked with the stored activation for the input gradient, which is requested a tile ahead), and ONE wait for
@@ -203,7 +203,7 @@ __device__ __forceinline__ void tall_wait_all() { asm volatile("s_waitcnt vmcnt(
 // Requires K == lda == 256 (a row is exactly one 1 KB DMA piece) and a 16-byte aligned A; N <= 256 arbitrary.
 template <int EPI>
 __global__ __launch_bounds__(512, 1) void k_gemm_tall(const float* __restrict__ A, const float4* __restrict__ P, float* __restrict__ C,
-                                                      int ldc, int M, int N, const float* __restrict__ aux, int act, int ntiles, int dbg) {
+                                                      int ldc, int M, int N, const float* __restrict__ aux, int act, int ntiles) {
     extern __shared__ __attribute__((aligned(16))) float Hs[];     // [2][64][LDH]
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)reinterpret_cast<unsigned char*>(Hs);
@@ -217,7 +217,6 @@ __global__ __launch_bounds__(512, 1) void k_gemm_tall(const float* __restrict__ 
     // on the way in: LDS-DMA at 4 bytes per lane lets each lane name the element it fetches (4 instructions per row instead of 1).
     const unsigned perm_voff = 4u * (unsigned)(8 * (lane >> 3) + 2 * (lane & 3) + ((lane >> 2) & 1));   // slot `lane` of a 64-slot piece <- this k (bytes)
     auto fetch_half = [&](int tile, int buf, int p, int half) {   // half a row (2 pieces of 256 B) of tile -> LDS buffer buf; rows past M are zero-filled
-        if (OMDS_DBG(dbg) & 1) return;                    // experiment builds: no A traffic (the product runs on whatever the buffer holds)
         const int row = p * 8 + wave;
         const size_t g = (size_t)tile * TALL_ROWS + row;
         const unsigned dst = lds0 + (unsigned)(buf * TALL_BUF + row * (LDH * 4));
@@ -231,7 +230,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm_tall(const float* __restrict__ 
     auto aux_row = [&](int tile, int p) {                 // the stored activation the input gradient of `tile` is masked with
         const size_t g = (size_t)tile * TALL_ROWS + p * 8 + wave;
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (g < (size_t)M && !(OMDS_DBG(dbg) & 4)) {
+        if (g < (size_t)M) {
             const float* src = aux + g * ldc + kq;
             if (c_vec && kq + 3 < N) {
                 typedef float nt_f4 __attribute__((ext_vector_type(4)));
@@ -250,7 +249,6 @@ __global__ __launch_bounds__(512, 1) void k_gemm_tall(const float* __restrict__ 
         return *reinterpret_cast<const float4*>(Hs + buf * (TALL_ROWS * LDH) + (p * 8 + wave) * LDH + kq);
     };
     auto drain_row = [&](int tile, int p, float4 v, const float4& a) {   // parked output row of `tile` (already read: v) -> C
-        if (OMDS_DBG(dbg) & 2) return;                    // experiment builds: no C traffic
         const size_t g = (size_t)tile * TALL_ROWS + p * 8 + wave;
         if (g >= (size_t)M) return;                       // wave-uniform
         if constexpr (EPI == 2) {
@@ -709,9 +707,8 @@ template <int EPI>
 static int launch_gemm_tall(hipStream_t s, float4* pack, const float* A, int lda, const float* W, int ldw, int trans, float* C, int ldc, int M, int N, int K,
                             const float* aux, int act) {
     static std::atomic<uint64_t> configured{0};    // per device: function attributes belong to the device the kernel is loaded on
-    static const int dbg = OMDS_EXP_ENV("OMDS_TALL_DBG", 0);   // experiment builds: 1 no A traffic, 2 no C traffic, 4 no mask traffic, 8 the general kernel instead
     const int lds = 2 * TALL_BUF;
-    if ((dbg & 8) || OMDS_TRAINER_GENERAL()) return 1;
+    if (OMDS_TRAINER_GENERAL()) return 1;
     if (!pack || lda != 256 || K != 256 || (reinterpret_cast<size_t>(A) & 15)) return 1;   // the general kernel takes it
     if (omds_first_use_on_device(configured)) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_tall<0>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -720,11 +717,11 @@ static int launch_gemm_tall(hipStream_t s, float4* pack, const float* A, int lda
     }
     hipLaunchKernelGGL(k_pack256, dim3(8 * 32 * 64 / 256), dim3(256), 0, s, W, ldw, N, K, trans, pack);
     const int ntiles = (M + TALL_ROWS - 1) / TALL_ROWS;
-    hipLaunchKernelGGL((k_gemm_tall<EPI>), dim3((unsigned)std::min(ntiles, omds_cu_count())), dim3(512), lds, s, A, pack, C, ldc, M, N, aux, act, ntiles, dbg);
+    hipLaunchKernelGGL((k_gemm_tall<EPI>), dim3((unsigned)std::min(ntiles, omds_cu_count())), dim3(512), lds, s, A, pack, C, ldc, M, N, aux, act, ntiles);
     return 0;
 }
 
-static bool thin_off() { static const int dbg = OMDS_EXP_ENV("OMDS_TALL_DBG", 0); return (dbg & 16) != 0 || OMDS_TRAINER_GENERAL(); }   // experiment builds: bit 16 = the general kernel everywhere
+static bool thin_off() { return OMDS_TRAINER_GENERAL(); }   // the test hook: the general kernel everywhere
 template <int EPI>
 static bool launch_gemm_thin(hipStream_t s, const float* A, int lda, const float* W, int ldw, int trans, float* C, int ldc, int M, int N, int K,
                              const float* aux, int act) {

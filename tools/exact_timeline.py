@@ -8,8 +8,6 @@ usage: python tools/exact_timeline.py [rollouts]
 import ctypes as C
 import os, sys
 import numpy as np
-os.environ.setdefault("OMDS_SCREEN_AUDIT", "0")
-os.environ.setdefault("OMDS_SCREEN_SWEEP", "0")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import optimalmodulationds_amd._lib as L
@@ -23,6 +21,7 @@ z = np.load(os.path.join(ROOT, "tests", "golden", "weights", "franka.npz"))
 W = [z[f"W{i}"] for i in range(5)]; b = [z[f"b{i}"] for i in range(5)]
 obs, q0, qf = scenes.shelf_scene(), scenes.FRANKA_Q0, scenes.FRANKA_QF
 eng = Engine(7, N, H, k, max_obs=max(64, obs.shape[0]))
+eng.set_screening_audit(0); eng.set_screening_sweep(0)
 eng.set_mlp(W, b); eng.set_obstacles(obs)
 eng.params.dt, eng.params.dst_thr, eng.params.ignored_links = 0.5, 0.01, 0b111
 eng.push_params(); eng.set_ds(qf)
