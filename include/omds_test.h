@@ -1,6 +1,6 @@
 /*
  * omds_test.h -- test hooks of the MI355X-native MPPI rollout path.  NOT part of the product ABI: libomds_hip.so does not export
- * them.  They exist in libomds_hip_test.so (`make test-lib`: the same objects except capi, tail_kernel and train, which are compiled
+ * them.  They exist in libomds_hip_test.so (`make test-lib`: the same objects except mlp_pack, screening, tail_kernel and train, which are compiled
  * with -DOMDS_TEST_HOOKS; the sin / cos hooks live beside k_encode in train.hip), which tests/ load explicitly
  * (optimalmodulationds_amd._lib.load_test_hooks()).  Neither library reads experiment environment variables.
  */
@@ -29,8 +29,9 @@ OMDS_API int omds_debug_force_tile_rows(int tail_sel_rows, int tail_rows);
 OMDS_API int omds_debug_trainer_general_gemm(int on);
 /* The HOST half of omds_set_mlp_ex alone: argument validation, zero-padding to the kernels' width and every MFMA fragment pack
  * (fp32 forward / backward, 16-row, 4-row-group, fp16 screening slices), with no device and no context -- the sanitizer build
- * (`make asan`) runs it on the CPU (tests/test_asan_cpu.py).  *checksum = FNV-1a over all packs, *bytes = their total size (NULL =
- * skip); the message of a failure through omds_last_error(NULL).                                                          */
+ * (`make asan`) runs it on the CPU (tests/test_asan_cpu.py).  *checksum = FNV-1a over ALL packs -- the screening pack, every pack
+ * omds_set_mlp_ex uploads (one table serves both, MlpPacks::for_each_pack), and the screening pack again in a reversed unit order
+ * -- *bytes = their total size (NULL = skip); the message of a failure through omds_last_error(NULL).                       */
 OMDS_API int omds_test_pack_mlp(int n_dof, int n_linear, const int32_t* in_dims, const int32_t* out_dims, const float* const* W,
                                 const float* const* b, int act, float out_div, int n_skips, const int32_t* skip_after,
                                 uint64_t* checksum, int64_t* bytes);

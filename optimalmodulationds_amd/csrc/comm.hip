@@ -105,8 +105,8 @@ thread_local std::string g_comm_err;
 
 void omds_comm_release(omds_ctx* ctx) {
     if (ctx->comm) { (void)rccl().CommDestroy(static_cast<ncclComm_t>(ctx->comm)); ctx->comm = nullptr; }
-    if (ctx->d_gather) { (void)hipFree(ctx->d_gather); ctx->d_gather = nullptr; }
-    if (ctx->h_gather) { (void)hipHostFree(ctx->h_gather); ctx->h_gather = nullptr; }
+    ctx->d_gather.reset();
+    ctx->h_gather.reset();
     ctx->comm_rank = 0;
     ctx->comm_world = 1;
 }
@@ -145,9 +145,8 @@ int omds_comm_init_rank(omds_ctx* ctx, const uint8_t* id128, int rank, int world
     ctx->comm = comm;
     ctx->comm_rank = rank;
     ctx->comm_world = world;
-    const size_t gb = (size_t)world * (1 + OMDS_MAX_DOF) * sizeof(float);
-    CK(hipMalloc(&ctx->d_gather, gb));
-    CK(hipHostMalloc(&ctx->h_gather, gb));
+    CK(ctx->d_gather.alloc((size_t)world * (1 + OMDS_MAX_DOF)));
+    CK(ctx->h_gather.alloc((size_t)world * (1 + OMDS_MAX_DOF)));
     return OMDS_OK;
 }
 

@@ -9,7 +9,7 @@
 
 #include "omds.h"
 
-// The library reads OMDS_SCREEN (0 | 1: the screening mode of contexts left on "auto"), OMDS_ROCTX and OMDS_RCCL_LIB from the
+// The library reads OMDS_SCREEN (0 | 1 | 2: the screening mode of contexts left on the default, -1), OMDS_ROCTX and OMDS_RCCL_LIB from the
 // environment, nothing else (tests/test_capi_cpu.py).
 
 constexpr int OMDS_WIDTH = 256;        // hidden width the MFMA kernels are specialised for
@@ -78,7 +78,7 @@ struct MlpDev {
     uint16_t* scrQ;      // [4 pieces][n_traj][8]
     uint16_t* scrP;      // [4 pieces][max_obs][8]
 #ifdef OMDS_TIMELINE
-    unsigned long long* tl;   // diagnostic build only (make TIMELINE=1): [workgroup][8] phase timestamps of k_pass1
+    unsigned long long* tl;   // diagnostic build only (make timeline): [workgroup][16] phase timestamps of k_pass1
 #endif
 };
 
@@ -152,100 +152,178 @@ struct StepArgs {
     omds_params prm;
 };
 
+// Owner of one device allocation (Pinned: of one pinned host allocation).  Every d_* / h_* member of omds_ctx is one of these: a
+// buffer is freed where its owner dies or is re-allocated, nowhere else.  The frees run on whatever device is current: every
+// entry point, omds_destroy included, makes the context's device current first.
+template <typename T, bool Pinned = false>
+class DevBuf {
+    T* p_ = nullptr;
+    size_t n_ = 0;
+public:
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { reset(); }
+    void reset() {
+        if (p_) (void)(Pinned ? hipHostFree(p_) : hipFree(p_));
+        p_ = nullptr;
+        n_ = 0;
+    }
+    hipError_t alloc(size_t count) {   // count elements, contents undefined; the old allocation goes first
+        reset();
+        void* q = nullptr;
+        const hipError_t e = Pinned ? hipHostMalloc(&q, count * sizeof(T)) : hipMalloc(&q, count * sizeof(T));
+        if (e == hipSuccess) { p_ = static_cast<T*>(q); n_ = count; }
+        return e;
+    }
+    hipError_t reserve(size_t count) { return count <= n_ ? hipSuccess : alloc(count); }   // grow only, contents not kept
+    T* get() const { return p_; }
+    operator T*() const { return p_; }
+    size_t count() const { return n_; }
+    size_t bytes() const { return n_ * sizeof(T); }
+};
+template <typename T> using PinBuf = DevBuf<T, true>;
+
+// What the selection (k_select, or the flush phase of k_screen) produces per horizon step
+struct SelectSink {
+    int* rowlist = nullptr;   // [N*O] compact list of candidate rows t*O + o
+    float* listDa = nullptr;  // [N*O] their screening values (what k_exact compares its exact values with), or nullptr
+    int* range = nullptr;     // [N][4] start and length of each rollout's entries in the list, tau (float bits), unused
+    int* total = nullptr;     // number of listed rows (zeroed before the launch)
+    int k = 0;
+    float delta = 0.f;        // tau = (k-th smallest screening value) + delta
+    // AUDIT sample (DESIGN.md 4.3): a non-candidate pair is recorded when (hash(pair ^ audit_seed) & audit_mask) == 0 (mask
+    // 0xffffffff: never) as (row = (step_row0 + t) * O + o, screening value) in a list of the whole propagate;
+    // omds_launch_audit evaluates the list in fp32 against the layer-1 slabs of all horizon steps: max (Da - D) -> maxerr_bits[2]
+    unsigned audit_mask = 0xffffffffu;
+    unsigned audit_seed = 0;  // changes with every horizon step and propagate, so that over time every pair gets audited
+    int* audit_rows = nullptr;   // [audit_cap]
+    float* audit_da = nullptr;   // [audit_cap]
+    int* audit_total = nullptr;  // entries recorded so far in this propagate (may exceed audit_cap: the excess is dropped)
+    int audit_cap = 0;
+    int step_row0 = 0;        // (step - 1) * N: row of rollout 0 in the all-steps layer-1 table k_audit reads
+};
+
+// Host state of the screening controller (screening.hip: pass 1 in fp16 + exact re-selection, screen_kernel.hip): mode, bound,
+// calibration, unit order of the pack, audit sample, sweeps, verdict, statistics.  The other files go through the methods below,
+// screen_wanted / screen_calibrated, screen_begin_propagate / screen_finish_propagate / screened_verdict and the omds_screen_*
+// getters (capi_internal.h); the fields are screening.hip's.
+struct ScreenHost {
+    bool ok = false;             // packs present (a network the screening kernel takes)
+    int mode = -1;               // -1 = the library's default (off, or what OMDS_SCREEN says), 0 = off, 1 = on, 2 = on where it pays
+    float eps = 0.f;             // bound assumed on |screening value - fp32 value| of the rows that are not re-evaluated; 0 = not calibrated yet
+    bool cal = false;
+    bool eps_fixed = false;      // eps given by the caller (omds_set_screening(mode, eps > 0)): never recalibrated
+    bool suspended = false;      // three propagates in a row fell back to fp32: the fp32 step until the next calibration
+    int consec = 0;              // consecutive fallbacks
+    std::vector<float> obs_cal;  // the obstacle set the bound was calibrated against (scene_changed compares)
+    // statistics
+    double rows = 0.0, steps = 0.0, audit_rows = 0.0;   // since the last omds_prof_reset: candidate rows, (rollout, step)s, audit rows
+    long long fallbacks = 0;     // since creation
+    long long fb_error = 0, fb_slack = 0, fb_overflow = 0;   // ... by what tripped them (omds_screen_fallback_stats)
+    long long suspensions = 0;   // times three fallbacks in a row (or a non-finite error) suspended screening
+    long long recals = 0;        // calibrations run since creation
+    float err_seen = 0.f;        // largest |Da - D| seen on candidates since the last calibration
+    float audit_err_seen = 0.f;  // largest Da - D seen on audit rows since the last calibration
+    float sweep_err_seen = 0.f;  // largest |Da - D| a sweep saw since the last calibration
+    // Unit order of the screening pack (mlp_pack.hip: build_screen_pack, screening.hip: screen_reorder).  k_screen skips the k-chunks
+    // whose 16 units are zero for all 32 pairs of a wave; which units fire depends on the trained weights (a third of the shipped
+    // network's never do), so every calibration first sorts the hidden units by how often they fire on a uniform sample of its
+    // batch's pairs.
+    std::vector<std::vector<float>> W, b;   // the network, zero-padded to width 256 (host copy for building the pack again)
+    std::vector<int32_t> out_dims;
+    bool reorder_pending = false;  // set by a calibration: the order is refined behind the next accepted propagate, on its rollouts' states
+    long long reorders = 0;
+    DevBuf<int> d_tmp;           // [8] device words of screen_reorder: error words of its k_exact launch (unused), the list length
+    int never_fired[OMDS_MAX_HIDDEN + 1] = {0};   // per hidden level: units that fired in no row of the last reorder's sample
+    // audit sample: d_audit_rows / d_audit_da hold the same number of entries
+    int audit_one_in = 128;      // a non-candidate pair is audited with probability 1 / audit_one_in (power of two; 0 = no audit)
+    unsigned audit_counter = 0;  // feeds the audit hash: another sample every step of every propagate
+    DevBuf<int> d_audit_rows;    // audit sample of a propagate: pair rows into d_FqAll's row space, their screening values
+    DevBuf<float> d_audit_da;
+    // sweeps
+    int sweep_every = 32;        // every sweep_every-th screened propagate checks ALL pairs of its last step in fp32 (0 = never)
+    bool sweep_all_steps = false;  // ... of EVERY horizon step (soak runs: omds_set_screening_sweep(every, 1))
+    DevBuf<float> d_sweepD, d_sweepDa;   // [N*max_obs] fp32 values / screening values of the step being swept (allocated at the first sweep)
+    DevBuf<unsigned long long> d_sweep_hist;   // [OMDS_SWEEP_HIST_WORDS] accumulated statistics of every sweep since creation / the last reset
+    long long propagates = 0;    // screened propagates since creation
+    bool sweep_force_next = false;   // the screening pack was re-sorted after its bound was measured: the next screened propagate carries a sweep
+    long long sweeps = 0;        // sweeps run since creation
+    bool sweep_now = false;      // the propagate being finished carried a sweep (d_scerr[3] is valid)
+    int sweep_steps_now = 0;     // ... of this many steps
+    // the running propagate
+    DevBuf<SelectSink> d_sinks;  // [H] SelectSink of every horizon step (device copy + pinned staging)
+    PinBuf<SelectSink> h_sinks;
+    PinBuf<float> h_verdict;     // [4 + H + 2]: d_scerr, d_sctotal of the propagate being finished
+
+    // the bound is measured again at the next screened propagate
+    void forget_calibration() { cal = false; suspended = false; consec = 0; }
+    // a network is about to be installed (fused or wide): nothing measured on the old one stands
+    void reset_for_new_network() {
+        forget_calibration();
+        ok = false;
+        if (!eps_fixed) eps = 0.f;
+        W.clear(); b.clear(); out_dims.clear();
+        reorder_pending = false;
+    }
+    // the installed network has a screening pack; the padded fp32 weights stay on the host for building it again in another unit order
+    void adopt_pack(std::vector<std::vector<float>>&& W_, std::vector<std::vector<float>>&& b_, std::vector<int32_t>&& dims_) {
+        ok = true; W = std::move(W_); b = std::move(b_); out_dims = std::move(dims_);
+    }
+    void scene_changed(const float* xyzr, int n_obs);   // omds_set_obstacles: forgets the calibration when the scene left what it was measured on
+    void links_changed() { if (!eps_fixed) forget_calibration(); }   // another set of links enters the pass-1 minimum
+    void reset_stats() { rows = 0.0; steps = 0.0; audit_rows = 0.0; }   // omds_prof_reset
+};
+
 struct omds_ctx {
     omds_config cfg{};
     omds_params prm{};
     int dev = 0;
     hipStream_t stream = nullptr;
     std::string err;
-    float* h_verdict = nullptr;          // pinned [4 + H + 2]: d_scerr, d_sctotal of the propagate being finished
     // network
     bool have_mlp = false;
     MlpDev mlp{};
     WideNet wide{};              // networks with a hidden layer wider than 256 (its buffers live in mlp_allocs)
-    std::vector<void*> mlp_allocs;
+    std::vector<void*> mlp_allocs;   // owner of everything MlpDev, ScreenDev and WideNet point to (network.hip: drop_network)
     int act = OMDS_ACT_RELU;
     double f_fwd = 0.0, f_bwd = 0.0;   // algorithmic FLOPs of one network forward / backward row
     // screening (pass 1 in fp16 + exact re-selection, screen_kernel.hip)
     ScreenDev screen{};
-    bool screen_ok = false;      // packs present (ReLU network)
-    int screen_mode = -1;        // -1 = auto (on for large pair counts), 0 = off, 1 = forced on
-    float screen_eps = 0.f;      // bound assumed on |screening value - fp32 value| of the rows that are not re-evaluated; 0 = not calibrated yet
-    bool screen_cal = false;
-    int* d_rowlist = nullptr;    // [N*max_obs] candidate pairs
-    int* d_range = nullptr;      // [N][2] each rollout's range of the list
+    ScreenHost scr;
+    DevBuf<int> d_rowlist;       // [N*max_obs] candidate pairs
+    DevBuf<int> d_range;         // [N][2] each rollout's range of the list
     int ex_cap = 0;              // entries the k_exact output arrays hold (N * 32)
-    float* d_exD = nullptr;      // [ex_cap] pass-1 value / pass-2 distance / arg-min link / ReLU masks of each list entry
-    float* d_exDr = nullptr;
-    int* d_exMin = nullptr;
-    uint32_t* d_exMask = nullptr;
+    DevBuf<float> d_exD;         // [ex_cap] pass-1 value / pass-2 distance / arg-min link / ReLU masks of each list entry
+    DevBuf<float> d_exDr;
+    DevBuf<int> d_exMin;
+    DevBuf<uint32_t> d_exMask;
     // the all-fp32 step without a second forward (pass1_tile mode 6): per PAIR what k_exact leaves per candidate
-    float* d_allDr = nullptr; int* d_allMin = nullptr; uint32_t* d_allMask = nullptr;   // [all_cap], [all_cap], [all_cap][all_nhid][8]
-    long long all_cap = 0; int all_nhid = 0;
+    DevBuf<float> d_allDr; DevBuf<int> d_allMin; DevBuf<uint32_t> d_allMask;   // [pairs], [pairs], [pairs][all_nhid][8]
+    int all_nhid = 0;
     long long all_failed_pairs = -1; int all_failed_nhid = -1;   // the last request these three could not be allocated for (not retried until it changes)
-    float* d_exDeriv = nullptr;  // tanh networks: [hidden layers][ex_cap][256] activation derivatives of the list entries (allocated by omds_set_mlp)
-    int* d_sctotal = nullptr;    // [H+2]: candidate rows listed per horizon step; [H+1]: audit entries recorded in this propagate
-    int* d_audit_rows = nullptr; // [audit_cap] audit sample of a propagate: pair rows into d_FqAll's row space, their screening values
-    float* d_audit_da = nullptr;
-    int audit_cap = 0;
-    float* d_FqAll = nullptr;  // [H][N][OMDS_FROW] encoded joint inputs at the states of every horizon step (kept by a screened propagate with an audit sample)
-    unsigned* d_scerr = nullptr; // [4]: max |screening - exact| over the candidates (float bits); rollouts whose slack guard failed;
+    DevBuf<float> d_exDeriv;     // tanh networks: [hidden layers][ex_cap][256] activation derivatives of the list entries (allocated at the first screened tanh step)
+    DevBuf<int> d_sctotal;       // [H+2]: candidate rows listed per horizon step; [H+1]: audit entries recorded in this propagate
+    DevBuf<float> d_FqAll;       // [H][N][OMDS_FROW] encoded joint inputs at the states of every horizon step (kept by a screened propagate with an audit sample)
+    DevBuf<unsigned> d_scerr;    // [4]: max |screening - exact| over the candidates (float bits); rollouts whose slack guard failed;
                                  //      max (screening - exact) over the audit sample (float bits); calibration scratch
-    double screen_rows = 0.0;    // statistics since the last omds_prof_reset: candidate rows, (rollout, step)s, audit rows
-    double screen_steps = 0.0;
-    double screen_audit_rows = 0.0;
-    long long screen_fallbacks = 0;      // since creation
-    long long screen_fb_error = 0, screen_fb_slack = 0, screen_fb_overflow = 0;   // ... by what tripped them (omds_screen_fallback_stats)
-    long long screen_suspensions = 0;    // times three fallbacks in a row (or a non-finite error) suspended screening
-    long long screen_recals = 0;         // calibrations run since creation
-    // Unit order of the screening pack (capi.hip: build_screen_pack / screen_reorder).  k_screen skips the k-chunks whose 16 units are
-    // zero for all 32 pairs of a wave; which units fire depends on the trained weights (a third of the shipped network's never do),
-    // so every calibration first sorts the hidden units by how often they fire on a uniform sample of its batch's pairs.
-    std::vector<std::vector<float>> scr_W, scr_b;   // the network, zero-padded to width 256 (host copy for building the pack again)
-    std::vector<int32_t> scr_out_dims;
-    bool scr_reorder_pending = false;    // set by a calibration: the order is refined behind the next accepted propagate, on its rollouts' states
-    long long scr_reorders = 0;
-    int* d_scr_tmp = nullptr;            // [8] device words of screen_reorder: error words of its k_exact launch (unused), the list length
-    int scr_never_fired[OMDS_MAX_HIDDEN + 1] = {0};   // per hidden level: units that fired in no row of the last reorder's sample
-    float screen_err_seen = 0.f;         // largest |Da - D| seen on candidates since the last calibration
-    float screen_audit_err_seen = 0.f;   // largest Da - D seen on audit rows since the last calibration
-    bool screen_eps_fixed = false;       // eps given by the caller (omds_set_screening(mode, eps > 0)): never recalibrated
-    bool screen_suspended = false;       // three propagates in a row fell back to fp32: the fp32 step until the next calibration
-    int screen_consec = 0;               // consecutive fallbacks
-    int audit_one_in = 128;              // a non-candidate pair is audited with probability 1 / audit_one_in (power of two; 0 = no audit)
-    unsigned audit_counter = 0;          // feeds the audit hash: another sample every step of every propagate
-    int sweep_every = 32;                // every sweep_every-th screened propagate checks ALL pairs of its last step in fp32 (0 = never)
-    bool sweep_all_steps = false;        // ... of EVERY horizon step (soak runs: omds_set_screening_sweep(every, 1))
-    float* d_sweepD = nullptr;           // [N*max_obs] fp32 values / screening values of the step being swept (allocated at the first sweep)
-    float* d_sweepDa = nullptr;
-    size_t sweep_cap = 0;                // pairs the two buffers hold
-    unsigned long long* d_sweep_hist = nullptr;   // [OMDS_SWEEP_HIST_WORDS] accumulated statistics of every sweep since creation / the last reset
-    long long screen_propagates = 0;     // screened propagates since creation
-    bool sweep_force_next = false;       // the screening pack was re-sorted after its bound was measured: the next screened propagate carries a sweep
-    long long screen_sweeps = 0;         // sweeps run since creation
-    float screen_sweep_err_seen = 0.f;   // largest |Da - D| a sweep saw since the last calibration
-    bool sweep_now = false;              // the propagate being finished carried a sweep (d_scerr[3] is valid)
-    int sweep_steps_now = 0;             // ... of this many steps
-    std::vector<float> obs_cal;          // the obstacle set the bound was calibrated against (omds_set_obstacles compares)
     std::vector<float> obs_now;          // host copy of the current obstacle set
     bool have_rollouts = false;          // d_trajT holds the rollouts of a finished propagate (calibration draws states from them)
     // scene
     int n_obs = 0;
-    float* d_obs = nullptr;      // [max_obs][4]
-    float* d_Fp = nullptr;     // [max_obs][OMDS_FROW] encoded obstacle points [p, sin p, cos p] at their feature slots (the joints' slots zero)
-    uint16_t* d_FpH = nullptr;   // [4][n_obs][8] fp16 network inputs of the obstacle points for the screening kernel
-    uint16_t* d_FqH = nullptr;   // [4][batch][8] rollout states likewise
-    uint16_t* d_FqS = nullptr;   // skip-connection networks with a screening network: MlpDev::scrQ / scrP
-    uint16_t* d_FpS = nullptr;
-    float* d_listDa = nullptr;   // [N*max_obs] screening values of the candidate list (k_screen's selecting flush)
-    void* d_sinks = nullptr;     // [H] SelectSink of every horizon step of the running propagate (device copy + pinned staging)
-    void* h_sinks = nullptr;
-    float* d_radius = nullptr;   // [max_obs]
+    DevBuf<float> d_obs;         // [max_obs][4]
+    DevBuf<float> d_Fp;          // [max_obs][OMDS_FROW] encoded obstacle points [p, sin p, cos p] at their feature slots (the joints' slots zero)
+    DevBuf<uint16_t> d_FpH;      // [4][n_obs][8] fp16 network inputs of the obstacle points for the screening kernel
+    DevBuf<uint16_t> d_FqH;      // [4][batch][8] rollout states likewise
+    DevBuf<uint16_t> d_FqS;      // skip-connection networks with a screening network: MlpDev::scrQ / scrP
+    DevBuf<uint16_t> d_FpS;
+    DevBuf<float> d_listDa;      // [N*max_obs] screening values of the candidate list (k_screen's selecting flush)
+    DevBuf<float> d_radius;      // [max_obs]
     // DS / cost
     bool have_ds = false, have_cost = false;
     float qf[OMDS_MAX_DOF] = {0};
-    float* d_A = nullptr;        // [n][n] MPPI_toy nominal DS matrix (omds_set_ds_matrix), used when have_A
-    float* d_seds = nullptr;     // [G][omds_seds_stride(n)] SEDS components (omds_set_ds_seds), used when seds_G > 0
+    DevBuf<float> d_A;           // [n][n] MPPI_toy nominal DS matrix (omds_set_ds_matrix), used when have_A
+    DevBuf<float> d_seds;        // [G][omds_seds_stride(n)] SEDS components (omds_set_ds_seds), used when seds_G > 0
     int seds_G = 0;
     float seds_lin_thr = 1e-2f, seds_thr = 1e-2f;
     bool have_A = false;
@@ -253,60 +331,58 @@ struct omds_ctx {
     float dh[(OMDS_MAX_DOF + 1) * 4] = {0};
     float goal_fk[OMDS_MAX_DOF * 3] = {0};
     // rollout state, SoA (rollout index fastest)
-    float* d_trajT = nullptr;    // [H][n][N]
-    float* d_distT = nullptr;    // [H][N]
-    float* d_dotT = nullptr;     // [H][N]
-    float* d_actT = nullptr;     // [H][N]
-    float* d_normalT = nullptr;  // [H][n][N]
-    float* d_kvalT = nullptr;    // [H][Kmax][N]
-    float* d_qdotT = nullptr;    // [n][N]
-    float* d_maxact = nullptr;   // [Kmax][N] running max_h(phi*act)
-    float* d_phisum0 = nullptr;  // [Kmax] sum_h phi of local rollout 0
-    float* d_qstage = nullptr;   // [n][N] staging for dist_grad batches / per-rollout starts
+    DevBuf<float> d_trajT;       // [H][n][N]
+    DevBuf<float> d_distT;       // [H][N]
+    DevBuf<float> d_dotT;        // [H][N]
+    DevBuf<float> d_actT;        // [H][N]
+    DevBuf<float> d_normalT;     // [H][n][N]
+    DevBuf<float> d_kvalT;       // [H][Kmax][N]
+    DevBuf<float> d_qdotT;       // [n][N]
+    DevBuf<float> d_maxact;      // [Kmax][N] running max_h(phi*act)
+    DevBuf<float> d_phisum0;     // [Kmax] sum_h phi of local rollout 0
+    DevBuf<float> d_qstage;      // [n][N] staging for dist_grad batches / per-rollout starts
     // policy samples, SoA
     int n_kernels = 0;
-    float* d_muT = nullptr;      // [Kmax][n][N]
-    float* d_sigmaT = nullptr;   // [Kmax][N]
-    float* d_alphaT = nullptr;   // [Kmax][n][N]
-    float* d_means = nullptr;    // [Kmax*(2n+1)] mu_c, sigma_c, alpha_c staging
+    DevBuf<float> d_muT;         // [Kmax][n][N]
+    DevBuf<float> d_sigmaT;      // [Kmax][N]
+    DevBuf<float> d_alphaT;      // [Kmax][n][N]
+    DevBuf<float> d_means;       // [Kmax*(2n+1)] mu_c, sigma_c, alpha_c staging
     // network scratch
-    float* d_Fq = nullptr;     // [Nrows][OMDS_FROW] encoded joint states [q, sin q, cos q] at their feature slots (d_Fq, d_Dmin and d_ex* are SCRATCH between propagates: calibration and the
-    float* d_Dmin = nullptr;     // [N][max_obs]    screening pack's re-sort overwrite them after the results have been published)
-    int32_t* d_idx = nullptr;    // [N][k]
-    float* d_gradx = nullptr;    // [N*k][d]
-    float* d_drow = nullptr;     // [N*k]
-    float* d_yraw = nullptr;     // [N*k][16]
-    int32_t* d_minidx = nullptr; // [N*k]
-    float* d_dscr = nullptr;     // tanh only: [hidden layers][N*k padded to 32][256] activation derivatives
-    float* d_dist = nullptr;     // [N]
-    float* d_nngrad = nullptr;   // [N][n]
-    float* d_uev = nullptr;      // omds_weighted_update_eval scratch (first use): cost [N], maxact [Kmax][N], phisum0 [Kmax], act [N][H]
-    float* d_evalT = nullptr;    // omds_cost_eval scratch (first use): caller tensors in SoA + their cost
-    float* d_vjp_xyzr = nullptr; // omds_mlp_forward_vjp scratch (first use): per-row points, their layer-1 halves, zero radii
-    float* d_vjp_B = nullptr;
-    int vjp_cap = 0;             // rows the three hold
-    float* d_vjp_rad = nullptr;
+    DevBuf<float> d_Fq;          // [Nrows][OMDS_FROW] encoded joint states [q, sin q, cos q] at their feature slots (d_Fq, d_Dmin and d_ex* are SCRATCH between propagates: calibration and the
+    DevBuf<float> d_Dmin;        // [N][max_obs]    screening pack's re-sort overwrite them after the results have been published)
+    DevBuf<int32_t> d_idx;       // [N][k]
+    DevBuf<float> d_gradx;       // [N*k][d]
+    DevBuf<float> d_drow;        // [N*k]
+    DevBuf<float> d_yraw;        // [N*k][16]
+    DevBuf<int32_t> d_minidx;    // [N*k]
+    DevBuf<float> d_dscr;        // tanh only: [hidden layers][N*k padded to 32][256] activation derivatives
+    DevBuf<float> d_dist;        // [N]
+    DevBuf<float> d_nngrad;      // [N][n]
+    DevBuf<float> d_uev;         // omds_weighted_update_eval scratch (first use): cost [N], maxact [Kmax][N], phisum0 [Kmax], act [N][H]
+    DevBuf<float> d_evalT;       // omds_cost_eval scratch (first use): caller tensors in SoA + their cost
+    DevBuf<float> d_vjp_xyzr;    // omds_mlp_forward_vjp scratch (first use), for n_traj * n_closest rows: per-row points, their layer-1 halves, zero radii
+    DevBuf<float> d_vjp_B;
+    DevBuf<float> d_vjp_rad;
     // cost / reduction
-    float* d_cost = nullptr;     // [N]
-    float* d_w = nullptr;        // [N] unnormalised weights
-    float* d_red = nullptr;      // packed reduction buffer
-    float* h_red = nullptr;      // pinned mirror
-    float* h_in = nullptr;       // pinned staging of the small per-iteration inputs: [0, 7) q_cur, then the policy means
-    float* d_qcur = nullptr;     // [n] start state of a broadcast propagate
+    DevBuf<float> d_cost;        // [N]
+    DevBuf<float> d_w;           // [N] unnormalised weights
+    DevBuf<float> d_red;         // packed reduction buffer
+    PinBuf<float> h_red;         // pinned mirror
+    PinBuf<float> h_in;          // pinned staging of the small per-iteration inputs: [0, 7) q_cur, then the policy means
+    DevBuf<float> d_qcur;        // [n] start state of a broadcast propagate
     hipEvent_t ev_in_q = nullptr, ev_in_means = nullptr;   // the H2D copies out of h_in have executed (back-to-back calls)
     bool have_cost_vals = false;
     // kernel-candidate scratch
-    unsigned char* d_cflags = nullptr;  // [N][H]
-    int* d_ccounts = nullptr;           // [N]
-    int* d_coffsets = nullptr;          // [N+1]
+    DevBuf<unsigned char> d_cflags;  // [N][H]
+    DevBuf<int> d_ccounts;           // [N]
+    DevBuf<int> d_coffsets;          // [N+1]
     // staging
-    float* d_stage = nullptr;    // transposition staging for host copies
-    size_t stage_bytes = 0;
+    DevBuf<float> d_stage;       // transposition staging for host copies
     // multi-GPU (comm.hip): RCCL communicator of the rollout shards, nullptr = single shard
     void* comm = nullptr;        // ncclComm_t
     int comm_rank = 0, comm_world = 1;
-    float* d_gather = nullptr;   // [world][1+n] (min cost, qdot of the arg-min) of every shard
-    float* h_gather = nullptr;   // pinned mirror
+    DevBuf<float> d_gather;      // [world][1+n] (min cost, qdot of the arg-min) of every shard
+    PinBuf<float> h_gather;      // pinned mirror
     // profiling
     bool prof_on = false;
     int prof_stride = 1;         // bracket every prof_stride-th launch of the dominant kernel with events
@@ -363,7 +439,6 @@ int omds_wide_network(omds_ctx* ctx, const float* qT, int ldq, int B);
 int omds_wide_vjp(omds_ctx* ctx, const float* d_x, int rows, int seed_col = -1);
 
 // ---- launchers implemented in screen_kernel.hip -----------------------------------------------
-struct SelectSink;
 // sel != nullptr (a DEVICE pointer to the step's sink; needs omds_screen_can_select(O)): every workgroup owns whole rollouts
 // and its flush phase selects their candidates from LDS -- Dmin is not written and no k_select runs; otherwise the N x O
 // matrix goes to Dmin
@@ -396,25 +471,6 @@ struct ExactOut {
 void omds_launch_pass1_emit(hipStream_t s, const MlpDev& m, const float* Fq, const float* Fp, const float* radius,
                             int O, int B, uint32_t ignored, float* Dmin, const ExactOut& ex);
 
-// What the selection (k_select, or the flush phase of k_screen) produces per horizon step
-struct SelectSink {
-    int* rowlist = nullptr;   // [N*O] compact list of candidate rows t*O + o
-    float* listDa = nullptr;  // [N*O] their screening values (what k_exact compares its exact values with), or nullptr
-    int* range = nullptr;     // [N][4] start and length of each rollout's entries in the list, tau (float bits), unused
-    int* total = nullptr;     // number of listed rows (zeroed before the launch)
-    int k = 0;
-    float delta = 0.f;        // tau = (k-th smallest screening value) + delta
-    // AUDIT sample (DESIGN.md 4.3): a non-candidate pair is recorded when (hash(pair ^ audit_seed) & audit_mask) == 0 (mask
-    // 0xffffffff: never) as (row = (step_row0 + t) * O + o, screening value) in a list of the whole propagate;
-    // omds_launch_audit evaluates the list in fp32 against the layer-1 slabs of all horizon steps: max (Da - D) -> maxerr_bits[2]
-    unsigned audit_mask = 0xffffffffu;
-    unsigned audit_seed = 0;  // changes with every horizon step and propagate, so that over time every pair gets audited
-    int* audit_rows = nullptr;   // [audit_cap]
-    float* audit_da = nullptr;   // [audit_cap]
-    int* audit_total = nullptr;  // entries recorded so far in this propagate (may exceed audit_cap: the excess is dropped)
-    int audit_cap = 0;
-    int step_row0 = 0;        // (step - 1) * N: row of rollout 0 in the all-steps layer-1 table k_audit reads
-};
 void omds_launch_select(hipStream_t s, const float* Dmin, int B, int O, const SelectSink& sel);
 void omds_launch_audit(hipStream_t s, const MlpDev& m, const float* FqAll, const float* Fp, const float* radius, int O,
                        uint32_t ignored, const int* rows, const float* da, const int* total, int cap, unsigned* maxerr_bits);
@@ -437,8 +493,8 @@ void omds_launch_exact(hipStream_t s, const MlpDev& m, const float* Fq, const fl
 void omds_launch_modulate(hipStream_t s, const StepArgs& a);
 // fused per-step tail (tail_kernel.hip): top-k + pass 2 + blend + modulation + next-step layer-1 half
 bool omds_tail_supported(int n_dof, int k);
-int omds_tail_scratch_rows(int N, int k);
-int omds_tail_rows(int N, int k, bool g4_ok = false);   // pass-2 tile height (16 | 32; 4 = 4-row groups, only with g4_ok) for N rollouts with k closest obstacles   // rows of the tanh-derivative scratch the tail may touch (either tile height)
+int omds_tail_scratch_rows(int N, int k);   // rows of the tanh-derivative scratch the tail may touch (either tile height)
+int omds_tail_rows(int N, int k, bool g4_ok = false);   // pass-2 tile height (16 | 32; 4 = 4-row groups, only with g4_ok) for N rollouts with k closest obstacles
 // FqOut: where the next step's encoded joint inputs go (nullptr: in place).  guard_range / e_bound / viol: screened tanh step --
 // Dmin holds exact values on the candidates and screening values elsewhere; the tail counts the rollouts whose k-th smallest
 // value is not e_bound below k_select's tau (range[4 t + 2]) into *viol

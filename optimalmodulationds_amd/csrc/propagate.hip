@@ -1,0 +1,317 @@
+// The propagate step: which launch sequence a context runs per horizon step (choose_route), the sequences themselves, and
+// omds_propagate / omds_get_rollouts / omds_get_rollout_rows.  Nothing of the screening controller lives here: the screened
+// routes get their plan from screen_begin_propagate and hand what they measured to screen_finish_propagate (screening.hip).
+#include "capi_internal.h"
+
+// The one-launch small-scene step (step_small.hip) when the scene qualifies and the batch is small enough that the
+// two-kernel step's tail would sit on a fraction of the CUs (at R rollouts per workgroup; beyond ~3 rounds of workgroups
+// k_pass1 + the 16/32-row MFMA tail win back what the extra launch costs).
+bool small_step_wanted(omds_ctx* ctx) {
+    if (ctx->wide.on || (ctx->cfg.flags & (OMDS_FLAG_UNFUSED_STEP | OMDS_FLAG_TWO_KERNEL_STEP))) return false;
+    const int R = omds_step_small_rollouts(ctx->mlp, ctx->cfg.n_dof, ctx->n_obs, ctx->cfg.n_closest);
+    if (R <= 0) return false;
+    return (ctx->cfg.n_traj + R - 1) / R <= 768;
+}
+
+// Emit route: per PAIR what k_exact leaves per candidate (d_allDr / d_allMin / d_allMask), for n_traj * max_obs pairs.  Allocated
+// at the first use, grown when the scene or the network asks for more; a request that failed is remembered and not retried at
+// every propagate (hipMalloc / hipFree synchronise the device) until it changes.
+static bool acquire_emit_buffers(omds_ctx* ctx) {
+    const long long pairs = (long long)ctx->cfg.n_traj * ctx->cfg.max_obs;
+    const int nhid = ctx->mlp.nhh + 1;
+    const bool fits = (long long)ctx->d_allDr.count() >= pairs && ctx->all_nhid >= nhid;
+    if (fits || (ctx->all_failed_pairs == pairs && ctx->all_failed_nhid == nhid)) return fits;
+    ctx->d_allDr.reset(); ctx->d_allMin.reset(); ctx->d_allMask.reset();
+    ctx->all_nhid = 0;
+    const size_t mask_bytes = (size_t)pairs * nhid * 32;
+    if (mask_bytes <= ((size_t)8 << 30) && ctx->d_allDr.alloc((size_t)pairs) == hipSuccess &&
+        ctx->d_allMin.alloc((size_t)pairs) == hipSuccess && ctx->d_allMask.alloc(mask_bytes / 4) == hipSuccess) {
+        ctx->all_nhid = nhid;
+        return true;
+    }
+    (void)hipGetLastError();
+    ctx->d_allDr.reset(); ctx->d_allMin.reset(); ctx->d_allMask.reset();
+    ctx->all_failed_pairs = pairs; ctx->all_failed_nhid = nhid;
+    return false;
+}
+
+// Screened tanh step: k_exact hands 1 - h^2 of every candidate's hidden units to k_tail_sel (ExactOut::deriv), so the step has
+// the ReLU step's shape -- no matrix, no k_select, no second forward in the tail.  The buffer is allocated at the first
+// screened tanh step; if that fails (an enormous batch) the step keeps the matrix route.
+static bool acquire_deriv_buffer(omds_ctx* ctx) {
+    if (ctx->d_exDeriv) return true;
+    if (ctx->d_exDeriv.alloc((size_t)(ctx->mlp.nhh + 1) * (size_t)ctx->ex_cap * OMDS_WIDTH) == hipSuccess) return true;
+    (void)hipGetLastError();
+    return false;
+}
+
+// THE ROUTES OF A STEP.  Per horizon step a context runs exactly one of these launch sequences:
+//
+//   route         kernels per horizon step                                   when
+//   ------------  ---------------------------------------------------------  ----------------------------------------------------
+//   Unfused       enqueue_network (k_pass1, k_topk, k_pass2 -- or the wide    OMDS_FLAG_UNFUSED_STEP, an (n_dof, n_closest) the tail
+//                 network's GEMMs, or k_net_small) + k_modulate              kernels are not built for, a SEDS nominal DS (only
+//                                                                            k_modulate carries that branch), a wide network
+//   ScreenList    k_screen [+ k_select unless it selects in its flush]       screening requested and usable; ReLU network, or tanh
+//                 + k_exact + k_tail_sel                                     with the derivative hand-over buffer (d_exDeriv)
+//   ScreenMatrix  k_screen + k_select + k_exact + k_tail                     screening requested and usable; tanh network whose
+//                                                                            d_exDeriv could not be allocated
+//   SmallScene    k_step_small                                               small_step_wanted: few obstacles, few workgroups
+//   Emit          k_pass1 (emitting pass 2's forward of every pair)          ReLU network without skips, no OMDS_FLAG_TAIL_FORWARD,
+//                 + k_tail_sel (backward only)                               n_traj * n_obs <= 24 576 pairs, buffers available
+//   Dense         k_pass1 + k_tail                                           everything else
+//
+// Both screened routes add, per propagate, the sweep of a step when one is due (k_pass1 + k_screen + k_sweep_hist) and k_audit
+// behind the loop (screening.hip).  choose_route acquires the lazily allocated buffers the route it is about to pick needs, and
+// picks the next one down when they cannot be had.
+//
+// Emit: SMALL BATCHES of the all-fp32 step of a ReLU network run without a second forward: k_pass1 in its emitting mode leaves, for
+// EVERY pair, what pass 2's forward would compute for it (pass-2 distance, arg-min link, ReLU masks: the two forwards are
+// bit-identical), and k_tail_sel selects from the row of Dmin and runs the backward alone.  The chain of a step loses three
+// dependent GEMMs: integrator tick (N = 1) 0.66 -> 0.56 ms per 10-step propagate, planner defaults (N = 40) 1.02 -> 0.95.
+// Up to 24 576 pairs only: the masks cost the pass-1 epilogue 32 ballots + 64 single-lane LDS stores per wave and layer, which
+// a throughput-bound launch cannot hide (k_pass1 +18 % at 1024 x 294, the step 29.5 -> 33.3 ms: EXPERIMENTS.md B.5).
+static bool fused_step_available(const omds_ctx* ctx) {
+    return !(ctx->cfg.flags & OMDS_FLAG_UNFUSED_STEP) && omds_tail_supported(ctx->cfg.n_dof, ctx->cfg.n_closest) && ctx->seds_G == 0 && !ctx->wide.on;
+}
+
+StepRoute choose_route(omds_ctx* ctx, bool screen_requested) {
+    const int n = ctx->cfg.n_dof, k = ctx->cfg.n_closest;
+    const bool relu = ctx->mlp.act == OMDS_ACT_RELU;
+    if (!fused_step_available(ctx)) return StepRoute::Unfused;
+    if (screen_requested) return (relu || acquire_deriv_buffer(ctx)) ? StepRoute::ScreenList : StepRoute::ScreenMatrix;
+    if (small_step_wanted(ctx)) return StepRoute::SmallScene;
+    if (relu && !(ctx->cfg.flags & OMDS_FLAG_TAIL_FORWARD) && ctx->mlp.skip_mask == 0 && ctx->mlp.nhh >= 1 && omds_tail_sel_supported(n, k) &&
+        (long long)ctx->cfg.n_traj * ctx->n_obs <= 24576 && acquire_emit_buffers(ctx))
+        return StepRoute::Emit;
+    return StepRoute::Dense;
+}
+
+static int enqueue_unfused(omds_ctx* ctx, StepArgs& a) {
+    int rc;
+    for (int i = 1; i <= a.H; ++i) {   // MPPI.py:101: H network evaluations, the last velocity is not integrated
+        if ((rc = enqueue_network(ctx, ctx->d_trajT + (size_t)(i - 1) * a.n * a.N, a.N, a.N))) return rc;
+        a.step = i;
+        omds_launch_modulate(ctx->stream, a);
+    }
+    return OMDS_OK;
+}
+
+static int enqueue_small_scene(omds_ctx* ctx, StepArgs& a) {
+    const int N = a.N;
+    int rc;
+    omds_launch_rollout_features(ctx->stream, ctx->mlp, ctx->d_trajT, N, N, ctx->d_Fq, nullptr, N);
+    for (int i = 1; i <= a.H; ++i) {
+        RoctxRange r1("TAG: evaluate NN_2-5 + Modulation-propagation (fused small-scene step)");
+        a.step = i;
+        if ((rc = prof_begin(ctx))) return rc;
+        omds_launch_step_small(ctx->stream, ctx->mlp, ctx->d_Fp, ctx->d_radius, ctx->d_obs, ctx->d_Fq, ctx->n_obs,
+                               ctx->prm.ignored_links, a);
+        if ((rc = prof_end(ctx, (int64_t)N * ctx->n_obs, (double)N * ctx->n_obs * ctx->f_fwd + (double)N * a.k * ctx->f_bwd, "k_step_small"))) return rc;
+    }
+    return OMDS_OK;
+}
+
+// Two launches per step: k_pass1 over all (rollout, obstacle) pairs, then the rollout-local tail.
+// (Measured and rejected: independent rollout groups on separate HIP streams for small batches --
+// planar7_1024x32 ran 9.0 M rollout-steps/s on one stream, 7.1 / 3.3 / 2.4 M on 2 / 4 / 8 -- and a two-half
+// ping-pong for large batches with event-chained pass-1 launches so that one half's tail runs under the
+// other half's pass 1: parity-green, but the half-size launches drain twice per step, 1.00 M vs 1.03 M.)
+static int enqueue_dense(omds_ctx* ctx, StepArgs& a) {
+    const int N = a.N;
+    int rc;
+    omds_launch_rollout_features(ctx->stream, ctx->mlp, ctx->d_trajT, N, N, ctx->d_Fq, nullptr, N);
+    for (int i = 1; i <= a.H; ++i) {
+        {
+            RoctxRange r1("TAG: evaluate NN_2 (forward pass)");
+            if ((rc = prof_begin(ctx))) return rc;
+            omds_launch_pass1(ctx->stream, ctx->mlp, ctx->d_Fq, ctx->d_Fp, ctx->d_radius, ctx->n_obs, N,
+                              ctx->prm.ignored_links, ctx->d_Dmin);
+            if ((rc = prof_end(ctx, (int64_t)N * ctx->n_obs))) return rc;
+        }
+        RoctxRange r2("TAG: evaluate NN_3-5 + Modulation-propagation");
+        a.step = i;
+        omds_launch_tail(ctx->stream, ctx->mlp, ctx->d_Fp, ctx->d_radius, ctx->d_obs, ctx->d_Dmin, ctx->d_Fq,
+                         ctx->d_dscr, ctx->n_obs, a);
+    }
+    return OMDS_OK;
+}
+
+// Pass 1 leaves pass 2's forward of every pair (pass1_tile mode 6); the tail runs the top-k over the rollout's row of Dmin, takes
+// the masks of the k selected pairs and runs the backward, blend, modulation and Euler step.
+static int enqueue_emit(omds_ctx* ctx, StepArgs& a) {
+    const int N = a.N;
+    int rc;
+    const ExactOut ex_all{ctx->d_Dmin, ctx->d_allDr, ctx->d_allMin, ctx->d_allMask, (int)std::min<long long>((long long)N * ctx->n_obs, 0x7fffffffLL)};
+    omds_launch_rollout_features(ctx->stream, ctx->mlp, ctx->d_trajT, N, N, ctx->d_Fq, nullptr, N);
+    for (int i = 1; i <= a.H; ++i) {
+        {
+            RoctxRange r1("TAG: evaluate NN_2 (forward pass)");
+            if ((rc = prof_begin(ctx))) return rc;
+            omds_launch_pass1_emit(ctx->stream, ctx->mlp, ctx->d_Fq, ctx->d_Fp, ctx->d_radius, ctx->n_obs, N,
+                                   ctx->prm.ignored_links, ctx->d_Dmin, ex_all);
+            if ((rc = prof_end(ctx, (int64_t)N * ctx->n_obs))) return rc;
+        }
+        RoctxRange r2("TAG: evaluate NN_3-5 + Modulation-propagation");
+        a.step = i;
+        omds_launch_tail_sel(ctx->stream, ctx->mlp, ctx->d_Fp, ctx->d_radius, ctx->d_obs, ctx->d_Fq, ctx->n_obs, a,
+                             nullptr, nullptr, ex_all, nullptr, 0, 0.f, nullptr);   // (no window, no slack to count: viol = NULL)
+    }
+    return OMDS_OK;
+}
+
+// k_pass1 becomes k_screen (fp16) + the selection + k_exact (fp32 on the candidates only).  list_tail (ScreenList): k_exact leaves
+// what pass 2's forward would produce per list entry and k_tail_sel runs the backward only; otherwise (ScreenMatrix) k_exact
+// patches the matrix and k_tail runs as in the dense step, guarded by the selection's tau.
+static int enqueue_screened(omds_ctx* ctx, StepArgs& a, bool list_tail) {
+    const int N = a.N, H = a.H;
+    int rc;
+    ScreenPlan p;
+    if ((rc = screen_begin_propagate(ctx, a, list_tail, &p))) return rc;
+    omds_launch_rollout_features(ctx->stream, ctx->mlp, ctx->d_trajT, N, N, p.fq0, ctx->d_FqH, N);
+    for (int i = 1; i <= H; ++i) {
+        float* fq_i = p.fq0 + (size_t)(i - 1) * p.fq_slab;
+        float* fq_next = p.fq0 + (size_t)std::min(i, H - 1) * p.fq_slab;
+        {
+            RoctxRange r1("TAG: evaluate NN_2 (forward pass)");
+            if ((rc = prof_begin(ctx))) return rc;
+            omds_launch_screen(ctx->stream, ctx->screen, ctx->mlp, ctx->d_FqH, ctx->cfg.n_traj, ctx->d_FpH, ctx->cfg.max_obs, ctx->d_radius, ctx->n_obs, N,
+                               ctx->prm.ignored_links, ctx->d_Dmin, p.fuse_select ? p.d_sinks + (i - 1) : nullptr);
+            if ((rc = prof_end(ctx, (int64_t)N * ctx->n_obs, -1.0, "k_screen"))) return rc;
+            if (!p.fuse_select) omds_launch_select(ctx->stream, ctx->d_Dmin, N, ctx->n_obs, p.h_sinks[i - 1]);
+            omds_launch_exact(ctx->stream, ctx->mlp, fq_i, ctx->d_Fp, ctx->d_radius, ctx->n_obs, N,
+                              ctx->prm.ignored_links, ctx->d_Dmin, ctx->d_rowlist, p.h_sinks[i - 1].total, ctx->d_scerr, p.ex);
+        }
+        enqueue_sweep_of_step(ctx, fq_i, N, i);
+        RoctxRange r2("TAG: evaluate NN_3-5 + Modulation-propagation");
+        a.step = i;
+        if (list_tail)
+            omds_launch_tail_sel(ctx->stream, ctx->mlp, ctx->d_Fp, ctx->d_radius, ctx->d_obs, fq_next, ctx->n_obs, a,
+                                 ctx->d_rowlist, ctx->d_range, p.ex, ctx->d_FqH, N, p.eps, ctx->d_scerr + 1);
+        else
+            omds_launch_tail(ctx->stream, ctx->mlp, ctx->d_Fp, ctx->d_radius, ctx->d_obs, ctx->d_Dmin, fq_i,
+                             ctx->d_dscr, ctx->n_obs, a, ctx->d_FqH, N, fq_next, ctx->d_range, p.eps, ctx->d_scerr + 1);
+    }
+    return screen_finish_propagate(ctx, p);
+}
+
+int enqueue_rollouts(omds_ctx* ctx, StepArgs& a, StepRoute route) {
+    switch (route) {
+        case StepRoute::Unfused: return enqueue_unfused(ctx, a);
+        case StepRoute::SmallScene: return enqueue_small_scene(ctx, a);
+        case StepRoute::Dense: return enqueue_dense(ctx, a);
+        case StepRoute::Emit: return enqueue_emit(ctx, a);
+        case StepRoute::ScreenList: return enqueue_screened(ctx, a, true);
+        case StepRoute::ScreenMatrix: return enqueue_screened(ctx, a, false);
+    }
+    return OMDS_ERR_INVALID_ARG;
+}
+
+extern "C" {
+
+int omds_propagate(omds_ctx* ctx, const float* q_cur, int per_rollout) {
+    RoctxRange range("TAG: general propagation");
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    REQUIRE(q_cur, OMDS_ERR_INVALID_ARG, "omds_propagate: null q_cur");
+    int rc;
+    if ((rc = check_ready(ctx, true))) return rc;
+    CK(hipSetDevice(ctx->dev));
+    const int N = ctx->cfg.n_traj, H = ctx->cfg.horizon, n = ctx->cfg.n_dof;
+    // all_traj[:, 0, :] = q_cur  (MPPI.py:99)
+    if (per_rollout) {
+        CK(hipMemcpyAsync(ctx->d_stage, q_cur, (size_t)N * n * 4, hipMemcpyHostToDevice, ctx->stream));
+        omds_launch_transpose(ctx->stream, ctx->d_stage, ctx->d_trajT, N, n);
+        CK(hipStreamSynchronize(ctx->stream));  // q_cur is caller memory
+    } else {
+        // pinned staging + a device slot of its own (d_qcur): no synchronisation, and the policy means that k_sample may not
+        // have consumed yet (d_means) stay untouched
+        CK(hipEventSynchronize(ctx->ev_in_q));
+        std::memcpy(ctx->h_in, q_cur, (size_t)n * 4);
+        CK(hipMemcpyAsync(ctx->d_qcur, ctx->h_in, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+        CK(hipEventRecord(ctx->ev_in_q, ctx->stream));
+        omds_launch_broadcast_q(ctx->stream, ctx->d_qcur, n, N, ctx->d_trajT);
+    }
+    StepArgs a{};
+    a.N = N; a.H = H; a.n = n; a.K = ctx->n_kernels; a.Kmax = ctx->cfg.n_kernel_max; a.k = ctx->cfg.n_closest; a.d = ctx->mlp.d;
+    a.trajT = ctx->d_trajT; a.distT = ctx->d_distT; a.dotT = ctx->d_dotT; a.actT = ctx->d_actT; a.normalT = ctx->d_normalT;
+    a.kvalT = ctx->d_kvalT; a.qdotT = ctx->d_qdotT; a.maxact = ctx->d_maxact; a.phisum0 = ctx->d_phisum0;
+    a.muT = ctx->d_muT; a.sigmaT = ctx->d_sigmaT; a.alphaT = ctx->d_alphaT; a.gradx = ctx->d_gradx; a.drow = ctx->d_drow;
+    std::memcpy(a.qf, ctx->qf, sizeof(a.qf));
+    a.A = ctx->have_A ? ctx->d_A.get() : nullptr;
+    a.seds = ctx->seds_G > 0 ? ctx->d_seds.get() : nullptr;
+    a.seds_G = ctx->seds_G; a.seds_lin_thr = ctx->seds_lin_thr; a.seds_thr = ctx->seds_thr;
+    a.prm = ctx->prm;
+    // screening where the context asks for it, the fused step runs and a bound stands (measured now when none does)
+    bool screen = fused_step_available(ctx) && screen_wanted(ctx);
+    if (screen && (rc = screen_calibrated(ctx, q_cur, &screen))) return rc;
+    if ((rc = enqueue_rollouts(ctx, a, choose_route(ctx, screen)))) return rc;
+    CK(hipGetLastError());
+    ctx->have_cost_vals = false;
+    CK(hipStreamSynchronize(ctx->stream));
+    ctx->have_rollouts = true;
+    if (screen && (rc = screened_verdict(ctx, a))) return rc;
+    return OMDS_OK;
+}
+
+int omds_get_rollouts(omds_ctx* ctx, float* all_traj, float* closest_dist_all, float* kernel_val_all, float* dot_products,
+                      float* kernel_activations, float* qdot, float* normal) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    CK(hipSetDevice(ctx->dev));
+    const int N = ctx->cfg.n_traj, H = ctx->cfg.horizon, n = ctx->cfg.n_dof, K = ctx->n_kernels, Km = ctx->cfg.n_kernel_max;
+    auto fetch = [&](const float* srcT, float* dst, int X, int Xld) -> int {
+        if (!dst || X == 0) return OMDS_OK;
+        omds_launch_permute_hxn_to_nhx(ctx->stream, srcT, ctx->d_stage, H, X, N, Xld);
+        CK(hipMemcpyAsync(dst, ctx->d_stage, (size_t)N * H * X * 4, hipMemcpyDeviceToHost, ctx->stream));
+        CK(hipStreamSynchronize(ctx->stream));
+        return OMDS_OK;
+    };
+    int rc;
+    if ((rc = fetch(ctx->d_trajT, all_traj, n, n))) return rc;
+    if ((rc = fetch(ctx->d_distT, closest_dist_all, 1, 1))) return rc;
+    if ((rc = fetch(ctx->d_kvalT, kernel_val_all, K, Km))) return rc;
+    if ((rc = fetch(ctx->d_dotT, dot_products, 1, 1))) return rc;
+    if ((rc = fetch(ctx->d_actT, kernel_activations, 1, 1))) return rc;
+    if ((rc = fetch(ctx->d_normalT, normal, n, n))) return rc;
+    if (qdot) {
+        omds_launch_transpose(ctx->stream, ctx->d_qdotT, ctx->d_stage, n, N);
+        CK(hipMemcpyAsync(qdot, ctx->d_stage, (size_t)N * n * 4, hipMemcpyDeviceToHost, ctx->stream));
+        CK(hipStreamSynchronize(ctx->stream));
+    }
+    return OMDS_OK;
+}
+
+// The rows of a few rollouts (reference layouts): what a planner loop reads per iteration -- the best rollout for its FK
+// payload, the rollout a new kernel's centre came from (frankaPlanner.py:147-168) -- without moving the N x H tensors.
+int omds_get_rollout_rows(omds_ctx* ctx, const int32_t* t, int count, float* all_traj, float* closest_dist_all, float* kernel_val_all,
+                          float* dot_products, float* kernel_activations, float* qdot, float* normal) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    const int N = ctx->cfg.n_traj, H = ctx->cfg.horizon, n = ctx->cfg.n_dof, K = ctx->n_kernels, Km = ctx->cfg.n_kernel_max;
+    REQUIRE(t && count >= 1 && count <= N, OMDS_ERR_INVALID_ARG, "omds_get_rollout_rows: need 1 <= count <= n_traj and a non-null index array");
+    for (int r = 0; r < count; ++r) REQUIRE(t[r] >= 0 && t[r] < N, OMDS_ERR_INVALID_ARG, "omds_get_rollout_rows: rollout index out of range");
+    REQUIRE(ctx->have_rollouts, OMDS_ERR_NOT_INITIALISED, "omds_get_rollout_rows: no rollouts yet (omds_propagate)");
+    CK(hipSetDevice(ctx->dev));
+    const size_t per = (size_t)H * (2 * n + 3 + K) + n;   // floats per rollout over all seven outputs
+    REQUIRE((per * count + count) * 4 <= ctx->d_stage.bytes(), OMDS_ERR_INVALID_ARG, "omds_get_rollout_rows: too many rollouts for the staging buffer");
+    int* d_t = reinterpret_cast<int*>(ctx->d_stage + per * count);
+    CK(hipMemcpyAsync(d_t, t, (size_t)count * 4, hipMemcpyHostToDevice, ctx->stream));
+    struct Out { const float* src; float* dst; int Hh, X, Xld; };
+    const Out outs[] = {{ctx->d_trajT, all_traj, H, n, n}, {ctx->d_distT, closest_dist_all, H, 1, 1}, {ctx->d_kvalT, kernel_val_all, H, K, Km},
+                        {ctx->d_dotT, dot_products, H, 1, 1}, {ctx->d_actT, kernel_activations, H, 1, 1}, {ctx->d_qdotT, qdot, 1, n, n},
+                        {ctx->d_normalT, normal, H, n, n}};
+    size_t off = 0, offs[7];
+    for (int i = 0; i < 7; ++i) {
+        offs[i] = off;
+        if (!outs[i].dst || outs[i].X == 0) continue;
+        omds_launch_gather_rows(ctx->stream, outs[i].src, ctx->d_stage + off, d_t, count, outs[i].Hh, outs[i].X, N, outs[i].Xld);
+        off += (size_t)count * outs[i].Hh * outs[i].X;
+    }
+    CK(hipGetLastError());
+    std::vector<float> host(off);
+    if (off) CK(hipMemcpyAsync(host.data(), ctx->d_stage, off * 4, hipMemcpyDeviceToHost, ctx->stream));
+    CK(hipStreamSynchronize(ctx->stream));
+    for (int i = 0; i < 7; ++i)
+        if (outs[i].dst && outs[i].X) std::memcpy(outs[i].dst, host.data() + offs[i], (size_t)count * outs[i].Hh * outs[i].X * 4);
+    return OMDS_OK;
+}
+
+}  // extern "C"

@@ -35,7 +35,7 @@
 //   * persistent workgroups (one per CU) loop over their tiles: the ring never drains, no refill gap between tiles.
 //   * ReLU networks: a k-chunk (16 hidden units) whose activations are zero for all 32 pairs of the wave adds nothing to any
 //     output, so its MFMAs are not issued (a ballot per tested chunk and layer, a scalar branch per MFMA of chunks 8-15).  The
-//     host orders the units of this pack by how often they fire (capi.hip: screen_reorder), which puts the units a trained
+//     host orders the units of this pack by how often they fire (screening.hip: screen_reorder), which puts the units a trained
 //     network never uses -- 300 of the shipped one's 1024 -- into whole chunks: a quarter of the MFMAs go (EXPERIMENTS.md C 4.1d).
 #include <algorithm>
 #include <cstdio>
@@ -746,7 +746,7 @@ void omds_launch_audit(hipStream_t s, const MlpDev& m, const float* FqAll, const
 }
 
 // ------------------------------------------------------------------------------------------------
-// Calibration of the screening bound on the device (capi.hip: calibrate_screen): B states -- the even ones uniform inside the
+// Calibration of the screening bound on the device (screening.hip: calibrate_screen): B states -- the even ones uniform inside the
 // joint box, the odd ones drawn from the rollouts of the last propagate (where the next rollouts will live), or scattered
 // around the start state while there are none yet -- and the largest |screening value - fp32 value| over their B x O pairs.
 // ------------------------------------------------------------------------------------------------
@@ -907,7 +907,7 @@ static void launch_screen_n(hipStream_t s, dim3 grid, size_t lds, size_t lds_max
 
 void omds_launch_screen(hipStream_t s, const ScreenDev& sd, const MlpDev& m, const uint16_t* FqH, int ldFq, const uint16_t* FpH,
                         int ldFp, const float* radius, int O, int B, uint32_t ignored, float* Dmin, const SelectSink* sel) {
-    // sel: DEVICE pointer to this step's sink (capi.hip uploads the sinks of all horizon steps before the loop)
+    // sel: DEVICE pointer to this step's sink (screening.hip uploads the sinks of all horizon steps before the loop)
     const long long total = (long long)B * O;
     if (total <= 0) return;
     ScreenArgs a;

@@ -62,7 +62,7 @@ class Engine:
         else:
             dims = np.concatenate((ins[:1], outs)).astype(np.int32)
             self._ck(self.lib.omds_set_mlp(self.h, nl, L.iptr(dims), Wp, bp, a, float(out_div)))
-        # a rejected network leaves the previous one installed (capi.hip), so the wrapper's view changes only on success
+        # a rejected network leaves the previous one installed (network.hip), so the wrapper's view changes only on success
         self.C = C_out
         self.n_hidden_levels = nl - 1
         self.d = int(ins[0]) // 3                       # raw network inputs: n + 3, or n + 2 for the toy networks
@@ -323,7 +323,7 @@ class Engine:
 
     # ---- screening of pass 1 (fp16 + exact re-selection) ----------------------------------------
     def set_screening(self, mode=-1, eps=0.0):
-        """mode: -1 auto, 0 off (fp32 pass 1), 1 on; eps > 0 fixes the error bound, 0 keeps bound and calibration
+        """mode: -1 library default (off, or `OMDS_SCREEN`), 0 off, 1 on, 2 on where it pays; eps > 0 fixes the error bound, 0 keeps bound and calibration
         (mode change only), < 0 discards the calibration (measured again at the next screened propagate)."""
         self._ck(self.lib.omds_set_screening(self.h, int(mode), float(eps)))
 

@@ -1,7 +1,8 @@
 """Host code of the library under AddressSanitizer + UBSan ("-fsanitize=address host build"), on the CPU.
 
-`make asan` instruments the translation units that hold the host logic -- capi.hip (argument validation, the MFMA pack builders of
-omds_set_mlp(_ex), omds_apply_update), comm.hip (the RCCL loader) and train.hip (the trainer's host side); device code is the release
+`make asan` instruments the translation units that hold the host logic -- the files of the C ABI (context, mlp_pack, network, screening, propagate, update, sdf_data: argument
+validation, the MFMA pack builders of omds_set_mlp(_ex), omds_apply_update), comm.hip (the RCCL loader) and train.hip (the trainer's
+host side); device code is the release
 build (GPU sanitizers are not available on this pool).  A child process with the sanitizer runtime preloaded drives everything
 that needs no GPU: the update arithmetic, the pack builders on every network layout the fixtures hold (256x4 ReLU, 128-wide, skip
 concatenation, tanh 256x3, the toy networks' planar inputs) and their error paths, context creation failing without a device,
