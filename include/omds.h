@@ -67,6 +67,9 @@ typedef struct {
 /* k_pass1 multiplies every k-chunk of every layer instead of compacting every tile to the hidden units that fire in it (the exact
  * zero-skip of ReLU networks: same bits either way); for A/B runs and the tests that compare the two                              */
 #define OMDS_FLAG_DENSE_PASS1 8
+/* pass 1 over the plain row space at every horizon step: a propagate from ONE state (per_rollout == 0) evaluates its first step
+ * for each of the N rollouts instead of once for all of them (same bits either way); for A/B runs and the tests that compare */
+#define OMDS_FLAG_NATURAL_PASS1 16
 
 /* The constants the reference hard-codes inside propagate() (MPPI.py:117-217,277) and
  * LinDS (LinDS.py:9), as parameters; omds_default_params() fills the reference values.   */

@@ -39,6 +39,7 @@ class OmdsParams(C.Structure):
 FLAG_UNFUSED_STEP = 1
 FLAG_TAIL_FORWARD = 4      # the fp32 step's tail keeps its own forward (omds.h: OMDS_FLAG_TAIL_FORWARD)
 FLAG_DENSE_PASS1 = 8       # k_pass1 multiplies every k-chunk (omds.h: OMDS_FLAG_DENSE_PASS1; same bits as the per-tile compaction)
+FLAG_NATURAL_PASS1 = 16    # first step of a propagate from one state evaluated per rollout (omds.h: OMDS_FLAG_NATURAL_PASS1; same bits)
 FLAG_TWO_KERNEL_STEP = 2   # keep few-obstacle scenes on k_pass1 + k_tail (omds.h: OMDS_FLAG_TWO_KERNEL_STEP)   # omds_config.flags
 # omds_params.variant / cost_terms bits (include/omds.h)
 VARIANT_KVAL_TIMES_ACT = 1

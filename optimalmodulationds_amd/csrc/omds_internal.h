@@ -308,6 +308,7 @@ struct omds_ctx {
     DevBuf<unsigned> d_scerr;    // [4]: max |screening - exact| over the candidates (float bits); rollouts whose slack guard failed;
                                  //      max (screening - exact) over the audit sample (float bits); calibration scratch
     std::vector<float> obs_now;          // host copy of the current obstacle set
+    bool shared_start = false;           // the propagate in flight starts every rollout at ONE state (omds_propagate, per_rollout == 0)
     bool have_rollouts = false;          // d_trajT holds the rollouts of a finished propagate (calibration draws states from them)
     // scene
     int n_obs = 0;
@@ -497,11 +498,12 @@ int omds_tail_scratch_rows(int N, int k);   // rows of the tanh-derivative scrat
 int omds_tail_rows(int N, int k, bool g4_ok = false);   // pass-2 tile height (16 | 32; 4 = 4-row groups, only with g4_ok) for N rollouts with k closest obstacles
 // FqOut: where the next step's encoded joint inputs go (nullptr: in place).  guard_range / e_bound / viol: screened tanh step --
 // Dmin holds exact values on the candidates and screening values elsewhere; the tail counts the rollouts whose k-th smallest
-// value is not e_bound below k_select's tau (range[4 t + 2]) into *viol
+// value is not e_bound below k_select's tau (range[4 t + 2]) into *viol.  shared_row: Dmin is ONE row [O] that every rollout
+// selects from (the first step of a propagate that starts all rollouts at one state)
 void omds_launch_tail(hipStream_t s, const MlpDev& m, const float* Fp, const float* radius, const float* xyzr,
                       const float* Dmin, float* Fq, float* dscr, int O, const StepArgs& st,
                       uint16_t* FqH = nullptr, int ldF = 0, float* FqOut = nullptr, const int* guard_range = nullptr,
-                      float e_bound = 0.f, unsigned* viol = nullptr);
+                      float e_bound = 0.f, unsigned* viol = nullptr, bool shared_row = false);
 // screened step's tail: top-k over the candidates k_exact evaluated + pass-2 backward on its masks + the rest of k_tail
 bool omds_tail_sel_supported(int n_dof, int k);
 int omds_cu_count();   // CUs of the current device (asked once per device)

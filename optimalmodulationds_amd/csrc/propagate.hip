@@ -59,7 +59,8 @@ static bool acquire_deriv_buffer(omds_ctx* ctx) {
 //   SmallScene    k_step_small                                               small_step_wanted: few obstacles, few workgroups
 //   Emit          k_pass1 (emitting pass 2's forward of every pair)          ReLU network without skips, no OMDS_FLAG_TAIL_FORWARD,
 //                 + k_tail_sel (backward only)                               n_traj * n_obs <= 24 576 pairs, buffers available
-//   Dense         k_pass1 + k_tail                                           everything else
+//   Dense         k_pass1 + k_tail                                           everything else (step 1 of a propagate from one state:
+//                                                                            k_pass1 over ONE rollout's rows, enqueue_dense)
 //
 // Both screened routes add, per propagate, the sweep of a step when one is due (k_pass1 + k_screen + k_sweep_hist) and k_audit
 // behind the loop (screening.hip).  choose_route acquires the lazily allocated buffers the route it is about to pick needs, and
@@ -121,18 +122,25 @@ static int enqueue_dense(omds_ctx* ctx, StepArgs& a) {
     const int N = a.N;
     int rc;
     omds_launch_rollout_features(ctx->stream, ctx->mlp, ctx->d_trajT, N, N, ctx->d_Fq, nullptr, N);
+    // SHARED FIRST STEP: a propagate from one state (per_rollout == 0, what every planner iteration does) holds N copies of that
+    // state at step 1, so its N x O pairs are N copies of O rows.  Pass 1 evaluates rollout 0's O rows once and every rollout's
+    // tail selects from that row of Dmin (row stride 0).  A row's chain never depends on its tile-mates and every tile shape
+    // computes the same bits, so the step's results are those of the full launch (OMDS_FLAG_NATURAL_PASS1 keeps that one).
+    const bool shared = ctx->shared_start && !(ctx->cfg.flags & OMDS_FLAG_NATURAL_PASS1);
     for (int i = 1; i <= a.H; ++i) {
+        const bool one_row = shared && i == 1;
+        const int B = one_row ? 1 : N;
         {
             RoctxRange r1("TAG: evaluate NN_2 (forward pass)");
             if ((rc = prof_begin(ctx))) return rc;
-            omds_launch_pass1(ctx->stream, ctx->mlp, ctx->d_Fq, ctx->d_Fp, ctx->d_radius, ctx->n_obs, N,
+            omds_launch_pass1(ctx->stream, ctx->mlp, ctx->d_Fq, ctx->d_Fp, ctx->d_radius, ctx->n_obs, B,
                               ctx->prm.ignored_links, ctx->d_Dmin);
-            if ((rc = prof_end(ctx, (int64_t)N * ctx->n_obs))) return rc;
+            if ((rc = prof_end(ctx, (int64_t)B * ctx->n_obs))) return rc;
         }
         RoctxRange r2("TAG: evaluate NN_3-5 + Modulation-propagation");
         a.step = i;
         omds_launch_tail(ctx->stream, ctx->mlp, ctx->d_Fp, ctx->d_radius, ctx->d_obs, ctx->d_Dmin, ctx->d_Fq,
-                         ctx->d_dscr, ctx->n_obs, a);
+                         ctx->d_dscr, ctx->n_obs, a, nullptr, 0, nullptr, nullptr, 0.f, nullptr, one_row);
     }
     return OMDS_OK;
 }
@@ -217,6 +225,7 @@ int omds_propagate(omds_ctx* ctx, const float* q_cur, int per_rollout) {
     if ((rc = check_ready(ctx, true))) return rc;
     CK(hipSetDevice(ctx->dev));
     const int N = ctx->cfg.n_traj, H = ctx->cfg.horizon, n = ctx->cfg.n_dof;
+    ctx->shared_start = per_rollout == 0;
     // all_traj[:, 0, :] = q_cur  (MPPI.py:99)
     if (per_rollout) {
         CK(hipMemcpyAsync(ctx->d_stage, q_cur, (size_t)N * n * 4, hipMemcpyHostToDevice, ctx->stream));

@@ -20,6 +20,7 @@ struct TailArgs {
     const float* radius;
     const float* xyzr;
     const float* Dmin;   // [N][O]
+    int ldD;             // row stride of Dmin: O, or 0 when every rollout reads ONE row (the shared first step of a propagate)
     float* Fq;         // [N][OMDS_FROW] encoded joint inputs, in: this step, out: next step (rows of the workgroup's own rollouts)
     float* FqOut;      // where the next step's rows go: Fq itself, or the next slab when all steps' halves are kept
     _Float16* FqH;       // next step's states as fp16 network inputs for the screening kernel (nullptr: not screening)
@@ -69,13 +70,13 @@ __global__ __launch_bounds__(P2_NT) void k_tail(TailArgs a) {
     for (int rl = wave; rl < RW; rl += 8) {
         const int t = t_base + rl;
         if (t >= N) break;
-        topk_row(a.Dmin + (size_t)t * O, O, k, lane, [&](int j, int bi) {
+        topk_row(a.Dmin + (size_t)t * a.ldD, O, k, lane, [&](int j, int bi) {
             sm.rowT[rl * k + j] = t;
             sm.rowO[rl * k + j] = bi;
             // screened step of a tanh network: the matrix holds exact values on the candidates and screening values (all above
             // tau) elsewhere; the k smallest are exact ones, and no unevaluated row can belong among them, as long as the k-th
             // stays e_bound below tau (the slack guard)
-            if (a.range && j == k - 1 && !(__builtin_bit_cast(float, a.range[4 * t + 2]) - a.Dmin[(size_t)t * O + bi] >= a.e_bound)) atomicAdd(a.viol, 1u);
+            if (a.range && j == k - 1 && !(__builtin_bit_cast(float, a.range[4 * t + 2]) - a.Dmin[(size_t)t * a.ldD + bi] >= a.e_bound)) atomicAdd(a.viol, 1u);
         });
     }
     __syncthreads();
@@ -427,7 +428,7 @@ void omds_launch_tail_sel(hipStream_t s, const MlpDev& m, const float* Fp, const
     a.FqH = reinterpret_cast<_Float16*>(FqH);
     a.ldF = ldF;
     a.n_slots = 0;
-    a.m = m; a.Fp = Fp; a.radius = radius; a.xyzr = xyzr; a.Dmin = nullptr; a.Fq = Fq; a.FqOut = Fq; a.dscr = nullptr; a.O = O; a.st = st;
+    a.m = m; a.Fp = Fp; a.radius = radius; a.xyzr = xyzr; a.Dmin = nullptr; a.ldD = O; a.Fq = Fq; a.FqOut = Fq; a.dscr = nullptr; a.O = O; a.st = st;
     a.rowlist = rowlist; a.range = range; a.ex = ex;
     if (m.act == OMDS_ACT_TANH) {   // derivative rows instead of masks: 16- or 32-row tiles (the 4-row-group backward is a ReLU-mask form)
         const int rows = tail_sel_rows(st.N, st.k, false);
@@ -496,8 +497,9 @@ int omds_tail_scratch_rows(int N, int k) {
 
 void omds_launch_tail(hipStream_t s, const MlpDev& m, const float* Fp, const float* radius, const float* xyzr,
                       const float* Dmin, float* Fq, float* dscr, int O, const StepArgs& st, uint16_t* FqH, int ldF,
-                      float* FqOut, const int* guard_range, float e_bound, unsigned* viol) {
+                      float* FqOut, const int* guard_range, float e_bound, unsigned* viol, bool shared_row) {
     TailArgs a;
+    a.ldD = shared_row ? 0 : O;
     a.FqH = reinterpret_cast<_Float16*>(FqH);
     a.ldF = ldF;
     const int rows = omds_tail_rows(st.N, st.k, m.act == OMDS_ACT_RELU && m.skip_mask == 0 && m.nhh >= 1);
