@@ -140,6 +140,34 @@ OMDS_API int omds_set_mlp_ex(omds_ctx* ctx, int n_linear, const int32_t* in_dims
 /* MPPI.update_obstacles (MPPI.py:347-350): xyzr is [O,4] spheres (x,y,z,r).  n_obs may exceed config.max_obs: the obstacle
  * buffers then grow (to twice n_obs) inside the context -- handle, network, samples, communicator and screening state stay. */
 OMDS_API int omds_set_obstacles(omds_ctx* ctx, const float* xyzr, int n_obs);
+/* THE OBSTACLE HORIZON (new work: the reference holds one self.obs for all H steps of a propagate, MPPI.py:347-350).  Step i of
+ * omds_propagate (1-based) evaluates the network at all_traj[:, i-1]; with a horizon it sees the spheres of SLAB i-1 of a table
+ * [H,O,4] instead of the current scene: collision distance, kernel-candidate search and modulation of steps 2..H then run against
+ * the scene as it is predicted for their time, not frozen at now.  Slab 0 is always the current scene, so omds_dist_grad and the
+ * other batch entry points (which keep reading it) stay consistent with step 1.  Only the distance field moves: the modulation does
+ * not subtract the obstacle's velocity.  Without a horizon nothing changes: same launches, same bits.
+ *   omds_obstacle_horizon_predict : host only (no context, no GPU), the DEFINITION of constant-velocity prediction:
+ *                           out[h][o][c] = fmaf(vel[o][c], (float)h * dt, xyzr[o][c]) for c < 3 and h >= 1 (the product one fp32
+ *                           multiply), out[0][o] = xyzr[o], out[h][o][3] = xyzr[o][3].  xyzr [O,4], vel [O,3], out [H,O,4].
+ *   omds_set_obstacle_motion : constant velocities vel [O,3] of the n_obs spheres of the last omds_set_obstacles; the table is
+ *                           built on the device by the same formula with the params.dt in force at the propagate, and built again
+ *                           when vel, dt or the network changed.  Planar-point networks (dims[0] = 3(n+2)) ignore vel[:,2] as they
+ *                           ignore z.  NULL clears the horizon.
+ *   omds_set_obstacle_horizon : the caller's own predictions xyzr_h [H,O,4] (a motion predictor, radii inflated with h: the radius
+ *                           may differ per slab).  n_obs must be the scene's and slab 0 the current scene bit for bit, else
+ *                           OMDS_ERR_INVALID_ARG.  NULL clears the horizon.
+ *   omds_get_obstacle_horizon : the table the next propagate will use (built now if it is stale) into xyzr_h [H,O,4] (NULL: no copy);
+ *                           *mode_out = 0 none (every slab is the static scene), 1 motion, 2 explicit.
+ * omds_set_obstacles CLEARS the horizon (MPPI.update_obstacles keeps its meaning); a setter before any scene is
+ * OMDS_ERR_NOT_INITIALISED.  The tables (H * max_obs * 37 floats: 2.8 MB at H = 32, 588 spheres) are allocated at the first setter and
+ * grow with the other obstacle buffers.  SCREENING: while a horizon is set omds_propagate runs the all-fp32 step whatever mode was
+ * requested -- the bound eps was calibrated on the static scene and the audit takes one scene for all steps; omds_screen_stats
+ * reports active = 0, the calibration is kept and screening resumes when the horizon is cleared.  Networks wider than 256:
+ * omds_propagate returns OMDS_ERR_UNSUPPORTED while a horizon is set.                                                              */
+OMDS_API int omds_obstacle_horizon_predict(const float* xyzr, const float* vel, int n_obs, int horizon, float dt, float* out);
+OMDS_API int omds_set_obstacle_motion(omds_ctx* ctx, const float* vel);
+OMDS_API int omds_set_obstacle_horizon(omds_ctx* ctx, const float* xyzr_h, int n_obs);
+OMDS_API int omds_get_obstacle_horizon(omds_ctx* ctx, float* xyzr_h, int32_t* mode_out);
 /* LinDS(q_goal) / MPPI.reset_DS / switch_DS_idx (LinDS.py:7-10, MPPI.py:76-84). */
 OMDS_API int omds_set_ds(omds_ctx* ctx, const float* q_goal);
 /* MPPI_toy's nominal DS (MPPI_toy.py:89-91): velocity = (q - q_goal) @ A, A [n,n] row-major, not

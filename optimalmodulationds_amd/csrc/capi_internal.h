@@ -1,5 +1,5 @@
 // Host-only declarations shared by the translation units of the C ABI (include/omds.h): context.hip, mlp_pack.hip, network.hip,
-// screening.hip, propagate.hip, update.hip and sdf_data.hip.  No kernel file includes this header.
+// screening.hip, propagate.hip, update.hip, sdf_data.hip and obstacle_horizon.hip.  No kernel file includes this header.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -148,10 +148,26 @@ int build_mlp_packs(int n, int n_linear, const int32_t* in_dims, const int32_t* 
                     const float* const* b, int act, float out_div, int n_skips, const int32_t* skip_after, MlpPacks& pk,
                     std::string& err);
 
+// ---- obstacle_horizon.hip: per-step obstacle tables of a propagate ------------------------------------------------------------
+// The three obstacle tables a launch reads: Fp [O][OMDS_FROW], radius [O], obs [O][4]
+struct ObsTables { const float* Fp; const float* radius; const float* obs; };
+// ... of horizon step `step` (1-based): slab step - 1 of the horizon while one is set, else the static scene (step 0: the static
+// scene in any case, for the batch entry points; slab 0 holds the same values)
+inline ObsTables obstacle_tables(const omds_ctx* ctx, int step = 0) {
+    if (ctx->hz_mode == 0 || step < 1) return {ctx->d_Fp, ctx->d_radius, ctx->d_obs};
+    const size_t r = (size_t)(step - 1) * ctx->hz_ld;
+    return {ctx->d_hzFp + r * OMDS_FROW, ctx->d_hzRadius + r, ctx->d_hzObs + r * 4};
+}
+int alloc_obstacle_horizon(omds_ctx* ctx);             // the tables for cfg.horizon x cfg.max_obs (first setter; grow_obstacle_capacity)
+void clear_obstacle_horizon(omds_ctx* ctx);            // omds_set_obstacles: back to the static scene
+void obstacle_horizon_network_changed(omds_ctx* ctx);  // omds_set_mlp*: the feature slabs are derived again at the next propagate
+int prepare_obstacle_horizon(omds_ctx* ctx);           // omds_propagate: rebuilds the tables when they are dirty (one launch)
+
 // ---- network.hip ------------------------------------------------------------------------------------------------------------
 void release_network(omds_ctx* ctx);   // frees omds_ctx::mlp_allocs (omds_destroy; every install starts with it)
-// the distance network on a batch of states qT [n][ldq]: Fq -> pass 1 -> top-k -> pass 2 (or the context's other arithmetic)
-int enqueue_network(omds_ctx* ctx, const float* qT, int ldq, int B);
+// the distance network on a batch of states qT [n][ldq] against the obstacle tables t: Fq -> pass 1 -> top-k -> pass 2 (or the
+// context's other arithmetic)
+int enqueue_network(omds_ctx* ctx, const float* qT, int ldq, int B, const ObsTables& t);
 
 // ---- screening.hip: the controller of the screened step -----------------------------------------------------------------------
 bool screen_wanted(omds_ctx* ctx);   // mode, packs, not suspended: this propagate should screen

@@ -1,14 +1,14 @@
 // C ABI of libomds_hip.so (include/omds.h), host side: the context's lifetime and buffers, the scene, DS, parameter, cost and
 // policy-sample setters and getters, and the measurement entry points.  The other concerns live in mlp_pack.hip (weight packs),
 // network.hip (installing and evaluating the distance network), screening.hip (the screened step's controller), propagate.hip
-// (the step's routes), update.hip (cost and the cost-weighted update) and sdf_data.hip.
+// (the step's routes), update.hip (cost and the cost-weighted update), sdf_data.hip and obstacle_horizon.hip (per-step obstacle tables).
 #include "capi_internal.h"
 
 thread_local std::string g_create_err;
 
 extern "C" {
 
-int omds_version(void) { return 501; }
+int omds_version(void) { return 502; }
 
 int omds_device_count(int32_t* count) {
     if (!count) return OMDS_ERR_INVALID_ARG;
@@ -201,9 +201,11 @@ static int grow_obstacle_capacity(omds_ctx* ctx, int n_obs) {
     // (n_obs == 0) and the next omds_set_obstacles starts the growth again (max_obs == 0) instead of touching freed buffers
     ctx->n_obs = 0;
     ctx->cfg.max_obs = 0;
-    const bool had_FpS = ctx->d_FpS != nullptr;
+    const bool had_FpS = ctx->d_FpS != nullptr, had_horizon = ctx->d_hzFp != nullptr;
     ctx->d_obs.reset(); ctx->d_Fp.reset(); ctx->d_radius.reset(); ctx->d_FpH.reset(); ctx->d_Dmin.reset();
     ctx->d_rowlist.reset(); ctx->d_listDa.reset(); ctx->d_FpS.reset();
+    ctx->d_hzVel.reset(); ctx->d_hzObs.reset(); ctx->d_hzRadius.reset(); ctx->d_hzFp.reset();
+    ctx->hz_ld = 0;
     CK(ctx->d_obs.alloc(Om * 4));
     CK(ctx->d_Fp.alloc(std::max(Om, rows2) * OMDS_FROW));
     CK(hipMemsetAsync(ctx->d_Fp, 0, std::max(Om, rows2) * OMDS_FROW * 4, ctx->stream));   // the joints' slots and the padding stay zero
@@ -232,6 +234,7 @@ static int grow_obstacle_capacity(omds_ctx* ctx, int n_obs) {
     }
     ctx->cfg.max_obs = (int)Om;
     ctx->n_obs = 0;
+    if (had_horizon) { const int rc = alloc_obstacle_horizon(ctx); if (rc) return rc; }
     return OMDS_OK;
 }
 
@@ -241,6 +244,7 @@ int omds_set_obstacles(omds_ctx* ctx, const float* xyzr, int n_obs) {
     REQUIRE(n_obs >= ctx->cfg.n_closest, OMDS_ERR_INVALID_ARG, "omds_set_obstacles: fewer obstacles than n_closest");
     CK(hipSetDevice(ctx->dev));
     int rc;
+    clear_obstacle_horizon(ctx);   // the new scene stands still until the caller says otherwise (omds_set_obstacle_motion / _horizon)
     if (n_obs > ctx->cfg.max_obs && (rc = grow_obstacle_capacity(ctx, n_obs))) return rc;
     CK(hipMemcpyAsync(ctx->d_obs, xyzr, (size_t)n_obs * 16, hipMemcpyHostToDevice, ctx->stream));
     ctx->n_obs = n_obs;

@@ -79,6 +79,36 @@ __global__ __launch_bounds__(256) void k_obstacle_features(MlpDev m, const float
     }
 }
 
+// The same tables for every slab of an obstacle horizon (omds.h: omds_set_obstacle_motion / omds_set_obstacle_horizon): row
+// h * ld + o of obsT / radiusT / FpT is obstacle o as step h + 1 of a propagate sees it.  vel != nullptr: the position is
+// xyzr + (h dt) vel, ONE fp32 product and one fmaf (slab 0: xyzr itself), the arithmetic of omds_obstacle_horizon_predict; a
+// planar-point network (po = 2) keeps z.  vel == nullptr: obsT holds the caller's spheres.  No fp16 tables: a propagate with a
+// horizon is not screened.
+__global__ __launch_bounds__(256) void k_obstacle_horizon_features(MlpDev m, const float* __restrict__ xyzr, const float* __restrict__ vel,
+                                                                   float dt, int H, int O, int ld, float* __restrict__ obsT,
+                                                                   float* __restrict__ radiusT, float* __restrict__ FpT) {
+    const int r = blockIdx.x * 64 + (threadIdx.x >> 2), c = threadIdx.x & 3, n = m.n_dof, d = m.d, po = d - n;
+    if (r >= H * O) return;
+    const int h = r / O, o = r - h * O;
+    const size_t row = (size_t)h * ld + o;
+    float p;
+    if (vel) {
+        p = xyzr[o * 4 + c];
+        if (c < po && h > 0) {
+            const float t = (float)h * dt;
+            p = fmaf(vel[o * 3 + c], t, p);
+        }
+        obsT[row * 4 + c] = p;
+    } else {
+        p = obsT[row * 4 + c];
+    }
+    if (c == 3) { radiusT[row] = p; return; }
+    if (c >= po) return;
+    FpT[row * OMDS_FROW + n + c] = p;
+    FpT[row * OMDS_FROW + d + n + c] = omds_sinf(p);
+    FpT[row * OMDS_FROW + 2 * d + n + c] = omds_cosf(p);
+}
+
 template <int MT, int MR, int NR, int ACT>
 __global__ __launch_bounds__((Geo<MT, MR, NR>::NT)) void k_pass1(MlpDev m, const float* __restrict__ Fq,
                                                                const float* __restrict__ Fp,
@@ -224,6 +254,13 @@ void omds_launch_rollout_features(hipStream_t s, const MlpDev& m, const float* q
 void omds_launch_obstacle_features(hipStream_t s, const MlpDev& m, const float* xyzr, int O, float* Fp, float* radius, uint16_t* FpH, int ldF) {
     if (O <= 0) return;
     hipLaunchKernelGGL(k_obstacle_features, dim3((O + 63) / 64), dim3(256), 0, s, m, xyzr, O, Fp, radius, reinterpret_cast<_Float16*>(FpH), ldF);
+}
+
+void omds_launch_obstacle_horizon_features(hipStream_t s, const MlpDev& m, const float* xyzr, const float* vel, float dt, int H, int O,
+                                           int ld, float* obsT, float* radiusT, float* FpT) {
+    if (H <= 0 || O <= 0) return;
+    hipLaunchKernelGGL(k_obstacle_horizon_features, dim3((unsigned)(((long long)H * O + 63) / 64)), dim3(256), 0, s, m, xyzr, vel, dt, H, O, ld,
+                       obsT, radiusT, FpT);
 }
 
 template <int MT, int MR, int NR, int ACT>

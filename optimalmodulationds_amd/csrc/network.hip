@@ -25,7 +25,7 @@ static int drop_network(omds_ctx* ctx) {
 }
 
 // ---- distance network on a batch: Fq -> pass 1 -> top-k -> pass 2 ---------------------------------
-int enqueue_network(omds_ctx* ctx, const float* qT, int ldq, int B) {
+int enqueue_network(omds_ctx* ctx, const float* qT, int ldq, int B, const ObsTables& t) {
     const MlpDev& m = ctx->mlp;
     const int O = ctx->n_obs, k = ctx->cfg.n_closest;
     if (ctx->wide.on) {   // a hidden layer wider than 256: the unfused GEMM path (wide_kernels.hip)
@@ -40,17 +40,17 @@ int enqueue_network(omds_ctx* ctx, const float* qT, int ldq, int B) {
     int rc;
     if (small_step_wanted(ctx)) {   // the arithmetic the step of this context uses: the batch entry point reproduces it bit for bit
         if ((rc = prof_begin(ctx))) return rc;
-        omds_launch_net_small(ctx->stream, m, ctx->d_Fp, ctx->d_radius, ctx->d_obs, ctx->d_Fq, O, ctx->prm.ignored_links,
+        omds_launch_net_small(ctx->stream, m, t.Fp, t.radius, t.obs, ctx->d_Fq, O, ctx->prm.ignored_links,
                               ctx->cfg.n_dof, k, qT, ldq, B, ctx->d_gradx, ctx->d_drow, ctx->d_idx, ctx->d_Dmin);
         if ((rc = prof_end(ctx, (int64_t)B * O, (double)B * O * ctx->f_fwd + (double)B * k * ctx->f_bwd, "k_step_small"))) return rc;
         CK(hipGetLastError());
         return OMDS_OK;
     }
     if ((rc = prof_begin(ctx))) return rc;
-    omds_launch_pass1(ctx->stream, m, ctx->d_Fq, ctx->d_Fp, ctx->d_radius, O, B, ctx->prm.ignored_links, ctx->d_Dmin);
+    omds_launch_pass1(ctx->stream, m, ctx->d_Fq, t.Fp, t.radius, O, B, ctx->prm.ignored_links, ctx->d_Dmin);
     if ((rc = prof_end(ctx, (int64_t)B * O))) return rc;
     omds_launch_topk(ctx->stream, ctx->d_Dmin, B, O, k, ctx->d_idx);
-    omds_launch_pass2(ctx->stream, m, ctx->d_Fq, ctx->d_Fp, ctx->d_radius, ctx->d_obs, ctx->d_idx, B, k, qT, ldq,
+    omds_launch_pass2(ctx->stream, m, ctx->d_Fq, t.Fp, t.radius, t.obs, ctx->d_idx, B, k, qT, ldq,
                       ctx->d_gradx, ctx->d_drow, nullptr, nullptr, ctx->d_dscr);
     CK(hipGetLastError());
     return OMDS_OK;
@@ -127,6 +127,7 @@ static int set_mlp_wide(omds_ctx* ctx, int n_linear, const int32_t* in_dims, con
     for (int i = 0; i < n_linear; ++i) ctx->f_fwd += 2.0 * in_dims[i] * out_dims[i];
     ctx->f_bwd = ctx->f_fwd - 2.0 * in_dims[n_linear - 1] * out_dims[n_linear - 1];
     ctx->have_mlp = true;
+    obstacle_horizon_network_changed(ctx);
     return OMDS_OK;
 }
 
@@ -210,6 +211,7 @@ int omds_set_mlp_ex(omds_ctx* ctx, int n_linear, const int32_t* in_dims, const i
     ctx->f_fwd = pk.f_fwd;
     ctx->f_bwd = pk.f_bwd;
     ctx->have_mlp = true;
+    obstacle_horizon_network_changed(ctx);
     if (ctx->n_obs > 0) {  // re-derive the obstacle half of layer 1 for the new weights
         omds_launch_obstacle_features(ctx->stream, ctx->mlp, ctx->d_obs, ctx->n_obs, ctx->d_Fp, ctx->d_radius, ctx->d_FpH, ctx->cfg.max_obs);
         CK(hipGetLastError());
@@ -228,7 +230,7 @@ int omds_dist_grad(omds_ctx* ctx, const float* q, int B, float* distance, float*
     const int n = ctx->cfg.n_dof, k = ctx->cfg.n_closest, O = ctx->n_obs, d = ctx->mlp.d;
     CK(hipMemcpyAsync(ctx->d_stage, q, (size_t)B * n * 4, hipMemcpyHostToDevice, ctx->stream));
     omds_launch_transpose(ctx->stream, ctx->d_stage, ctx->d_qstage, B, n);   // -> [n][B]
-    if ((rc = enqueue_network(ctx, ctx->d_qstage, B, B))) return rc;
+    if ((rc = enqueue_network(ctx, ctx->d_qstage, B, B, obstacle_tables(ctx)))) return rc;
     omds_launch_blend(ctx->stream, ctx->d_gradx, ctx->d_drow, B, k, d, n, ctx->prm.softmax_k, ctx->d_dist, ctx->d_nngrad);
     CK(hipGetLastError());
     if (distance) CK(hipMemcpyAsync(distance, ctx->d_dist, (size_t)B * 4, hipMemcpyDeviceToHost, ctx->stream));

@@ -1,0 +1,138 @@
+// The obstacle horizon: per-step obstacle tables of a propagate (omds.h: omds_obstacle_horizon_predict, omds_set_obstacle_motion,
+// omds_set_obstacle_horizon, omds_get_obstacle_horizon).  Step i of omds_propagate evaluates the network at all_traj[:, i - 1] and
+// reads slab i - 1 of d_hzObs / d_hzRadius / d_hzFp (obstacle_tables, capi_internal.h); slab 0 is the current scene, whose static
+// tables (d_obs / d_radius / d_Fp) every other entry point keeps using.  The tables are allocated at the first setter, grown with
+// the other obstacle buffers (context.hip), and rebuilt by ONE launch (k_obstacle_horizon_features) when the velocities, params.dt
+// or the network changed since they were built.
+#include "capi_internal.h"
+
+// slab h of a sphere moving at constant velocity: one fp32 product, one fmaf; slab 0 is the sphere itself
+static inline float moved(float x, float v, int h, float dt) {
+    if (h == 0) return x;
+    const float t = (float)h * dt;
+    return fmaf(v, t, x);
+}
+
+int alloc_obstacle_horizon(omds_ctx* ctx) {
+    const size_t H = ctx->cfg.horizon, ld = ((size_t)ctx->cfg.max_obs + 15) / 16 * 16;
+    REQUIRE(H * ld < ((size_t)1 << 31), OMDS_ERR_INVALID_ARG, "obstacle horizon: horizon * max_obs must stay below 2^31");
+    ctx->hz_ld = 0;
+    CK(ctx->d_hzVel.alloc(ld * 3));
+    CK(ctx->d_hzObs.alloc(H * ld * 4));
+    CK(ctx->d_hzRadius.alloc(H * ld));
+    CK(ctx->d_hzFp.alloc(H * ld * OMDS_FROW));
+    ctx->hz_ld = (int)ld;
+    ctx->hz_zero = true;
+    return OMDS_OK;
+}
+
+void clear_obstacle_horizon(omds_ctx* ctx) {
+    ctx->hz_mode = 0;
+    ctx->hz_dirty = false;
+    ctx->hz_vel.clear();
+    ctx->hz_table.clear();
+}
+
+void obstacle_horizon_network_changed(omds_ctx* ctx) {
+    ctx->hz_zero = true;   // the slot assignment of the encoded rows follows the network's d
+    if (ctx->hz_mode) ctx->hz_dirty = true;
+}
+
+int prepare_obstacle_horizon(omds_ctx* ctx) {
+    if (ctx->hz_mode == 0) return OMDS_OK;
+    if (ctx->hz_mode == 1 && ctx->hz_dt != ctx->prm.dt) ctx->hz_dirty = true;
+    if (!ctx->hz_dirty) return OMDS_OK;
+    REQUIRE(ctx->have_mlp, OMDS_ERR_NOT_INITIALISED, "distance network not set (omds_set_mlp)");
+    const int H = ctx->cfg.horizon, O = ctx->n_obs, ld = ctx->hz_ld;
+    if (ctx->hz_zero) {   // the joints' slots and the padding stay zero
+        CK(hipMemsetAsync(ctx->d_hzFp, 0, ctx->d_hzFp.bytes(), ctx->stream));
+        ctx->hz_zero = false;
+    }
+    const float* vel = nullptr;
+    if (ctx->hz_mode == 1) {
+        CK(hipMemcpyAsync(ctx->d_hzVel, ctx->hz_vel.data(), (size_t)O * 12, hipMemcpyHostToDevice, ctx->stream));
+        vel = ctx->d_hzVel;
+    } else {
+        CK(hipMemcpy2DAsync(ctx->d_hzObs, (size_t)ld * 16, ctx->hz_table.data(), (size_t)O * 16, (size_t)O * 16, H, hipMemcpyHostToDevice, ctx->stream));
+    }
+    omds_launch_obstacle_horizon_features(ctx->stream, ctx->mlp, ctx->d_obs, vel, ctx->prm.dt, H, O, ld, ctx->d_hzObs, ctx->d_hzRadius, ctx->d_hzFp);
+    CK(hipGetLastError());
+    CK(hipStreamSynchronize(ctx->stream));   // the copies above read pageable host memory of the context
+    ctx->hz_dt = ctx->prm.dt;
+    ctx->hz_dirty = false;
+    return OMDS_OK;
+}
+
+// what both setters need before they touch the context: a scene, and the tables
+static int horizon_ready(omds_ctx* ctx, const char* who) {
+    if (ctx->n_obs <= 0) { ctx->err = std::string(who) + ": obstacles not set (omds_set_obstacles)"; return OMDS_ERR_NOT_INITIALISED; }
+    CK(hipSetDevice(ctx->dev));
+    if (!ctx->d_hzFp || ctx->hz_ld < ctx->cfg.max_obs) {
+        CK(hipStreamSynchronize(ctx->stream));
+        return alloc_obstacle_horizon(ctx);
+    }
+    return OMDS_OK;
+}
+
+extern "C" {
+
+int omds_obstacle_horizon_predict(const float* xyzr, const float* vel, int n_obs, int horizon, float dt, float* out) {
+    if (!xyzr || !vel || !out || n_obs < 1 || horizon < 1) {
+        g_create_err = "omds_obstacle_horizon_predict: need non-null xyzr [O,4], vel [O,3], out [H,O,4] and n_obs, horizon >= 1";
+        return OMDS_ERR_INVALID_ARG;
+    }
+    for (int h = 0; h < horizon; ++h)
+        for (int o = 0; o < n_obs; ++o) {
+            float* q = out + ((size_t)h * n_obs + o) * 4;
+            for (int c = 0; c < 3; ++c) q[c] = moved(xyzr[(size_t)o * 4 + c], vel[(size_t)o * 3 + c], h, dt);
+            q[3] = xyzr[(size_t)o * 4 + 3];
+        }
+    return OMDS_OK;
+}
+
+int omds_set_obstacle_motion(omds_ctx* ctx, const float* vel) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    int rc;
+    if ((rc = horizon_ready(ctx, "omds_set_obstacle_motion"))) return rc;
+    clear_obstacle_horizon(ctx);
+    if (!vel) return OMDS_OK;
+    ctx->hz_vel.assign(vel, vel + (size_t)ctx->n_obs * 3);
+    ctx->hz_mode = 1;
+    ctx->hz_dirty = true;
+    return OMDS_OK;
+}
+
+int omds_set_obstacle_horizon(omds_ctx* ctx, const float* xyzr_h, int n_obs) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    int rc;
+    if ((rc = horizon_ready(ctx, "omds_set_obstacle_horizon"))) return rc;
+    if (!xyzr_h) { clear_obstacle_horizon(ctx); return OMDS_OK; }
+    REQUIRE(n_obs == ctx->n_obs, OMDS_ERR_INVALID_ARG, "omds_set_obstacle_horizon: n_obs differs from the scene's (omds_set_obstacles)");
+    REQUIRE(ctx->obs_now.size() == (size_t)n_obs * 4 && std::memcmp(xyzr_h, ctx->obs_now.data(), (size_t)n_obs * 16) == 0, OMDS_ERR_INVALID_ARG,
+            "omds_set_obstacle_horizon: slab 0 must be the current scene bit for bit (omds_set_obstacles)");
+    clear_obstacle_horizon(ctx);
+    ctx->hz_table.assign(xyzr_h, xyzr_h + (size_t)ctx->cfg.horizon * n_obs * 4);
+    ctx->hz_mode = 2;
+    ctx->hz_dirty = true;
+    return OMDS_OK;
+}
+
+int omds_get_obstacle_horizon(omds_ctx* ctx, float* xyzr_h, int32_t* mode_out) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    REQUIRE(ctx->n_obs > 0, OMDS_ERR_NOT_INITIALISED, "omds_get_obstacle_horizon: obstacles not set (omds_set_obstacles)");
+    const int H = ctx->cfg.horizon, O = ctx->n_obs;
+    if (mode_out) *mode_out = ctx->hz_mode;
+    if (ctx->hz_mode == 0) {   // every step sees the static scene
+        for (int h = 0; xyzr_h && h < H; ++h) std::memcpy(xyzr_h + (size_t)h * O * 4, ctx->obs_now.data(), (size_t)O * 16);
+        return OMDS_OK;
+    }
+    CK(hipSetDevice(ctx->dev));
+    int rc;
+    if ((rc = prepare_obstacle_horizon(ctx))) return rc;
+    if (!xyzr_h) return OMDS_OK;
+    CK(hipMemcpy2DAsync(xyzr_h, (size_t)O * 16, ctx->d_hzObs, (size_t)ctx->hz_ld * 16, (size_t)O * 16, H, hipMemcpyDeviceToHost, ctx->stream));
+    CK(hipStreamSynchronize(ctx->stream));
+    return OMDS_OK;
+}
+
+}  // extern "C"

@@ -320,6 +320,18 @@ struct omds_ctx {
     DevBuf<uint16_t> d_FpS;
     DevBuf<float> d_listDa;      // [N*max_obs] screening values of the candidate list (k_screen's selecting flush)
     DevBuf<float> d_radius;      // [max_obs]
+    // obstacle horizon (obstacle_horizon.hip): step i of a propagate reads slab i - 1 of these instead of d_obs / d_radius / d_Fp
+    int hz_mode = 0;             // 0 none (every step sees the static tables), 1 constant velocities, 2 the caller's table
+    bool hz_dirty = false;       // the tables do not hold what the next propagate needs (velocities, dt or the network changed)
+    bool hz_zero = false;        // d_hzFp has to be zeroed before it is written (a new allocation, or another network's slot assignment)
+    float hz_dt = 0.f;           // params.dt the motion tables were built with
+    int hz_ld = 0;               // rows per slab (max_obs rounded up to 16)
+    std::vector<float> hz_vel;   // [n_obs][3] host copy of the velocities (mode 1)
+    std::vector<float> hz_table; // [H][n_obs][4] host copy of the caller's table (mode 2)
+    DevBuf<float> d_hzVel;       // [hz_ld][3]
+    DevBuf<float> d_hzObs;       // [H][hz_ld][4]
+    DevBuf<float> d_hzRadius;    // [H][hz_ld]
+    DevBuf<float> d_hzFp;        // [H][hz_ld][OMDS_FROW]
     // DS / cost
     bool have_ds = false, have_cost = false;
     float qf[OMDS_MAX_DOF] = {0};
@@ -420,6 +432,12 @@ int omds_update_impl(omds_ctx* ctx, bool use_comm, float rate, float ker_thr, fl
 void omds_launch_rollout_features(hipStream_t s, const MlpDev& m, const float* qT, int ldq, int B, float* Fq, uint16_t* FqH = nullptr, int ldF = 0,
                                   int slab = 0);
 void omds_launch_obstacle_features(hipStream_t s, const MlpDev& m, const float* xyzr, int O, float* Fp, float* radius, uint16_t* FpH = nullptr, int ldF = 0);
+// The obstacle tables of H horizon slabs of ld rows each: obsT [H][ld][4], radiusT [H][ld], FpT [H][ld][OMDS_FROW] (zeroed once for
+// the network's d, like Fp).  vel != nullptr: slab h holds xyzr [O][4] moved by h * dt * vel [O][3] (omds.h:
+// omds_obstacle_horizon_predict; planar-point networks keep z); vel == nullptr: obsT already holds the caller's spheres and only
+// radiusT / FpT are derived from it
+void omds_launch_obstacle_horizon_features(hipStream_t s, const MlpDev& m, const float* xyzr, const float* vel, float dt, int H, int O,
+                                           int ld, float* obsT, float* radiusT, float* FpT);
 void omds_launch_pass1(hipStream_t s, const MlpDev& m, const float* Fq, const float* Fp, const float* radius,
                        int O, int B, uint32_t ignored_links, float* Dmin);
 void omds_launch_topk(hipStream_t s, const float* Dmin, int B, int O, int k, int32_t* idx);

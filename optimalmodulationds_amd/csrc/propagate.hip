@@ -91,7 +91,7 @@ StepRoute choose_route(omds_ctx* ctx, bool screen_requested) {
 static int enqueue_unfused(omds_ctx* ctx, StepArgs& a) {
     int rc;
     for (int i = 1; i <= a.H; ++i) {   // MPPI.py:101: H network evaluations, the last velocity is not integrated
-        if ((rc = enqueue_network(ctx, ctx->d_trajT + (size_t)(i - 1) * a.n * a.N, a.N, a.N))) return rc;
+        if ((rc = enqueue_network(ctx, ctx->d_trajT + (size_t)(i - 1) * a.n * a.N, a.N, a.N, obstacle_tables(ctx, i)))) return rc;
         a.step = i;
         omds_launch_modulate(ctx->stream, a);
     }
@@ -106,7 +106,8 @@ static int enqueue_small_scene(omds_ctx* ctx, StepArgs& a) {
         RoctxRange r1("TAG: evaluate NN_2-5 + Modulation-propagation (fused small-scene step)");
         a.step = i;
         if ((rc = prof_begin(ctx))) return rc;
-        omds_launch_step_small(ctx->stream, ctx->mlp, ctx->d_Fp, ctx->d_radius, ctx->d_obs, ctx->d_Fq, ctx->n_obs,
+        const ObsTables t = obstacle_tables(ctx, i);
+        omds_launch_step_small(ctx->stream, ctx->mlp, t.Fp, t.radius, t.obs, ctx->d_Fq, ctx->n_obs,
                                ctx->prm.ignored_links, a);
         if ((rc = prof_end(ctx, (int64_t)N * ctx->n_obs, (double)N * ctx->n_obs * ctx->f_fwd + (double)N * a.k * ctx->f_bwd, "k_step_small"))) return rc;
     }
@@ -130,16 +131,17 @@ static int enqueue_dense(omds_ctx* ctx, StepArgs& a) {
     for (int i = 1; i <= a.H; ++i) {
         const bool one_row = shared && i == 1;
         const int B = one_row ? 1 : N;
+        const ObsTables t = obstacle_tables(ctx, i);   // slab i - 1 of an obstacle horizon; slab 0 is one scene for all rollouts
         {
             RoctxRange r1("TAG: evaluate NN_2 (forward pass)");
             if ((rc = prof_begin(ctx))) return rc;
-            omds_launch_pass1(ctx->stream, ctx->mlp, ctx->d_Fq, ctx->d_Fp, ctx->d_radius, ctx->n_obs, B,
+            omds_launch_pass1(ctx->stream, ctx->mlp, ctx->d_Fq, t.Fp, t.radius, ctx->n_obs, B,
                               ctx->prm.ignored_links, ctx->d_Dmin);
             if ((rc = prof_end(ctx, (int64_t)B * ctx->n_obs))) return rc;
         }
         RoctxRange r2("TAG: evaluate NN_3-5 + Modulation-propagation");
         a.step = i;
-        omds_launch_tail(ctx->stream, ctx->mlp, ctx->d_Fp, ctx->d_radius, ctx->d_obs, ctx->d_Dmin, ctx->d_Fq,
+        omds_launch_tail(ctx->stream, ctx->mlp, t.Fp, t.radius, t.obs, ctx->d_Dmin, ctx->d_Fq,
                          ctx->d_dscr, ctx->n_obs, a, nullptr, 0, nullptr, nullptr, 0.f, nullptr, one_row);
     }
     return OMDS_OK;
@@ -153,16 +155,17 @@ static int enqueue_emit(omds_ctx* ctx, StepArgs& a) {
     const ExactOut ex_all{ctx->d_Dmin, ctx->d_allDr, ctx->d_allMin, ctx->d_allMask, (int)std::min<long long>((long long)N * ctx->n_obs, 0x7fffffffLL)};
     omds_launch_rollout_features(ctx->stream, ctx->mlp, ctx->d_trajT, N, N, ctx->d_Fq, nullptr, N);
     for (int i = 1; i <= a.H; ++i) {
+        const ObsTables t = obstacle_tables(ctx, i);
         {
             RoctxRange r1("TAG: evaluate NN_2 (forward pass)");
             if ((rc = prof_begin(ctx))) return rc;
-            omds_launch_pass1_emit(ctx->stream, ctx->mlp, ctx->d_Fq, ctx->d_Fp, ctx->d_radius, ctx->n_obs, N,
+            omds_launch_pass1_emit(ctx->stream, ctx->mlp, ctx->d_Fq, t.Fp, t.radius, ctx->n_obs, N,
                                    ctx->prm.ignored_links, ctx->d_Dmin, ex_all);
             if ((rc = prof_end(ctx, (int64_t)N * ctx->n_obs))) return rc;
         }
         RoctxRange r2("TAG: evaluate NN_3-5 + Modulation-propagation");
         a.step = i;
-        omds_launch_tail_sel(ctx->stream, ctx->mlp, ctx->d_Fp, ctx->d_radius, ctx->d_obs, ctx->d_Fq, ctx->n_obs, a,
+        omds_launch_tail_sel(ctx->stream, ctx->mlp, t.Fp, t.radius, t.obs, ctx->d_Fq, ctx->n_obs, a,
                              nullptr, nullptr, ex_all, nullptr, 0, 0.f, nullptr);   // (no window, no slack to count: viol = NULL)
     }
     return OMDS_OK;
@@ -223,7 +226,10 @@ int omds_propagate(omds_ctx* ctx, const float* q_cur, int per_rollout) {
     REQUIRE(q_cur, OMDS_ERR_INVALID_ARG, "omds_propagate: null q_cur");
     int rc;
     if ((rc = check_ready(ctx, true))) return rc;
+    REQUIRE(!(ctx->hz_mode && ctx->wide.on), OMDS_ERR_UNSUPPORTED,
+            "omds_propagate: an obstacle horizon is not supported on networks wider than 256 (clear it: omds_set_obstacle_motion(ctx, NULL))");
     CK(hipSetDevice(ctx->dev));
+    if ((rc = prepare_obstacle_horizon(ctx))) return rc;
     const int N = ctx->cfg.n_traj, H = ctx->cfg.horizon, n = ctx->cfg.n_dof;
     ctx->shared_start = per_rollout == 0;
     // all_traj[:, 0, :] = q_cur  (MPPI.py:99)

@@ -10,6 +10,7 @@
 
 bool screen_wanted(omds_ctx* ctx) {
     if (!ctx->scr.ok || ctx->scr.suspended) return false;
+    if (ctx->hz_mode) return false;   // an obstacle horizon: the bound and k_audit are about ONE scene for all steps (omds.h)
     int mode = ctx->scr.mode;
     if (mode < 0) {   // the library's default: the all-fp32 step -- screening is OPT-IN (omds.h); OMDS_SCREEN=0|1|2 sets the default of such contexts
         static int env = -2;

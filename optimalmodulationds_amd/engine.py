@@ -74,6 +74,37 @@ class Engine:
         self.n_obs = obs.shape[0]
         self.max_obs = max(self.max_obs, self.n_obs)
 
+    # ---- obstacle horizon: step i of a propagate sees slab i - 1 of a table [H, O, 4] (omds.h) ---------------------------------
+    def set_obstacle_motion(self, vel):
+        """Constant velocities ``vel`` [O, 3] of the spheres of the last ``set_obstacles``: step i of ``propagate`` sees them moved by
+        (i - 1) dt vel (the table is built on the device with the ``params.dt`` in force at the propagate).  ``None`` clears it;
+        so does every ``set_obstacles``."""
+        if vel is None:
+            self._ck(self.lib.omds_set_obstacle_motion(self.h, None))
+            return
+        v = L.f32(vel).reshape(-1, 3)
+        if self.n_obs and v.shape[0] != self.n_obs:      # (no scene yet: the library says so)
+            raise ValueError(f"set_obstacle_motion: velocities must be [{self.n_obs}, 3], got {v.shape}")
+        self._ck(self.lib.omds_set_obstacle_motion(self.h, L.fptr(v)))
+
+    def set_obstacle_horizon(self, xyzr_h):
+        """The caller's own predictions ``xyzr_h`` [H, O, 4] (radii may change per slab); slab 0 must be the current scene bit for
+        bit.  ``None`` clears it; so does every ``set_obstacles``."""
+        if xyzr_h is None:
+            self._ck(self.lib.omds_set_obstacle_horizon(self.h, None, 0))
+            return
+        t = L.f32(xyzr_h)
+        if t.ndim != 3 or t.shape[0] != self.H or t.shape[2] != 4:
+            raise ValueError(f"set_obstacle_horizon: the table must be [{self.H}, O, 4], got {t.shape}")
+        self._ck(self.lib.omds_set_obstacle_horizon(self.h, L.fptr(t), t.shape[1]))
+
+    def get_obstacle_horizon(self):
+        """(table [H, O, 4] the next propagate will use, mode): mode 0 none (every slab is the static scene), 1 motion, 2 explicit."""
+        out = np.zeros((self.H, self.n_obs, 4), np.float32)
+        mode = np.zeros(1, np.int32)
+        self._ck(self.lib.omds_get_obstacle_horizon(self.h, L.fptr(out), L.iptr(mode)))
+        return out, int(mode[0])
+
     def set_ds(self, q_goal):
         q = L.f32(q_goal).reshape(self.n)
         self._ck(self.lib.omds_set_ds(self.h, L.fptr(q)))
@@ -421,6 +452,21 @@ def _prof_read_ex(self):
 
 
 Engine.prof_read_ex = _prof_read_ex
+
+
+def predict_obstacle_horizon(obs, vel, horizon, dt):
+    """Constant-velocity prediction on the host (omds_obstacle_horizon_predict, no GPU): obs [O, 4], vel [O, 3] ->
+    [horizon, O, 4] with slab h = obs moved by (h dt) vel, radii kept.  What ``Engine.set_obstacle_motion`` builds on the device."""
+    lib = L.load()
+    o = L.f32(obs).reshape(-1, 4)
+    v = L.f32(vel).reshape(-1, 3)
+    if v.shape[0] != o.shape[0]:
+        raise ValueError(f"predict_obstacle_horizon: {o.shape[0]} obstacles but {v.shape[0]} velocities")
+    out = np.zeros((int(horizon), o.shape[0], 4), np.float32)
+    rc = lib.omds_obstacle_horizon_predict(L.fptr(o), L.fptr(v), o.shape[0], int(horizon), float(dt), L.fptr(out))
+    if rc != 0:
+        raise L.OmdsError(f"omds_obstacle_horizon_predict failed ({rc}): {lib.omds_last_error(None).decode()}")
+    return out
 
 
 def red_layout(K, n):

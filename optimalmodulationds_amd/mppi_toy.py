@@ -51,12 +51,17 @@ class MPPI(_MPPI):
         self.dst_thr = 0.1                          # MPPI_toy.py:56
         toy_params(self._engine.params)
 
-    def update_obstacles(self, obs):
+    def update_obstacles(self, obs, velocities=None):
+        """obs [O, 3] discs (x, y, r); velocities [O, 2] (planar) or None: see ``mppi.MPPI.update_obstacles``."""
         obs3 = _np(obs).reshape(-1, 3)
         obs4 = np.zeros((obs3.shape[0], 4), np.float32)
         obs4[:, :2] = obs3[:, :2]
         obs4[:, 3] = obs3[:, 2]
-        return super().update_obstacles(obs4)
+        vel3 = None
+        if velocities is not None:
+            vel3 = np.zeros((obs3.shape[0], 3), np.float32)
+            vel3[:, :2] = _np(velocities).reshape(obs3.shape[0], 2)
+        return super().update_obstacles(obs4, vel3)
 
     def _push(self):
         before = self._pushed_version
