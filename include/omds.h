@@ -144,8 +144,9 @@ OMDS_API int omds_set_obstacles(omds_ctx* ctx, const float* xyzr, int n_obs);
  * omds_propagate (1-based) evaluates the network at all_traj[:, i-1]; with a horizon it sees the spheres of SLAB i-1 of a table
  * [H,O,4] instead of the current scene: collision distance, kernel-candidate search and modulation of steps 2..H then run against
  * the scene as it is predicted for their time, not frozen at now.  Slab 0 is always the current scene, so omds_dist_grad and the
- * other batch entry points (which keep reading it) stay consistent with step 1.  Only the distance field moves: the modulation does
- * not subtract the obstacle's velocity.  Without a horizon nothing changes: same launches, same bits.
+ * other batch entry points (which keep reading it) stay consistent with step 1.  By default only the distance field moves; with
+ * omds_set_obstacle_frame the modulation also runs in the frame in which the obstacle rests (THE MOVING FRAME, below).  Without a
+ * horizon nothing changes: same launches, same bits.
  *   omds_obstacle_horizon_predict : host only (no context, no GPU), the DEFINITION of constant-velocity prediction:
  *                           out[h][o][c] = fmaf(vel[o][c], (float)h * dt, xyzr[o][c]) for c < 3 and h >= 1 (the product one fp32
  *                           multiply), out[0][o] = xyzr[o], out[h][o][3] = xyzr[o][3].  xyzr [O,4], vel [O,3], out [H,O,4].
@@ -168,6 +169,40 @@ OMDS_API int omds_obstacle_horizon_predict(const float* xyzr, const float* vel, 
 OMDS_API int omds_set_obstacle_motion(omds_ctx* ctx, const float* vel);
 OMDS_API int omds_set_obstacle_horizon(omds_ctx* ctx, const float* xyzr_h, int n_obs);
 OMDS_API int omds_get_obstacle_horizon(omds_ctx* ctx, float* xyzr_h, int32_t* mode_out);
+/* THE MOVING FRAME (new work; the standard remedy of the modulation-DS literature for moving obstacles).  M = E diag(l_nv, l_tau, ..) E^T
+ * removes the normal component of the velocity near a surface as if that surface were at rest: against a sphere that approaches, a
+ * rollout that stands still is "safe" and is hit anyway, and l_vel ("already moving away") switches the modulation off for a robot
+ * that retreats more slowly than the obstacle chases.  With the frame on and a MOTION horizon set, every step evaluates the
+ * modulation relative to the obstacle's velocity as the joints see it, and adds that velocity back.
+ *   omds_moving_frame_velocity : host only (no context, no GPU), the DEFINITION.  gradx [k,d] are the full input gradients of the k
+ *       selected rows (d = n_dof + 3, or n_dof + 2 for planar points: vel[:,2] is then not read), drow [k] their distances, vel [k,3]
+ *       the velocity of the sphere of each row.  In fp32, every fmaf one rounding, sums ascending from 0:
+ *         mx = max_j softmax_k drow_j;  s = sum_j expf(softmax_k drow_j - mx);  w_j = expf(softmax_k drow_j - mx) / s
+ *         for j ascending: g[c] = fmaf(gradx_j[c], w_j, g[c]) (c < n);  s_j = fmaf chain over a of gradx_j[n+a] vel_j[a];
+ *                          rate = fmaf(s_j, w_j, rate)
+ *         gn = sqrtf(fmaf chain of g[c] g[c]);  r = rate / gn, 0 if gn == 0 or r is not finite, else clamped to +-max_speed
+ *         qo[c] = -r * (g[c] / gn), 0 if gn == 0
+ *       rate is the rate at which the blended distance changes because the spheres move (negative: they approach); qo is the
+ *       minimum-norm joint velocity that keeps it constant.  max_speed <= 0 selects 1.
+ *   omds_set_obstacle_frame : a preference of the context, off at creation; max_speed <= 0 selects the default 1.0, the unit speed
+ *       rollout velocities are normalised to.  It survives omds_set_obstacles (which clears the horizon: the frame then has no
+ *       effect until velocities are set again).  At omds_propagate: frame off, or no horizon -- exactly the launches and bits
+ *       without it; a motion horizon -- the step below on every unscreened route (the fused kernels then run on 16- or 32-row
+ *       tiles); an explicit table -- OMDS_ERR_UNSUPPORTED (the table carries no velocities).
+ *       THE STEP: up to g, distance, normal, l_n, l_tau, the RBF policy and vnorm = |v| nothing changes.  Then v_rel = v - qo;
+ *       dot = g^ . v_rel/|v_rel| (what dot_products holds and what feeds l_vel, hence l_nv, the activation and the kernel-candidate
+ *       search); vt = v_rel + (act pol) vnorm; u = l_tau vt + ((l_nv - l_tau)(g^ . vt)) g^; s = |u| (1 where <= norm_clamp);
+ *       u = nan_to_num(u / s); in collision u coll_slow + g^ vnorm coll_repulse; u_world = u + qo; q_next = q + dt u_world, and qdot
+ *       of step 1 is u_world.  With qo = 0 every line is the arithmetic without the frame.
+ *   omds_get_obstacle_frame : the preference, its clamp, and *in_effect = 1 when the next propagate will run the step above.
+ *   omds_approach_rate : the batch form beside omds_dist_grad, on the device: rate [B] and qo [B,n] of the states q [B,n] against
+ *       the current scene (slab 0) and the motion's velocities, clamped by the frame's max_speed -- a driver's feed-forward term.
+ *       OMDS_ERR_NOT_INITIALISED without a motion horizon.                                                                        */
+OMDS_API int omds_moving_frame_velocity(int n_dof, int d, int k, const float* gradx, const float* drow, const float* vel,
+                                        float softmax_k, float max_speed, float* rate_out, float* qo_out);
+OMDS_API int omds_set_obstacle_frame(omds_ctx* ctx, int moving, float max_speed);
+OMDS_API int omds_get_obstacle_frame(omds_ctx* ctx, int32_t* moving, float* max_speed, int32_t* in_effect);
+OMDS_API int omds_approach_rate(omds_ctx* ctx, const float* q, int batch, float* rate, float* qo);
 /* LinDS(q_goal) / MPPI.reset_DS / switch_DS_idx (LinDS.py:7-10, MPPI.py:76-84). */
 OMDS_API int omds_set_ds(omds_ctx* ctx, const float* q_goal);
 /* MPPI_toy's nominal DS (MPPI_toy.py:89-91): velocity = (q - q_goal) @ A, A [n,n] row-major, not

@@ -75,6 +75,10 @@ SIGNATURES = {
     "omds_set_obstacle_motion": (C.c_int, [C.c_void_p, F32P]),
     "omds_set_obstacle_horizon": (C.c_int, [C.c_void_p, F32P, C.c_int]),
     "omds_get_obstacle_horizon": (C.c_int, [C.c_void_p, F32P, I32P]),
+    "omds_moving_frame_velocity": (C.c_int, [C.c_int, C.c_int, C.c_int, F32P, F32P, F32P, C.c_float, C.c_float, F32P, F32P]),
+    "omds_set_obstacle_frame": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
+    "omds_get_obstacle_frame": (C.c_int, [C.c_void_p, I32P, F32P, I32P]),
+    "omds_approach_rate": (C.c_int, [C.c_void_p, F32P, C.c_int, F32P, F32P]),
     "omds_set_ds": (C.c_int, [C.c_void_p, F32P]),
     "omds_set_ds_matrix": (C.c_int, [C.c_void_p, F32P, F32P]),
     "omds_set_ds_seds": (C.c_int, [C.c_void_p, F32P, C.c_int, F32P, F32P, F32P, F32P, F32P, F32P, C.c_float, C.c_float]),
@@ -159,7 +163,7 @@ TEST_HOOK_SIGNATURES = {
 }
 TEST_LIB_PATH = os.path.join(_HERE, "csrc", "libomds_hip_test.so")
 
-ABI_VERSION = 502      # omds_version() of the library this binding was written against
+ABI_VERSION = 503      # omds_version() of the library this binding was written against
 _libs = {}             # path -> bound CDLL
 
 

@@ -244,8 +244,49 @@ __global__ __launch_bounds__(256) void k_blend(const float* __restrict__ gradx, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// the moving frame's two quantities, standalone form for omds_approach_rate (omds.h: omds_moving_frame_velocity; the arithmetic
+// of modulate_core<.., FRAME = true>, step_device.h)
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_approach_rate(const float* __restrict__ gradx, const float* __restrict__ drow,
+                                                       const int32_t* __restrict__ idx, const float* __restrict__ vel, int ldv, int B,
+                                                       int k, int d, int n, float softmax_k, float max_speed,
+                                                       float* __restrict__ rate_out, float* __restrict__ qo_out) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= B) return;
+    float mx = -__builtin_inff();
+    for (int j = 0; j < k; ++j) mx = fmaxf(mx, softmax_k * drow[t * k + j]);
+    float s = 0.f;
+    for (int j = 0; j < k; ++j) s += expf(softmax_k * drow[t * k + j] - mx);
+    float g[OMDS_MAX_DOF], rate = 0.f, gn2 = 0.f;
+    for (int c = 0; c < n; ++c) g[c] = 0.f;
+    for (int j = 0; j < k; ++j) {
+        const float w = expf(softmax_k * drow[t * k + j] - mx) / s;
+        const float* gr = gradx + (size_t)(t * k + j) * d;
+        const float* vo = vel + (size_t)idx[t * k + j] * ldv;
+        for (int c = 0; c < n; ++c) g[c] = fmaf(gr[c], w, g[c]);
+        float sj = 0.f;
+        for (int c = 0; c < d - n; ++c) sj = fmaf(gr[n + c], vo[c], sj);
+        rate = fmaf(sj, w, rate);
+    }
+    for (int c = 0; c < n; ++c) gn2 = fmaf(g[c], g[c], gn2);
+    const float gn = sqrtf(gn2);
+    float r = rate / gn;
+    if (gn == 0.f || !(fabsf(r) <= 3.402823466e+38f)) r = 0.f;
+    r = fminf(fmaxf(r, -max_speed), max_speed);
+    rate_out[t] = rate;
+    for (int c = 0; c < n; ++c) qo_out[(size_t)t * n + c] = gn == 0.f ? 0.f : -r * (g[c] / gn);
+}
+
+// ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
+void omds_launch_approach_rate(hipStream_t s, const float* gradx, const float* drow, const int32_t* idx, const float* vel, int ldv,
+                               int B, int k, int d, int n, float softmax_k, float max_speed, float* rate, float* qo) {
+    if (B <= 0) return;
+    hipLaunchKernelGGL(k_approach_rate, dim3((B + 255) / 256), dim3(256), 0, s, gradx, drow, idx, vel, ldv, B, k, d, n, softmax_k, max_speed,
+                       rate, qo);
+}
+
 void omds_launch_rollout_features(hipStream_t s, const MlpDev& m, const float* qT, int ldq, int B, float* Fq, uint16_t* FqH, int ldF, int slab) {
     if (B <= 0) return;
     hipLaunchKernelGGL(k_rollout_features, dim3((B + 31) / 32), dim3(256), 0, s, m, qT, ldq, B, Fq, reinterpret_cast<_Float16*>(FqH), ldF, slab);

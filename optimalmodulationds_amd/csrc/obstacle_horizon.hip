@@ -135,4 +135,75 @@ int omds_get_obstacle_horizon(omds_ctx* ctx, float* xyzr_h, int32_t* mode_out) {
     return OMDS_OK;
 }
 
+// ---- the moving frame (omds.h: THE MOVING FRAME) --------------------------------------------------------------------------------
+int omds_moving_frame_velocity(int n_dof, int d, int k, const float* gradx, const float* drow, const float* vel, float softmax_k,
+                               float max_speed, float* rate_out, float* qo_out) {
+    if (!gradx || !drow || !vel || !rate_out || !qo_out || n_dof < 1 || n_dof > OMDS_MAX_DOF || k < 1 || (d != n_dof + 2 && d != n_dof + 3) ||
+        max_speed != max_speed) {
+        g_create_err = "omds_moving_frame_velocity: need non-null gradx [k,d], drow [k], vel [k,3], rate_out [1], qo_out [n_dof], "
+                       "1 <= n_dof <= 7, k >= 1, d = n_dof + 2 or n_dof + 3, and a max_speed that is a number";
+        return OMDS_ERR_INVALID_ARG;
+    }
+    if (!(max_speed > 0.f)) max_speed = 1.f;
+    float mx = -INFINITY, s = 0.f, g[OMDS_MAX_DOF] = {0}, rate = 0.f, gn2 = 0.f;
+    for (int j = 0; j < k; ++j) mx = fmaxf(mx, softmax_k * drow[j]);
+    for (int j = 0; j < k; ++j) s += expf(softmax_k * drow[j] - mx);
+    for (int j = 0; j < k; ++j) {
+        const float w = expf(softmax_k * drow[j] - mx) / s;
+        const float* gr = gradx + (size_t)j * d;
+        for (int c = 0; c < n_dof; ++c) g[c] = fmaf(gr[c], w, g[c]);
+        float sj = 0.f;
+        for (int c = 0; c < d - n_dof; ++c) sj = fmaf(gr[n_dof + c], vel[(size_t)j * 3 + c], sj);
+        rate = fmaf(sj, w, rate);
+    }
+    for (int c = 0; c < n_dof; ++c) gn2 = fmaf(g[c], g[c], gn2);
+    const float gn = sqrtf(gn2);
+    float r = rate / gn;
+    if (gn == 0.f || !std::isfinite(r)) r = 0.f;
+    r = fminf(fmaxf(r, -max_speed), max_speed);
+    *rate_out = rate;
+    for (int c = 0; c < n_dof; ++c) qo_out[c] = gn == 0.f ? 0.f : -r * (g[c] / gn);
+    return OMDS_OK;
+}
+
+int omds_set_obstacle_frame(omds_ctx* ctx, int moving, float max_speed) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    REQUIRE(max_speed == max_speed && max_speed < INFINITY, OMDS_ERR_INVALID_ARG, "omds_set_obstacle_frame: max_speed is not a finite number");
+    ctx->frame_on = moving != 0;
+    ctx->frame_max = max_speed > 0.f ? max_speed : 1.f;
+    return OMDS_OK;
+}
+
+int omds_get_obstacle_frame(omds_ctx* ctx, int32_t* moving, float* max_speed, int32_t* in_effect) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    if (moving) *moving = ctx->frame_on ? 1 : 0;
+    if (max_speed) *max_speed = ctx->frame_max;
+    if (in_effect) *in_effect = (ctx->frame_on && ctx->hz_mode == 1) ? 1 : 0;
+    return OMDS_OK;
+}
+
+int omds_approach_rate(omds_ctx* ctx, const float* q, int B, float* rate, float* qo) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    REQUIRE(q && B >= 1 && B <= ctx->cfg.n_traj, OMDS_ERR_INVALID_ARG, "omds_approach_rate: need 1 <= batch <= n_traj and non-null q");
+    int rc;
+    if ((rc = check_ready(ctx, false))) return rc;
+    REQUIRE(ctx->hz_mode == 1, OMDS_ERR_NOT_INITIALISED, "omds_approach_rate: no obstacle velocities (omds_set_obstacle_motion)");
+    CK(hipSetDevice(ctx->dev));
+    if ((rc = prepare_obstacle_horizon(ctx))) return rc;   // the velocities reach the device with the tables
+    const int n = ctx->cfg.n_dof, k = ctx->cfg.n_closest, d = ctx->mlp.d;
+    CK(ctx->d_frameOut.reserve((size_t)ctx->cfg.n_traj * (1 + n)));
+    float* d_rate = ctx->d_frameOut;
+    float* d_qo = d_rate + ctx->cfg.n_traj;
+    CK(hipMemcpyAsync(ctx->d_stage, q, (size_t)B * n * 4, hipMemcpyHostToDevice, ctx->stream));
+    omds_launch_transpose(ctx->stream, ctx->d_stage, ctx->d_qstage, B, n);   // -> [n][B]
+    if ((rc = enqueue_network(ctx, ctx->d_qstage, B, B, obstacle_tables(ctx)))) return rc;   // the current scene: slab 0
+    omds_launch_approach_rate(ctx->stream, ctx->d_gradx, ctx->d_drow, ctx->d_idx, ctx->d_hzVel, 3, B, k, d, n, ctx->prm.softmax_k,
+                              ctx->frame_max, d_rate, d_qo);
+    CK(hipGetLastError());
+    if (rate) CK(hipMemcpyAsync(rate, d_rate, (size_t)B * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (qo) CK(hipMemcpyAsync(qo, d_qo, (size_t)B * n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    CK(hipStreamSynchronize(ctx->stream));
+    return OMDS_OK;
+}
+
 }  // extern "C"

@@ -149,6 +149,12 @@ struct StepArgs {
     const float* seds;   // SEDS components [G][omds_seds_stride(n)]: mu_in[n], b[n], prior, den, sigma_inv[n][n], A[n][n]; nullptr = not SEDS
     int seds_G;
     float seds_lin_thr, seds_thr;
+    // the step in the moving obstacle's frame (omds_set_obstacle_frame with a motion horizon; step_device.h: FRAME)
+    int frame;             // 1: the launchers pick the FRAME instantiation of their kernel
+    float frame_max;       // clamp of the approach speed |rate| / |g|
+    const float* hzVel;    // [obstacle][ldVel] velocities of the motion horizon (omds_ctx::d_hzVel)
+    int ldVel;
+    const int* rowObs;     // [N][k] obstacle of every gradient row of a.gradx (k_modulate; the fused kernels hold theirs in LDS)
     omds_params prm;
 };
 
@@ -332,6 +338,10 @@ struct omds_ctx {
     DevBuf<float> d_hzObs;       // [H][hz_ld][4]
     DevBuf<float> d_hzRadius;    // [H][hz_ld]
     DevBuf<float> d_hzFp;        // [H][hz_ld][OMDS_FROW]
+    // the moving frame (omds_set_obstacle_frame): a preference; it acts on a propagate while hz_mode == 1
+    bool frame_on = false;
+    float frame_max = 1.f;       // clamp of the approach speed (the unit speed rollout velocities are normalised to)
+    DevBuf<float> d_frameOut;    // [n_traj][1 + n] omds_approach_rate: rate, then qo (allocated at the first call)
     // DS / cost
     bool have_ds = false, have_cost = false;
     float qf[OMDS_MAX_DOF] = {0};
@@ -446,6 +456,10 @@ void omds_launch_pass2(hipStream_t s, const MlpDev& m, const float* Fq, const fl
                        float* gradx, float* drow, float* yraw, int32_t* minidx, float* dscr, int seed_col = -1);
 void omds_launch_blend(hipStream_t s, const float* gradx, const float* drow, int B, int k, int d, int n,
                        float softmax_k, float* dist, float* nngrad);
+// k_blend's sibling (omds_approach_rate): per state the rate at which the blended distance changes because the k selected spheres
+// move at vel [obstacle][ldv], and the joint velocity that keeps it constant; idx [B][k] = the obstacle of every gradient row
+void omds_launch_approach_rate(hipStream_t s, const float* gradx, const float* drow, const int32_t* idx, const float* vel, int ldv,
+                               int B, int k, int d, int n, float softmax_k, float max_speed, float* rate, float* qo);
 
 // ---- train.hip: the trainer's exact-fp32 MFMA GEMM, for callers outside the trainer (wide_kernels.hip) -------------------
 // Out [B][out] = act(H [B][in] . W^T + b), W [out][in] row-major like torch; act: OMDS_ACT_* or -1 (none)

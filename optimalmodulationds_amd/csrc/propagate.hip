@@ -228,6 +228,9 @@ int omds_propagate(omds_ctx* ctx, const float* q_cur, int per_rollout) {
     if ((rc = check_ready(ctx, true))) return rc;
     REQUIRE(!(ctx->hz_mode && ctx->wide.on), OMDS_ERR_UNSUPPORTED,
             "omds_propagate: an obstacle horizon is not supported on networks wider than 256 (clear it: omds_set_obstacle_motion(ctx, NULL))");
+    REQUIRE(!(ctx->frame_on && ctx->hz_mode == 2), OMDS_ERR_UNSUPPORTED,
+            "omds_propagate: the moving frame needs the obstacles' velocities, and an explicit horizon table carries none (set them with "
+            "omds_set_obstacle_motion, or switch the frame off: omds_set_obstacle_frame(ctx, 0, 0))");
     CK(hipSetDevice(ctx->dev));
     if ((rc = prepare_obstacle_horizon(ctx))) return rc;
     const int N = ctx->cfg.n_traj, H = ctx->cfg.horizon, n = ctx->cfg.n_dof;
@@ -256,6 +259,11 @@ int omds_propagate(omds_ctx* ctx, const float* q_cur, int per_rollout) {
     a.seds = ctx->seds_G > 0 ? ctx->d_seds.get() : nullptr;
     a.seds_G = ctx->seds_G; a.seds_lin_thr = ctx->seds_lin_thr; a.seds_thr = ctx->seds_thr;
     a.prm = ctx->prm;
+    // the moving frame: the preference acts while a motion horizon holds the velocities (d_hzVel, uploaded with the tables above)
+    a.frame = (ctx->frame_on && ctx->hz_mode == 1) ? 1 : 0;
+    a.frame_max = ctx->frame_max;
+    a.hzVel = ctx->d_hzVel; a.ldVel = 3;
+    a.rowObs = ctx->d_idx;
     // screening where the context asks for it, the fused step runs and a bound stands (measured now when none does)
     bool screen = fused_step_available(ctx) && screen_wanted(ctx);
     if (screen && (rc = screen_calibrated(ctx, q_cur, &screen))) return rc;

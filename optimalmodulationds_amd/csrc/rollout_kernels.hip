@@ -23,19 +23,20 @@
 #include "step_device.h"
 #include "philox_device.h"
 
-template <int ND>
+template <int ND, bool FRAME = false>
 __global__ __launch_bounds__(256) void k_modulate(StepArgs a) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= a.N) return;
     float q[ND], qn[ND];
 #pragma unroll
     for (int j = 0; j < ND; ++j) q[j] = a.trajT[((size_t)(a.step - 1) * ND + j) * a.N + t];
-    modulate_core<ND, 1, true>(a, a.step, t, 0, a.gradx, a.drow, t * a.k, q, qn);
+    modulate_core<ND, 1, true, FRAME>(a, a.step, t, 0, a.gradx, a.drow, t * a.k, q, qn, a.rowObs);
 }
 
 template <int ND>
 static void launch_modulate_t(hipStream_t s, const StepArgs& a) {
-    hipLaunchKernelGGL(k_modulate<ND>, dim3((a.N + 255) / 256), dim3(256), 0, s, a);
+    if (a.frame) hipLaunchKernelGGL((k_modulate<ND, true>), dim3((a.N + 255) / 256), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((k_modulate<ND, false>), dim3((a.N + 255) / 256), dim3(256), 0, s, a);
 }
 
 void omds_launch_modulate(hipStream_t s, const StepArgs& a) {

@@ -34,9 +34,12 @@ __device__ __forceinline__ float gsig(float x, const float* s) {
 // WITH_SEDS: compile the SEDS nominal-DS branch in.  Only the stand-alone k_modulate does (omds_propagate routes contexts with a
 // SEDS nominal DS through the step of stand-alone kernels): inlined into the fused step kernels the branch costs them 10-16
 // registers and 1-3 % on every workload, out of line (a device function call) 226 registers and 20 %.
-template <int ND, int NSUB, bool WITH_SEDS = false>
+// FRAME: the step in the frame in which the blended obstacle rests (omds.h: THE MOVING FRAME).  A template parameter for the same
+// reason: without it the function is the code it was, instruction for instruction.  rowObs[grow0 + jj] is the obstacle of gradient
+// row jj (global memory or LDS); only FRAME reads it, with a.hzVel.
+template <int ND, int NSUB, bool WITH_SEDS = false, bool FRAME = false>
 __device__ __forceinline__ void modulate_core(const StepArgs& a, const int i, int t, int sub, const float* gradx, const float* drow,
-                                              int grow0, const float (&q_in)[ND], float (&q_next)[ND]) {
+                                              int grow0, const float (&q_in)[ND], float (&q_next)[ND], const int* rowObs = nullptr) {
     const int N = a.N;
     const omds_params& p = a.prm;
     float q[ND], v[ND], vhat[ND], g[ND], vt[ND], u[ND], pol[ND];
@@ -158,6 +161,18 @@ __device__ __forceinline__ void modulate_core(const StepArgs& a, const int i, in
 #pragma unroll
         for (int j = 0; j < ND; ++j) g[j] += gr[j] * w;
     }
+    // FRAME: rate at which the blended distance changes because the k spheres move (omds_moving_frame_velocity, omds.h)
+    [[maybe_unused]] float rate = 0.f;
+    if constexpr (FRAME) {
+        for (int jj = 0; jj < k; ++jj) {
+            const float w = expf(p.softmax_k * dr[jj] - mx) / ssum;
+            const float* gr = gradx + (size_t)(grow0 + jj) * d;
+            const float* vo = a.hzVel + (size_t)rowObs[grow0 + jj] * a.ldVel;
+            float sj = 0.f;
+            for (int c = 0; c < d - ND; ++c) sj = fmaf(gr[ND + c], vo[c], sj);
+            rate = fmaf(sj, w, rate);
+        }
+    }
     OMDS_MOD_STAMP(13);
     const float distance = dr[0] - p.dst_thr;                               // MPPI.py:117
     if (sub == 0) a.distT[(size_t)(i - 1) * N + t] = distance;
@@ -171,6 +186,28 @@ __device__ __forceinline__ void modulate_core(const StepArgs& a, const int i, in
         g[j] = g[j] / gn;                                                    // E[:, :, 0]  (MPPI.py:126)
         if (sub == 0) a.normalT[((size_t)(i - 1) * ND + j) * N + t] = g[j];
         dot += g[j] * vhat[j];
+    }
+    // FRAME: qo = -r g/|g|, the obstacle's velocity as the joints see it; the nominal velocity relative to it replaces v in the dot
+    // product (and below in the total velocity): with qo = 0 every operation returns its operand
+    [[maybe_unused]] float qo[ND];
+    if constexpr (FRAME) {
+        float r = rate / gn;
+        if (gn == 0.f || !(fabsf(r) <= FLT_MAX_F)) r = 0.f;
+        r = fminf(fmaxf(r, -a.frame_max), a.frame_max);
+        float rn2 = 0.f;
+#pragma unroll
+        for (int j = 0; j < ND; ++j) {
+            qo[j] = gn == 0.f ? 0.f : -r * g[j];
+            v[j] = v[j] - qo[j];
+            rn2 += v[j] * v[j];
+        }
+        const float rn = sqrtf(rn2);
+        dot = 0.f;
+#pragma unroll
+        for (int j = 0; j < ND; ++j) {
+            vhat[j] = v[j] / rn;
+            dot += g[j] * vhat[j];
+        }
     }
     if (sub == 0) a.dotT[(size_t)(i - 1) * N + t] = dot;
     const float l_vel = gsig(dot, p.lvel);
@@ -249,6 +286,10 @@ __device__ __forceinline__ void modulate_core(const StepArgs& a, const int i, in
     if (distance < 0.f) {
 #pragma unroll
         for (int j = 0; j < ND; ++j) { u[j] *= p.coll_slow; u[j] += (g[j] * vnorm) * p.coll_repulse; }
+    }
+    if constexpr (FRAME) {   // back to the world frame
+#pragma unroll
+        for (int j = 0; j < ND; ++j) u[j] = u[j] + qo[j];
     }
 #pragma unroll
     for (int j = 0; j < ND; ++j) q_next[j] = q[j] + p.dt * u[j];

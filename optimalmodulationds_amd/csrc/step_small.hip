@@ -55,7 +55,8 @@ __device__ __forceinline__ uint32_t ss_mask_bit(const uint32_t* maskS, int nhid,
     return (mr[col >> 5] >> (col & 31)) & 1u;
 }
 
-template <int ND, int TR>
+// FRAME: the modulation runs in the moving obstacle's frame (step_device.h), in an instantiation of its own
+template <int ND, int TR, bool FRAME = false>
 __global__ __launch_bounds__(SS_NT, TR == 16 ? 4 : 2) void k_step_small(SmallArgs a) {
     constexpr int ACT = OMDS_ACT_RELU;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -220,7 +221,7 @@ __global__ __launch_bounds__(SS_NT, TR == 16 ? 4 : 2) void k_step_small(SmallArg
             float q[ND], qn[ND];
 #pragma unroll
             for (int j = 0; j < ND; ++j) q[j] = qT[(size_t)j * ldq + t];
-            modulate_core<ND, 16>(a.st, a.st.step, t, sub, gx, dr, rl * k, q, qn);
+            modulate_core<ND, 16, false, FRAME>(a.st, a.st.step, t, sub, gx, dr, rl * k, q, qn, selO);
             if (sub < ND) {
                 float v = qn[0];
 #pragma unroll
@@ -266,19 +267,24 @@ static int small_tile_rows(const MlpDev& m, int n_dof, int O, int k) {
     return r16 == r32 ? 16 : 32;
 }
 
-template <int ND, int TR>
+template <int ND, int TR, bool FRAME = false>
 static void launch_small_r(hipStream_t s, const SmallArgs& a) {
     static std::atomic<uint64_t> configured{0};
     if (omds_first_use_on_device(configured))
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_step_small<ND, TR>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_step_small<ND, TR, FRAME>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)small_lds_bytes(OMDS_MAX_HIDDEN + 1, TR));
-    hipLaunchKernelGGL((k_step_small<ND, TR>), dim3((a.B + a.R - 1) / a.R), dim3(SS_NT), small_lds_bytes(a.m.nhh + 1, TR), s, a);
+    hipLaunchKernelGGL((k_step_small<ND, TR, FRAME>), dim3((a.B + a.R - 1) / a.R), dim3(SS_NT), small_lds_bytes(a.m.nhh + 1, TR), s, a);
 }
 template <int ND>
 static void launch_small_t(hipStream_t s, SmallArgs& a, int k) {
     const int TR = small_tile_rows(a.m, ND, a.O, k);
     a.R = small_rollouts(a.m, ND, a.O, k, TR);
     if (a.R <= 0) return;
+    if (a.o_gradx == nullptr && a.st.frame) {   // the step form in the moving frame
+        if (TR == 16) launch_small_r<ND, 16, true>(s, a);
+        else launch_small_r<ND, 32, true>(s, a);
+        return;
+    }
     if (TR == 16) launch_small_r<ND, 16>(s, a);
     else launch_small_r<ND, 32>(s, a);
 }

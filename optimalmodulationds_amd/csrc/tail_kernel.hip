@@ -37,7 +37,9 @@ struct TailArgs {
     StepArgs st;
 };
 
-template <int ND, int ACT, int ROWS>
+// FRAME: the modulation runs in the moving obstacle's frame (step_device.h); its own instantiation, so that the kernel of every
+// other propagate is the code it was
+template <int ND, int ACT, int ROWS, bool FRAME = false>
 __global__ __launch_bounds__(P2_NT) void k_tail(TailArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const MlpDev& m = a.m;
@@ -100,7 +102,7 @@ __global__ __launch_bounds__(P2_NT) void k_tail(TailArgs a) {
             float q[ND], qn[ND];
 #pragma unroll
             for (int j = 0; j < ND; ++j) q[j] = qT[(size_t)j * N + t];
-            modulate_core<ND, 16>(a.st, a.st.step, t, sub, gx, dr, rl * k, q, qn);
+            modulate_core<ND, 16, false, FRAME>(a.st, a.st.step, t, sub, gx, dr, rl * k, q, qn, sm.rowO);
             if (sub < ND) {
                 float v = qn[0];
 #pragma unroll
@@ -152,7 +154,7 @@ static size_t tail_lds_bytes(int nhid);
 // (ExactOut::deriv, 1 KB per entry and layer); the backward reads the selected entries' rows through sm.rowE -- the same
 // numbers pass 2's own forward would have written to its scratch, so the tanh tail drops its forward too.
 // ------------------------------------------------------------------------------------------------
-template <int ND, int ROWS, int ACT = OMDS_ACT_RELU>
+template <int ND, int ROWS, int ACT = OMDS_ACT_RELU, bool FRAME = false>
 __global__ __launch_bounds__(P2_NT) void k_tail_sel(TailArgs a) {
     static_assert(ACT == OMDS_ACT_RELU || ROWS != 4, "the 4-row-group backward works on ReLU masks");
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -310,7 +312,7 @@ __global__ __launch_bounds__(P2_NT) void k_tail_sel(TailArgs a) {
             float q[ND], qn[ND];
 #pragma unroll
             for (int j = 0; j < ND; ++j) q[j] = qT[(size_t)j * N + t];
-            modulate_core<ND, 16>(a.st, a.st.step, t, sub, gx, dr, rl * k, q, qn);
+            modulate_core<ND, 16, false, FRAME>(a.st, a.st.step, t, sub, gx, dr, rl * k, q, qn, sm.rowO);
             if (sub < ND) {
                 float v = qn[0];
 #pragma unroll
@@ -368,19 +370,23 @@ static void tail_tl_dump(hipStream_t s, int step, int grid) {
 static void tail_tl_dump(hipStream_t, int, int) {}
 #endif
 
-template <int ND, int ROWS, int ACT = OMDS_ACT_RELU>
+template <int ND, int ROWS, int ACT = OMDS_ACT_RELU, bool FRAME = false>
 static void launch_tail_sel_t(hipStream_t s, const TailArgs& a) {
     static std::atomic<uint64_t> configured{0};
     const size_t extra = 32 * 4;   // sel
     if (omds_first_use_on_device(configured)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tail_sel<ND, ROWS, ACT>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tail_sel<ND, ROWS, ACT, FRAME>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)(tail_lds_bytes(OMDS_MAX_HIDDEN + 1) + extra));
     }
     const int RW = (ROWS == 4 ? 20 : ROWS) / a.st.k;
     const int grid = (a.st.N + RW - 1) / RW;
-    hipLaunchKernelGGL((k_tail_sel<ND, ROWS, ACT>), dim3(grid), dim3(P2_NT), tail_lds_bytes(a.m.nhh + 1) + extra, s, a);
+    hipLaunchKernelGGL((k_tail_sel<ND, ROWS, ACT, FRAME>), dim3(grid), dim3(P2_NT), tail_lds_bytes(a.m.nhh + 1) + extra, s, a);
     tail_tl_dump(s, a.st.step, grid);
 }
+
+// The step in the moving frame (StepArgs::frame) runs on 16- or 32-row tiles: every tile shape computes the same bits, so the 4-row
+// groups are a choice of speed that the frame's instantiations do without.
+static int frame_rows(int rows, int k) { return rows != 4 ? rows : (k <= 16 ? 16 : 32); }
 
 // 16-row tiles (bit-identical to 32-row ones, mlp_device.h) while their workgroups still fit the CUs two at a time: twice as
 // many, half as long, and the second resident fills the first one's top-k / gather / modulation phases
@@ -430,6 +436,17 @@ void omds_launch_tail_sel(hipStream_t s, const MlpDev& m, const float* Fp, const
     a.n_slots = 0;
     a.m = m; a.Fp = Fp; a.radius = radius; a.xyzr = xyzr; a.Dmin = nullptr; a.ldD = O; a.Fq = Fq; a.FqOut = Fq; a.dscr = nullptr; a.O = O; a.st = st;
     a.rowlist = rowlist; a.range = range; a.ex = ex;
+    if (st.frame) {
+        const int rows = frame_rows(tail_sel_rows(st.N, st.k, false), st.k);
+        if (m.act == OMDS_ACT_TANH) {
+            if (st.n == 7) { if (rows == 16) launch_tail_sel_t<7, 16, OMDS_ACT_TANH, true>(s, a); else launch_tail_sel_t<7, 32, OMDS_ACT_TANH, true>(s, a); }
+            else { if (rows == 16) launch_tail_sel_t<2, 16, OMDS_ACT_TANH, true>(s, a); else launch_tail_sel_t<2, 32, OMDS_ACT_TANH, true>(s, a); }
+        } else {
+            if (st.n == 7) { if (rows == 16) launch_tail_sel_t<7, 16, OMDS_ACT_RELU, true>(s, a); else launch_tail_sel_t<7, 32, OMDS_ACT_RELU, true>(s, a); }
+            else { if (rows == 16) launch_tail_sel_t<2, 16, OMDS_ACT_RELU, true>(s, a); else launch_tail_sel_t<2, 32, OMDS_ACT_RELU, true>(s, a); }
+        }
+        return;
+    }
     if (m.act == OMDS_ACT_TANH) {   // derivative rows instead of masks: 16- or 32-row tiles (the 4-row-group backward is a ReLU-mask form)
         const int rows = tail_sel_rows(st.N, st.k, false);
         if (st.n == 7) { if (rows == 16) launch_tail_sel_t<7, 16, OMDS_ACT_TANH>(s, a); else launch_tail_sel_t<7, 32, OMDS_ACT_TANH>(s, a); }
@@ -446,21 +463,28 @@ static size_t tail_lds_bytes(int nhid) {
            (32 * 12 + 32 + 32 * 3 * OMDS_MAX_DOF) * 4;
 }
 
-template <int ND, int ACT, int ROWS>
+template <int ND, int ACT, int ROWS, bool FRAME = false>
 static void launch_tail_a(hipStream_t s, const TailArgs& a) {
     static std::atomic<uint64_t> configured{0};
     if (omds_first_use_on_device(configured)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tail<ND, ACT, ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tail<ND, ACT, ROWS, FRAME>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)tail_lds_bytes(OMDS_MAX_HIDDEN + 1));
     }
     const int RW = (ROWS == 4 ? 20 : ROWS) / a.st.k;
     const int grid = (a.st.N + RW - 1) / RW;
-    hipLaunchKernelGGL((k_tail<ND, ACT, ROWS>), dim3(grid), dim3(P2_NT), tail_lds_bytes(a.m.nhh + 1), s, a);
+    hipLaunchKernelGGL((k_tail<ND, ACT, ROWS, FRAME>), dim3(grid), dim3(P2_NT), tail_lds_bytes(a.m.nhh + 1), s, a);
     tail_tl_dump(s, a.st.step, grid);
 }
 
 template <int ND, int ROWS>
 static void launch_tail_t(hipStream_t s, const TailArgs& a) {
+    if constexpr (ROWS != 4) {
+        if (a.st.frame) {
+            if (a.m.act == OMDS_ACT_RELU) launch_tail_a<ND, OMDS_ACT_RELU, ROWS, true>(s, a);
+            else launch_tail_a<ND, OMDS_ACT_TANH, ROWS, true>(s, a);
+            return;
+        }
+    }
     if (a.m.act == OMDS_ACT_RELU) launch_tail_a<ND, OMDS_ACT_RELU, ROWS>(s, a);
     else if constexpr (ROWS != 4) launch_tail_a<ND, OMDS_ACT_TANH, ROWS>(s, a);
 }
@@ -502,7 +526,8 @@ void omds_launch_tail(hipStream_t s, const MlpDev& m, const float* Fp, const flo
     a.ldD = shared_row ? 0 : O;
     a.FqH = reinterpret_cast<_Float16*>(FqH);
     a.ldF = ldF;
-    const int rows = omds_tail_rows(st.N, st.k, m.act == OMDS_ACT_RELU && m.skip_mask == 0 && m.nhh >= 1);
+    int rows = omds_tail_rows(st.N, st.k, m.act == OMDS_ACT_RELU && m.skip_mask == 0 && m.nhh >= 1);
+    if (st.frame) rows = frame_rows(rows, st.k);
     const int RW = (rows == 4 ? 20 : rows) / st.k;
     a.n_slots = (st.N + RW - 1) / RW;
     a.rowlist = nullptr; a.range = guard_range; a.ex = ExactOut{}; a.e_bound = e_bound; a.viol = viol;

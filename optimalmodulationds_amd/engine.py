@@ -105,6 +105,27 @@ class Engine:
         self._ck(self.lib.omds_get_obstacle_horizon(self.h, L.fptr(out), L.iptr(mode)))
         return out, int(mode[0])
 
+    # ---- the moving frame: the modulation relative to the obstacle's velocity as the joints see it (omds.h) ---------------------
+    def set_obstacle_frame(self, moving, max_speed=None):
+        """A preference: with ``moving`` and a motion horizon (``set_obstacle_motion``) every step of ``propagate`` modulates in the
+        frame in which the blended obstacle rests and adds its velocity back.  ``max_speed`` clamps the approach speed (None: 1.0,
+        the unit speed of the rollouts).  Without a motion horizon it changes nothing; with an explicit table ``propagate`` raises."""
+        self._ck(self.lib.omds_set_obstacle_frame(self.h, 1 if moving else 0, 0.0 if max_speed is None else float(max_speed)))
+
+    def get_obstacle_frame(self):
+        """(moving, max_speed, in_effect): the preference, its clamp, and whether the next propagate runs in the moving frame."""
+        mv, eff, ms = np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(1, np.float32)
+        self._ck(self.lib.omds_get_obstacle_frame(self.h, L.iptr(mv), L.fptr(ms), L.iptr(eff)))
+        return bool(mv[0]), float(ms[0]), bool(eff[0])
+
+    def approach_rate(self, q):
+        """States ``q`` [B, n] -> (rate [B], qo [B, n]) against the current scene and the motion's velocities: the rate at which the
+        blended distance changes because the spheres move (negative: approaching) and the joint velocity that keeps it constant."""
+        q = L.f32(q).reshape(-1, self.n)
+        rate, qo = np.zeros(q.shape[0], np.float32), np.zeros((q.shape[0], self.n), np.float32)
+        self._ck(self.lib.omds_approach_rate(self.h, L.fptr(q), q.shape[0], L.fptr(rate), L.fptr(qo)))
+        return rate, qo
+
     def set_ds(self, q_goal):
         q = L.f32(q_goal).reshape(self.n)
         self._ck(self.lib.omds_set_ds(self.h, L.fptr(q)))
@@ -467,6 +488,24 @@ def predict_obstacle_horizon(obs, vel, horizon, dt):
     if rc != 0:
         raise L.OmdsError(f"omds_obstacle_horizon_predict failed ({rc}): {lib.omds_last_error(None).decode()}")
     return out
+
+
+def moving_frame_velocity(gradx, drow, vel, n_dof, softmax_k=-10.0, max_speed=1.0):
+    """The moving frame's definition on the host (omds_moving_frame_velocity, no GPU): gradx [k, d] full input gradients of the k
+    selected rows, drow [k] their distances, vel [k, 3] the velocity of each row's sphere -> (rate, qo [n_dof])."""
+    lib = L.load()
+    g = L.f32(gradx)
+    g = g.reshape(-1, g.shape[-1])
+    k, d = g.shape
+    dr, v = L.f32(drow).reshape(-1), L.f32(vel).reshape(-1, 3)
+    if dr.shape[0] != k or v.shape[0] != k:
+        raise ValueError(f"moving_frame_velocity: {k} gradient rows but {dr.shape[0]} distances and {v.shape[0]} velocities")
+    rate, qo = np.zeros(1, np.float32), np.zeros(int(n_dof), np.float32)
+    rc = lib.omds_moving_frame_velocity(int(n_dof), d, k, L.fptr(g), L.fptr(dr), L.fptr(v), float(softmax_k), float(max_speed),
+                                        L.fptr(rate), L.fptr(qo))
+    if rc != 0:
+        raise L.OmdsError(f"omds_moving_frame_velocity failed ({rc}): {lib.omds_last_error(None).decode()}")
+    return float(rate[0]), qo
 
 
 def red_layout(K, n):

@@ -124,10 +124,11 @@ class MPPI:
         self.qf = self.DS.q_goal.squeeze()
         self.Cost = Cost(self.qf, self.dh_params, owner=self)
 
-    def update_obstacles(self, obs, velocities=None):
+    def update_obstacles(self, obs, velocities=None, moving_frame=False):
         """MPPI.py:347-350.  ``velocities`` [O, 3] (new here; the reference's obstacle streamers know them and drop them): step i of
         the next propagates sees the spheres moved by (i - 1) dt velocities instead of frozen at ``obs`` (Engine.set_obstacle_motion,
-        with the ``dt`` in force at the propagate).  Every call without them is the reference's: a static scene."""
+        with the ``dt`` in force at the propagate).  Every call without them is the reference's: a static scene.  ``moving_frame``: the
+        modulation also runs relative to those velocities (Engine.set_obstacle_frame); it needs ``velocities`` to act."""
         self.obs = torch.as_tensor(_np(obs)).reshape(-1, 4)
         self.n_obs = self.obs.shape[0]
         vel = None if velocities is None else _np(velocities).reshape(self.n_obs, 3)
@@ -137,6 +138,7 @@ class MPPI:
         self._max_obs = self._engine.max_obs
         if vel is not None:                          # (set_obstacles cleared the previous motion)
             self._engine.set_obstacle_motion(vel)
+        self._engine.set_obstacle_frame(bool(moving_frame))
         return 0
 
     # ---- parameters -> device ----------------------------------------------------------------------
