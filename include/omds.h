@@ -70,6 +70,15 @@ typedef struct {
 /* pass 1 over the plain row space at every horizon step: a propagate from ONE state (per_rollout == 0) evaluates its first step
  * for each of the N rollouts instead of once for all of them (same bits either way); for A/B runs and the tests that compare */
 #define OMDS_FLAG_NATURAL_PASS1 16
+/* every pass-1 tile covers consecutive rows of the rollout-major pair space, instead of a block of rollouts x obstacles that are
+ * neighbours in a key order of their layer-1 signs, which the full launches of the compacting kernel form so that the rows of a tile
+ * fire alike (same bits either way: a row does not depend on its tile-mates); for A/B runs and the tests that compare the two    */
+#define OMDS_FLAG_NATURAL_TILES 32
+/* the block order of the tiles at every batch size, not only from OMDS_BLOCK_TILES_MIN_PAIRS rollout-obstacle pairs on, below which
+ * the ordering launch costs more than it saves (EXPERIMENTS.md R12: bracketed by 150 528 pairs, slower, and 301 056, faster, at 294
+ * obstacles; not located); for A/B runs and the tests, which run small batches                                                    */
+#define OMDS_FLAG_BLOCK_TILES 64
+#define OMDS_BLOCK_TILES_MIN_PAIRS 262144
 
 /* The constants the reference hard-codes inside propagate() (MPPI.py:117-217,277) and
  * LinDS (LinDS.py:9), as parameters; omds_default_params() fills the reference values.   */

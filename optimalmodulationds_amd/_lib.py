@@ -40,6 +40,8 @@ FLAG_UNFUSED_STEP = 1
 FLAG_TAIL_FORWARD = 4      # the fp32 step's tail keeps its own forward (omds.h: OMDS_FLAG_TAIL_FORWARD)
 FLAG_DENSE_PASS1 = 8       # k_pass1 multiplies every k-chunk (omds.h: OMDS_FLAG_DENSE_PASS1; same bits as the per-tile compaction)
 FLAG_NATURAL_PASS1 = 16    # first step of a propagate from one state evaluated per rollout (omds.h: OMDS_FLAG_NATURAL_PASS1; same bits)
+FLAG_NATURAL_TILES = 32    # pass-1 tiles over consecutive rows instead of key-ordered rollout x obstacle blocks (omds.h: OMDS_FLAG_NATURAL_TILES; same bits)
+FLAG_BLOCK_TILES = 64      # the block order at every batch size, not only from 262 144 pairs on (omds.h: OMDS_FLAG_BLOCK_TILES; same bits)
 FLAG_TWO_KERNEL_STEP = 2   # keep few-obstacle scenes on k_pass1 + k_tail (omds.h: OMDS_FLAG_TWO_KERNEL_STEP)   # omds_config.flags
 # omds_params.variant / cost_terms bits (include/omds.h)
 VARIANT_KVAL_TIMES_ACT = 1
@@ -161,6 +163,11 @@ TEST_HOOK_SIGNATURES = {
     "omds_test_trig": (C.c_int, [F32P, F32P, F32P, C.c_int64]),
     "omds_test_trig_sweep": (C.c_int, [C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64)]),
 }
+# include/omds_test_tiles.h: the hooks of the block-ordered pass 1, in the test library likewise
+TILE_HOOK_SIGNATURES = {
+    "omds_test_tile_orders": (C.c_int, [C.c_void_p, I32P, I32P]),
+    "omds_test_read_dmin": (C.c_int, [C.c_void_p, F32P]),
+}
 TEST_LIB_PATH = os.path.join(_HERE, "csrc", "libomds_hip_test.so")
 
 ABI_VERSION = 503      # omds_version() of the library this binding was written against
@@ -219,7 +226,7 @@ def load_test_hooks():
     """libomds_hip_test.so: the product's objects plus the hooks of include/omds_test.h (damage the screening inputs, force a tile
     shape, the trainer's general GEMM, the host half of omds_set_mlp_ex, the encoding's sin / cos).  For tests only:
     ``Engine(..., lib=load_test_hooks())``."""
-    return load(TEST_LIB_PATH, TEST_HOOK_SIGNATURES)
+    return load(TEST_LIB_PATH, dict(TEST_HOOK_SIGNATURES, **TILE_HOOK_SIGNATURES))
 
 
 def f32(a, shape=None):

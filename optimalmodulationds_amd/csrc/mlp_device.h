@@ -882,10 +882,20 @@ __device__ __forceinline__ void gemm_gather(const float* __restrict__ Hw, const 
 #define OMDS_DYN_PRIO_EPI 3
 #endif
 #define OMDS_DYN_PRIO(p) __builtin_amdgcn_s_setprio(p)
-template <int MT, int MR>
+// BLK (k_pass1_dyn_blk): the tile is a block of MT / 4 consecutive rollouts of the rollout order x 4 consecutive obstacles of the
+// obstacle order (tile_order.hip) instead of MT consecutive rows: row r = rollout slot r / 4, obstacle slot r % 4.  Both orders are
+// padded with their last entry, so a partial block holds copies of rows it has anyway (they add nothing to the union of firing
+// units) and only the stores look at the counts.  Dmin stays [N][O] in the caller's indices: four scalars per row group.
+struct TileBlock {
+    const int* rp;   // the block's rollouts: MT / 4 entries of the rollout order, the first nr of them real
+    const int* op;   // the block's obstacles: 4 entries of the obstacle order, the first no of them real
+    int nr, no;
+};
+template <int MT, int MR, bool BLK = false>
 __device__ __forceinline__ void pass1_tile_dyn(const MlpDev& m, float* smem, const float* __restrict__ Fq, const float* __restrict__ Fp,
                                                const float* __restrict__ radius, int O, long long total_rows, uint32_t ignored,
-                                               float* __restrict__ Dmin, const long long row0, const OmdsDivisor odiv) {
+                                               float* __restrict__ Dmin, const long long row0, const OmdsDivisor odiv,
+                                               const TileBlock blk = TileBlock{}) {
     using G = Geo<MT, MR, 1>;
     static_assert(G::NW == 8 && G::WM == 1, "eight waves, wave w owns the units 32 w .. 32 w + 31 of every level");
     float* Hs = smem;                                              // [MT][LDH]
@@ -905,7 +915,38 @@ __device__ __forceinline__ void pass1_tile_dyn(const MlpDev& m, float* smem, con
 #endif
 
     // ---- the tile's encoded inputs (as pass1_tile, un-listed rows) -------------------------------------------------
-    {
+    if constexpr (BLK) {
+        // wave wv fills rows wv + 8 it: obstacle slot wv & 3 in all of them, rollout slots (wv >> 2) + 2 it.  The ids are wave-uniform:
+        // scalar loads, all of them issued before the first is used
+        constexpr int IT = MT / G::NW;
+        const __amdgpu_buffer_rsrc_t qr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Fq), 0, 0x7fffffff, 0x00020000);
+        const __amdgpu_buffer_rsrc_t pr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Fp), 0, 0x7fffffff, 0x00020000);
+        const bool hi = lane >= 32;
+        const int f4 = (lane & 31) * 4;
+        const int offp = blk.op[wv & 3] * (OMDS_FROW * 4);
+        int offq[IT];
+#pragma unroll
+        for (int it = 0; it < IT; ++it) offq[it] = blk.rp[(wv >> 2) + 2 * it] * (OMDS_FROW * 4);
+        const uint32_t fp = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(pr, offp + f4, 0, 0);
+        uint32_t fv[IT / 2];
+#pragma unroll
+        for (int it = 0; it < IT; it += 2)
+            fv[it / 2] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(qr, (hi ? offq[it + 1] : offq[it]) + f4, 0, 0) | fp;
+        uint32_t* frow = reinterpret_cast<uint32_t*>(Hs) + (wv + (hi ? G::NW : 0)) * LDH + omds_kpos(lane & 31);
+#pragma unroll
+        for (int it = 0; it < IT; it += 2) frow[it * G::NW * LDH] = fv[it / 2];
+        // what the last layer needs of the block: rowRad[0 .. 3] the obstacles' radii, behind them the rollout of every slot and the
+        // obstacle of every slot (-1: padding, not stored)
+        int* slotT = reinterpret_cast<int*>(rowRad + 4);
+        int* slotO = slotT + MT / 4;
+        if (tid < 4) {
+            const int o = blk.op[tid];
+            rowRad[tid] = radius[o];
+            slotO[tid] = tid < blk.no ? o : -1;
+        } else if (tid >= 64 && tid < 64 + MT / 4) {
+            slotT[tid - 64] = tid - 64 < blk.nr ? blk.rp[tid - 64] : -1;
+        }
+    } else {
         constexpr int IT = MT / G::NW;
         const unsigned row0u = (unsigned)row0;
         const unsigned t0 = odiv.div(row0u);
@@ -1081,7 +1122,7 @@ __device__ __forceinline__ void pass1_tile_dyn(const MlpDev& m, float* smem, con
         const int j = lane & 15;
         const float bj = m.bl[j];
         const bool pad = j >= m.C, ign = (ignored >> j) & 1u;
-        const float4 rr = *reinterpret_cast<const float4*>(rowRad + r4);
+        const float4 rr = *reinterpret_cast<const float4*>(rowRad + (BLK ? 0 : r4));   // BLK: the four rows of a group are the block's four obstacles
         const float rad[4] = {rr.x, rr.y, rr.z, rr.w};
         float y[4];
 #pragma unroll
@@ -1094,6 +1135,20 @@ __device__ __forceinline__ void pass1_tile_dyn(const MlpDev& m, float* smem, con
             v = fminf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, false)));
             y[reg] = v;
         }
+        if constexpr (BLK) {
+            if (j == 0) {
+                const int* slotT = reinterpret_cast<const int*>(rowRad + 4);
+                const int t = slotT[r4 >> 2];
+                if (t >= 0) {
+                    const int4 oo = *reinterpret_cast<const int4*>(slotT + MT / 4);
+                    float* drow = Dmin + (size_t)t * O;
+                    if (oo.x >= 0) drow[oo.x] = y[0];
+                    if (oo.y >= 0) drow[oo.y] = y[1];
+                    if (oo.z >= 0) drow[oo.z] = y[2];
+                    if (oo.w >= 0) drow[oo.w] = y[3];
+                }
+            }
+        } else
         if (j == 0) {
             const long long g = row0 + r4;
             if (g + 3 < total_rows) {

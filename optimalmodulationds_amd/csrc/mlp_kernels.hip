@@ -150,6 +150,27 @@ __global__ __launch_bounds__(512) void k_pass1_dyn(const float* __restrict__ Fq,
     else pass1_tile_dyn<32, 1>(m, smem, Fq, Fp, radius, O, total_rows, ignored, Dmin, (long long)n_big * 64 + (long long)(b - n_big) * 32, odiv);
 }
 
+// ... on block-ordered tiles (pass1_tile_dyn<.., BLK>; tile_order.hip): workgroup b < n_big is block (b / ncb, b % ncb) of the grid of
+// 16-rollout x 4-obstacle blocks over the first nrb16 * 16 entries of rperm, the rest are the 8 x 4 blocks of the remaining entries
+__global__ __launch_bounds__(512) void k_pass1_dyn_blk(const float* __restrict__ Fq, const float* __restrict__ Fp,
+                                                       const float* __restrict__ radius, float* __restrict__ Dmin,
+                                                       const int* __restrict__ rperm, const int* __restrict__ operm, int N, int O,
+                                                       uint32_t ignored, int n_big, int nrb16, OmdsDivisor cdiv, MlpDev m) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const unsigned ncb = (unsigned)(O + 3) >> 2;
+    if ((int)blockIdx.x < n_big) {
+        const unsigned b = blockIdx.x, rbk = cdiv.div(b), cbk = b - rbk * ncb;
+        const int r0 = (int)rbk * 16, o0 = (int)cbk * 4;
+        pass1_tile_dyn<64, 2, true>(m, smem, Fq, Fp, radius, O, 0, ignored, Dmin, 0, cdiv,
+                                    TileBlock{rperm + r0, operm + o0, min(16, N - r0), min(4, O - o0)});
+    } else {
+        const unsigned b = blockIdx.x - (unsigned)n_big, rbk = cdiv.div(b), cbk = b - rbk * ncb;
+        const int r0 = nrb16 * 16 + (int)rbk * 8, o0 = (int)cbk * 4;
+        pass1_tile_dyn<32, 1, true>(m, smem, Fq, Fp, radius, O, 0, ignored, Dmin, 0, cdiv,
+                                    TileBlock{rperm + r0, operm + o0, min(8, N - r0), min(4, O - o0)});
+    }
+}
+
 // The same two kernels in pass1_tile's MODE 6 (kernels of their own: the tuned mode-0 kernels keep their argument lists and code):
 // beside Dmin every pair's pass-2 distance, arg-min link and ReLU masks go to `ex`, indexed by the pair.
 template <int MT, int MR, int NR, int ACT>
@@ -381,6 +402,26 @@ void omds_launch_pass1(hipStream_t s, const MlpDev& m, const float* Fq, const fl
         case Pass1Size::Small: launch_pass1_t<32, 1, 1>(s, m, Fq, Fp, radius, O, total, ignored, Dmin); break;
         case Pass1Size::Tiny: launch_pass1_t<16, 1, 1>(s, m, Fq, Fp, radius, O, total, ignored, Dmin); break;
     }
+}
+
+// The block-ordered form of the compacting launch: the same size classes, counted in blocks.  A Large launch ends on 8 x 4 blocks
+// (32-row tiles) over its last ceil(256 / ncb) * 16 rollouts, about the one round of 512 workgroups of the natural launch.
+bool omds_pass1_blocks_ok(const MlpDev& m, int N, int O) {
+    return m.compact && pass1_size((long long)N * O) != Pass1Size::Tiny && N <= OMDS_ORDER_MAX_ROLLOUTS && O <= OMDS_ORDER_MAX_OBS;
+}
+void omds_launch_pass1_blocks(hipStream_t s, const MlpDev& m, const float* Fq, const float* Fp, const float* radius, int O, int N,
+                              uint32_t ignored, float* Dmin, const int* rperm, const int* operm) {
+    const size_t lds = (size_t)64 * LDH * 4 + 64 * 4 + 32 + (size_t)OMDS_IDS * 4;
+    static std::atomic<uint64_t> configured{0};
+    if (omds_first_use_on_device(configured))
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pass1_dyn_blk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const Pass1Size size = pass1_size((long long)N * O);
+    const int ncb = (O + 3) / 4;
+    const int nrb16 = size == Pass1Size::Large ? std::max(N / 16 - (256 + ncb - 1) / ncb, 0) : size == Pass1Size::Medium ? N / 16 : 0;
+    const long long n_big = (long long)nrb16 * ncb;
+    const long long n_small = (long long)((N - nrb16 * 16 + 7) / 8) * ncb;
+    hipLaunchKernelGGL(k_pass1_dyn_blk, dim3((unsigned)(n_big + n_small)), dim3(512), lds, s, Fq, Fp, radius, Dmin, rperm, operm, N, O, ignored,
+                       (int)n_big, nrb16, OmdsDivisor::make((unsigned)ncb), m);
 }
 
 // pass 1 that also leaves every pair's pass-2 distance, arg-min link and ReLU masks (pass1_tile MODE 6) -- the same tile choice as

@@ -128,6 +128,20 @@ struct WideNet {
     float* G[2] = {nullptr, nullptr}; // [rows2][max width] gradient ping-pong
 };
 
+// ---- tile_order.hip: the row order of the block-ordered pass 1 ------------------------------------------------------------------
+constexpr int OMDS_KEY_UNITS = 12;             // sign bits of a rollout's / an obstacle's key
+constexpr int OMDS_ORDER_MAX_OBS = 4096;       // the orders are ranked in LDS: largest scene and batch they are formed for
+constexpr int OMDS_ORDER_MAX_ROLLOUTS = 8192;
+struct TileKeys {                              // device: written by k_tile_pick once per propagate, read by k_rollout_order at every step
+    float W[OMDS_KEY_UNITS][OMDS_FROW];        // layer-1 weights of the key units over the feature slots of Fq / Fp
+    float cR[OMDS_KEY_UNITS];                  // bias + mean obstacle share: what a rollout's share is compared against
+    int unit[OMDS_KEY_UNITS];
+};
+inline int omds_order_pad(int n) { return ((n + 15) & ~15) + 16; }   // entries of an order: whole blocks, the padding names the last row again
+// pick: choose the key units on Fq and order the obstacles of Fp first (the first full launch of a propagate); then rperm from Fq
+void omds_launch_tile_order(hipStream_t s, const MlpDev& m, const float* Fq, int N, const float* Fp, int O, TileKeys* keys,
+                            int* rperm, int* operm, bool pick);
+
 struct ProfEvents {
     std::vector<hipEvent_t> start, stop;
     size_t used = 0;
@@ -374,6 +388,8 @@ struct omds_ctx {
     DevBuf<float> d_Fq;          // [Nrows][OMDS_FROW] encoded joint states [q, sin q, cos q] at their feature slots (d_Fq, d_Dmin and d_ex* are SCRATCH between propagates: calibration and the
     DevBuf<float> d_Dmin;        // [N][max_obs]    screening pack's re-sort overwrite them after the results have been published)
     DevBuf<int32_t> d_idx;       // [N][k]
+    DevBuf<int> d_rperm, d_operm;   // block-ordered pass 1 (tile_order.hip): rollout order of the step, obstacle order of the propagate
+    DevBuf<TileKeys> d_tileKeys;    // ... and the key units of the propagate (allocated at the first block-ordered launch)
     DevBuf<float> d_gradx;       // [N*k][d]
     DevBuf<float> d_drow;        // [N*k]
     DevBuf<float> d_yraw;        // [N*k][16]
@@ -450,6 +466,12 @@ void omds_launch_obstacle_horizon_features(hipStream_t s, const MlpDev& m, const
                                            int ld, float* obsT, float* radiusT, float* FpT);
 void omds_launch_pass1(hipStream_t s, const MlpDev& m, const float* Fq, const float* Fp, const float* radius,
                        int O, int B, uint32_t ignored_links, float* Dmin);
+// The block-ordered full launch of the compacting kernel (k_pass1_dyn_blk): a 64-row tile is 16 consecutive entries of rperm x 4
+// consecutive entries of operm (a 32-row tile: 8 x 4), Dmin stays [N][O] in the caller's obstacle index.  rperm / operm hold
+// omds_order_pad(N) / omds_order_pad(O) entries (tile_order.hip).  Only where omds_pass1_blocks_ok says so.
+bool omds_pass1_blocks_ok(const MlpDev& m, int N, int O);
+void omds_launch_pass1_blocks(hipStream_t s, const MlpDev& m, const float* Fq, const float* Fp, const float* radius, int O, int N,
+                              uint32_t ignored_links, float* Dmin, const int* rperm, const int* operm);
 void omds_launch_topk(hipStream_t s, const float* Dmin, int B, int O, int k, int32_t* idx);
 void omds_launch_pass2(hipStream_t s, const MlpDev& m, const float* Fq, const float* Fp, const float* radius,
                        const float* xyzr, const int32_t* idx, int B, int k, const float* qT, int ldq,

@@ -2,6 +2,9 @@
 // omds_propagate / omds_get_rollouts / omds_get_rollout_rows.  Nothing of the screening controller lives here: the screened
 // routes get their plan from screen_begin_propagate and hand what they measured to screen_finish_propagate (screening.hip).
 #include "capi_internal.h"
+#ifdef OMDS_TEST_HOOKS
+#include "omds_test_tiles.h"
+#endif
 
 // The one-launch small-scene step (step_small.hip) when the scene qualifies and the batch is small enough that the
 // two-kernel step's tail would sit on a fraction of the CUs (at R rollouts per workgroup; beyond ~3 rounds of workgroups
@@ -114,6 +117,21 @@ static int enqueue_small_scene(omds_ctx* ctx, StepArgs& a) {
     return OMDS_OK;
 }
 
+// The orders of the block-ordered pass 1 (tile_order.hip), allocated at the first launch that uses them and zeroed, so that every
+// entry names a row of the tables whatever happens; a request that failed leaves the step on the natural order.
+static bool acquire_order_buffers(omds_ctx* ctx) {
+    const size_t nr = (size_t)omds_order_pad(ctx->cfg.n_traj), no = (size_t)omds_order_pad(ctx->cfg.max_obs);
+    if (ctx->d_tileKeys && ctx->d_rperm.count() >= nr && ctx->d_operm.count() >= no) return true;
+    if (ctx->d_rperm.alloc(nr) == hipSuccess && ctx->d_operm.alloc(no) == hipSuccess && ctx->d_tileKeys.alloc(1) == hipSuccess &&
+        hipMemsetAsync(ctx->d_rperm, 0, nr * sizeof(int), ctx->stream) == hipSuccess &&
+        hipMemsetAsync(ctx->d_operm, 0, no * sizeof(int), ctx->stream) == hipSuccess &&
+        hipMemsetAsync(ctx->d_tileKeys, 0, sizeof(TileKeys), ctx->stream) == hipSuccess)
+        return true;
+    (void)hipGetLastError();
+    ctx->d_rperm.reset(); ctx->d_operm.reset(); ctx->d_tileKeys.reset();
+    return false;
+}
+
 // Two launches per step: k_pass1 over all (rollout, obstacle) pairs, then the rollout-local tail.
 // (Measured and rejected: independent rollout groups on separate HIP streams for small batches --
 // planar7_1024x32 ran 9.0 M rollout-steps/s on one stream, 7.1 / 3.3 / 2.4 M on 2 / 4 / 8 -- and a two-half
@@ -128,6 +146,17 @@ static int enqueue_dense(omds_ctx* ctx, StepArgs& a) {
     // tail selects from that row of Dmin (row stride 0).  A row's chain never depends on its tile-mates and every tile shape
     // computes the same bits, so the step's results are those of the full launch (OMDS_FLAG_NATURAL_PASS1 keeps that one).
     const bool shared = ctx->shared_start && !(ctx->cfg.flags & OMDS_FLAG_NATURAL_PASS1);
+    // BLOCK-ORDERED TILES: every full launch of the compacting kernel forms its tiles from 16 (8) rollouts x 4 obstacles that are
+    // neighbours in a key order of the rollouts (formed again at every step, k_rollout_order) and of the obstacles (formed with
+    // the key units at the first full launch of the propagate, k_tile_pick, on slab 0 of an obstacle horizon): rows that fire alike
+    // share a tile, and the exact zero-skip multiplies fewer chunks.  A row's bits do not depend on its tile-mates
+    // (OMDS_FLAG_NATURAL_TILES keeps the rows in their order).  The ordering launches sit INSIDE the profiling bracket of pass 1:
+    // they are part of what the launch costs.
+    // Below OMDS_BLOCK_TILES_MIN_PAIRS the natural order stays: at 128 / 256 / 512 rollouts x 294 obstacles the block order ran 8.2 / 3.5 /
+    // 3.1 % slower (the ordering launch in front of a short pass 1), at 1024 and 4096 rollouts 3.6 / 5.0 % faster (EXPERIMENTS.md R12).
+    const bool blocks = !(ctx->cfg.flags & OMDS_FLAG_NATURAL_TILES) && omds_pass1_blocks_ok(ctx->mlp, N, ctx->n_obs) &&
+                        ((ctx->cfg.flags & OMDS_FLAG_BLOCK_TILES) || (long long)N * ctx->n_obs >= OMDS_BLOCK_TILES_MIN_PAIRS) && acquire_order_buffers(ctx);
+    bool picked = false;
     for (int i = 1; i <= a.H; ++i) {
         const bool one_row = shared && i == 1;
         const int B = one_row ? 1 : N;
@@ -135,8 +164,16 @@ static int enqueue_dense(omds_ctx* ctx, StepArgs& a) {
         {
             RoctxRange r1("TAG: evaluate NN_2 (forward pass)");
             if ((rc = prof_begin(ctx))) return rc;
-            omds_launch_pass1(ctx->stream, ctx->mlp, ctx->d_Fq, t.Fp, t.radius, ctx->n_obs, B,
-                              ctx->prm.ignored_links, ctx->d_Dmin);
+            if (blocks && !one_row) {
+                omds_launch_tile_order(ctx->stream, ctx->mlp, ctx->d_Fq, N, obstacle_tables(ctx, 1).Fp, ctx->n_obs, ctx->d_tileKeys,
+                                       ctx->d_rperm, ctx->d_operm, !picked);
+                picked = true;
+                omds_launch_pass1_blocks(ctx->stream, ctx->mlp, ctx->d_Fq, t.Fp, t.radius, ctx->n_obs, N, ctx->prm.ignored_links,
+                                         ctx->d_Dmin, ctx->d_rperm, ctx->d_operm);
+            } else {
+                omds_launch_pass1(ctx->stream, ctx->mlp, ctx->d_Fq, t.Fp, t.radius, ctx->n_obs, B,
+                                  ctx->prm.ignored_links, ctx->d_Dmin);
+            }
             if ((rc = prof_end(ctx, (int64_t)B * ctx->n_obs))) return rc;
         }
         RoctxRange r2("TAG: evaluate NN_3-5 + Modulation-propagation");
@@ -336,5 +373,26 @@ int omds_get_rollout_rows(omds_ctx* ctx, const int32_t* t, int count, float* all
         if (outs[i].dst && outs[i].X) std::memcpy(outs[i].dst, host.data() + offs[i], (size_t)count * outs[i].Hh * outs[i].X * 4);
     return OMDS_OK;
 }
+
+#ifdef OMDS_TEST_HOOKS
+// Test hooks (include/omds_test_tiles.h; libomds_hip_test.so only): the orders of the last block-ordered launch, the last step's Dmin
+int omds_test_tile_orders(omds_ctx* ctx, int32_t* rperm, int32_t* operm) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    REQUIRE(ctx->d_rperm && ctx->d_operm, OMDS_ERR_NOT_INITIALISED, "omds_test_tile_orders: no block-ordered launch has run on this context");
+    CK(hipSetDevice(ctx->dev));
+    CK(hipStreamSynchronize(ctx->stream));
+    if (rperm) CK(hipMemcpy(rperm, ctx->d_rperm, (size_t)ctx->cfg.n_traj * 4, hipMemcpyDeviceToHost));
+    if (operm) CK(hipMemcpy(operm, ctx->d_operm, (size_t)ctx->n_obs * 4, hipMemcpyDeviceToHost));
+    return OMDS_OK;
+}
+int omds_test_read_dmin(omds_ctx* ctx, float* dmin) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    REQUIRE(dmin && ctx->have_rollouts, OMDS_ERR_NOT_INITIALISED, "omds_test_read_dmin: no propagate has run on this context");
+    CK(hipSetDevice(ctx->dev));
+    CK(hipStreamSynchronize(ctx->stream));
+    CK(hipMemcpy(dmin, ctx->d_Dmin, (size_t)ctx->cfg.n_traj * ctx->n_obs * 4, hipMemcpyDeviceToHost));
+    return OMDS_OK;
+}
+#endif
 
 }  // extern "C"

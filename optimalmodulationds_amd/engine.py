@@ -411,6 +411,20 @@ class Engine:
         kernels; 0 = the launcher's own choice again."""
         self._ck(self.lib.omds_debug_force_tile_rows(int(tail_sel_rows), int(tail_rows)))
 
+    def test_tile_orders(self):
+        """Test hook (include/omds_test_tiles.h; needs ``lib=_lib.load_test_hooks()``): (rperm [n_traj], operm [n_obs]) of the last
+        block-ordered pass-1 launch (``flags``: ``_lib.FLAG_BLOCK_TILES`` forces that order, ``FLAG_NATURAL_TILES`` forbids it)."""
+        rperm, operm = np.zeros(self.N, np.int32), np.zeros(self.n_obs, np.int32)
+        self._ck(self.lib.omds_test_tile_orders(self.h, L.iptr(rperm), L.iptr(operm)))
+        return rperm, operm
+
+    def test_read_dmin(self):
+        """Test hook (include/omds_test_tiles.h; needs ``lib=_lib.load_test_hooks()``): the [n_traj, n_obs] pass-1 matrix the last
+        step of the last propagate left."""
+        out = np.zeros((self.N, self.n_obs), np.float32)
+        self._ck(self.lib.omds_test_read_dmin(self.h, L.fptr(out)))
+        return out
+
     def screen_mindist(self, q):
         q = L.f32(q).reshape(-1, self.n)
         out = np.zeros((q.shape[0], self.n_obs), np.float32)
