@@ -484,7 +484,9 @@ OMDS_API int omds_screen_stats(omds_ctx* ctx, int32_t* active, float* eps, float
  * omds_trainer_set_val_data (which = 1: train_sdf.py:84-86, 117-121; no weight copy, the optimizer state untouched); pred_out
  * [B, C] or NULL.  omds_trainer_get / set_optimizer_state: torch.optim.Adam's exp_avg (m) and exp_avg_sq (v) of every weight and
  * bias and the step count -- what train_sdf.py:130-138 saves as optimizer.state_dict() and a resumed run restores (arrays shaped
- * like the weights; get: a NULL array or entry is skipped).                                                               */
+ * like the weights; get: a NULL array or entry is skipped).  From a zero optimizer state (a new trainer, or after
+ * omds_trainer_set_weights) omds_trainer_step with lr = 0, beta1 = beta2 = 0 and eps > 0 leaves the weights as they are and
+ * exp_avg equal to the gradient bit for bit (exp_avg_sq its square): how tests/test_gpu_train_grad.py reads gradients.          */
 typedef struct omds_trainer omds_trainer;
 OMDS_API int omds_trainer_create(int device, int n_linear, const int32_t* dims, int act, omds_trainer** out);
 OMDS_API void omds_trainer_destroy(omds_trainer* tr);

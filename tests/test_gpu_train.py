@@ -4,7 +4,8 @@ tests/golden/train_sdf_planar2.npz (tools/make_golden_train.py), (b) the numpy o
 same ops at the shipped network size (30 -> 256 x 4 -> 9).  Bars: loss 1e-5 relative at every epoch; weight DELTAS (what the
 training moved) relative to the largest delta: 1e-4 after 10 epochs, 2e-3 after 100 -- Adam divides by sqrt(v): where a
 gradient is at rounding level two fp32 evaluations step in different directions, and the numpy restatement itself is
-9e-4 from the torch run after 100 epochs (tests/test_oracle_golden.py)."""
+9e-4 from the torch run after 100 epochs (tests/test_oracle_golden.py).  These are bars on whole training runs; the bars on a single
+gradient (every dW and db against float64, on every kernel route) and on a single Adam step are in tests/test_gpu_train_grad.py."""
 import numpy as np
 import pytest
 
