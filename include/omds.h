@@ -170,9 +170,11 @@ OMDS_API int omds_set_obstacles(omds_ctx* ctx, const float* xyzr, int n_obs);
  *                           *mode_out = 0 none (every slab is the static scene), 1 motion, 2 explicit.
  * omds_set_obstacles CLEARS the horizon (MPPI.update_obstacles keeps its meaning); a setter before any scene is
  * OMDS_ERR_NOT_INITIALISED.  The tables (H * max_obs * 37 floats: 2.8 MB at H = 32, 588 spheres) are allocated at the first setter and
- * grow with the other obstacle buffers.  SCREENING: while a horizon is set omds_propagate runs the all-fp32 step whatever mode was
- * requested -- the bound eps was calibrated on the static scene and the audit takes one scene for all steps; omds_screen_stats
- * reports active = 0, the calibration is kept and screening resumes when the horizon is cleared.  Networks wider than 256:
+ * grow with the other obstacle buffers.  SCREENING: by default a horizon puts omds_propagate on the all-fp32 step whatever mode was
+ * requested; omds_screen_stats reports active = 0, the calibration is kept and screening resumes when the horizon is cleared.
+ * With omds_set_screening_horizon(ctx, 1) (below, beside omds_set_screening) a propagate with a horizon is screened like a static
+ * one: every step's fp16 pass, re-evaluation, sweep and audit rows read that step's slab (fp16 tables per slab, H * max_obs * 64
+ * bytes more, twice that for skip-connection networks), and the bound is measured on three slabs.  Networks wider than 256:
  * omds_propagate returns OMDS_ERR_UNSUPPORTED while a horizon is set.                                                              */
 OMDS_API int omds_obstacle_horizon_predict(const float* xyzr, const float* vel, int n_obs, int horizon, float dt, float* out);
 OMDS_API int omds_set_obstacle_motion(omds_ctx* ctx, const float* vel);
@@ -390,9 +392,20 @@ OMDS_API int omds_apply_update(int n_kernels, int n_dof, int horizon, const floa
  *     (tools/studies/reorder_cost.py), and the propagate after the second re-sort carries a sweep (+1 ms).  A translating
  *     scene does not recalibrate; a caller who SWAPS scenes at rate and cannot take the spike fixes the bound (eps > 0) or
  *     switches screening off for those iterations;
+ *     UNDER AN OBSTACLE HORIZON (omds_set_screening_horizon on): the same states are measured against slabs 0, (H-1)/2 and H-1
+ *     (duplicates once), each on its own fp32 / fp16 tables, and eps = 6 x the maximum over them; the re-sort stays on slab 0.  The
+ *     calibration records slab 0, the LAST slab and that a horizon was in effect.  A screened propagate with a horizon first
+ *     discards a calibration that was made without one, or whose recorded last slab differs from the present one by the test
+ *     above (count, radius, 0.1 per coordinate; the last slab is omds_obstacle_horizon_predict's, or the caller's table's) -- and
+ *     so recalibrates inside that propagate.  Hence: a scene that keeps translating at constant velocities recalibrates no more
+ *     often than a static translating one; a bound set by the caller (eps > 0) is never recalibrated; a calibration made under
+ *     a horizon also covers the static scene, so clearing the horizon does not recalibrate.  LATENCY: the measuring part (the
+ *     fp32 and the f16 pass) then runs on three slabs instead of one; the cost of the first screened propagate under a horizon
+ *     has not been measured yet (tools/studies/screen_horizon_cost.py measures it);
  *   - every step of every propagate: |Da - D| of every candidate; Da - D of the AUDIT rows, a pseudo-random 1-in-`one_in`
  *     sample (another one every step) of the pairs that are not candidates, re-evaluated in fp32 by one launch at the end
- *     of the horizon loop (k_audit); the slack of every rollout (tau - exact k-th smallest >= eps).
+ *     of the horizon loop (k_audit; under a horizon every audit row against the slab of its own step, still one launch); the
+ *     slack of every rollout (tau - exact k-th smallest >= eps).
  *   - every 32nd screened propagate (omds_set_screening_sweep): a SWEEP -- all N x O pairs of the propagate's last horizon
  *     step (soak runs: of EVERY horizon step) in fp32 beside all their screening values, max |Da - D| over every one of them,
  *     and the distribution of Da - D over the pairs that were not candidates (omds_screen_sweep_hist): the quantity the
@@ -416,6 +429,13 @@ OMDS_API int omds_apply_update(int n_kernels, int n_dof, int horizon, const floa
  * seen since the last calibration, suspended flag, calibrations run since creation.                                   */
 OMDS_API int omds_set_screening(omds_ctx* ctx, int mode, float eps);
 OMDS_API int omds_set_screening_audit(omds_ctx* ctx, int one_in);
+/* Screening while an obstacle horizon is set.  on = 0 (default at creation): as before -- a horizon puts the context on the
+ * all-fp32 step and omds_screen_stats reports active = 0.  on = 1: a propagate with a horizon (motion or explicit table, with or
+ * without the moving frame) is screened under the same mode / eps / audit / sweep settings and the same contract as a static one.
+ * *in_effect = 1 when the next propagate would run a screened route with a horizon set (NULL = skip).  Where horizon * max_obs
+ * rounded up to 16 reaches 2^24 rows the audit sample is not taken (as for n_traj * horizon * n_obs >= 2^31).                     */
+OMDS_API int omds_set_screening_horizon(omds_ctx* ctx, int on);
+OMDS_API int omds_get_screening_horizon(omds_ctx* ctx, int32_t* on, int32_t* in_effect);
 /* every = 0: no sweeps; default 32.  all_steps = 0: a sweeping propagate checks its last horizon step (0.5 % of the run at the
  * default period); 1: every horizon step (a soak / qualification mode: each step then also runs the fp32 pass 1, so the propagate
  * is slower than the unscreened one).  Stats: the setting, sweeps (swept steps) run since creation, largest |Da - D| a sweep saw

@@ -119,6 +119,8 @@ SIGNATURES = {
                                                F32P]),
     "omds_set_screening": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
     "omds_set_screening_audit": (C.c_int, [C.c_void_p, C.c_int]),
+    "omds_set_screening_horizon": (C.c_int, [C.c_void_p, C.c_int]),
+    "omds_get_screening_horizon": (C.c_int, [C.c_void_p, I32P, I32P]),
     "omds_screen_audit_stats": (C.c_int, [C.c_void_p, I32P, C.POINTER(C.c_double), F32P, I32P, C.POINTER(C.c_int64)]),
     "omds_screen_fallback_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "omds_screen_order_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), I32P, C.c_int]),
@@ -168,9 +170,13 @@ TILE_HOOK_SIGNATURES = {
     "omds_test_tile_orders": (C.c_int, [C.c_void_p, I32P, I32P]),
     "omds_test_read_dmin": (C.c_int, [C.c_void_p, F32P]),
 }
+# include/omds_test_horizon.h: the hook of screening under an obstacle horizon, in the test library likewise
+HORIZON_HOOK_SIGNATURES = {
+    "omds_test_screen_corrupt_slab": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float]),
+}
 TEST_LIB_PATH = os.path.join(_HERE, "csrc", "libomds_hip_test.so")
 
-ABI_VERSION = 503      # omds_version() of the library this binding was written against
+ABI_VERSION = 504      # omds_version() of the library this binding was written against
 _libs = {}             # path -> bound CDLL
 
 
@@ -226,7 +232,7 @@ def load_test_hooks():
     """libomds_hip_test.so: the product's objects plus the hooks of include/omds_test.h (damage the screening inputs, force a tile
     shape, the trainer's general GEMM, the host half of omds_set_mlp_ex, the encoding's sin / cos).  For tests only:
     ``Engine(..., lib=load_test_hooks())``."""
-    return load(TEST_LIB_PATH, dict(TEST_HOOK_SIGNATURES, **TILE_HOOK_SIGNATURES))
+    return load(TEST_LIB_PATH, dict(TEST_HOOK_SIGNATURES, **TILE_HOOK_SIGNATURES, **HORIZON_HOOK_SIGNATURES))
 
 
 def f32(a, shape=None):

@@ -158,6 +158,18 @@ inline ObsTables obstacle_tables(const omds_ctx* ctx, int step = 0) {
     const size_t r = (size_t)(step - 1) * ctx->hz_ld;
     return {ctx->d_hzFp + r * OMDS_FROW, ctx->d_hzRadius + r, ctx->d_hzObs + r * 4};
 }
+// ... and what the screening kernel reads beside them: the fp16 table of the obstacle points with its row capacity, the radii, and
+// the network descriptor carrying the skip-connection operand (MlpDev::scrP) of the same table.  Step i of a propagate with a
+// horizon: slab i - 1 of d_hzFpH / d_hzFpS / d_hzRadius (built by prepare_obstacle_horizon while screening over the horizon is on)
+struct ScreenTables { const uint16_t* FpH; int ld; const float* radius; MlpDev m; };
+inline ScreenTables screen_tables(const omds_ctx* ctx, int step = 0) {
+    if (ctx->hz_mode == 0 || step < 1) return {ctx->d_FpH, ctx->cfg.max_obs, ctx->d_radius, ctx->mlp};
+    const size_t r = (size_t)(step - 1) * ctx->hz_ld;
+    ScreenTables t{ctx->d_hzFpH + r * 32, ctx->hz_ld, ctx->d_hzRadius + r, ctx->mlp};
+    if (t.m.scrP) t.m.scrP = ctx->d_hzFpS + r * 32;
+    return t;
+}
+void obstacle_horizon_last_slab(const omds_ctx* ctx, std::vector<float>& out);   // [n_obs][4] the scene step H sees, on the host
 int alloc_obstacle_horizon(omds_ctx* ctx);             // the tables for cfg.horizon x cfg.max_obs (first setter; grow_obstacle_capacity)
 void clear_obstacle_horizon(omds_ctx* ctx);            // omds_set_obstacles: back to the static scene
 void obstacle_horizon_network_changed(omds_ctx* ctx);  // omds_set_mlp*: the feature slabs are derived again at the next propagate
@@ -170,7 +182,7 @@ void release_network(omds_ctx* ctx);   // frees omds_ctx::mlp_allocs (omds_destr
 int enqueue_network(omds_ctx* ctx, const float* qT, int ldq, int B, const ObsTables& t);
 
 // ---- screening.hip: the controller of the screened step -----------------------------------------------------------------------
-bool screen_wanted(omds_ctx* ctx);   // mode, packs, not suspended: this propagate should screen
+bool screen_wanted(omds_ctx* ctx);   // mode, packs, not suspended, no horizon unless screening over it is on: this propagate should screen
 // calibrates when no bound stands (q_center: the start state of the propagate); *usable = a bound exists and screening is not suspended
 int screen_calibrated(omds_ctx* ctx, const float* q_center, bool* usable);
 // What screen_begin_propagate hands the horizon loop of the screened routes
@@ -195,5 +207,6 @@ int screened_verdict(omds_ctx* ctx, StepArgs& a);
 // ---- propagate.hip ------------------------------------------------------------------------------------------------------------
 enum class StepRoute { Unfused, SmallScene, Dense, Emit, ScreenList, ScreenMatrix };
 bool small_step_wanted(omds_ctx* ctx);
+bool fused_step_available(const omds_ctx* ctx);   // the fused tail kernels take this context (else Unfused, never screened)
 StepRoute choose_route(omds_ctx* ctx, bool screen_requested);
 int enqueue_rollouts(omds_ctx* ctx, StepArgs& a, StepRoute route);

@@ -8,7 +8,7 @@ thread_local std::string g_create_err;
 
 extern "C" {
 
-int omds_version(void) { return 503; }
+int omds_version(void) { return 504; }
 
 int omds_device_count(int32_t* count) {
     if (!count) return OMDS_ERR_INVALID_ARG;
@@ -204,7 +204,7 @@ static int grow_obstacle_capacity(omds_ctx* ctx, int n_obs) {
     const bool had_FpS = ctx->d_FpS != nullptr, had_horizon = ctx->d_hzFp != nullptr;
     ctx->d_obs.reset(); ctx->d_Fp.reset(); ctx->d_radius.reset(); ctx->d_FpH.reset(); ctx->d_Dmin.reset();
     ctx->d_rowlist.reset(); ctx->d_listDa.reset(); ctx->d_FpS.reset();
-    ctx->d_hzVel.reset(); ctx->d_hzObs.reset(); ctx->d_hzRadius.reset(); ctx->d_hzFp.reset();
+    ctx->d_hzVel.reset(); ctx->d_hzObs.reset(); ctx->d_hzRadius.reset(); ctx->d_hzFp.reset(); ctx->d_hzFpH.reset(); ctx->d_hzFpS.reset();
     ctx->hz_ld = 0;
     CK(ctx->d_obs.alloc(Om * 4));
     CK(ctx->d_Fp.alloc(std::max(Om, rows2) * OMDS_FROW));

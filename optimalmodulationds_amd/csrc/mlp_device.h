@@ -400,13 +400,18 @@ struct OmdsDivisor {
 // pass-2 distance, arg-min link, ReLU masks -- for EVERY pair, indexed by the pair (ex->dr / amin / mask [row]): the forward of
 // the k rows a rollout ends up selecting has been computed here anyway, so the tail selects from Dmin and runs the backward only.
 // The arithmetic of a row is the same in all forms and independent of the other rows of the tile: bit-identical results.
-template <int MT, int MR, int NR, int ACT, int MODE = 0>
+// SLAB (the audit sample of a propagate with an obstacle horizon, MODE 4 only): Fp / radius hold one slab of slab_ld rows per
+// horizon step and the pair's rollout index tt runs over all steps' states, ndiv.div(tt) = tt / N being its step: the obstacle row
+// is (tt / N) * slab_ld + o.  A template flag: without it the function is the code it was.
+template <int MT, int MR, int NR, int ACT, int MODE = 0, bool SLAB = false>
 __device__ __forceinline__ void pass1_tile(const MlpDev& m, float* smem, const float* __restrict__ Fq,
                                            const float* __restrict__ Fp, const float* __restrict__ radius, int O,
                                            long long total_rows, uint32_t ignored, float* __restrict__ Dmin,
                                            const long long row0, const OmdsDivisor odiv,
                                            const int* __restrict__ rowlist = nullptr, unsigned* maxerr_bits = nullptr,
-                                           const ExactOut* ex = nullptr) {
+                                           const ExactOut* ex = nullptr, [[maybe_unused]] const OmdsDivisor ndiv = OmdsDivisor{0u, 0},
+                                           [[maybe_unused]] const unsigned slab_ld = 0u) {
+    static_assert(!SLAB || MODE == 4, "obstacle slabs per listed row: the audit sample only");
     constexpr bool LIST = MODE == 1 || MODE == 3 || MODE == 4 || MODE == 5, EMIT = MODE == 1 || MODE == 2 || MODE == 6, DERIV = MODE == 5;
     constexpr bool EMITY = EMIT || DERIV;   // pass 2's distance and arg-min link per row (ex->dr, ex->amin)
     static_assert(!DERIV || MT == 16, "the derivative hand-over is written for the 16-row tiles of k_exact");
@@ -483,7 +488,8 @@ __device__ __forceinline__ void pass1_tile(const MlpDev& m, float* smem, const f
                     if (ok[h]) {
                         idx = __builtin_amdgcn_readfirstlane(rowlist[row0 + wv + (it + h) * G::NW]);
                         const unsigned tt = odiv.div((unsigned)idx);
-                        const int oo = (int)((unsigned)idx - tt * (unsigned)O);
+                        int oo = (int)((unsigned)idx - tt * (unsigned)O);
+                        if constexpr (SLAB) oo += (int)(ndiv.div(tt) * slab_ld);   // the row of the step's slab (wave-uniform, like tt)
                         offq[h] = (int)(tt * (OMDS_FROW * 4)); offp[h] = oo * (OMDS_FROW * 4);
                         rad = radius[oo];
                     }
@@ -526,7 +532,9 @@ __device__ __forceinline__ void pass1_tile(const MlpDev& m, float* smem, const f
                     unsigned pair;
                     if constexpr (LIST) pair = (unsigned)rowIdx[r];
                     else pair = (unsigned)row0 + (unsigned)r;
-                    const unsigned t = odiv.div(pair), o = pair - t * (unsigned)O;
+                    const unsigned t = odiv.div(pair);
+                    unsigned o = pair - t * (unsigned)O;
+                    if constexpr (SLAB) o += ndiv.div(t) * slab_ld;
                     v = __builtin_bit_cast(uint32_t, Fq[(size_t)t * OMDS_FROW + f]) | __builtin_bit_cast(uint32_t, Fp[(size_t)o * OMDS_FROW + f]);
                 }
                 reinterpret_cast<uint32_t*>(Hs)[r * LDH + omds_kpos(c0 + f)] = v;

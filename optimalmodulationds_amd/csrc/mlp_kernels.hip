@@ -82,11 +82,14 @@ __global__ __launch_bounds__(256) void k_obstacle_features(MlpDev m, const float
 // The same tables for every slab of an obstacle horizon (omds.h: omds_set_obstacle_motion / omds_set_obstacle_horizon): row
 // h * ld + o of obsT / radiusT / FpT is obstacle o as step h + 1 of a propagate sees it.  vel != nullptr: the position is
 // xyzr + (h dt) vel, ONE fp32 product and one fmaf (slab 0: xyzr itself), the arithmetic of omds_obstacle_horizon_predict; a
-// planar-point network (po = 2) keeps z.  vel == nullptr: obsT holds the caller's spheres.  No fp16 tables: a propagate with a
-// horizon is not screened.
+// planar-point network (po = 2) keeps z.  vel == nullptr: obsT holds the caller's spheres.
+// FpHT / scrPT (optional; screening over the horizon, omds_set_screening_horizon): the fp16 tables k_obstacle_features writes, one
+// per slab -- [H][4 pieces][ld][8], slab h being an omds_screen_fidx / omds_screen_sidx table of row capacity ld at element offset
+// h * 32 ld -- from the same p, sin p, cos p rounded to fp16: slab 0 holds the bits of the static tables.
 __global__ __launch_bounds__(256) void k_obstacle_horizon_features(MlpDev m, const float* __restrict__ xyzr, const float* __restrict__ vel,
                                                                    float dt, int H, int O, int ld, float* __restrict__ obsT,
-                                                                   float* __restrict__ radiusT, float* __restrict__ FpT) {
+                                                                   float* __restrict__ radiusT, float* __restrict__ FpT,
+                                                                   _Float16* __restrict__ FpHT, _Float16* __restrict__ scrPT) {
     const int r = blockIdx.x * 64 + (threadIdx.x >> 2), c = threadIdx.x & 3, n = m.n_dof, d = m.d, po = d - n;
     if (r >= H * O) return;
     const int h = r / O, o = r - h * O;
@@ -104,9 +107,22 @@ __global__ __launch_bounds__(256) void k_obstacle_horizon_features(MlpDev m, con
     }
     if (c == 3) { radiusT[row] = p; return; }
     if (c >= po) return;
+    const float sp = omds_sinf(p), cp = omds_cosf(p);
     FpT[row * OMDS_FROW + n + c] = p;
-    FpT[row * OMDS_FROW + d + n + c] = omds_sinf(p);
-    FpT[row * OMDS_FROW + 2 * d + n + c] = omds_cosf(p);
+    FpT[row * OMDS_FROW + d + n + c] = sp;
+    FpT[row * OMDS_FROW + 2 * d + n + c] = cp;
+    if (FpHT) {
+        _Float16* F = FpHT + (size_t)h * 32 * ld;
+        F[omds_screen_fidx(n + c, o, ld)] = (_Float16)p;
+        F[omds_screen_fidx(d + n + c, o, ld)] = (_Float16)sp;
+        F[omds_screen_fidx(2 * d + n + c, o, ld)] = (_Float16)cp;
+        if (scrPT) {
+            _Float16* S = scrPT + (size_t)h * 32 * ld;
+            S[omds_screen_sidx(n + c, 3 * d, o, ld)] = (_Float16)p;
+            S[omds_screen_sidx(d + n + c, 3 * d, o, ld)] = (_Float16)sp;
+            S[omds_screen_sidx(2 * d + n + c, 3 * d, o, ld)] = (_Float16)cp;
+        }
+    }
 }
 
 template <int MT, int MR, int NR, int ACT>
@@ -319,10 +335,10 @@ void omds_launch_obstacle_features(hipStream_t s, const MlpDev& m, const float* 
 }
 
 void omds_launch_obstacle_horizon_features(hipStream_t s, const MlpDev& m, const float* xyzr, const float* vel, float dt, int H, int O,
-                                           int ld, float* obsT, float* radiusT, float* FpT) {
+                                           int ld, float* obsT, float* radiusT, float* FpT, uint16_t* FpHT, uint16_t* scrPT) {
     if (H <= 0 || O <= 0) return;
     hipLaunchKernelGGL(k_obstacle_horizon_features, dim3((unsigned)(((long long)H * O + 63) / 64)), dim3(256), 0, s, m, xyzr, vel, dt, H, O, ld,
-                       obsT, radiusT, FpT);
+                       obsT, radiusT, FpT, reinterpret_cast<_Float16*>(FpHT), reinterpret_cast<_Float16*>(scrPT));
 }
 
 template <int MT, int MR, int NR, int ACT>

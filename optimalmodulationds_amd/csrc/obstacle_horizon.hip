@@ -13,17 +13,36 @@ static inline float moved(float x, float v, int h, float dt) {
     return fmaf(v, t, x);
 }
 
+// The fp16 slab tables of the screened routes exist only where they can be used: screening over the horizon switched on
+// (omds_set_screening_horizon) and a network with a screening pack; d_hzFpS only for its skip-connection form (MlpDev::scrP).
+static bool horizon_fp16_wanted(const omds_ctx* ctx) { return ctx->scr.over_horizon && ctx->scr.ok && !ctx->wide.on; }
+
+// (re-)allocates what of the fp16 tables is wanted and missing; the caller has synchronised the stream or is about to rebuild
+static int alloc_horizon_fp16(omds_ctx* ctx) {
+    if (!horizon_fp16_wanted(ctx) || ctx->hz_ld <= 0) return OMDS_OK;
+    const size_t count = (size_t)ctx->cfg.horizon * ctx->hz_ld * 32;
+    const bool skip = ctx->mlp.scrP != nullptr;
+    if (ctx->d_hzFpH.count() >= count && (!skip || ctx->d_hzFpS.count() >= count)) return OMDS_OK;
+    CK(hipStreamSynchronize(ctx->stream));
+    if (ctx->d_hzFpH.count() < count) CK(ctx->d_hzFpH.alloc(count));
+    if (skip && ctx->d_hzFpS.count() < count) CK(ctx->d_hzFpS.alloc(count));
+    ctx->hz_zero = true;
+    if (ctx->hz_mode) ctx->hz_dirty = true;
+    return OMDS_OK;
+}
+
 int alloc_obstacle_horizon(omds_ctx* ctx) {
     const size_t H = ctx->cfg.horizon, ld = ((size_t)ctx->cfg.max_obs + 15) / 16 * 16;
     REQUIRE(H * ld < ((size_t)1 << 31), OMDS_ERR_INVALID_ARG, "obstacle horizon: horizon * max_obs must stay below 2^31");
     ctx->hz_ld = 0;
+    ctx->d_hzFpH.reset(); ctx->d_hzFpS.reset();   // sized by ld: allocated again below when they are wanted
     CK(ctx->d_hzVel.alloc(ld * 3));
     CK(ctx->d_hzObs.alloc(H * ld * 4));
     CK(ctx->d_hzRadius.alloc(H * ld));
     CK(ctx->d_hzFp.alloc(H * ld * OMDS_FROW));
     ctx->hz_ld = (int)ld;
     ctx->hz_zero = true;
-    return OMDS_OK;
+    return alloc_horizon_fp16(ctx);
 }
 
 void clear_obstacle_horizon(omds_ctx* ctx) {
@@ -41,11 +60,17 @@ void obstacle_horizon_network_changed(omds_ctx* ctx) {
 int prepare_obstacle_horizon(omds_ctx* ctx) {
     if (ctx->hz_mode == 0) return OMDS_OK;
     if (ctx->hz_mode == 1 && ctx->hz_dt != ctx->prm.dt) ctx->hz_dirty = true;
+    int rc;
+    if ((rc = alloc_horizon_fp16(ctx))) return rc;   // screening over the horizon was switched on, or the network brought a pack: dirty
     if (!ctx->hz_dirty) return OMDS_OK;
     REQUIRE(ctx->have_mlp, OMDS_ERR_NOT_INITIALISED, "distance network not set (omds_set_mlp)");
     const int H = ctx->cfg.horizon, O = ctx->n_obs, ld = ctx->hz_ld;
+    const bool fp16 = horizon_fp16_wanted(ctx) && ctx->d_hzFpH;
+    uint16_t* FpS = (fp16 && ctx->mlp.scrP) ? ctx->d_hzFpS.get() : nullptr;
     if (ctx->hz_zero) {   // the joints' slots and the padding stay zero
         CK(hipMemsetAsync(ctx->d_hzFp, 0, ctx->d_hzFp.bytes(), ctx->stream));
+        if (ctx->d_hzFpH) CK(hipMemsetAsync(ctx->d_hzFpH, 0, ctx->d_hzFpH.bytes(), ctx->stream));
+        if (ctx->d_hzFpS) CK(hipMemsetAsync(ctx->d_hzFpS, 0, ctx->d_hzFpS.bytes(), ctx->stream));
         ctx->hz_zero = false;
     }
     const float* vel = nullptr;
@@ -55,12 +80,28 @@ int prepare_obstacle_horizon(omds_ctx* ctx) {
     } else {
         CK(hipMemcpy2DAsync(ctx->d_hzObs, (size_t)ld * 16, ctx->hz_table.data(), (size_t)O * 16, (size_t)O * 16, H, hipMemcpyHostToDevice, ctx->stream));
     }
-    omds_launch_obstacle_horizon_features(ctx->stream, ctx->mlp, ctx->d_obs, vel, ctx->prm.dt, H, O, ld, ctx->d_hzObs, ctx->d_hzRadius, ctx->d_hzFp);
+    omds_launch_obstacle_horizon_features(ctx->stream, ctx->mlp, ctx->d_obs, vel, ctx->prm.dt, H, O, ld, ctx->d_hzObs, ctx->d_hzRadius, ctx->d_hzFp,
+                                          fp16 ? ctx->d_hzFpH.get() : nullptr, FpS);
     CK(hipGetLastError());
     CK(hipStreamSynchronize(ctx->stream));   // the copies above read pageable host memory of the context
     ctx->hz_dt = ctx->prm.dt;
     ctx->hz_dirty = false;
     return OMDS_OK;
+}
+
+// The last slab of the horizon on the host, [n_obs][4]: what the screening calibration records and compares (screening.hip).  The
+// arithmetic of the tables: omds_obstacle_horizon_predict's for a motion (a planar-point network keeps z), the caller's for a table.
+void obstacle_horizon_last_slab(const omds_ctx* ctx, std::vector<float>& out) {
+    const int H = ctx->cfg.horizon, O = ctx->n_obs;
+    if (ctx->hz_mode == 2) {
+        out.assign(ctx->hz_table.begin() + (size_t)(H - 1) * O * 4, ctx->hz_table.begin() + (size_t)H * O * 4);
+        return;
+    }
+    out = ctx->obs_now;
+    if (ctx->hz_mode != 1) return;
+    const int po = ctx->mlp.d - ctx->mlp.n_dof;
+    for (int o = 0; o < O; ++o)
+        for (int c = 0; c < po && c < 3; ++c) out[(size_t)o * 4 + c] = moved(out[(size_t)o * 4 + c], ctx->hz_vel[(size_t)o * 3 + c], H - 1, ctx->prm.dt);
 }
 
 // what both setters need before they touch the context: a scene, and the tables

@@ -237,6 +237,11 @@ struct ScreenHost {
     bool suspended = false;      // three propagates in a row fell back to fp32: the fp32 step until the next calibration
     int consec = 0;              // consecutive fallbacks
     std::vector<float> obs_cal;  // the obstacle set the bound was calibrated against (scene_changed compares)
+    // screening while an obstacle horizon is set (omds_set_screening_horizon): the calibration then measures slabs 0, (H-1)/2 and
+    // H-1 and remembers the last one (horizon_changed compares)
+    bool over_horizon = false;   // the caller's switch; off: a horizon puts the context on the all-fp32 step
+    bool cal_horizon = false;    // the standing calibration was measured with a horizon in effect
+    std::vector<float> last_cal; // [n_obs][4] the last slab it was measured on
     // statistics
     double rows = 0.0, steps = 0.0, audit_rows = 0.0;   // since the last omds_prof_reset: candidate rows, (rollout, step)s, audit rows
     long long fallbacks = 0;     // since creation
@@ -291,6 +296,8 @@ struct ScreenHost {
         ok = true; W = std::move(W_); b = std::move(b_); out_dims = std::move(dims_);
     }
     void scene_changed(const float* xyzr, int n_obs);   // omds_set_obstacles: forgets the calibration when the scene left what it was measured on
+    // a screened propagate with a horizon: forgets a calibration made without one, or one whose last slab is not `last` [n_obs][4] any more
+    void horizon_changed(const float* last, int n_obs);
     void links_changed() { if (!eps_fixed) forget_calibration(); }   // another set of links enters the pass-1 minimum
     void reset_stats() { rows = 0.0; steps = 0.0; audit_rows = 0.0; }   // omds_prof_reset
 };
@@ -343,7 +350,7 @@ struct omds_ctx {
     // obstacle horizon (obstacle_horizon.hip): step i of a propagate reads slab i - 1 of these instead of d_obs / d_radius / d_Fp
     int hz_mode = 0;             // 0 none (every step sees the static tables), 1 constant velocities, 2 the caller's table
     bool hz_dirty = false;       // the tables do not hold what the next propagate needs (velocities, dt or the network changed)
-    bool hz_zero = false;        // d_hzFp has to be zeroed before it is written (a new allocation, or another network's slot assignment)
+    bool hz_zero = false;        // d_hzFp (and the fp16 tables) have to be zeroed before they are written (a new allocation, or another network's slot assignment)
     float hz_dt = 0.f;           // params.dt the motion tables were built with
     int hz_ld = 0;               // rows per slab (max_obs rounded up to 16)
     std::vector<float> hz_vel;   // [n_obs][3] host copy of the velocities (mode 1)
@@ -352,6 +359,8 @@ struct omds_ctx {
     DevBuf<float> d_hzObs;       // [H][hz_ld][4]
     DevBuf<float> d_hzRadius;    // [H][hz_ld]
     DevBuf<float> d_hzFp;        // [H][hz_ld][OMDS_FROW]
+    DevBuf<uint16_t> d_hzFpH;    // [H][4][hz_ld][8] fp16 screening inputs per slab (only while scr.over_horizon and a screening pack exist)
+    DevBuf<uint16_t> d_hzFpS;    // ... and the concatenation operand of skip-connection networks (MlpDev::scrP per slab)
     // the moving frame (omds_set_obstacle_frame): a preference; it acts on a propagate while hz_mode == 1
     bool frame_on = false;
     float frame_max = 1.f;       // clamp of the approach speed (the unit speed rollout velocities are normalised to)
@@ -461,9 +470,10 @@ void omds_launch_obstacle_features(hipStream_t s, const MlpDev& m, const float* 
 // The obstacle tables of H horizon slabs of ld rows each: obsT [H][ld][4], radiusT [H][ld], FpT [H][ld][OMDS_FROW] (zeroed once for
 // the network's d, like Fp).  vel != nullptr: slab h holds xyzr [O][4] moved by h * dt * vel [O][3] (omds.h:
 // omds_obstacle_horizon_predict; planar-point networks keep z); vel == nullptr: obsT already holds the caller's spheres and only
-// radiusT / FpT are derived from it
+// radiusT / FpT are derived from it.  FpHT / scrPT (optional): the fp16 screening tables of every slab, [H][4][ld][8] (zeroed once
+// likewise; scrPT only for skip-connection networks): slab h is an omds_screen_fidx / omds_screen_sidx table of capacity ld
 void omds_launch_obstacle_horizon_features(hipStream_t s, const MlpDev& m, const float* xyzr, const float* vel, float dt, int H, int O,
-                                           int ld, float* obsT, float* radiusT, float* FpT);
+                                           int ld, float* obsT, float* radiusT, float* FpT, uint16_t* FpHT = nullptr, uint16_t* scrPT = nullptr);
 void omds_launch_pass1(hipStream_t s, const MlpDev& m, const float* Fq, const float* Fp, const float* radius,
                        int O, int B, uint32_t ignored_links, float* Dmin);
 // The block-ordered full launch of the compacting kernel (k_pass1_dyn_blk): a 64-row tile is 16 consecutive entries of rperm x 4
@@ -527,8 +537,11 @@ void omds_launch_pass1_emit(hipStream_t s, const MlpDev& m, const float* Fq, con
                             int O, int B, uint32_t ignored, float* Dmin, const ExactOut& ex);
 
 void omds_launch_select(hipStream_t s, const float* Dmin, int B, int O, const SelectSink& sel);
+// slab_ld > 0 (an obstacle horizon): Fp / radius hold one slab of slab_ld rows per horizon step, and a listed row of step i (rollout
+// index (i - 1) * N + t of FqAll) reads its obstacle from slab i - 1 (k_audit_slabs); needs H * slab_ld * OMDS_FROW * 4 < 2^31
 void omds_launch_audit(hipStream_t s, const MlpDev& m, const float* FqAll, const float* Fp, const float* radius, int O,
-                       uint32_t ignored, const int* rows, const float* da, const int* total, int cap, unsigned* maxerr_bits);
+                       uint32_t ignored, const int* rows, const float* da, const int* total, int cap, unsigned* maxerr_bits,
+                       int N = 0, int slab_ld = 0);
 // calibration of the screening bound on the device: the batch of states, and max |x - y| into *out_bits (float bits, atomicMax)
 void omds_launch_calib_states(hipStream_t s, float* qT, int B, int n, const float* lo, const float* hi, const float* center,
                               const float* trajT, int N, int H, unsigned seed);

@@ -66,7 +66,9 @@ static bool acquire_deriv_buffer(omds_ctx* ctx) {
 //                                                                            k_pass1 over ONE rollout's rows, enqueue_dense)
 //
 // Both screened routes add, per propagate, the sweep of a step when one is due (k_pass1 + k_screen + k_sweep_hist) and k_audit
-// behind the loop (screening.hip).  choose_route acquires the lazily allocated buffers the route it is about to pick needs, and
+// behind the loop (screening.hip).  Under an obstacle horizon every route reads slab i - 1 at step i (obstacle_tables); the screened
+// routes only run then when the caller switched screening over the horizon on (screen_wanted) and read the slab's fp16 tables too
+// (screen_tables), as do the sweep and -- per listed row -- k_audit_slabs.  choose_route acquires the lazily allocated buffers the route it is about to pick needs, and
 // picks the next one down when they cannot be had.
 //
 // Emit: SMALL BATCHES of the all-fp32 step of a ReLU network run without a second forward: k_pass1 in its emitting mode leaves, for
@@ -75,7 +77,7 @@ static bool acquire_deriv_buffer(omds_ctx* ctx) {
 // dependent GEMMs: integrator tick (N = 1) 0.66 -> 0.56 ms per 10-step propagate, planner defaults (N = 40) 1.02 -> 0.95.
 // Up to 24 576 pairs only: the masks cost the pass-1 epilogue 32 ballots + 64 single-lane LDS stores per wave and layer, which
 // a throughput-bound launch cannot hide (k_pass1 +18 % at 1024 x 294, the step 29.5 -> 33.3 ms: EXPERIMENTS.md B.5).
-static bool fused_step_available(const omds_ctx* ctx) {
+bool fused_step_available(const omds_ctx* ctx) {
     return !(ctx->cfg.flags & OMDS_FLAG_UNFUSED_STEP) && omds_tail_supported(ctx->cfg.n_dof, ctx->cfg.n_closest) && ctx->seds_G == 0 && !ctx->wide.on;
 }
 
@@ -220,24 +222,28 @@ static int enqueue_screened(omds_ctx* ctx, StepArgs& a, bool list_tail) {
     for (int i = 1; i <= H; ++i) {
         float* fq_i = p.fq0 + (size_t)(i - 1) * p.fq_slab;
         float* fq_next = p.fq0 + (size_t)std::min(i, H - 1) * p.fq_slab;
+        // slab i - 1 of an obstacle horizon, fp32 and fp16 (screening over the horizon, omds_set_screening_horizon); else the static scene.
+        // The rows of the candidate list name the caller's obstacle index in either case (the moving frame's d_hzVel is indexed by it)
+        const ObsTables t = obstacle_tables(ctx, i);
+        const ScreenTables st = screen_tables(ctx, i);
         {
             RoctxRange r1("TAG: evaluate NN_2 (forward pass)");
             if ((rc = prof_begin(ctx))) return rc;
-            omds_launch_screen(ctx->stream, ctx->screen, ctx->mlp, ctx->d_FqH, ctx->cfg.n_traj, ctx->d_FpH, ctx->cfg.max_obs, ctx->d_radius, ctx->n_obs, N,
+            omds_launch_screen(ctx->stream, ctx->screen, st.m, ctx->d_FqH, ctx->cfg.n_traj, st.FpH, st.ld, st.radius, ctx->n_obs, N,
                                ctx->prm.ignored_links, ctx->d_Dmin, p.fuse_select ? p.d_sinks + (i - 1) : nullptr);
             if ((rc = prof_end(ctx, (int64_t)N * ctx->n_obs, -1.0, "k_screen"))) return rc;
             if (!p.fuse_select) omds_launch_select(ctx->stream, ctx->d_Dmin, N, ctx->n_obs, p.h_sinks[i - 1]);
-            omds_launch_exact(ctx->stream, ctx->mlp, fq_i, ctx->d_Fp, ctx->d_radius, ctx->n_obs, N,
+            omds_launch_exact(ctx->stream, ctx->mlp, fq_i, t.Fp, t.radius, ctx->n_obs, N,
                               ctx->prm.ignored_links, ctx->d_Dmin, ctx->d_rowlist, p.h_sinks[i - 1].total, ctx->d_scerr, p.ex);
         }
         enqueue_sweep_of_step(ctx, fq_i, N, i);
         RoctxRange r2("TAG: evaluate NN_3-5 + Modulation-propagation");
         a.step = i;
         if (list_tail)
-            omds_launch_tail_sel(ctx->stream, ctx->mlp, ctx->d_Fp, ctx->d_radius, ctx->d_obs, fq_next, ctx->n_obs, a,
+            omds_launch_tail_sel(ctx->stream, ctx->mlp, t.Fp, t.radius, t.obs, fq_next, ctx->n_obs, a,
                                  ctx->d_rowlist, ctx->d_range, p.ex, ctx->d_FqH, N, p.eps, ctx->d_scerr + 1);
         else
-            omds_launch_tail(ctx->stream, ctx->mlp, ctx->d_Fp, ctx->d_radius, ctx->d_obs, ctx->d_Dmin, fq_i,
+            omds_launch_tail(ctx->stream, ctx->mlp, t.Fp, t.radius, t.obs, ctx->d_Dmin, fq_i,
                              ctx->d_dscr, ctx->n_obs, a, ctx->d_FqH, N, fq_next, ctx->d_range, p.eps, ctx->d_scerr + 1);
     }
     return screen_finish_propagate(ctx, p);
@@ -303,6 +309,11 @@ int omds_propagate(omds_ctx* ctx, const float* q_cur, int per_rollout) {
     a.rowObs = ctx->d_idx;
     // screening where the context asks for it, the fused step runs and a bound stands (measured now when none does)
     bool screen = fused_step_available(ctx) && screen_wanted(ctx);
+    if (screen && ctx->hz_mode) {   // a bound measured without a horizon, or on another last slab, does not stand for this one (omds.h)
+        std::vector<float> last;
+        obstacle_horizon_last_slab(ctx, last);
+        ctx->scr.horizon_changed(last.data(), ctx->n_obs);
+    }
     if (screen && (rc = screen_calibrated(ctx, q_cur, &screen))) return rc;
     if ((rc = enqueue_rollouts(ctx, a, choose_route(ctx, screen)))) return rc;
     CK(hipGetLastError());

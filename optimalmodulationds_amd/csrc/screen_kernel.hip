@@ -725,20 +725,57 @@ __global__ __launch_bounds__(512) void k_audit(MlpDev m, const float* __restrict
     }
 }
 
+// k_audit of a propagate with an obstacle horizon: Fp / radius hold H slabs of slab_ld rows, and a listed row (step_row0 + t) * O + o
+// with step_row0 = (step - 1) * N reads obstacle row (step - 1) * slab_ld + o -- the scene its step saw (ndiv divides by N;
+// pass1_tile's SLAB flag).  A kernel of its own, the same rounds of tiles: k_audit keeps its argument list and its code.  Still ONE
+// launch for all steps.
+template <int ACT>
+__global__ __launch_bounds__(512) void k_audit_slabs(MlpDev m, const float* __restrict__ FqAll, const float* __restrict__ Fp,
+                                                     const float* __restrict__ radius, int O, uint32_t ignored, OmdsDivisor odiv,
+                                                     const int* __restrict__ rows, const int* __restrict__ total, int cap,
+                                                     unsigned* __restrict__ maxerr_bits, ExactOut ex, OmdsDivisor ndiv, unsigned slab_ld) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int n = min(*total, cap);
+    const int G = (int)gridDim.x;
+    const int full = n / (64 * G);
+    const int rest0 = full * 64 * G, rest = n - rest0;
+    for (int r = 0; r < full; ++r) {
+        pass1_tile<64, 2, 1, ACT, 4, true>(m, smem, FqAll, Fp, radius, O, n, ignored, nullptr, ((long long)r * G + blockIdx.x) * 64, odiv, rows, maxerr_bits, &ex, ndiv, slab_ld);
+        __syncthreads();
+    }
+    if (rest > 32 * G) {
+        if ((long long)blockIdx.x * 64 < rest)
+            pass1_tile<64, 2, 1, ACT, 4, true>(m, smem, FqAll, Fp, radius, O, n, ignored, nullptr, rest0 + (long long)blockIdx.x * 64, odiv, rows, maxerr_bits, &ex, ndiv, slab_ld);
+    } else if ((long long)blockIdx.x * 32 < rest) {
+        pass1_tile<32, 1, 1, ACT, 4, true>(m, smem, FqAll, Fp, radius, O, n, ignored, nullptr, rest0 + (long long)blockIdx.x * 32, odiv, rows, maxerr_bits, &ex, ndiv, slab_ld);
+    }
+}
+
 void omds_launch_audit(hipStream_t s, const MlpDev& m, const float* FqAll, const float* Fp, const float* radius, int O,
-                       uint32_t ignored, const int* rows, const float* da, const int* total, int cap, unsigned* maxerr_bits) {
+                       uint32_t ignored, const int* rows, const float* da, const int* total, int cap, unsigned* maxerr_bits,
+                       int N, int slab_ld) {
     if (cap <= 0) return;
     const size_t lds = (size_t)64 * LDH * 4 + 64 * 4 + 64 * 4;
     static std::atomic<uint64_t> configured{0};
     if (omds_first_use_on_device(configured)) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_audit<OMDS_ACT_RELU>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_audit<OMDS_ACT_TANH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_audit_slabs<OMDS_ACT_RELU>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_audit_slabs<OMDS_ACT_TANH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }
     ExactOut ex{};
     ex.Da = da;
     // the list length is only known on the device: a grid of two resident 64-row workgroups per CU strides over it
     const unsigned grid = (unsigned)std::min<long long>(((long long)cap + 63) / 64, 512);
     const OmdsDivisor od = OmdsDivisor::make((unsigned)O);
+    if (slab_ld > 0) {   // an obstacle horizon: the row's step picks its slab
+        const OmdsDivisor nd = OmdsDivisor::make((unsigned)N);
+        if (m.act == OMDS_ACT_RELU)
+            hipLaunchKernelGGL((k_audit_slabs<OMDS_ACT_RELU>), dim3(grid), dim3(512), lds, s, m, FqAll, Fp, radius, O, ignored, od, rows, total, cap, maxerr_bits, ex, nd, (unsigned)slab_ld);
+        else
+            hipLaunchKernelGGL((k_audit_slabs<OMDS_ACT_TANH>), dim3(grid), dim3(512), lds, s, m, FqAll, Fp, radius, O, ignored, od, rows, total, cap, maxerr_bits, ex, nd, (unsigned)slab_ld);
+        return;
+    }
     if (m.act == OMDS_ACT_RELU)
         hipLaunchKernelGGL((k_audit<OMDS_ACT_RELU>), dim3(grid), dim3(512), lds, s, m, FqAll, Fp, radius, O, ignored, od, rows, total, cap, maxerr_bits, ex);
     else

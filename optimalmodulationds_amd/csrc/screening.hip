@@ -6,11 +6,14 @@
 #include "capi_internal.h"
 #ifdef OMDS_TEST_HOOKS
 #include "omds_test.h"
+#include "omds_test_horizon.h"
 #endif
 
 bool screen_wanted(omds_ctx* ctx) {
     if (!ctx->scr.ok || ctx->scr.suspended) return false;
-    if (ctx->hz_mode) return false;   // an obstacle horizon: the bound and k_audit are about ONE scene for all steps (omds.h)
+    // an obstacle horizon is screened only where the caller asked for it (omds_set_screening_horizon): the routes, the sweep and
+    // k_audit then read the step's slab, and the bound is measured on three slabs (calibrate_screen); otherwise the all-fp32 step
+    if (ctx->hz_mode && !ctx->scr.over_horizon) return false;
     int mode = ctx->scr.mode;
     if (mode < 0) {   // the library's default: the all-fp32 step -- screening is OPT-IN (omds.h); OMDS_SCREEN=0|1|2 sets the default of such contexts
         static int env = -2;
@@ -114,9 +117,16 @@ static int screen_reorder(omds_ctx* ctx, int B, bool from_rollouts) {
 // screened propagate after omds_set_mlp, after omds_set_obstacles with a changed scene (scene_differs_from_calibration), after
 // a change of ignored_links and on request (omds_set_screening(mode, eps < 0)).  Between calibrations every propagate
 // re-measures the error on its candidates and on the audit sample of the unevaluated pairs (omds_propagate).
+// With an obstacle horizon in effect (screen_wanted let it through) the same states are measured against slabs 0, (H-1)/2 and H-1
+// -- k_pass1 and k_screen on each slab's fp32 / fp16 tables -- and eps is 6 x the maximum over them; the unit re-sort stays on
+// slab 0 (no returned number depends on it).  What the calibration stood on is recorded: slab 0, the last slab, and that a horizon
+// was in effect (ScreenHost::horizon_changed).
 static int calibrate_screen(omds_ctx* ctx, const float* q_center) {
     ctx->scr.cal = true;
     ctx->scr.obs_cal = ctx->obs_now;
+    ctx->scr.cal_horizon = ctx->hz_mode != 0;
+    if (ctx->scr.cal_horizon) obstacle_horizon_last_slab(ctx, ctx->scr.last_cal);
+    else ctx->scr.last_cal.clear();
     const int n = ctx->cfg.n_dof, O = ctx->n_obs;
     const int B = std::min(ctx->cfg.n_traj, 1024);
     float lo[OMDS_MAX_DOF], hi[OMDS_MAX_DOF];
@@ -133,10 +143,18 @@ static int calibrate_screen(omds_ctx* ctx, const float* q_center) {
     ctx->scr.reorder_pending = true;
     if (ctx->scr.eps_fixed && ctx->scr.eps > 0.f) return OMDS_OK;   // the bound was set by the caller (omds_set_screening)
     float* apx = ctx->d_stage;   // [B][O] screening values (d_stage holds >= n_traj * max_obs floats)
-    omds_launch_pass1(ctx->stream, ctx->mlp, ctx->d_Fq, ctx->d_Fp, ctx->d_radius, O, B, ctx->prm.ignored_links, ctx->d_Dmin);
-    omds_launch_screen(ctx->stream, ctx->screen, ctx->mlp, ctx->d_FqH, ctx->cfg.n_traj, ctx->d_FpH, ctx->cfg.max_obs, ctx->d_radius, O, B, ctx->prm.ignored_links, apx);
     CK(hipMemsetAsync(ctx->d_scerr + 3, 0, 4, ctx->stream));
-    omds_launch_max_abs_diff(ctx->stream, ctx->d_Dmin, apx, (long long)B * O, ctx->d_scerr + 3);
+    const int Hh = ctx->cfg.horizon;
+    int steps[3] = {1, (Hh - 1) / 2 + 1, Hh}, n_steps = 0;   // horizon steps whose slabs are measured (step i reads slab i - 1), duplicates removed
+    for (int j = 0; j < (ctx->scr.cal_horizon ? 3 : 1); ++j)
+        if (n_steps == 0 || steps[j] != steps[n_steps - 1]) steps[n_steps++] = steps[j];
+    for (int j = 0; j < n_steps; ++j) {   // the maximum over the slabs: k_max_abs_diff accumulates into the same word
+        const ObsTables t = obstacle_tables(ctx, steps[j]);
+        const ScreenTables st = screen_tables(ctx, steps[j]);
+        omds_launch_pass1(ctx->stream, ctx->mlp, ctx->d_Fq, t.Fp, t.radius, O, B, ctx->prm.ignored_links, ctx->d_Dmin);
+        omds_launch_screen(ctx->stream, ctx->screen, st.m, ctx->d_FqH, ctx->cfg.n_traj, st.FpH, st.ld, st.radius, O, B, ctx->prm.ignored_links, apx);
+        omds_launch_max_abs_diff(ctx->stream, ctx->d_Dmin, apx, (long long)B * O, ctx->d_scerr + 3);
+    }
     CK(hipGetLastError());
     float worst = 0.f;
     CK(hipMemcpyAsync(&worst, ctx->d_scerr + 3, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -167,16 +185,28 @@ int screen_calibrated(omds_ctx* ctx, const float* q_center, bool* usable) {
 // Another obstacle count, another radius, or any sphere more than 0.1 (scene units: metres for the Franka scenes) away from
 // where it was: a translating / vibrating scene (obstacleStreamer.py:125-137) keeps its bound, a swapped scene does not.
 // (Every step of every propagate additionally audits a sample of the unevaluated pairs, omds.h.)
-void ScreenHost::scene_changed(const float* xyzr, int n_obs) {
-    if (!cal || eps_fixed) return;
-    bool differs = obs_cal.size() != (size_t)n_obs * 4;
+static bool scene_differs(const std::vector<float>& was, const float* xyzr, int n_obs) {
+    bool differs = was.size() != (size_t)n_obs * 4;
     for (int i = 0; i < n_obs && !differs; ++i) {
-        const float* a = &obs_cal[(size_t)i * 4];
+        const float* a = &was[(size_t)i * 4];
         const float* b = xyzr + (size_t)i * 4;
         for (int c = 0; c < 3; ++c) differs = differs || !(std::fabs(a[c] - b[c]) <= 0.1f);
         differs = differs || !(std::fabs(a[3] - b[3]) <= 1e-6f);
     }
-    if (differs) forget_calibration();   // calibrate again at the next screened propagate, against THIS scene
+    return differs;
+}
+void ScreenHost::scene_changed(const float* xyzr, int n_obs) {
+    if (!cal || eps_fixed) return;
+    if (scene_differs(obs_cal, xyzr, n_obs)) forget_calibration();   // calibrate again at the next screened propagate, against THIS scene
+}
+// The same question about the far end of an obstacle horizon, asked at every screened propagate that has one: a bound measured
+// without a horizon has seen slab 0 only, and one measured on another last slab (other velocities, another table; the same test)
+// does not stand for this one.  Slab 0 is omds_set_obstacles' business (scene_changed), so a scene that keeps translating at
+// constant velocities recalibrates as often as a static translating scene does; a bound measured under a horizon also covers the
+// static scene (clearing the horizon forgets nothing); the caller's own bound is never forgotten.
+void ScreenHost::horizon_changed(const float* last, int n_obs) {
+    if (!cal || eps_fixed) return;
+    if (!cal_horizon || scene_differs(last_cal, last, n_obs)) forget_calibration();
 }
 
 // Buffers of the audit sample (allocated at the first screened propagate, grown when the scene or the rate asks for more):
@@ -187,6 +217,8 @@ static int prepare_audit(omds_ctx* ctx, SelectSink& sk) {
     sk.audit_mask = 0xffffffffu;
     const long long N = ctx->cfg.n_traj, H = ctx->cfg.horizon, O = ctx->n_obs;
     if (S.audit_one_in <= 0 || N * H * O >= (1LL << 31)) return OMDS_OK;   // no audit (or a row space beyond 32-bit indices)
+    // an obstacle horizon: k_audit_slabs gathers the obstacle rows of all slabs through one buffer descriptor with 32-bit byte offsets
+    if (ctx->hz_mode && (long long)H * ctx->hz_ld * (OMDS_FROW * 4) >= (1LL << 31)) return OMDS_OK;
     const size_t want = (size_t)(N * H * (2 * O / S.audit_one_in + 4));
     if (want > std::min(S.d_audit_rows.count(), S.d_audit_da.count())) {
         CK(hipStreamSynchronize(ctx->stream));
@@ -229,8 +261,10 @@ static int prepare_sweep(omds_ctx* ctx) {
 void enqueue_sweep_of_step(omds_ctx* ctx, const float* fq_step, int N, int step) {
     if (!ctx->scr.sweep_now || !(ctx->scr.sweep_all_steps || step == ctx->cfg.horizon)) return;
     RoctxRange r4("screening sweep (all pairs of this step in fp32)");
-    omds_launch_pass1(ctx->stream, ctx->mlp, fq_step, ctx->d_Fp, ctx->d_radius, ctx->n_obs, N, ctx->prm.ignored_links, ctx->scr.d_sweepD);
-    omds_launch_screen(ctx->stream, ctx->screen, ctx->mlp, ctx->d_FqH, ctx->cfg.n_traj, ctx->d_FpH, ctx->cfg.max_obs, ctx->d_radius, ctx->n_obs, N,
+    const ObsTables t = obstacle_tables(ctx, step);   // the scene this step saw: its slab of an obstacle horizon
+    const ScreenTables st = screen_tables(ctx, step);
+    omds_launch_pass1(ctx->stream, ctx->mlp, fq_step, t.Fp, t.radius, ctx->n_obs, N, ctx->prm.ignored_links, ctx->scr.d_sweepD);
+    omds_launch_screen(ctx->stream, ctx->screen, st.m, ctx->d_FqH, ctx->cfg.n_traj, st.FpH, st.ld, st.radius, ctx->n_obs, N,
                        ctx->prm.ignored_links, ctx->scr.d_sweepDa);
     omds_launch_sweep_hist(ctx->stream, ctx->scr.d_sweepD, ctx->scr.d_sweepDa, ctx->d_range, N, ctx->n_obs, ctx->scr.eps, ctx->scr.d_sweep_hist, ctx->d_scerr + 3);
     ctx->scr.sweep_steps_now++;
@@ -298,8 +332,12 @@ int screen_finish_propagate(omds_ctx* ctx, const ScreenPlan& plan) {
     const SelectSink& sink = plan.h_sinks[0];   // the audit list is one for the whole propagate
     if (sink.audit_rows) {
         RoctxRange r3("screening audit sample (fp32 re-evaluation of unevaluated pairs)");
-        omds_launch_audit(ctx->stream, ctx->mlp, ctx->d_FqAll, ctx->d_Fp, ctx->d_radius, ctx->n_obs, ctx->prm.ignored_links,
-                          sink.audit_rows, sink.audit_da, sink.audit_total, sink.audit_cap, ctx->d_scerr);
+        if (ctx->hz_mode)   // every listed row against the slab of ITS step, still in one launch
+            omds_launch_audit(ctx->stream, ctx->mlp, ctx->d_FqAll, ctx->d_hzFp, ctx->d_hzRadius, ctx->n_obs, ctx->prm.ignored_links,
+                              sink.audit_rows, sink.audit_da, sink.audit_total, sink.audit_cap, ctx->d_scerr, ctx->cfg.n_traj, ctx->hz_ld);
+        else
+            omds_launch_audit(ctx->stream, ctx->mlp, ctx->d_FqAll, ctx->d_Fp, ctx->d_radius, ctx->n_obs, ctx->prm.ignored_links,
+                              sink.audit_rows, sink.audit_da, sink.audit_total, sink.audit_cap, ctx->d_scerr);
     }
     CK(hipGetLastError());
     CK(hipMemcpyAsync(ctx->scr.h_verdict, ctx->d_scerr, 16, hipMemcpyDeviceToHost, ctx->stream));
@@ -372,12 +410,30 @@ int omds_set_screening(omds_ctx* ctx, int mode, float eps) {
     ctx->scr.mode = mode;
     if (eps > 0.f) {            // the caller's bound instead of a calibration (the run-time checks still widen it when they must)
         ctx->scr.eps = eps; ctx->scr.eps_fixed = true; ctx->scr.cal = true;
-        ctx->scr.obs_cal = ctx->obs_now;
+        ctx->scr.obs_cal = ctx->obs_now; ctx->scr.cal_horizon = false; ctx->scr.last_cal.clear();
         ctx->scr.suspended = false; ctx->scr.consec = 0;
     } else if (eps < 0.f) {     // forget the calibration: measured again at the next screened propagate
         ctx->scr.eps = 0.f; ctx->scr.eps_fixed = false;
         ctx->scr.forget_calibration();
     }                           // eps == 0: the mode only; bound, calibration and everything measured so far stay
+    return OMDS_OK;
+}
+int omds_set_screening_horizon(omds_ctx* ctx, int on) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    REQUIRE(on == 0 || on == 1, OMDS_ERR_INVALID_ARG, "omds_set_screening_horizon: on in {0, 1}");
+    const bool was = ctx->scr.over_horizon;
+    ctx->scr.over_horizon = on != 0;
+    if (was && !on && (ctx->d_hzFpH || ctx->d_hzFpS)) {   // the fp16 slab tables go: the context is what it was before the switch
+        CK(hipSetDevice(ctx->dev));
+        CK(hipStreamSynchronize(ctx->stream));
+        ctx->d_hzFpH.reset(); ctx->d_hzFpS.reset();
+    }
+    return OMDS_OK;   // on: prepare_obstacle_horizon builds the fp16 slab tables with the next rebuild
+}
+int omds_get_screening_horizon(omds_ctx* ctx, int32_t* on, int32_t* in_effect) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    if (on) *on = ctx->scr.over_horizon ? 1 : 0;
+    if (in_effect) *in_effect = (ctx->hz_mode && ctx->scr.over_horizon && fused_step_available(ctx) && screen_wanted(ctx)) ? 1 : 0;
     return OMDS_OK;
 }
 int omds_set_screening_audit(omds_ctx* ctx, int one_in) {
@@ -470,6 +526,27 @@ int omds_screen_debug_corrupt(omds_ctx* ctx, int what, int index, float value) {
     for (int part = 0; part < 3; ++part) {
         const uint16_t h = f32_to_f16_bits(f[part]);
         CK(hipMemcpy(ctx->d_FpH + omds_screen_fidx(part * d + n, index, ld), &h, 2, hipMemcpyHostToDevice));
+    }
+    return OMDS_OK;
+}
+// omds_test_screen_corrupt_slab (include/omds_test_horizon.h; tests/test_gpu_screen_horizon.py): what = 1 above for ONE slab of an
+// obstacle horizon -- the fp16 network sees that sphere elsewhere at that step only, the fp32 tables stay
+int omds_test_screen_corrupt_slab(omds_ctx* ctx, int slab, int index, float dx) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    REQUIRE(ctx->hz_mode && ctx->d_hzFpH && !ctx->hz_dirty, OMDS_ERR_NOT_INITIALISED,
+            "omds_test_screen_corrupt_slab: no fp16 slab tables (omds_set_screening_horizon, a horizon, then omds_get_obstacle_horizon)");
+    REQUIRE(slab >= 0 && slab < ctx->cfg.horizon && index >= 0 && index < ctx->n_obs, OMDS_ERR_INVALID_ARG,
+            "omds_test_screen_corrupt_slab: slab and obstacle index in range");
+    CK(hipSetDevice(ctx->dev));
+    CK(hipStreamSynchronize(ctx->stream));
+    const int n = ctx->cfg.n_dof, d = ctx->mlp.d, ld = ctx->hz_ld;
+    float x0 = 0.f;   // the sphere's x in that slab as the tables hold it
+    CK(hipMemcpy(&x0, ctx->d_hzObs + ((size_t)slab * ld + index) * 4, 4, hipMemcpyDeviceToHost));
+    const float x = x0 + dx;
+    const float f[3] = {x, std::sin(x), std::cos(x)};
+    for (int part = 0; part < 3; ++part) {
+        const uint16_t h = f32_to_f16_bits(f[part]);
+        CK(hipMemcpy(ctx->d_hzFpH + (size_t)slab * 32 * ld + omds_screen_fidx(part * d + n, index, ld), &h, 2, hipMemcpyHostToDevice));
     }
     return OMDS_OK;
 }

@@ -379,6 +379,18 @@ class Engine:
         (mode change only), < 0 discards the calibration (measured again at the next screened propagate)."""
         self._ck(self.lib.omds_set_screening(self.h, int(mode), float(eps)))
 
+    def set_screening_horizon(self, on=True):
+        """Screening while an obstacle horizon is set (``set_obstacle_motion`` / ``set_obstacle_horizon``).  Off (the default): a
+        horizon puts the context on the all-fp32 step.  On: such a propagate is screened like a static one, every step against its
+        own slab (omds.h: omds_set_screening_horizon)."""
+        self._ck(self.lib.omds_set_screening_horizon(self.h, 1 if on else 0))
+
+    def get_screening_horizon(self):
+        """(on, in_effect): the switch, and whether the next propagate would run a screened route with a horizon set."""
+        on, eff = np.zeros(1, np.int32), np.zeros(1, np.int32)
+        self._ck(self.lib.omds_get_screening_horizon(self.h, L.iptr(on), L.iptr(eff)))
+        return bool(on[0]), bool(eff[0])
+
     def set_screening_audit(self, one_in=64):
         """Audit sample of the pairs the screened step does not re-evaluate: 1 in ``one_in`` (power of two), 0 = none."""
         self._ck(self.lib.omds_set_screening_audit(self.h, int(one_in)))
@@ -405,6 +417,11 @@ class Engine:
         """Test hook (include/omds_test.h; needs ``lib=_lib.load_test_hooks()``): 0 = zero a weight fragment of the fp16 pack,
         1 = shift an obstacle in the screening inputs."""
         self._ck(self.lib.omds_screen_debug_corrupt(self.h, int(what), int(index), float(value)))
+
+    def test_screen_corrupt_slab(self, slab, index, dx):
+        """Test hook (include/omds_test_horizon.h; needs ``lib=_lib.load_test_hooks()``): shift obstacle ``index`` by ``dx`` along x
+        in the fp16 screening table of horizon slab ``slab`` only; the tables must exist (``get_obstacle_horizon`` builds them)."""
+        self._ck(self.lib.omds_test_screen_corrupt_slab(self.h, int(slab), int(index), float(dx)))
 
     def debug_force_tile_rows(self, tail_sel_rows=0, tail_rows=0):
         """Test hook (include/omds_test.h; needs ``lib=_lib.load_test_hooks()``; wide to that library): tile shape of the tail

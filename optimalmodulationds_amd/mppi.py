@@ -141,6 +141,13 @@ class MPPI:
         self._engine.set_obstacle_frame(bool(moving_frame))
         return 0
 
+    def set_screening(self, mode, eps=0.0, over_horizon=False):
+        """The screened pass 1 (Engine.set_screening: mode -1 | 0 | 1 | 2, ``eps`` as there); ``over_horizon``: also while
+        ``update_obstacles(..., velocities=)`` has set an obstacle horizon (Engine.set_screening_horizon), which otherwise puts the
+        propagate on the all-fp32 step."""
+        self._engine.set_screening(mode, eps)
+        self._engine.set_screening_horizon(bool(over_horizon))
+
     # ---- parameters -> device ----------------------------------------------------------------------
     def _push(self):
         """The mutable attributes the reference's callers poke (dt, dst_thr, ignored_links, Policy.p, DS, Cost limits) -> the

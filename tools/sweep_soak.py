@@ -9,6 +9,12 @@ Legs: the shelf (static; moving like bench.py's dynamic workload), every streame
 networks.  Prints a report (committed as profiles/r04_screen_error_hist.txt):
 
     python tools/sweep_soak.py [--pairs 1e10] > profiles/r04_screen_error_hist.txt
+
+--legs moving: the MOVING-SCENE legs instead -- obstacle velocities (a motion horizon: every step sees its own slab) with screening
+over the horizon (omds_set_screening_horizon), the scene advanced by v dt from iteration to iteration; the same with the moving
+frame; the caller's own table with radii growing over the horizon; the tanh and skip-connection networks.  Sized to a few minutes:
+
+    python tools/sweep_soak.py --legs moving --pairs 3e10 > profiles/r14_screen_horizon_error_hist.txt
 """
 import argparse
 import json
@@ -46,8 +52,9 @@ def make_engine(kind, N, H, obs, act="relu"):
     return e
 
 
-def run_leg(name, e, n_iter, obs_of=None, uniform_starts=False, seed=0):
-    """n_iter planner iterations (sample + propagate + cost + update) with every step swept; returns the leg's statistics."""
+def run_leg(name, e, n_iter, obs_of=None, uniform_starts=False, seed=0, horizon_of=None):
+    """n_iter planner iterations (sample + propagate + cost + update) with every step swept; returns the leg's statistics.
+    horizon_of(e, it): sets the iteration's scene AND its obstacle horizon (set_obstacles clears the previous one)."""
     from optimalmodulationds_amd import scenes
     from optimalmodulationds_amd.cost import FRANKA_Q_MAX, FRANKA_Q_MIN
     rng = np.random.RandomState(1000 + seed)
@@ -63,6 +70,8 @@ def run_leg(name, e, n_iter, obs_of=None, uniform_starts=False, seed=0):
     for it in range(n_iter):
         if obs_of is not None:
             e.set_obstacles(obs_of(it))
+        if horizon_of is not None:
+            horizon_of(e, it)
         e.sample_policy(mu_c, sg_c, al_c, 0.0, 0.0, 3.0, K, seed=77 * 1000003 + 131 * seed + it)
         if uniform_starts:
             e.propagate(rng.uniform(lo, hi, (e.N, 7)).astype(np.float32))
@@ -138,13 +147,62 @@ def report(legs, out=sys.stdout):
     return dict(tot, worst_ratio=worst_ratio, tail_estimate=est)
 
 
+def moving_legs(a):
+    """Screening over an obstacle horizon, every step of every propagate swept against the slab it saw."""
+    from optimalmodulationds_amd import scenes
+    from optimalmodulationds_amd.engine import predict_obstacle_horizon
+    N, H, DT = a.rollouts, a.horizon, 0.5
+    shelf = scenes.shelf_scene()
+    O = shelf.shape[0]
+    share = lambda f: max(2, int(round(f * a.pairs / (N * H * O))))
+
+    def streamer(frame=False, table=False, period=8):
+        """The shelf's spheres drift at velocities uniform in +-0.2 m/s, drawn again every `period` iterations from the shelf itself
+        (up to 0.8 m of drift at dt = 0.5; the horizon adds up to (H - 1) dt v on top)."""
+        state = {}
+
+        def set_scene(e, it):
+            if it % period == 0:
+                state["vel"] = np.random.RandomState(500 + it).uniform(-0.2, 0.2, (O, 3)).astype(np.float32)
+                state["obs"] = shelf.copy()
+            else:
+                state["obs"] = state["obs"].copy()
+                state["obs"][:, :3] += np.float32(DT) * state["vel"]
+            e.set_obstacles(state["obs"])
+            if table:      # the caller's own predictions: the same motion, radii growing by 2 % per step
+                t = predict_obstacle_horizon(state["obs"], state["vel"], H, DT)
+                t[:, :, 3] *= (1 + np.float32(0.02) * np.arange(H, dtype=np.float32))[:, None]
+                e.set_obstacle_horizon(t)
+            else:
+                e.set_obstacle_motion(state["vel"])
+            e.set_obstacle_frame(frame)
+        return set_scene
+
+    legs = []
+    e = make_engine("franka", N, H, shelf)
+    e.set_screening_horizon(True)
+    legs.append(run_leg("shelf, motion horizon +-0.2 m/s", e, share(0.34), horizon_of=streamer(), seed=41))
+    legs.append(run_leg("  ... in the moving frame", e, share(0.22), horizon_of=streamer(frame=True), seed=42))
+    legs.append(run_leg("  ... explicit table, radii +2 %/step", e, share(0.16), horizon_of=streamer(table=True), seed=43))
+    e.close()
+    for kind, act, name, sd in (("franka_tanh", "tanh", "tanh 256x3, motion horizon", 44), ("franka_skip", "relu", "skip-connection net, motion horizon", 45)):
+        e = make_engine(kind, N, H, shelf, act=act)
+        e.set_screening_horizon(True)
+        legs.append(run_leg(name, e, share(0.14), horizon_of=streamer(), seed=sd))
+        e.close()
+    return legs
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=float, default=1.0e10, help="total (rollout, obstacle) pairs to sweep, split over the legs")
     ap.add_argument("--rollouts", type=int, default=4096)
     ap.add_argument("--horizon", type=int, default=32)
     ap.add_argument("--json", default=None, help="also write the raw per-leg numbers there")
+    ap.add_argument("--legs", default="static", choices=["static", "moving"], help="moving: the legs with an obstacle horizon (screening over it)")
     a = ap.parse_args()
+    if a.legs == "moving":
+        return finish(moving_legs(a), a)
     from optimalmodulationds_amd import scenes
     N, H = a.rollouts, a.horizon
     shelf = scenes.shelf_scene()
@@ -171,6 +229,10 @@ def main():
     e = make_engine("franka_skip", N, H, shelf)
     legs.append(run_leg("shelf, skip-connection net (synthetic)", e, share(0.12), seed=31))
     e.close()
+    finish(legs, a)
+
+
+def finish(legs, a):
     summary = report(legs)
     if a.json:
         with open(a.json, "w") as f:
