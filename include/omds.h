@@ -75,10 +75,10 @@ typedef struct {
  * fire alike (same bits either way: a row does not depend on its tile-mates); for A/B runs and the tests that compare the two    */
 #define OMDS_FLAG_NATURAL_TILES 32
 /* the block order of the tiles at every batch size, not only from OMDS_BLOCK_TILES_MIN_PAIRS rollout-obstacle pairs on, below which
- * the ordering launch costs more than it saves (EXPERIMENTS.md R12: bracketed by 150 528 pairs, slower, and 301 056, faster, at 294
+ * the ordering launches cost more than they save (EXPERIMENTS.md R15: bracketed by 112 896 pairs, slower, and 150 528, faster, at 294
  * obstacles; not located); for A/B runs and the tests, which run small batches                                                    */
 #define OMDS_FLAG_BLOCK_TILES 64
-#define OMDS_BLOCK_TILES_MIN_PAIRS 262144
+#define OMDS_BLOCK_TILES_MIN_PAIRS 131072
 
 /* The constants the reference hard-codes inside propagate() (MPPI.py:117-217,277) and
  * LinDS (LinDS.py:9), as parameters; omds_default_params() fills the reference values.   */

@@ -41,7 +41,7 @@ FLAG_TAIL_FORWARD = 4      # the fp32 step's tail keeps its own forward (omds.h:
 FLAG_DENSE_PASS1 = 8       # k_pass1 multiplies every k-chunk (omds.h: OMDS_FLAG_DENSE_PASS1; same bits as the per-tile compaction)
 FLAG_NATURAL_PASS1 = 16    # first step of a propagate from one state evaluated per rollout (omds.h: OMDS_FLAG_NATURAL_PASS1; same bits)
 FLAG_NATURAL_TILES = 32    # pass-1 tiles over consecutive rows instead of key-ordered rollout x obstacle blocks (omds.h: OMDS_FLAG_NATURAL_TILES; same bits)
-FLAG_BLOCK_TILES = 64      # the block order at every batch size, not only from 262 144 pairs on (omds.h: OMDS_FLAG_BLOCK_TILES; same bits)
+FLAG_BLOCK_TILES = 64      # the block order at every batch size, not only from 131 072 pairs on (omds.h: OMDS_FLAG_BLOCK_TILES; same bits)
 FLAG_TWO_KERNEL_STEP = 2   # keep few-obstacle scenes on k_pass1 + k_tail (omds.h: OMDS_FLAG_TWO_KERNEL_STEP)   # omds_config.flags
 # omds_params.variant / cost_terms bits (include/omds.h)
 VARIANT_KVAL_TIMES_ACT = 1
@@ -168,6 +168,7 @@ TEST_HOOK_SIGNATURES = {
 # include/omds_test_tiles.h: the hooks of the block-ordered pass 1, in the test library likewise
 TILE_HOOK_SIGNATURES = {
     "omds_test_tile_orders": (C.c_int, [C.c_void_p, I32P, I32P]),
+    "omds_test_tile_state": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), I32P, I32P, I32P, F32P, F32P, F32P]),
     "omds_test_read_dmin": (C.c_int, [C.c_void_p, F32P]),
 }
 # include/omds_test_horizon.h: the hook of screening under an obstacle horizon, in the test library likewise

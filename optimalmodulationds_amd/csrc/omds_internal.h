@@ -132,15 +132,25 @@ struct WideNet {
 constexpr int OMDS_KEY_UNITS = 12;             // sign bits of a rollout's / an obstacle's key
 constexpr int OMDS_ORDER_MAX_OBS = 4096;       // the orders are ranked in LDS: largest scene and batch they are formed for
 constexpr int OMDS_ORDER_MAX_ROLLOUTS = 8192;
-struct TileKeys {                              // device: written by k_tile_pick once per propagate, read by k_rollout_order at every step
+constexpr int OMDS_SHARE_ROWS = 32;            // rows of a row group of k_share_stats: one partial sum per unit and group
+struct TileKeys {                              // device: written by k_tile_pick once per propagate, read by k_order_keys at every step
     float W[OMDS_KEY_UNITS][OMDS_FROW];        // layer-1 weights of the key units over the feature slots of Fq / Fp
     float cR[OMDS_KEY_UNITS];                  // bias + mean obstacle share: what a rollout's share is compared against
     int unit[OMDS_KEY_UNITS];
+    float cO[OMDS_KEY_UNITS];                  // bias + mean rollout share: what an obstacle's share is compared against
 };
 inline int omds_order_pad(int n) { return ((n + 15) & ~15) + 16; }   // entries of an order: whole blocks, the padding names the last row again
-// pick: choose the key units on Fq and order the obstacles of Fp first (the first full launch of a propagate); then rperm from Fq
-void omds_launch_tile_order(hipStream_t s, const MlpDev& m, const float* Fq, int N, const float* Fp, int O, TileKeys* keys,
-                            int* rperm, int* operm, bool pick);
+inline int omds_share_groups(int n) { return (n + OMDS_SHARE_ROWS - 1) / OMDS_SHARE_ROWS; }
+struct TileOrderBufs {                         // device buffers of the ordering launches (omds_ctx owns them: acquire_order_buffers)
+    TileKeys* keys;
+    int *rperm, *operm;                        // [omds_order_pad(n)] the orders
+    unsigned *rkey, *okey;                     // [n] the keys they are the ranks of
+    float *sumO, *sumR;                        // [omds_share_groups(n)][OMDS_WIDTH] per-unit share sums of the row groups
+    int* cntR;                                 // ... and how many rollouts of a group fire
+};
+// pick: choose the key units on Fq and Fp and order the obstacles of Fp first (the first full launch of a propagate); then rperm from Fq
+void omds_launch_tile_order(hipStream_t s, const MlpDev& m, const float* Fq, int N, const float* Fp, int O, const TileOrderBufs& b,
+                            bool pick);
 
 struct ProfEvents {
     std::vector<hipEvent_t> start, stop;
@@ -399,6 +409,9 @@ struct omds_ctx {
     DevBuf<int32_t> d_idx;       // [N][k]
     DevBuf<int> d_rperm, d_operm;   // block-ordered pass 1 (tile_order.hip): rollout order of the step, obstacle order of the propagate
     DevBuf<TileKeys> d_tileKeys;    // ... and the key units of the propagate (allocated at the first block-ordered launch)
+    DevBuf<unsigned> d_rkey, d_okey;   // ... the keys the two orders rank, [n_traj] and [max_obs]
+    DevBuf<float> d_shareSum;       // ... per-unit share sums of the row groups [obstacle groups + rollout groups][OMDS_WIDTH]
+    DevBuf<int> d_shareCnt;         // ... and firing counts [rollout groups][OMDS_WIDTH]
     DevBuf<float> d_gradx;       // [N*k][d]
     DevBuf<float> d_drow;        // [N*k]
     DevBuf<float> d_yraw;        // [N*k][16]

@@ -123,14 +123,24 @@ static int enqueue_small_scene(omds_ctx* ctx, StepArgs& a) {
 // entry names a row of the tables whatever happens; a request that failed leaves the step on the natural order.
 static bool acquire_order_buffers(omds_ctx* ctx) {
     const size_t nr = (size_t)omds_order_pad(ctx->cfg.n_traj), no = (size_t)omds_order_pad(ctx->cfg.max_obs);
-    if (ctx->d_tileKeys && ctx->d_rperm.count() >= nr && ctx->d_operm.count() >= no) return true;
+    const size_t gr = (size_t)omds_share_groups(ctx->cfg.n_traj), go = (size_t)omds_share_groups(ctx->cfg.max_obs);
+    if (ctx->d_tileKeys && ctx->d_rperm.count() >= nr && ctx->d_operm.count() >= no && ctx->d_rkey.count() >= (size_t)ctx->cfg.n_traj &&
+        ctx->d_okey.count() >= (size_t)ctx->cfg.max_obs && ctx->d_shareSum.count() >= (go + gr) * OMDS_WIDTH && ctx->d_shareCnt.count() >= gr * OMDS_WIDTH)
+        return true;
     if (ctx->d_rperm.alloc(nr) == hipSuccess && ctx->d_operm.alloc(no) == hipSuccess && ctx->d_tileKeys.alloc(1) == hipSuccess &&
+        ctx->d_rkey.alloc((size_t)ctx->cfg.n_traj) == hipSuccess && ctx->d_okey.alloc((size_t)ctx->cfg.max_obs) == hipSuccess &&
+        ctx->d_shareSum.alloc((go + gr) * OMDS_WIDTH) == hipSuccess && ctx->d_shareCnt.alloc(gr * OMDS_WIDTH) == hipSuccess &&
         hipMemsetAsync(ctx->d_rperm, 0, nr * sizeof(int), ctx->stream) == hipSuccess &&
         hipMemsetAsync(ctx->d_operm, 0, no * sizeof(int), ctx->stream) == hipSuccess &&
-        hipMemsetAsync(ctx->d_tileKeys, 0, sizeof(TileKeys), ctx->stream) == hipSuccess)
+        hipMemsetAsync(ctx->d_tileKeys, 0, sizeof(TileKeys), ctx->stream) == hipSuccess &&
+        hipMemsetAsync(ctx->d_rkey, 0, ctx->d_rkey.bytes(), ctx->stream) == hipSuccess &&
+        hipMemsetAsync(ctx->d_okey, 0, ctx->d_okey.bytes(), ctx->stream) == hipSuccess &&
+        hipMemsetAsync(ctx->d_shareSum, 0, ctx->d_shareSum.bytes(), ctx->stream) == hipSuccess &&
+        hipMemsetAsync(ctx->d_shareCnt, 0, ctx->d_shareCnt.bytes(), ctx->stream) == hipSuccess)
         return true;
     (void)hipGetLastError();
     ctx->d_rperm.reset(); ctx->d_operm.reset(); ctx->d_tileKeys.reset();
+    ctx->d_rkey.reset(); ctx->d_okey.reset(); ctx->d_shareSum.reset(); ctx->d_shareCnt.reset();
     return false;
 }
 
@@ -149,13 +159,14 @@ static int enqueue_dense(omds_ctx* ctx, StepArgs& a) {
     // computes the same bits, so the step's results are those of the full launch (OMDS_FLAG_NATURAL_PASS1 keeps that one).
     const bool shared = ctx->shared_start && !(ctx->cfg.flags & OMDS_FLAG_NATURAL_PASS1);
     // BLOCK-ORDERED TILES: every full launch of the compacting kernel forms its tiles from 16 (8) rollouts x 4 obstacles that are
-    // neighbours in a key order of the rollouts (formed again at every step, k_rollout_order) and of the obstacles (formed with
-    // the key units at the first full launch of the propagate, k_tile_pick, on slab 0 of an obstacle horizon): rows that fire alike
+    // neighbours in a key order of the rollouts (formed again at every step: k_order_keys + k_order_rank) and of the obstacles (formed
+    // with the key units at the first full launch of the propagate, k_share_stats x 2 + k_tile_pick, on slab 0 of an obstacle horizon): rows that fire alike
     // share a tile, and the exact zero-skip multiplies fewer chunks.  A row's bits do not depend on its tile-mates
     // (OMDS_FLAG_NATURAL_TILES keeps the rows in their order).  The ordering launches sit INSIDE the profiling bracket of pass 1:
     // they are part of what the launch costs.
-    // Below OMDS_BLOCK_TILES_MIN_PAIRS the natural order stays: at 128 / 256 / 512 rollouts x 294 obstacles the block order ran 8.2 / 3.5 /
-    // 3.1 % slower (the ordering launch in front of a short pass 1), at 1024 and 4096 rollouts 3.6 / 5.0 % faster (EXPERIMENTS.md R12).
+    // Below OMDS_BLOCK_TILES_MIN_PAIRS the natural order stays: at 128 / 256 / 384 rollouts x 294 obstacles the block order ran 6.8 / 2.0 /
+    // 1.8 % slower (the ordering launches in front of a short pass 1 that does not fill the device twice over), at 512 / 768 / 1024
+    // rollouts 0.9 / 3.3 / 3.9 % faster (EXPERIMENTS.md R15).
     const bool blocks = !(ctx->cfg.flags & OMDS_FLAG_NATURAL_TILES) && omds_pass1_blocks_ok(ctx->mlp, N, ctx->n_obs) &&
                         ((ctx->cfg.flags & OMDS_FLAG_BLOCK_TILES) || (long long)N * ctx->n_obs >= OMDS_BLOCK_TILES_MIN_PAIRS) && acquire_order_buffers(ctx);
     bool picked = false;
@@ -167,8 +178,10 @@ static int enqueue_dense(omds_ctx* ctx, StepArgs& a) {
             RoctxRange r1("TAG: evaluate NN_2 (forward pass)");
             if ((rc = prof_begin(ctx))) return rc;
             if (blocks && !one_row) {
-                omds_launch_tile_order(ctx->stream, ctx->mlp, ctx->d_Fq, N, obstacle_tables(ctx, 1).Fp, ctx->n_obs, ctx->d_tileKeys,
-                                       ctx->d_rperm, ctx->d_operm, !picked);
+                float* const sumO = ctx->d_shareSum;
+                const TileOrderBufs ob{ctx->d_tileKeys, ctx->d_rperm, ctx->d_operm, ctx->d_rkey, ctx->d_okey, sumO,
+                                       sumO + (size_t)omds_share_groups(ctx->cfg.max_obs) * OMDS_WIDTH, ctx->d_shareCnt};
+                omds_launch_tile_order(ctx->stream, ctx->mlp, ctx->d_Fq, N, obstacle_tables(ctx, 1).Fp, ctx->n_obs, ob, !picked);
                 picked = true;
                 omds_launch_pass1_blocks(ctx->stream, ctx->mlp, ctx->d_Fq, t.Fp, t.radius, ctx->n_obs, N, ctx->prm.ignored_links,
                                          ctx->d_Dmin, ctx->d_rperm, ctx->d_operm);
@@ -394,6 +407,24 @@ int omds_test_tile_orders(omds_ctx* ctx, int32_t* rperm, int32_t* operm) {
     CK(hipStreamSynchronize(ctx->stream));
     if (rperm) CK(hipMemcpy(rperm, ctx->d_rperm, (size_t)ctx->cfg.n_traj * 4, hipMemcpyDeviceToHost));
     if (operm) CK(hipMemcpy(operm, ctx->d_operm, (size_t)ctx->n_obs * 4, hipMemcpyDeviceToHost));
+    return OMDS_OK;
+}
+int omds_test_tile_state(omds_ctx* ctx, uint32_t* rkey, uint32_t* okey, int32_t* rperm, int32_t* operm, int32_t* unit, float* W, float* cR, float* cO) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    REQUIRE(rkey && okey && rperm && operm && unit && W && cR && cO, OMDS_ERR_INVALID_ARG, "omds_test_tile_state: NULL output");
+    REQUIRE(ctx->d_rperm && ctx->d_operm && ctx->d_tileKeys, OMDS_ERR_NOT_INITIALISED, "omds_test_tile_state: no block-ordered launch has run on this context");
+    CK(hipSetDevice(ctx->dev));
+    CK(hipStreamSynchronize(ctx->stream));
+    TileKeys k;
+    CK(hipMemcpy(&k, ctx->d_tileKeys, sizeof(TileKeys), hipMemcpyDeviceToHost));
+    CK(hipMemcpy(rkey, ctx->d_rkey, (size_t)ctx->cfg.n_traj * 4, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(okey, ctx->d_okey, (size_t)ctx->n_obs * 4, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(rperm, ctx->d_rperm, (size_t)omds_order_pad(ctx->cfg.n_traj) * 4, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(operm, ctx->d_operm, (size_t)omds_order_pad(ctx->n_obs) * 4, hipMemcpyDeviceToHost));
+    std::memcpy(unit, k.unit, sizeof(k.unit));
+    std::memcpy(W, k.W, sizeof(k.W));
+    std::memcpy(cR, k.cR, sizeof(k.cR));
+    std::memcpy(cO, k.cO, sizeof(k.cO));
     return OMDS_OK;
 }
 int omds_test_read_dmin(omds_ctx* ctx, float* dmin) {

@@ -6,159 +6,172 @@
 // rollouts x consecutive obstacles of the two key orders.  Nothing here has to be exact: every permutation of the rows computes the
 // same bits, the order only decides how many chunks the products run over.
 //
-//   k_tile_pick     once per propagate, in front of its first full launch: the key units (the OMDS_KEY_UNITS units whose firing
-//                   rate over the N rollouts, obstacle share at its mean, is nearest 1/2; ties by lower unit index), their
-//                   weights and constants (TileKeys), and the obstacle order operm of the scene (slab 0 of an obstacle horizon)
-//   k_rollout_order once per horizon step, in front of that step's pass 1: the rollout order rperm from Fq
+// Four small kernels, each written once for a table of rows and used for the rollouts (Fq) and the obstacles (Fp) alike, each spread
+// over the device (a row group, a block of rows or a block of entries per workgroup):
 //
+//   k_share_stats   per unit the sum of the layer-1 shares of OMDS_SHARE_ROWS rows, and the number of them that fire against a
+//                   constant: partial sums [groups][256], reduced by their readers in ascending group order (no float atomics)
+//   k_tile_pick     the key units (the OMDS_KEY_UNITS units whose firing count over the N rollouts, obstacle share at its mean, is
+//                   nearest N / 2; ties by lower unit index), their weights and the constants of both keys (TileKeys)
+//   k_order_keys    key[i] = sign bits << 20 | i of the rows of a table
+//   k_order_rank    perm[rank of key[i]] = i; the owner of the last rank fills the padding
+//
+// Once per propagate, in front of its first full launch: stats(Fp of the scene, slab 0 of an obstacle horizon), stats(Fq), pick,
+// keys + rank of the obstacles, keys + rank of the rollouts; in front of every later step's pass 1: keys + rank of the rollouts.
 // Both orders are the ranks of (key << 20 | index): ties by lower index, the same permutation on every run.
 #include "omds_internal.h"
 
-__device__ __forceinline__ float order_dot32(const float (&w)[OMDS_FROW], const float* __restrict__ row) {
+constexpr int OMDS_KEY_ROWS = 64;        // rows (= threads) of a workgroup of k_order_keys
+constexpr int OMDS_RANK_LANES = 16;      // lanes that share the scan of one entry's rank
+constexpr int OMDS_RANK_ENTRIES = 256 / OMDS_RANK_LANES;   // entries ranked by a workgroup of k_order_rank
+
+// the partial sums of `groups` row groups, in ascending group order: every reader forms the same bits
+__device__ __forceinline__ float share_total(const float* __restrict__ part, int groups, int u) {
     float s = 0.f;
-#pragma unroll
-    for (int q = 0; q < OMDS_FROW / 4; ++q) {
-        const float4 v = reinterpret_cast<const float4*>(row)[q];
-        s = fmaf(w[4 * q], v.x, s); s = fmaf(w[4 * q + 1], v.y, s); s = fmaf(w[4 * q + 2], v.z, s); s = fmaf(w[4 * q + 3], v.w, s);
-    }
+    for (int g = 0; g < groups; ++g) s += part[(size_t)g * OMDS_WIDTH + u];
     return s;
 }
 
-// rank of every entry of key[0 .. n) (distinct values; key[n .. n4) hold 0xffffffff) -> perm[rank] = index; the owner of the
-// last rank also fills perm[n .. npad) with its index, so that a partial block reads valid rows
-__device__ __forceinline__ void order_place(const unsigned* key, int n, int n4, int i, int* __restrict__ perm, int npad) {
-    const unsigned mine = key[i];
-    int pos = 0;
-    for (int x = 0; x < n4; x += 4) {
-        const uint4 k = *reinterpret_cast<const uint4*>(key + x);
-        pos += (k.x < mine) + (k.y < mine) + (k.z < mine) + (k.w < mine);
+// Thread u = hidden unit u over the rows [blockIdx.x * OMDS_SHARE_ROWS ...) of a table: sum[group][u] = the sum of the unit's shares
+// (each table is zero in the other operand's slots: one 32-slot dot product serves both shares).  cnt != nullptr (the rollout
+// pass): also the number of rows with share + c[u] > 0, c = b1 + the mean share of the other table, whose partial sums (prev
+// [prev_groups][256] over prev_n rows) every workgroup reduces for itself.
+// The workgroup's rows reach LDS with one 16-byte load per thread, all in flight at once, and are read from there as broadcasts.
+__global__ __launch_bounds__(OMDS_WIDTH) void k_share_stats(const float* __restrict__ W1t, int F, const float* __restrict__ rows, int n,
+                                                            const float* __restrict__ b1, const float* __restrict__ prev, int prev_groups,
+                                                            int prev_n, float* __restrict__ sum, int* __restrict__ cnt) {
+    __shared__ __attribute__((aligned(16))) float x[OMDS_SHARE_ROWS][OMDS_FROW];
+    static_assert(OMDS_SHARE_ROWS * OMDS_FROW == 4 * OMDS_WIDTH, "one float4 per thread stages the row group");
+    const int u = threadIdx.x, r0 = blockIdx.x * OMDS_SHARE_ROWS, nr = min(OMDS_SHARE_ROWS, n - r0);
+    {
+        const int r = u / (OMDS_FROW / 4), q = u % (OMDS_FROW / 4);
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (r < nr) v = reinterpret_cast<const float4*>(rows + (size_t)(r0 + r) * OMDS_FROW)[q];
+        reinterpret_cast<float4*>(&x[r][0])[q] = v;
     }
-    perm[pos] = i;
-    if (pos == n - 1)
-        for (int p = n; p < npad; ++p) perm[p] = i;
-}
-
-__global__ __launch_bounds__(1024) void k_tile_pick(const float* __restrict__ W1t, const float* __restrict__ b1, int F,
-                                                    const float* __restrict__ Fq, int N, const float* __restrict__ Fp, int O,
-                                                    TileKeys* __restrict__ keys, int* __restrict__ operm, int Opad) {
-    __shared__ float part[4][OMDS_WIDTH];
-    __shared__ int cnt[4][OMDS_WIDTH];
-    __shared__ float meanO[OMDS_WIDTH], meanR[OMDS_WIDTH];
-    __shared__ int away[OMDS_WIDTH];                      // |2 firing rollouts - N| of a unit
-    __shared__ int sel[OMDS_KEY_UNITS];
-    __shared__ __attribute__((aligned(16))) float Wk[OMDS_KEY_UNITS][OMDS_FROW];
-    __shared__ float cO[OMDS_KEY_UNITS];
-    __shared__ __attribute__((aligned(16))) unsigned okey[OMDS_ORDER_MAX_OBS];
-    const int tid = threadIdx.x, u = tid & (OMDS_WIDTH - 1), g = tid >> 8;   // unit u over the rows g, g + 4, ...
     float w[OMDS_FROW];
 #pragma unroll
     for (int f = 0; f < OMDS_FROW; ++f) w[f] = f < F ? W1t[(size_t)f * OMDS_WIDTH + u] : 0.f;
-    // mean obstacle share of every unit (each table is zero in the other operand's slots: one dot product serves both shares)
-    float so = 0.f;
-    for (int o = g; o < O; o += 4) so += order_dot32(w, Fp + (size_t)o * OMDS_FROW);
-    part[g][u] = so;
+    float c = 0.f;
+    if (cnt) c = b1[u] + share_total(prev, prev_groups, u) / (float)prev_n;
     __syncthreads();
-    if (g == 0) meanO[u] = (part[0][u] + part[1][u] + part[2][u] + part[3][u]) / (float)O;
-    __syncthreads();
-    // firing rate and mean rollout share of every unit
-    const float c = b1[u] + meanO[u];
-    float sr = 0.f;
+    float s = 0.f;
     int fire = 0;
-    for (int t = g; t < N; t += 4) {
-        const float r = order_dot32(w, Fq + (size_t)t * OMDS_FROW);
-        sr += r;
-        fire += (r + c > 0.f) ? 1 : 0;
-    }
-    part[g][u] = sr;
-    cnt[g][u] = fire;
-    __syncthreads();
-    if (g == 0) {
-        meanR[u] = (part[0][u] + part[1][u] + part[2][u] + part[3][u]) / (float)N;
-        const int n2 = 2 * (cnt[0][u] + cnt[1][u] + cnt[2][u] + cnt[3][u]) - N;
-        away[u] = n2 < 0 ? -n2 : n2;
-    }
-    __syncthreads();
-    if (tid < OMDS_WIDTH) {
-        int rank = 0;
-        for (int v = 0; v < OMDS_WIDTH; ++v) rank += (away[v] < away[u] || (away[v] == away[u] && v < u)) ? 1 : 0;
-        if (rank < OMDS_KEY_UNITS) sel[rank] = u;
-    }
-    __syncthreads();
-    if (tid < OMDS_KEY_UNITS * OMDS_FROW) {
-        const int j = tid / OMDS_FROW, f = tid % OMDS_FROW;
-        const float v = f < F ? W1t[(size_t)f * OMDS_WIDTH + sel[j]] : 0.f;
-        Wk[j][f] = v;
-        keys->W[j][f] = v;
-    }
-    if (tid < OMDS_KEY_UNITS) {
-        const int s = sel[tid];
-        keys->cR[tid] = b1[s] + meanO[s];
-        keys->unit[tid] = s;
-        cO[tid] = b1[s] + meanR[s];
-    }
-    __syncthreads();
-    // the obstacle order: key bit j = unit sel[j] fires at obstacle o with the rollout share at its mean
-    const int O4 = (O + 3) & ~3;
-    for (int o = tid; o < O4; o += 1024) {
-        unsigned key = 0xffffffffu;
-        if (o < O) {
-            const float4* row = reinterpret_cast<const float4*>(Fp + (size_t)o * OMDS_FROW);
-            float x[OMDS_FROW];
+    for (int r = 0; r < nr; ++r) {
+        float d = 0.f;
 #pragma unroll
-            for (int q = 0; q < OMDS_FROW / 4; ++q) { const float4 v = row[q]; x[4 * q] = v.x; x[4 * q + 1] = v.y; x[4 * q + 2] = v.z; x[4 * q + 3] = v.w; }
-            unsigned bits = 0u;
-#pragma unroll 1
-            for (int j = 0; j < OMDS_KEY_UNITS; ++j) {
-                float s = cO[j];
-#pragma unroll
-                for (int f = 0; f < OMDS_FROW; ++f) s = fmaf(Wk[j][f], x[f], s);
-                bits |= (s > 0.f ? 1u : 0u) << j;
-            }
-            key = (bits << 20) | (unsigned)o;
+        for (int q = 0; q < OMDS_FROW / 4; ++q) {
+            const float4 v = reinterpret_cast<const float4*>(&x[r][0])[q];
+            d = fmaf(w[4 * q], v.x, d); d = fmaf(w[4 * q + 1], v.y, d); d = fmaf(w[4 * q + 2], v.z, d); d = fmaf(w[4 * q + 3], v.w, d);
         }
-        okey[o] = key;
+        s += d;
+        fire += (d + c > 0.f) ? 1 : 0;
     }
-    __syncthreads();
-    for (int o = tid; o < O; o += 1024) order_place(okey, O, O4, o, operm, Opad);
+    sum[(size_t)blockIdx.x * OMDS_WIDTH + u] = s;
+    if (cnt) cnt[(size_t)blockIdx.x * OMDS_WIDTH + u] = fire;
 }
 
-__global__ __launch_bounds__(256) void k_rollout_order(const TileKeys* __restrict__ keys, const float* __restrict__ Fq, int N,
-                                                       int* __restrict__ rperm, int Npad) {
-    extern __shared__ __attribute__((aligned(16))) unsigned rkey[];   // [N rounded up to 4]: every workgroup holds all keys, and ranks 256 of them
+// One workgroup, thread u = hidden unit u: the firing counts and both mean shares from the partial sums, the key units, TileKeys
+__global__ __launch_bounds__(OMDS_WIDTH) void k_tile_pick(const float* __restrict__ W1t, const float* __restrict__ b1, int F,
+                                                          const float* __restrict__ sumO, int groupsO, int O,
+                                                          const float* __restrict__ sumR, const int* __restrict__ cntR, int groupsR, int N,
+                                                          TileKeys* __restrict__ keys) {
+    __shared__ float meanO[OMDS_WIDTH], meanR[OMDS_WIDTH];
+    __shared__ int away[OMDS_WIDTH];                      // |2 firing rollouts - N| of a unit
+    __shared__ int sel[OMDS_KEY_UNITS];
+    const int u = threadIdx.x;
+    meanO[u] = share_total(sumO, groupsO, u) / (float)O;
+    meanR[u] = share_total(sumR, groupsR, u) / (float)N;
+    int fire = 0;
+    for (int g = 0; g < groupsR; ++g) fire += cntR[(size_t)g * OMDS_WIDTH + u];
+    const int n2 = 2 * fire - N;
+    away[u] = n2 < 0 ? -n2 : n2;
+    __syncthreads();
+    int rank = 0;
+    for (int v = 0; v < OMDS_WIDTH; ++v) rank += (away[v] < away[u] || (away[v] == away[u] && v < u)) ? 1 : 0;
+    if (rank < OMDS_KEY_UNITS) sel[rank] = u;
+    __syncthreads();
+    for (int e = u; e < OMDS_KEY_UNITS * OMDS_FROW; e += OMDS_WIDTH) {
+        const int j = e / OMDS_FROW, f = e % OMDS_FROW;
+        keys->W[j][f] = f < F ? W1t[(size_t)f * OMDS_WIDTH + sel[j]] : 0.f;
+    }
+    if (u < OMDS_KEY_UNITS) {
+        const int s = sel[u];
+        keys->cR[u] = b1[s] + meanO[s];
+        keys->cO[u] = b1[s] + meanR[s];
+        keys->unit[u] = s;
+    }
+}
+
+// Thread = row i of a table: key bit j = the key unit j fires at the row with the other operand's share at its mean (an ascending-f
+// fmaf chain from the constant c[j] = TileKeys::cR for the rollouts, ::cO for the obstacles), key[i] = bits << 20 | i
+__global__ __launch_bounds__(OMDS_KEY_ROWS) void k_order_keys(const TileKeys* __restrict__ keys, const float* __restrict__ c,
+                                                              const float* __restrict__ rows, int n, unsigned* __restrict__ key) {
     __shared__ __attribute__((aligned(16))) float Wk[OMDS_KEY_UNITS][OMDS_FROW];
-    __shared__ float cR[OMDS_KEY_UNITS];
-    const int tid = threadIdx.x;
-    for (int e = tid; e < OMDS_KEY_UNITS * OMDS_FROW; e += 256) Wk[e / OMDS_FROW][e % OMDS_FROW] = keys->W[e / OMDS_FROW][e % OMDS_FROW];
-    if (tid < OMDS_KEY_UNITS) cR[tid] = keys->cR[tid];
-    __syncthreads();
-    const int N4 = (N + 3) & ~3;
-    for (int t = tid; t < N4; t += 256) {
-        unsigned key = 0xffffffffu;
-        if (t < N) {
-            const float4* row = reinterpret_cast<const float4*>(Fq + (size_t)t * OMDS_FROW);
-            float x[OMDS_FROW];
+    __shared__ float ck[OMDS_KEY_UNITS];
+    const int tid = threadIdx.x, i = blockIdx.x * OMDS_KEY_ROWS + tid;
+    for (int e = tid; e < OMDS_KEY_UNITS * OMDS_FROW; e += OMDS_KEY_ROWS) Wk[e / OMDS_FROW][e % OMDS_FROW] = keys->W[e / OMDS_FROW][e % OMDS_FROW];
+    if (tid < OMDS_KEY_UNITS) ck[tid] = c[tid];
+    float x[OMDS_FROW];
+    if (i < n) {
+        const float4* row = reinterpret_cast<const float4*>(rows + (size_t)i * OMDS_FROW);
 #pragma unroll
-            for (int q = 0; q < OMDS_FROW / 4; ++q) { const float4 v = row[q]; x[4 * q] = v.x; x[4 * q + 1] = v.y; x[4 * q + 2] = v.z; x[4 * q + 3] = v.w; }
-            unsigned bits = 0u;
-#pragma unroll 1
-            for (int j = 0; j < OMDS_KEY_UNITS; ++j) {
-                float s = cR[j];
+        for (int q = 0; q < OMDS_FROW / 4; ++q) { const float4 v = row[q]; x[4 * q] = v.x; x[4 * q + 1] = v.y; x[4 * q + 2] = v.z; x[4 * q + 3] = v.w; }
+    } else {
 #pragma unroll
-                for (int f = 0; f < OMDS_FROW; ++f) s = fmaf(Wk[j][f], x[f], s);
-                bits |= (s > 0.f ? 1u : 0u) << j;
-            }
-            key = (bits << 20) | (unsigned)t;
-        }
-        rkey[t] = key;
+        for (int f = 0; f < OMDS_FROW; ++f) x[f] = 0.f;
     }
     __syncthreads();
-    const int t = blockIdx.x * 256 + tid;
-    if (t < N) order_place(rkey, N, N4, t, rperm, Npad);
+    unsigned bits = 0u;
+#pragma unroll 1
+    for (int j = 0; j < OMDS_KEY_UNITS; ++j) {
+        float s = ck[j];
+#pragma unroll
+        for (int f = 0; f < OMDS_FROW; ++f) s = fmaf(Wk[j][f], x[f], s);
+        bits |= (s > 0.f ? 1u : 0u) << j;
+    }
+    if (i < n) key[i] = (bits << 20) | (unsigned)i;
 }
 
-void omds_launch_tile_order(hipStream_t s, const MlpDev& m, const float* Fq, int N, const float* Fp, int O, TileKeys* keys,
-                            int* rperm, int* operm, bool pick) {
-    if (pick)
-        hipLaunchKernelGGL(k_tile_pick, dim3(1), dim3(1024), 0, s, m.W1t, m.b1, 3 * m.d, Fq, N, Fp, O, keys, operm, omds_order_pad(O));
-    hipLaunchKernelGGL(k_rollout_order, dim3((N + 255) / 256), dim3(256), (size_t)((N + 3) & ~3) * 4, s, keys, Fq, N, rperm, omds_order_pad(N));
+// Workgroup b ranks the entries [b * OMDS_RANK_ENTRIES ...) of key[0 .. n) (distinct values) against all n keys, held in LDS and
+// padded with 0xffffffff to whole scan rounds; OMDS_RANK_LANES lanes share an entry, each counting the smaller keys of every
+// OMDS_RANK_LANES-th 16-byte piece, summed over the lanes by shuffles.  perm[rank] = index; the owner of the last rank also fills
+// perm[n .. npad) with its index, so that a partial block reads valid rows.
+__global__ __launch_bounds__(256) void k_order_rank(const unsigned* __restrict__ key, int n, int* __restrict__ perm, int npad) {
+    extern __shared__ __attribute__((aligned(16))) unsigned lkey[];   // [n rounded up to 4 * OMDS_RANK_LANES]
+    const int tid = threadIdx.x, nl = (n + 4 * OMDS_RANK_LANES - 1) & ~(4 * OMDS_RANK_LANES - 1);
+    for (int x = tid; x < nl; x += 256) lkey[x] = x < n ? key[x] : 0xffffffffu;
+    __syncthreads();
+    const int lane = tid % OMDS_RANK_LANES, i = blockIdx.x * OMDS_RANK_ENTRIES + tid / OMDS_RANK_LANES;
+    const unsigned mine = lkey[min(i, n - 1)];
+    int pos = 0;
+    for (int x = 4 * lane; x < nl; x += 4 * OMDS_RANK_LANES) {
+        const uint4 k = *reinterpret_cast<const uint4*>(lkey + x);
+        pos += (k.x < mine) + (k.y < mine) + (k.z < mine) + (k.w < mine);
+    }
+#pragma unroll
+    for (int d = 1; d < OMDS_RANK_LANES; d <<= 1) pos += __shfl_xor(pos, d, OMDS_RANK_LANES);
+    if (i < n) {
+        if (lane == 0) perm[pos] = i;
+        if (pos == n - 1)
+            for (int p = n + lane; p < npad; p += OMDS_RANK_LANES) perm[p] = i;
+    }
+}
+
+static void launch_order(hipStream_t s, const TileKeys* keys, const float* c, const float* rows, int n, unsigned* key, int* perm) {
+    hipLaunchKernelGGL(k_order_keys, dim3((n + OMDS_KEY_ROWS - 1) / OMDS_KEY_ROWS), dim3(OMDS_KEY_ROWS), 0, s, keys, c, rows, n, key);
+    const size_t lds = (size_t)((n + 4 * OMDS_RANK_LANES - 1) & ~(4 * OMDS_RANK_LANES - 1)) * sizeof(unsigned);
+    hipLaunchKernelGGL(k_order_rank, dim3((n + OMDS_RANK_ENTRIES - 1) / OMDS_RANK_ENTRIES), dim3(256), lds, s, key, n, perm, omds_order_pad(n));
+}
+
+void omds_launch_tile_order(hipStream_t s, const MlpDev& m, const float* Fq, int N, const float* Fp, int O, const TileOrderBufs& b,
+                            bool pick) {
+    if (pick) {
+        const int gO = omds_share_groups(O), gR = omds_share_groups(N), F = 3 * m.d;
+        hipLaunchKernelGGL(k_share_stats, dim3(gO), dim3(OMDS_WIDTH), 0, s, m.W1t, F, Fp, O, m.b1, nullptr, 0, 1, b.sumO, nullptr);
+        hipLaunchKernelGGL(k_share_stats, dim3(gR), dim3(OMDS_WIDTH), 0, s, m.W1t, F, Fq, N, m.b1, b.sumO, gO, O, b.sumR, b.cntR);
+        hipLaunchKernelGGL(k_tile_pick, dim3(1), dim3(OMDS_WIDTH), 0, s, m.W1t, m.b1, F, b.sumO, gO, O, b.sumR, b.cntR, gR, N, b.keys);
+        launch_order(s, b.keys, b.keys->cO, Fp, O, b.okey, b.operm);
+    }
+    launch_order(s, b.keys, b.keys->cR, Fq, N, b.rkey, b.rperm);
 }

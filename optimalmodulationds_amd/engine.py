@@ -435,6 +435,22 @@ class Engine:
         self._ck(self.lib.omds_test_tile_orders(self.h, L.iptr(rperm), L.iptr(operm)))
         return rperm, operm
 
+    def test_tile_state(self):
+        """Test hook (include/omds_test_tiles.h; needs ``lib=_lib.load_test_hooks()``): what the ordering launches of the last
+        block-ordered pass 1 left, as a dict: ``rkey`` [n_traj] / ``okey`` [n_obs] (uint32: sign bits << 20 | index), ``rperm`` /
+        ``operm`` WITH their padding (``order_pad(n)`` entries), and the propagate's key units ``unit`` [12], ``W`` [12, 32],
+        ``cR`` [12], ``cO`` [12]."""
+        import ctypes as C
+        pad = lambda n: ((n + 15) & ~15) + 16      # omds_test_order_pad
+        out = {"rkey": np.zeros(self.N, np.uint32), "okey": np.zeros(self.n_obs, np.uint32),
+               "rperm": np.zeros(pad(self.N), np.int32), "operm": np.zeros(pad(self.n_obs), np.int32),
+               "unit": np.zeros(12, np.int32), "W": np.zeros((12, 32), np.float32), "cR": np.zeros(12, np.float32),
+               "cO": np.zeros(12, np.float32)}
+        u32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32))
+        self._ck(self.lib.omds_test_tile_state(self.h, u32(out["rkey"]), u32(out["okey"]), L.iptr(out["rperm"]), L.iptr(out["operm"]),
+                                               L.iptr(out["unit"]), L.fptr(out["W"]), L.fptr(out["cR"]), L.fptr(out["cO"])))
+        return out
+
     def test_read_dmin(self):
         """Test hook (include/omds_test_tiles.h; needs ``lib=_lib.load_test_hooks()``): the [n_traj, n_obs] pass-1 matrix the last
         step of the last propagate left."""
