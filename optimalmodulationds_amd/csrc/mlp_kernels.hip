@@ -25,7 +25,11 @@
 //     arithmetic of torch-CPU's addmm, bit for bit;
 //   * accumulators stay in registers until the whole layer is done, so the tile is updated in
 //     place (one LDS buffer, two barriers per layer).
-#include "mlp_device.h"
+#include "pass1_tile.h"
+#include "pass1_tile_dyn.h"
+#include "pass2_device.h"
+#include "topk_device.h"
+#include "trig_device.h"
 
 // ------------------------------------------------------------------------------------------------
 // encoded inputs [x, sin x, cos x] of the rollout states and of the obstacle points (network_macros_mod.py:139-140), each at its
@@ -187,7 +191,7 @@ __global__ __launch_bounds__(512) void k_pass1_dyn_blk(const float* __restrict__
     }
 }
 
-// The same two kernels in pass1_tile's MODE 6 (kernels of their own: the tuned mode-0 kernels keep their argument lists and code):
+// The same two kernels in pass1_tile's TileMode::EmitAll (kernels of their own: the tuned Dmin kernels keep their argument lists and code):
 // beside Dmin every pair's pass-2 distance, arg-min link and ReLU masks go to `ex`, indexed by the pair.
 template <int MT, int MR, int NR, int ACT>
 __global__ __launch_bounds__((Geo<MT, MR, NR>::NT)) void k_pass1e(MlpDev m, const float* __restrict__ Fq,
@@ -196,7 +200,7 @@ __global__ __launch_bounds__((Geo<MT, MR, NR>::NT)) void k_pass1e(MlpDev m, cons
                                                                 long long total_rows, uint32_t ignored,
                                                                 float* __restrict__ Dmin, OmdsDivisor odiv, ExactOut ex) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    pass1_tile<MT, MR, NR, ACT, 6>(m, smem, Fq, Fp, radius, O, total_rows, ignored, Dmin, (long long)blockIdx.x * MT, odiv, nullptr, nullptr, &ex);
+    pass1_tile<MT, MR, NR, ACT, TileMode::EmitAll>(m, smem, Fq, Fp, radius, O, total_rows, ignored, Dmin, (long long)blockIdx.x * MT, odiv, nullptr, nullptr, &ex);
 }
 template <int ACT>
 __global__ __launch_bounds__(512) void k_pass1e_mixed(const float* __restrict__ Fq, const float* __restrict__ Fp,
@@ -206,9 +210,9 @@ __global__ __launch_bounds__(512) void k_pass1e_mixed(const float* __restrict__ 
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int b = blockIdx.x;
     if (b < n_big) {
-        pass1_tile<64, 2, 1, ACT, 6>(m, smem, Fq, Fp, radius, O, total_rows, ignored, Dmin, (long long)b * 64, odiv, nullptr, nullptr, &ex);
+        pass1_tile<64, 2, 1, ACT, TileMode::EmitAll>(m, smem, Fq, Fp, radius, O, total_rows, ignored, Dmin, (long long)b * 64, odiv, nullptr, nullptr, &ex);
     } else {
-        pass1_tile<32, 1, 1, ACT, 6>(m, smem, Fq, Fp, radius, O, total_rows, ignored, Dmin,
+        pass1_tile<32, 1, 1, ACT, TileMode::EmitAll>(m, smem, Fq, Fp, radius, O, total_rows, ignored, Dmin,
                                      (long long)n_big * 64 + (long long)(b - n_big) * 32, odiv, nullptr, nullptr, &ex);
     }
 }
@@ -440,7 +444,7 @@ void omds_launch_pass1_blocks(hipStream_t s, const MlpDev& m, const float* Fq, c
                        (int)n_big, nrb16, OmdsDivisor::make((unsigned)ncb), m);
 }
 
-// pass 1 that also leaves every pair's pass-2 distance, arg-min link and ReLU masks (pass1_tile MODE 6) -- the same tile choice as
+// pass 1 that also leaves every pair's pass-2 distance, arg-min link and ReLU masks (pass1_tile, TileMode::EmitAll) -- the same tile choice as
 // omds_launch_pass1, so Dmin is the same launch shape's bits (they are the same bits in every shape anyway).  ReLU networks only.
 template <int MT, int MR, int NR>
 static void launch_pass1e_t(hipStream_t s, const MlpDev& m, const float* Fq, const float* Fp, const float* radius,

@@ -192,7 +192,7 @@ int build_mlp_packs(int n, int n_linear, const int32_t* in_dims, const int32_t* 
                     wb16[o] = make_float4(Wl[k0 * Wd + j], Wl[k1 * Wd + j], Wl[k2 * Wd + j], Wl[k3 * Wd + j]);
                 }
     }
-    // backward pack for the 4-row-group GEMM (v_mfma_f32_4x4x1, mlp_device.h gemm4): the gradient at a layer's inputs is
+    // backward pack for the 4-row-group GEMM (v_mfma_f32_4x4x1, gemm4 of mfma_gemm.h): the gradient at a layer's inputs is
     // sum_k G[row][k] W[k][j] (W [out = k][in = j]); lane l of column block cb holds W[4 kq .. 4 kq + 3][64 cb + l]
     // (and the forward pack of the same GEMM, pass2_body_g4: sum_k H[row][k] W[j][k], lane l of block cb holds W[64 cb + l][k0 .. k3])
     std::vector<float4>&wb4 = pk.wb4, &wf4 = pk.wf4;

@@ -47,7 +47,7 @@ struct MlpDev {
     const float4* W1f;   // [8 colblk][4 kchunk][64 lane] first layer, forward pack over the 3d encoded inputs (padded to K = 32)
     const float4* W1f16; // [16 colblk16][2 kchunk][64 lane] the same for the 16-row tiles
     const float4* W1b;   // [32 kchunk][64 lane] first layer, backward pack (cols = 3d features, padded to 32)
-    // EXACT ZERO-SKIP of k_pass1 by per-tile compaction (pass1_tile_dyn, mlp_device.h; ReLU networks without skips)
+    // EXACT ZERO-SKIP of k_pass1 by per-tile compaction (pass1_tile_dyn.h; ReLU networks without skips)
     const float* WhT;    // [nhh][256 unit][256 column] hidden->hidden weights transposed (a W^T row = the weights leaving one unit): the
                          // compacted products fetch their fragments by unit
     const float* WlT;    // [256 unit][16] last layer likewise (channels padded to 16)
@@ -335,7 +335,7 @@ struct omds_ctx {
     DevBuf<float> d_exDr;
     DevBuf<int> d_exMin;
     DevBuf<uint32_t> d_exMask;
-    // the all-fp32 step without a second forward (pass1_tile mode 6): per PAIR what k_exact leaves per candidate
+    // the all-fp32 step without a second forward (pass1_tile, TileMode::EmitAll): per PAIR what k_exact leaves per candidate
     DevBuf<float> d_allDr; DevBuf<int> d_allMin; DevBuf<uint32_t> d_allMask;   // [pairs], [pairs], [pairs][all_nhid][8]
     int all_nhid = 0;
     long long all_failed_pairs = -1; int all_failed_nhid = -1;   // the last request these three could not be allocated for (not retried until it changes)
@@ -542,8 +542,8 @@ struct ExactOut {
     int* amin;         // [cap] arg-min link over all raw outputs
     uint32_t* mask;    // [cap][nhid][8]
     int cap;           // entries the arrays hold (the list may be longer: the host then redoes the propagate in fp32)
-    const float* Da = nullptr;   // audit list only (pass1_tile mode 4): [entries] screening value of each listed pair
-    float* deriv = nullptr;      // tanh networks (pass1_tile mode 5): [hidden layers][cap][256] 1 - h^2 of every entry's hidden units
+    const float* Da = nullptr;   // audit list only (pass1_tile, TileMode::Audit): [entries] screening value of each listed pair
+    float* deriv = nullptr;      // tanh networks (pass1_tile, TileMode::ListDeriv): [hidden layers][cap][256] 1 - h^2 of every entry's hidden units
 };
 
 void omds_launch_pass1_emit(hipStream_t s, const MlpDev& m, const float* Fq, const float* Fp, const float* radius,

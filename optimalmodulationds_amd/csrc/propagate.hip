@@ -199,7 +199,7 @@ static int enqueue_dense(omds_ctx* ctx, StepArgs& a) {
     return OMDS_OK;
 }
 
-// Pass 1 leaves pass 2's forward of every pair (pass1_tile mode 6); the tail runs the top-k over the rollout's row of Dmin, takes
+// Pass 1 leaves pass 2's forward of every pair (pass1_tile, TileMode::EmitAll); the tail runs the top-k over the rollout's row of Dmin, takes
 // the masks of the k selected pairs and runs the backward, blend, modulation and Euler step.
 static int enqueue_emit(omds_ctx* ctx, StepArgs& a) {
     const int N = a.N;

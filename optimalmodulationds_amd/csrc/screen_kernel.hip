@@ -41,7 +41,7 @@
 #include <cstdio>
 #include <vector>
 
-#include "mlp_device.h"
+#include "pass1_tile.h"
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
@@ -174,13 +174,10 @@ __device__ __forceinline__ void tile_row(const ScreenArgs& a, long long p0, long
 typedef unsigned u4 __attribute__((ext_vector_type(4)));
 
 // wave-wide minimum of a float, result uniform over the wave (NaN never wins: v_min_f32 returns the other operand): four DPP
-// steps inside each row of 16 lanes (the patterns of pass1_tile's link minimum), then the four rows meet through SGPRs --
+// steps inside each row of 16 lanes (row16_min_f32, the link minimum of pass 1), then the four rows meet through SGPRs --
 // ~10 instructions where a __shfl_xor butterfly is 6 dependent ds_bpermute round trips
 __device__ __forceinline__ float wave_min_f32(float v) {
-    v = fminf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false)));
-    v = fminf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, false)));
-    v = fminf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, false)));
-    v = fminf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, false)));
+    v = row16_min_f32(v);
     const int iv = __builtin_bit_cast(int, v);
     const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(iv, 0)), r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(iv, 16));
     const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(iv, 32)), r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(iv, 48));
@@ -655,7 +652,7 @@ __global__ __launch_bounds__(SC_NT, SC_WAVES == 4 ? 1 : 2) void k_screen(ScreenA
 
 // ------------------------------------------------------------------------------------------------
 // k_select: one wave per rollout (select_rollout above), for the steps whose k_screen writes the matrix: rows too long for a
-// workgroup's LDS, and the matrix route of a tanh network whose derivative hand-over buffer could not be allocated (k_exact mode 3
+// workgroup's LDS, and the matrix route of a tanh network whose derivative hand-over buffer could not be allocated (k_exact, TileMode::ListPatch
 // writes the exact values into the matrix).
 // ------------------------------------------------------------------------------------------------
 struct SelectArgs {
@@ -674,14 +671,14 @@ __global__ __launch_bounds__(SEL_WAVES * 64) void k_select(SelectArgs a) {
 
 // ------------------------------------------------------------------------------------------------
 // k_exact: fp32 pass-1 tiles over the listed rows, 16 rows per tile (v_mfma_f32_16x16x4 fed in the k order of the 32-row
-// kernels: the same bits per row, mlp_device.h), up to three workgroups resident per CU (78 registers).  A tile is a chain of
+// kernels: the same bits per row, mfma_gemm.h), up to three workgroups resident per CU (78 registers).  A tile is a chain of
 // dependent GEMMs on one CU, so what counts is (a) the granularity -- 9.2 candidates per rollout at N = 1024 are 590 tiles of
 // 16 rows for 768 slots, where 32-row tiles were 295 for 256 CUs and the 39 left over doubled the launch time -- and (b)
 // co-residency: three tiles on a CU fill each other's barrier / epilogue / last-layer gaps.  Measured at 9.9 candidates per
 // rollout: 52.9 us, against 59.6 (32-row tiles, two resident), 64.1 (an equal share of 32 + 16 rows per CU, one after the
 // other) and 58.0 (16-row tiles, two resident).
 // ------------------------------------------------------------------------------------------------
-template <int ACT, int MODE>
+template <int ACT, TileMode MODE>
 __global__ __launch_bounds__(512, 6) void k_exact(MlpDev m, const float* __restrict__ Fq, const float* __restrict__ Fp,
                                                   const float* __restrict__ radius, int O, uint32_t ignored,
                                                   float* __restrict__ Dmin, OmdsDivisor odiv, const int* __restrict__ rowlist,
@@ -714,14 +711,14 @@ __global__ __launch_bounds__(512) void k_audit(MlpDev m, const float* __restrict
     const int full = n / (64 * G);                  // rounds in which every workgroup has a full tile
     const int rest0 = full * 64 * G, rest = n - rest0;
     for (int r = 0; r < full; ++r) {
-        pass1_tile<64, 2, 1, ACT, 4>(m, smem, FqAll, Fp, radius, O, n, ignored, nullptr, ((long long)r * G + blockIdx.x) * 64, odiv, rows, maxerr_bits, &ex);
+        pass1_tile<64, 2, 1, ACT, TileMode::Audit>(m, smem, FqAll, Fp, radius, O, n, ignored, nullptr, ((long long)r * G + blockIdx.x) * 64, odiv, rows, maxerr_bits, &ex);
         __syncthreads();
     }
     if (rest > 32 * G) {
         if ((long long)blockIdx.x * 64 < rest)
-            pass1_tile<64, 2, 1, ACT, 4>(m, smem, FqAll, Fp, radius, O, n, ignored, nullptr, rest0 + (long long)blockIdx.x * 64, odiv, rows, maxerr_bits, &ex);
+            pass1_tile<64, 2, 1, ACT, TileMode::Audit>(m, smem, FqAll, Fp, radius, O, n, ignored, nullptr, rest0 + (long long)blockIdx.x * 64, odiv, rows, maxerr_bits, &ex);
     } else if ((long long)blockIdx.x * 32 < rest) {
-        pass1_tile<32, 1, 1, ACT, 4>(m, smem, FqAll, Fp, radius, O, n, ignored, nullptr, rest0 + (long long)blockIdx.x * 32, odiv, rows, maxerr_bits, &ex);
+        pass1_tile<32, 1, 1, ACT, TileMode::Audit>(m, smem, FqAll, Fp, radius, O, n, ignored, nullptr, rest0 + (long long)blockIdx.x * 32, odiv, rows, maxerr_bits, &ex);
     }
 }
 
@@ -740,14 +737,14 @@ __global__ __launch_bounds__(512) void k_audit_slabs(MlpDev m, const float* __re
     const int full = n / (64 * G);
     const int rest0 = full * 64 * G, rest = n - rest0;
     for (int r = 0; r < full; ++r) {
-        pass1_tile<64, 2, 1, ACT, 4, true>(m, smem, FqAll, Fp, radius, O, n, ignored, nullptr, ((long long)r * G + blockIdx.x) * 64, odiv, rows, maxerr_bits, &ex, ndiv, slab_ld);
+        pass1_tile<64, 2, 1, ACT, TileMode::Audit, true>(m, smem, FqAll, Fp, radius, O, n, ignored, nullptr, ((long long)r * G + blockIdx.x) * 64, odiv, rows, maxerr_bits, &ex, ndiv, slab_ld);
         __syncthreads();
     }
     if (rest > 32 * G) {
         if ((long long)blockIdx.x * 64 < rest)
-            pass1_tile<64, 2, 1, ACT, 4, true>(m, smem, FqAll, Fp, radius, O, n, ignored, nullptr, rest0 + (long long)blockIdx.x * 64, odiv, rows, maxerr_bits, &ex, ndiv, slab_ld);
+            pass1_tile<64, 2, 1, ACT, TileMode::Audit, true>(m, smem, FqAll, Fp, radius, O, n, ignored, nullptr, rest0 + (long long)blockIdx.x * 64, odiv, rows, maxerr_bits, &ex, ndiv, slab_ld);
     } else if ((long long)blockIdx.x * 32 < rest) {
-        pass1_tile<32, 1, 1, ACT, 4, true>(m, smem, FqAll, Fp, radius, O, n, ignored, nullptr, rest0 + (long long)blockIdx.x * 32, odiv, rows, maxerr_bits, &ex, ndiv, slab_ld);
+        pass1_tile<32, 1, 1, ACT, TileMode::Audit, true>(m, smem, FqAll, Fp, radius, O, n, ignored, nullptr, rest0 + (long long)blockIdx.x * 32, odiv, rows, maxerr_bits, &ex, ndiv, slab_ld);
     }
 }
 
@@ -1005,10 +1002,10 @@ void omds_launch_select(hipStream_t s, const float* Dmin, int B, int O, const Se
     hipLaunchKernelGGL(k_select, dim3((B + SEL_WAVES - 1) / SEL_WAVES), dim3(SEL_WAVES * 64), 0, s, a);
 }
 
-// ReLU networks: mode 1 -- per entry the exact value, pass 2's distance / arg-min link and the ReLU masks, for k_tail_sel.
-// tanh networks: mode 5 -- the same with 1 - h^2 of every hidden unit (ex.deriv: 1 KB per entry and layer) in place of the masks, so
+// ReLU networks: TileMode::List -- per entry the exact value, pass 2's distance / arg-min link and the ReLU masks, for k_tail_sel.
+// tanh networks: TileMode::ListDeriv -- the same with 1 - h^2 of every hidden unit (ex.deriv: 1 KB per entry and layer) in place of the masks, so
 // that k_tail_sel<..., tanh> runs the backward only (round 4; 3 KB per candidate row of HBM traffic against a second forward in
-// the tail).  Without ex.deriv (a matrix-mode step: rows too long for the selecting flush AND no derivative buffer), mode 3: the
+// the tail).  Without ex.deriv (a matrix-mode step: rows too long for the selecting flush AND no derivative buffer), TileMode::ListPatch: the
 // exact value replaces the screening value in the matrix Dmin itself and k_tail takes its top-k from the matrix and runs its own
 // forward.  The grid is sized for EXACT_RESIDENT resident workgroups per CU; longer lists stride (the list length is only known
 // on the device).
@@ -1023,9 +1020,9 @@ void omds_launch_exact(hipStream_t s, const MlpDev& m, const float* Fq, const fl
     const unsigned grid = (unsigned)std::min<long long>(blocks_max, (long long)EXACT_RESIDENT * ncu);
     const OmdsDivisor od = OmdsDivisor::make((unsigned)O);
     if (m.act == OMDS_ACT_RELU)
-        hipLaunchKernelGGL((k_exact<OMDS_ACT_RELU, 1>), dim3(grid), dim3(512), lds, s, m, Fq, Fp, radius, O, ignored, Dmin, od, rowlist, total, maxerr_bits, ex);
+        hipLaunchKernelGGL((k_exact<OMDS_ACT_RELU, TileMode::List>), dim3(grid), dim3(512), lds, s, m, Fq, Fp, radius, O, ignored, Dmin, od, rowlist, total, maxerr_bits, ex);
     else if (ex.deriv)   // the derivative hand-over: k_tail_sel runs the backward on what this launch leaves per entry
-        hipLaunchKernelGGL((k_exact<OMDS_ACT_TANH, 5>), dim3(grid), dim3(512), lds, s, m, Fq, Fp, radius, O, ignored, Dmin, od, rowlist, total, maxerr_bits, ex);
+        hipLaunchKernelGGL((k_exact<OMDS_ACT_TANH, TileMode::ListDeriv>), dim3(grid), dim3(512), lds, s, m, Fq, Fp, radius, O, ignored, Dmin, od, rowlist, total, maxerr_bits, ex);
     else
-        hipLaunchKernelGGL((k_exact<OMDS_ACT_TANH, 3>), dim3(grid), dim3(512), lds, s, m, Fq, Fp, radius, O, ignored, Dmin, od, rowlist, total, maxerr_bits, ex);
+        hipLaunchKernelGGL((k_exact<OMDS_ACT_TANH, TileMode::ListPatch>), dim3(grid), dim3(512), lds, s, m, Fq, Fp, radius, O, ignored, Dmin, od, rowlist, total, maxerr_bits, ex);
 }

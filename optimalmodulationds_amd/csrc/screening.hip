@@ -27,7 +27,7 @@ bool screen_wanted(omds_ctx* ctx) {
     return (long long)ctx->cfg.n_traj * ctx->n_obs >= 64LL * 1024 && ctx->n_obs >= 4 * ctx->cfg.n_closest;
 }
 
-// The screening pack's unit order from what the network does on the calibration batch.  k_exact (the fp32 tile code, mode 1) is run
+// The screening pack's unit order from what the network does on the calibration batch.  k_exact (the fp32 tile code, TileMode::List) is run
 // once on a uniform pseudo-random sample of the (state, obstacle) pairs of the B calibration states (their layer-1 halves are in
 // d_Fq) and leaves their ReLU masks
 // (ExactOut::mask, [entries][hidden levels][8 words]); per hidden level the units are sorted by how many of the sampled 32-pair blocks
@@ -88,7 +88,7 @@ static int screen_reorder(omds_ctx* ctx, int B, bool from_rollouts) {
                 for (uint32_t w = mr[wi]; w; w &= w - 1) {
                     const int bit = __builtin_ctz(w);
                     // level 0: word 2c + h holds the ballot of component c over lanes 32h .. 32h + 31, lane l <-> unit 4l + c;
-                    // later levels: word wi holds units 32 wi .. 32 wi + 31 (mlp_device.h)
+                    // later levels: word wi holds units 32 wi .. 32 wi + 31 (pass1_tile.h)
                     count[L == 0 ? 4 * (32 * (wi & 1) + bit) + (wi >> 1) : 32 * wi + bit]++;
                 }
         }

@@ -3,12 +3,10 @@
 #pragma once
 #include "omds_internal.h"
 
-// phase stamps inside modulate_core for the k_tail_sel timeline build (-DOMDS_TAIL_TL, mlp_device.h); nothing otherwise
-#if defined(OMDS_TAIL_TL) && defined(OMDS_TL_STAMP)
+#include "timeline_device.h"
+
+// phase stamps inside modulate_core for the k_tail_sel timeline build (-DOMDS_TAIL_TL, timeline_device.h); nothing otherwise
 #define OMDS_MOD_STAMP(i) OMDS_TL_STAMP(i)
-#else
-#define OMDS_MOD_STAMP(i)
-#endif
 
 #define FLT_MAX_F 3.402823466e+38f
 

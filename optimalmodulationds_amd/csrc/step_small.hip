@@ -5,7 +5,7 @@
 // step (MPPI.py:102-223) -- needs no other workgroup: ONE launch per horizon step, one workgroup per R rollouts, no
 // min-distance matrix, no candidate list, no second forward:
 //
-//   1. pass1_tile (MODE 2): the fp32 forward of the R*O pairs on v_mfma_f32_32x32x2 -- the arithmetic of k_pass1, bit for
+//   1. pass1_tile (TileMode::SmallScene): the fp32 forward of the R*O pairs on v_mfma_f32_32x32x2 -- the arithmetic of k_pass1, bit for
 //      bit -- leaving per row the pass-1 value D (min over the un-ignored links), the pass-2 distance and arg-min link
 //      (over all outputs, robot_sdf.py:155) and the ReLU masks of every layer in LDS.
 //   2. per rollout: the k smallest D by (D, obstacle) -- its O values sit in one wave.
@@ -22,7 +22,9 @@
 // two-kernel step would leave its tail on a fraction of the CUs (omds_step_small_wanted).
 #include <algorithm>
 
-#include "mlp_device.h"
+#include "pass1_tile.h"
+#include "pass2_device.h"
+#include "trig_device.h"
 #include "step_device.h"
 
 constexpr int SS_RK = 4;      // backward rows per workgroup (R * k)
@@ -83,7 +85,7 @@ __global__ __launch_bounds__(SS_NT, TR == 16 ? 4 : 2) void k_step_small(SmallArg
     {
         const ExactOut ex{D1, Dr, Amin, nullptr, TR};
         const long long total = (long long)N * O;
-        pass1_tile<TR, 1, 1, ACT, 2>(m, smem, a.Fq, a.Fp, a.radius, O, total, a.ignored, nullptr, (long long)t_base * O, a.odiv,
+        pass1_tile<TR, 1, 1, ACT, TileMode::SmallScene>(m, smem, a.Fq, a.Fp, a.radius, O, total, a.ignored, nullptr, (long long)t_base * O, a.odiv,
                                      nullptr, nullptr, &ex);
     }
     if (tid < SS_RK) { selRow[tid] = -1; selT[tid] = 0; selO[tid] = 0; dr[tid] = 0.f; }
@@ -127,7 +129,7 @@ __global__ __launch_bounds__(SS_NT, TR == 16 ? 4 : 2) void k_step_small(SmallArg
     }
     __syncthreads();
 
-    // ---- 3. backward on the selected rows: ONE 4-row group on v_mfma_f32_4x4x1 (gemm4, mlp_device.h) -----------------------
+    // ---- 3. backward on the selected rows: ONE 4-row group on v_mfma_f32_4x4x1 (gemm4, mfma_gemm.h) -----------------------
     // Four rows are no 16-row MFMA problem (a 16-row tile would run at the 16-row rate to move four useful rows) but they are
     // exactly one row group of the 4x4x1 shape: waves 0-3 multiply 64 columns each, 256 dependent MFMAs per layer (one
     // accumulator chain in the k order of every other kernel: the gradient rows are the two-launch step's bit for bit), the

@@ -11,7 +11,10 @@
 
 #include <atomic>
 
-#include "mlp_device.h"
+#include "pass2_device.h"
+#include "timeline_device.h"
+#include "topk_device.h"
+#include "trig_device.h"
 #include "step_device.h"
 
 struct TailArgs {
@@ -186,7 +189,7 @@ __global__ __launch_bounds__(P2_NT) void k_tail_sel(TailArgs a) {
     for (int rl = wave; rl < RW; rl += 8) {
         const int t = t_base + rl;
         if (t >= N) break;
-        // rowlist == nullptr: EVERY pair of the rollout is an entry and the entry index is the pair index (pass1_tile mode 6: the
+        // rowlist == nullptr: EVERY pair of the rollout is an entry and the entry index is the pair index (pass1_tile, TileMode::EmitAll: the
         // all-fp32 step); no window, no slack to check
         const bool dense = a.rowlist == nullptr;
         const int base = dense ? t * O : a.range[4 * t], cnt = dense ? O : a.range[4 * t + 1];
@@ -254,7 +257,7 @@ __global__ __launch_bounds__(P2_NT) void k_tail_sel(TailArgs a) {
     __syncthreads();
     OMDS_TL_STAMP(2);
     if constexpr (ACT == OMDS_ACT_TANH) {
-        sm.rowE = sel;   // the backward gathers 1 - h^2 of row r from entry sel[r] of ExactOut::deriv (written by k_exact, mode 5)
+        sm.rowE = sel;   // the backward gathers 1 - h^2 of row r from entry sel[r] of ExactOut::deriv (written by k_exact, TileMode::ListDeriv)
     } else {
     // ---- the selected entries' masks -> LDS -> 16 bits per thread and layer in the MFMA C layout (what pass 2's forward
     //      would have left in sm.maskL): thread (wave = 32-column block, lane) owns column wave*32 + (lane&31) of rows crow(r, lane)
@@ -388,7 +391,7 @@ static void launch_tail_sel_t(hipStream_t s, const TailArgs& a) {
 // groups are a choice of speed that the frame's instantiations do without.
 static int frame_rows(int rows, int k) { return rows != 4 ? rows : (k <= 16 ? 16 : 32); }
 
-// 16-row tiles (bit-identical to 32-row ones, mlp_device.h) while their workgroups still fit the CUs two at a time: twice as
+// 16-row tiles (bit-identical to 32-row ones, mfma_gemm.h) while their workgroups still fit the CUs two at a time: twice as
 // many, half as long, and the second resident fills the first one's top-k / gather / modulation phases
 // Tile shapes (4 | 16 | 32 rows) forced by the test hook omds_debug_force_tile_rows (libomds_hip_test.so, include/omds_test.h):
 // every shape computes the same bits, and the tests say so by running them against each other.  The release library has no hook:

@@ -18,7 +18,8 @@
 #include <new>
 #include <vector>
 
-#include "mlp_device.h"   // gemm256: the fp32 MFMA GEMM core of the rollout kernels (k_pass1 runs it at 0.93 of the peak)
+#include "mfma_gemm.h"   // gemm256: the fp32 MFMA GEMM core of the rollout kernels (k_pass1 runs it at 0.93 of the peak)
+#include "trig_device.h"
 
 namespace {
 
@@ -155,7 +156,7 @@ __global__ __launch_bounds__(256) void k_gemm(const float* __restrict__ A, int l
 // operands through LDS 16 k at a time, two barriers per step: 0.62 of the fp32 MFMA peak.  Here a workgroup owns 64 rows and ALL
 // columns: its A tile [64 x 256] sits in LDS for the whole product (row stride 260: conflict-free 16-byte fragment reads), the
 // weights arrive as MFMA B fragments straight from L2 into registers (k_pack256 below re-packs the layer's matrix once per call:
-// 256 KB, every workgroup streams the same bytes), and the product is gemm256 of mlp_device.h -- fully unrolled, no VALU in the
+// 256 KB, every workgroup streams the same bytes), and the product is gemm256 of mfma_gemm.h -- fully unrolled, no VALU in the
 // loop, loads pinned between the MFMAs.  Two workgroups per CU: one's tile load / epilogue runs beside the other's GEMM.
 // Arithmetic of an output element: ONE fmaf chain over ascending k, like the general kernel's; deterministic, independent of M.
 __global__ __launch_bounds__(256) void k_pack256(const float* __restrict__ W, int ld, int N, int K, int trans, float4* __restrict__ P) {

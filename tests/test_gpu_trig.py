@@ -172,7 +172,7 @@ def test_forward_vjp_features(lib, hidden):
 
 
 def test_jacobian_sin_cos_columns(lib):
-    """omds_mlp_jacobian through the encoding's backward (mlp_device.h): d sin x_j / d x_j = cos x_j and d cos x_j / d x_j = -sin x_j,
+    """omds_mlp_jacobian through the encoding's backward (pe_chain_rule, pass2_device.h): d sin x_j / d x_j = cos x_j and d cos x_j / d x_j = -sin x_j,
     the hook's bits (x = ±0 left out: sin 0 = 0 switches both ReLU units of that feature off)."""
     x = _rows()
     eng = _engine(*_identity_net())

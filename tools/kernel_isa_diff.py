@@ -1,0 +1,102 @@
+#!/usr/bin/env python3
+"""Device assembly of two csrc directories, kernel by kernel (CPU only; hipcc cross-compiles).
+
+    python tools/kernel_isa_diff.py PARENT_CSRC CHILD_CSRC [--flags "-DOMDS_TIMELINE"] [--files mlp_kernels tail_kernel]
+
+Every kernel translation unit of each side (a .hip file with a __global__) is compiled with the Makefile's CXXFLAGS plus
+--cuda-device-only -S into a scratch directory, the assembly is cut per kernel symbol, and each kernel is reported as
+"identical" or with instruction count and resource figures of both sides.  It diffs and counts; it looks for no instruction.
+Exit status 1 when a kernel differs or exists on one side only.
+"""
+import argparse
+import concurrent.futures
+import pathlib
+import re
+import shutil
+import subprocess
+import sys
+import tempfile
+
+ROOT = pathlib.Path(__file__).resolve().parent.parent
+FIGURES = ["NumVgprs", "NumAgprs", "TotalNumSgprs", "ScratchSize", "LDSByteSize", "Occupancy"]
+
+
+def cxxflags(csrc):
+    """CXXFLAGS of csrc/Makefile; include/ is this checkout's (a scratch copy of csrc has none beside it)."""
+    line = next(l for l in (csrc / "Makefile").read_text().splitlines() if l.startswith("CXXFLAGS :="))
+    return line.split(":=", 1)[1].replace("$(ARCH)", "gfx950").replace("$(ROOT)", str(ROOT)).split()
+
+
+def compile_asm(job):
+    src, out, flags = job
+    subprocess.run(["/opt/rocm/bin/hipcc", *flags, "-Wno-unused-command-line-argument", "--cuda-device-only", "-S", str(src), "-o", str(out)], check=True)
+    return out
+
+
+def kernels(asm):
+    """{kernel name: (normalised body lines, figures)} of one assembly file."""
+    text = asm.read_text()
+    found = {}
+    for sym in re.findall(r"^\s*\.amdhsa_kernel (\S+)$", text, re.M):
+        start = text.index(f"\n{sym}:")
+        end = text.index("; Occupancy:", start)
+        chunk = text[start:text.index("\n", end)]
+        body = []
+        for line in chunk.splitlines():
+            line = re.sub(r"\.(LBB|Lfunc_end|Lfunc_begin|LJTI)\d+", r".\1", line.split(";")[0].rstrip())   # labels carry the function's index
+            line = line.replace(sym, "KERNEL")
+            if line.strip():
+                body.append(line)
+        figs = {k: int(re.search(rf"^; {k}: (\d+)", chunk, re.M).group(1)) for k in FIGURES}
+        code = body[:next(i for i, l in enumerate(body) if l.startswith("\t.section"))]
+        figs["instructions"] = sum(1 for l in code if re.match(r"\t[a-z]", l))
+        found[demangle(sym)] = (body, figs)
+    return found
+
+
+def demangle(sym):
+    """k_exact<0, 1> for _Z7k_exactILi0ELi1EEv...; an enumerator prints as its value, so a kernel keeps its name when an int parameter
+    becomes an enum.  Without c++filt the symbol itself."""
+    if not shutil.which("c++filt"):
+        return sym
+    name = subprocess.run(["c++filt", sym], capture_output=True, text=True).stdout.strip().replace("(anonymous namespace)::", "")
+    return re.sub(r"\(\w+\)(?=-?\d)", "", name).split("(")[0].removeprefix("void ")
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("parent", type=pathlib.Path)
+    ap.add_argument("child", type=pathlib.Path)
+    ap.add_argument("--flags", default="", help="extra compiler flags for both sides (a diagnostic build's defines)")
+    ap.add_argument("--files", nargs="*", help="translation units by stem (default: every .hip with a __global__)")
+    ap.add_argument("--jobs", type=int, default=4)
+    ap.add_argument("--scratch", help="keep the assembly in this directory instead of a temporary one")
+    a = ap.parse_args()
+    with tempfile.TemporaryDirectory() as tmp:
+        if a.scratch:
+            tmp = a.scratch
+            pathlib.Path(tmp).mkdir(parents=True, exist_ok=True)
+        jobs, stems = [], None
+        for side, csrc in (("parent", a.parent), ("child", a.child)):
+            units = sorted(p for p in csrc.glob("*.hip") if "__global__" in p.read_text() and (not a.files or p.stem in a.files))
+            stems = [p.stem for p in units] if stems is None else [s for s in stems if s in {p.stem for p in units}]
+            jobs += [(p, pathlib.Path(tmp) / f"{side}_{p.stem}.s", cxxflags(csrc) + a.flags.split()) for p in units]
+        with concurrent.futures.ThreadPoolExecutor(a.jobs) as pool:
+            list(pool.map(compile_asm, jobs))
+        differing = 0
+        for stem in stems:
+            old, new = kernels(pathlib.Path(tmp) / f"parent_{stem}.s"), kernels(pathlib.Path(tmp) / f"child_{stem}.s")
+            same = [s for s in old if s in new and old[s][0] == new[s][0]]
+            print(f"== {stem}: {len(same)} of {len(old)} kernels identical")
+            for sym in sorted(set(old) | set(new)):
+                if sym in same:
+                    continue
+                differing += 1
+                print(f"  {sym}")
+                for side, table in (("parent", old), ("child", new)):
+                    print(f"    {side:6s} " + ("absent" if sym not in table else "  ".join(f"{k} {v}" for k, v in table[sym][1].items())))
+        return 1 if differing else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -1,6 +1,6 @@
 // Microbenchmark of the pass-1 GEMM inner loop in isolation: one 64-row activation tile in LDS, packed weights
 // streamed from L2, 8 waves per workgroup (64 rows x 32 columns each), WGS workgroups per CU.
-#include "../../optimalmodulationds_amd/csrc/mlp_device.h"
+#include "../../optimalmodulationds_amd/csrc/mfma_gemm.h"
 #include <cstdio>
 #include <vector>
 
