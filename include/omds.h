@@ -214,6 +214,47 @@ OMDS_API int omds_moving_frame_velocity(int n_dof, int d, int k, const float* gr
 OMDS_API int omds_set_obstacle_frame(omds_ctx* ctx, int moving, float max_speed);
 OMDS_API int omds_get_obstacle_frame(omds_ctx* ctx, int32_t* moving, float* max_speed, int32_t* in_effect);
 OMDS_API int omds_approach_rate(omds_ctx* ctx, const float* q, int batch, float* rate, float* qo);
+/* THE SCENE FROM A DEPTH POINT CLOUD (new work: the reference's obstacle streamers send finished spheres).  A depth camera delivers
+ * 1e4 .. 1e5 points per frame, the robot's own arm among them; the three steps between it and omds_set_obstacles -- a workspace crop,
+ * a voxel down-sample, a robot self-filter -- run here, on the device, and the self-filter uses the distance network the context
+ * already holds.  Additive: no other entry point changes its launches or its bits.
+ *   omds_point_cloud_spheres : host only (no context, no GPU), the DEFINITION.  All fp32, every operation named one rounding:
+ *       inv = 1.0f / voxel (once);  a point with a coordinate that is not finite is dropped;  f_c = floorf((p_c - origin_c) * inv), the
+ *       point is kept only if 0 <= f_c < dims_c on all three axes (compared as floats, then converted);  cell = (i_z dims_y + i_y) dims_x
+ *       + i_x;  a cell is occupied when at least min_points points fall in it;  the output lists the occupied cells in ascending cell
+ *       order, each as the sphere (fmaf((float)i_c + 0.5f, voxel, origin_c), radius).  No centroids, no float atomics: the list is a
+ *       function of the SET of points, whatever their order.  xyz [P,3], 0 <= P <= 16 777 216; xyzr_out [cap,4]; *count_out = occupied
+ *       cells.  More of them than max_spheres or cap: OMDS_ERR_INVALID_ARG with *count_out set and nothing written.
+ *   omds_set_obstacles_from_cloud : the same list built on the device and installed as the scene.  xyz is host memory, or (xyz_on_device
+ *       = 1) device memory on the context's device that the caller has finished writing and leaves alone until the call returns.  One
+ *       pass over the points counts them per cell (integer atomics on a count buffer sized to the spec at first use); an ordered
+ *       compaction (per-block sums, a scan of the sums, per-block emission) writes the candidates in cell order, bit for bit the list
+ *       above.  q_now [n_dof] != NULL: THE SELF-FILTER -- candidate c is dropped when d_c <= self_margin, where d_c is the pass-1 value
+ *       of the library (minimum over the links not in params.ignored_links of y_j / out_div - radius) at the input (q_now, centre_c),
+ *       evaluated by the fp32 pass-1 kernels over one state with the candidates as its obstacle rows (a NaN distance keeps the sphere);
+ *       a second ordered compaction gives the final list.  It needs a network (else OMDS_ERR_NOT_INITIALISED) of hidden width <= 256
+ *       (else OMDS_ERR_UNSUPPORTED); with q_now == NULL neither applies.  If fewer than n_closest spheres remain, copies of spec.pad are
+ *       appended up to n_closest (omds_set_obstacles requires that many).  The list then goes through exactly what omds_set_obstacles
+ *       does (horizon cleared, buffers grown, screening told).  *n_spheres_out = spheres before padding, *n_occupied_out = occupied
+ *       cells before the self-filter (NULL = skip).  More occupied cells than max_spheres: OMDS_ERR_INVALID_ARG, *n_occupied_out set,
+ *       the scene exactly as it was -- that guarantee covers this refusal and the argument checks only: a HIP failure later in the call
+ *       leaves the context without a scene (and without a horizon) until the next successful scene setter.  Synchronous.
+ *   omds_get_obstacles : the scene in force, xyzr [n_obs,4] (NULL: the count only); host state, no GPU work.                          */
+typedef struct {
+    float   origin[3];    /* lower corner of the voxel grid                                           */
+    float   voxel;        /* edge length > 0                                                          */
+    int32_t dims[3];      /* cells per axis, each >= 1, product <= 4 194 304 (2^22)                   */
+    float   radius;       /* sphere radius; <= 0 selects 0.8660254f * voxel (the cell's circumsphere) */
+    int32_t min_points;   /* a cell is occupied when at least this many points fall in it; < 1 -> 1   */
+    int32_t max_spheres;  /* more occupied cells than this is an error; < 1 -> 4096; at most 65 536   */
+    float   self_margin;  /* self-filter threshold, used only when a joint state is passed            */
+    float   pad[4];       /* the sphere that fills an (almost) empty scene up to n_closest            */
+} omds_cloud_spec;
+OMDS_API int omds_point_cloud_spheres(const omds_cloud_spec* spec, const float* xyz, int64_t n_points, float* xyzr_out, int32_t cap,
+                                      int32_t* count_out);
+OMDS_API int omds_set_obstacles_from_cloud(omds_ctx* ctx, const omds_cloud_spec* spec, const float* xyz, int64_t n_points,
+                                           int xyz_on_device, const float* q_now, int32_t* n_spheres_out, int32_t* n_occupied_out);
+OMDS_API int omds_get_obstacles(omds_ctx* ctx, float* xyzr, int32_t* n_obs_out);
 /* LinDS(q_goal) / MPPI.reset_DS / switch_DS_idx (LinDS.py:7-10, MPPI.py:76-84). */
 OMDS_API int omds_set_ds(omds_ctx* ctx, const float* q_goal);
 /* MPPI_toy's nominal DS (MPPI_toy.py:89-91): velocity = (q - q_goal) @ A, A [n,n] row-major, not

@@ -58,6 +58,12 @@ class OmdsSdfDataSpec(C.Structure):
                 ("q_max", F32P), ("p_min", F32P), ("p_max", F32P), ("lspan", F32P)]
 
 
+class OmdsCloudSpec(C.Structure):
+    """omds_cloud_spec (include/omds.h): the voxel grid a point cloud is turned into obstacle spheres on."""
+    _fields_ = [("origin", C.c_float * 3), ("voxel", C.c_float), ("dims", C.c_int32 * 3), ("radius", C.c_float),
+                ("min_points", C.c_int32), ("max_spheres", C.c_int32), ("self_margin", C.c_float), ("pad", C.c_float * 4)]
+
+
 class OmdsError(RuntimeError):
     pass
 
@@ -81,6 +87,9 @@ SIGNATURES = {
     "omds_set_obstacle_frame": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
     "omds_get_obstacle_frame": (C.c_int, [C.c_void_p, I32P, F32P, I32P]),
     "omds_approach_rate": (C.c_int, [C.c_void_p, F32P, C.c_int, F32P, F32P]),
+    "omds_point_cloud_spheres": (C.c_int, [C.POINTER(OmdsCloudSpec), F32P, C.c_int64, F32P, C.c_int32, I32P]),
+    "omds_set_obstacles_from_cloud": (C.c_int, [C.c_void_p, C.POINTER(OmdsCloudSpec), C.c_void_p, C.c_int64, C.c_int, F32P, I32P, I32P]),
+    "omds_get_obstacles": (C.c_int, [C.c_void_p, F32P, I32P]),
     "omds_set_ds": (C.c_int, [C.c_void_p, F32P]),
     "omds_set_ds_matrix": (C.c_int, [C.c_void_p, F32P, F32P]),
     "omds_set_ds_seds": (C.c_int, [C.c_void_p, F32P, C.c_int, F32P, F32P, F32P, F32P, F32P, F32P, C.c_float, C.c_float]),
@@ -177,7 +186,7 @@ HORIZON_HOOK_SIGNATURES = {
 }
 TEST_LIB_PATH = os.path.join(_HERE, "csrc", "libomds_hip_test.so")
 
-ABI_VERSION = 504      # omds_version() of the library this binding was written against
+ABI_VERSION = 505      # omds_version() of the library this binding was written against
 _libs = {}             # path -> bound CDLL
 
 

@@ -1,5 +1,6 @@
 // Host-only declarations shared by the translation units of the C ABI (include/omds.h): context.hip, mlp_pack.hip, network.hip,
-// screening.hip, propagate.hip, update.hip, sdf_data.hip and obstacle_horizon.hip.  No kernel file includes this header.
+// screening.hip, propagate.hip, update.hip, sdf_data.hip, obstacle_horizon.hip and point_cloud.hip (the one of them that also holds
+// kernels, those of the voxel grid).  No other kernel file includes this header.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -174,6 +175,10 @@ int alloc_obstacle_horizon(omds_ctx* ctx);             // the tables for cfg.hor
 void clear_obstacle_horizon(omds_ctx* ctx);            // omds_set_obstacles: back to the static scene
 void obstacle_horizon_network_changed(omds_ctx* ctx);  // omds_set_mlp*: the feature slabs are derived again at the next propagate
 int prepare_obstacle_horizon(omds_ctx* ctx);           // omds_propagate: rebuilds the tables when they are dirty (one launch)
+
+// ---- context.hip: the scene ----------------------------------------------------------------------------------------------------
+int reserve_obstacle_capacity(omds_ctx* ctx, int n_obs);             // grows the obstacle buffers when n_obs exceeds max_obs (the scene is then gone)
+int install_obstacles(omds_ctx* ctx, const float* xyzr, int n_obs);   // the body of omds_set_obstacles behind its argument checks
 
 // ---- network.hip ------------------------------------------------------------------------------------------------------------
 void release_network(omds_ctx* ctx);   // frees omds_ctx::mlp_allocs (omds_destroy; every install starts with it)

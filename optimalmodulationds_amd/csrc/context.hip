@@ -8,7 +8,7 @@ thread_local std::string g_create_err;
 
 extern "C" {
 
-int omds_version(void) { return 504; }
+int omds_version(void) { return 505; }
 
 int omds_device_count(int32_t* count) {
     if (!count) return OMDS_ERR_INVALID_ARG;
@@ -238,10 +238,15 @@ static int grow_obstacle_capacity(omds_ctx* ctx, int n_obs) {
     return OMDS_OK;
 }
 
-int omds_set_obstacles(omds_ctx* ctx, const float* xyzr, int n_obs) {
-    if (!ctx) return OMDS_ERR_INVALID_ARG;
-    REQUIRE(xyzr && n_obs >= 1, OMDS_ERR_INVALID_ARG, "omds_set_obstacles: need n_obs >= 1 and a non-null [O,4] array");
-    REQUIRE(n_obs >= ctx->cfg.n_closest, OMDS_ERR_INVALID_ARG, "omds_set_obstacles: fewer obstacles than n_closest");
+}  // extern "C"
+
+int reserve_obstacle_capacity(omds_ctx* ctx, int n_obs) {
+    return n_obs > ctx->cfg.max_obs ? grow_obstacle_capacity(ctx, n_obs) : OMDS_OK;
+}
+
+// What omds_set_obstacles does with a checked list xyzr [n_obs][4] in host memory (n_obs >= n_closest): omds_set_obstacles_from_cloud
+// ends in the same body (point_cloud.hip)
+int install_obstacles(omds_ctx* ctx, const float* xyzr, int n_obs) {
     CK(hipSetDevice(ctx->dev));
     int rc;
     clear_obstacle_horizon(ctx);   // the new scene stands still until the caller says otherwise (omds_set_obstacle_motion / _horizon)
@@ -255,6 +260,22 @@ int omds_set_obstacles(omds_ctx* ctx, const float* xyzr, int n_obs) {
         CK(hipGetLastError());
     }
     CK(hipStreamSynchronize(ctx->stream));
+    return OMDS_OK;
+}
+
+extern "C" {
+
+int omds_set_obstacles(omds_ctx* ctx, const float* xyzr, int n_obs) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    REQUIRE(xyzr && n_obs >= 1, OMDS_ERR_INVALID_ARG, "omds_set_obstacles: need n_obs >= 1 and a non-null [O,4] array");
+    REQUIRE(n_obs >= ctx->cfg.n_closest, OMDS_ERR_INVALID_ARG, "omds_set_obstacles: fewer obstacles than n_closest");
+    return install_obstacles(ctx, xyzr, n_obs);
+}
+
+int omds_get_obstacles(omds_ctx* ctx, float* xyzr, int32_t* n_obs_out) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    if (n_obs_out) *n_obs_out = ctx->n_obs;
+    if (xyzr && ctx->n_obs > 0) std::memcpy(xyzr, ctx->obs_now.data(), (size_t)ctx->n_obs * 16);
     return OMDS_OK;
 }
 

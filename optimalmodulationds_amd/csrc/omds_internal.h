@@ -375,6 +375,12 @@ struct omds_ctx {
     bool frame_on = false;
     float frame_max = 1.f;       // clamp of the approach speed (the unit speed rollout velocities are normalised to)
     DevBuf<float> d_frameOut;    // [n_traj][1 + n] omds_approach_rate: rate, then qo (allocated at the first call)
+    // the scene from a point cloud (point_cloud.hip; all allocated at the first omds_set_obstacles_from_cloud, grown with the spec)
+    DevBuf<float> d_cloudXyz;         // [P][3] the points of a host cloud
+    DevBuf<unsigned> d_cloudCount;    // [cells rounded up to whole compaction blocks] points per cell
+    DevBuf<unsigned> d_cloudSums;     // [compaction blocks + 1] occupied items per block, scanned in place; the last word: their total
+    DevBuf<float4> d_cloudCand;       // [max_spheres] candidate spheres in cell order
+    DevBuf<float4> d_cloudKept;       // [max_spheres] ... and those the self-filter keeps
     // DS / cost
     bool have_ds = false, have_cost = false;
     float qf[OMDS_MAX_DOF] = {0};

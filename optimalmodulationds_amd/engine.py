@@ -74,6 +74,46 @@ class Engine:
         self.n_obs = obs.shape[0]
         self.max_obs = max(self.max_obs, self.n_obs)
 
+    # ---- the scene from a depth point cloud (omds.h: THE SCENE FROM A DEPTH POINT CLOUD) ------------------------------------------
+    def set_obstacles_from_cloud(self, points, spec, q=None):
+        """Crop, voxel down-sample and (``q`` [n] given: self-filter at that joint state, threshold ``spec.self_margin``) the cloud
+        ``points`` [P, 3] on the device and install the spheres as the scene -> (n_spheres before padding, n_occupied cells).
+        ``points``: host memory (numpy, a CPU tensor), or a float32 torch tensor on the context's device, which is passed by address.
+        ``spec``: an ``OmdsCloudSpec`` (``cloud_spec`` builds one)."""
+        if hasattr(points, "data_ptr") and not points.is_cuda:      # a torch tensor in host memory
+            points = points.detach().numpy()
+        if hasattr(points, "data_ptr"):      # a torch tensor on a device
+            if points.device.index != self.device:
+                raise ValueError(f"set_obstacles_from_cloud: a tensor must live on the context's device {self.device}, got {points.device}")
+            import torch
+            keep = points.detach().to(torch.float32).reshape(-1, 3).contiguous()
+            torch.cuda.current_stream(keep.device).synchronize()      # the library reads it on its own stream
+            addr, P, on_dev = keep.data_ptr() if keep.shape[0] else None, keep.shape[0], 1
+        else:
+            keep = L.f32(points).reshape(-1, 3)
+            addr, P, on_dev = L.fptr(keep) if keep.shape[0] else None, keep.shape[0], 0
+        qn = None if q is None else L.f32(q).reshape(self.n)
+        n_sph, n_occ = np.zeros(1, np.int32), np.zeros(1, np.int32)
+        rc = self.lib.omds_set_obstacles_from_cloud(self.h, C.byref(spec), addr, P, on_dev, L.fptr(qn), L.iptr(n_sph), L.iptr(n_occ))
+        n_obs = np.zeros(1, np.int32)
+        self.lib.omds_get_obstacles(self.h, None, L.iptr(n_obs))      # also after a failure: the context may have dropped its scene
+        self.n_obs = int(n_obs[0])
+        self.max_obs = max(self.max_obs, self.n_obs, int(n_occ[0]) if (rc == 0 and qn is not None) else 0)      # the candidates were obstacle rows
+        try:
+            self._ck(rc)
+        except L.OmdsError as e:
+            e.n_occupied = int(n_occ[0])
+            raise
+        return int(n_sph[0]), int(n_occ[0])
+
+    def get_obstacles(self):
+        """The scene in force, [n_obs, 4] (omds_get_obstacles; host state of the context, no GPU work)."""
+        n_obs = np.zeros(1, np.int32)
+        self._ck(self.lib.omds_get_obstacles(self.h, None, L.iptr(n_obs)))
+        out = np.zeros((int(n_obs[0]), 4), np.float32)
+        self._ck(self.lib.omds_get_obstacles(self.h, L.fptr(out), None))
+        return out
+
     # ---- obstacle horizon: step i of a propagate sees slab i - 1 of a table [H, O, 4] (omds.h) ---------------------------------
     def set_obstacle_motion(self, vel):
         """Constant velocities ``vel`` [O, 3] of the spheres of the last ``set_obstacles``: step i of ``propagate`` sees them moved by
@@ -535,6 +575,35 @@ def predict_obstacle_horizon(obs, vel, horizon, dt):
     if rc != 0:
         raise L.OmdsError(f"omds_obstacle_horizon_predict failed ({rc}): {lib.omds_last_error(None).decode()}")
     return out
+
+
+def cloud_spec(origin, voxel, dims, radius=0.0, min_points=1, max_spheres=4096, self_margin=0.0, pad=(10.0, 10.0, 10.0, 0.0)):
+    """An ``OmdsCloudSpec``: the voxel grid with lower corner ``origin``, edge ``voxel`` and ``dims`` cells per axis; ``radius <= 0``
+    selects the cell's circumsphere; ``pad`` is the sphere that fills a scene of fewer than n_closest spheres (default: far away)."""
+    s = L.OmdsCloudSpec()
+    s.origin[:] = [float(v) for v in origin]
+    s.voxel = float(voxel)
+    s.dims[:] = [int(v) for v in dims]
+    s.radius = float(radius)
+    s.min_points, s.max_spheres = int(min_points), int(max_spheres)
+    s.self_margin = float(self_margin)
+    s.pad[:] = [float(v) for v in pad]
+    return s
+
+
+def point_cloud_spheres(points, spec, cap=None):
+    """The definition on the host (omds_point_cloud_spheres, no GPU): points [P, 3] -> spheres [count, 4] of the occupied cells in
+    ascending cell order.  More of them than ``spec.max_spheres`` or ``cap`` raises; the error carries ``n_occupied``."""
+    lib = L.load()
+    p = L.f32(points).reshape(-1, 3)
+    cap = int(cap) if cap is not None else (spec.max_spheres if spec.max_spheres >= 1 else 4096)
+    out, cnt = np.zeros((max(cap, 1), 4), np.float32), np.zeros(1, np.int32)
+    rc = lib.omds_point_cloud_spheres(C.byref(spec), L.fptr(p) if p.shape[0] else None, p.shape[0], L.fptr(out), cap, L.iptr(cnt))
+    if rc != 0:
+        e = L.OmdsError(f"omds_point_cloud_spheres failed ({rc}): {lib.omds_last_error(None).decode()}")
+        e.n_occupied = int(cnt[0])
+        raise e
+    return out[:int(cnt[0])].copy()
 
 
 def moving_frame_velocity(gradx, drow, vel, n_dof, softmax_k=-10.0, max_speed=1.0):

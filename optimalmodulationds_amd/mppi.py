@@ -141,6 +141,27 @@ class MPPI:
         self._engine.set_obstacle_frame(bool(moving_frame))
         return 0
 
+    def update_obstacles_from_cloud(self, points, voxel, lo, hi, radius=None, self_margin=None, min_points=1, max_spheres=4096):
+        """The scene from a depth point cloud ``points`` [P, 3] (new here; numpy, or a torch tensor on the engine's device): cropped
+        to the box ``lo`` .. ``hi``, down-sampled to one sphere per occupied ``voxel`` cell (``radius`` None: the cell's circumsphere)
+        and, when ``self_margin`` is given, without the spheres the distance network places within that margin of the robot at
+        ``self.q_cur`` (Engine.set_obstacles_from_cloud).  Like ``update_obstacles`` it leaves a static scene in ``self.obs``.
+        Returns (spheres before padding to n_closest, occupied cells)."""
+        from .engine import cloud_spec
+        lo, hi = _np(lo).reshape(3).astype(np.float32), _np(hi).reshape(3).astype(np.float32)
+        dims = np.maximum(np.ceil((hi - lo) / np.float32(voxel) - 1e-4), 1).astype(np.int32)
+        spec = cloud_spec(lo, voxel, dims, 0.0 if radius is None else radius, min_points, max_spheres,
+                          0.0 if self_margin is None else self_margin)
+        q = None if self_margin is None else _np(self.q_cur).reshape(-1)
+        if q is not None:
+            self._push()                             # the filter takes its minimum over the links not in self.ignored_links
+        out = self._engine.set_obstacles_from_cloud(points, spec, q)
+        self.obs = torch.as_tensor(self._engine.get_obstacles())
+        self.n_obs = self.obs.shape[0]
+        self._max_obs = self._engine.max_obs
+        self._engine.set_obstacle_frame(False)       # as update_obstacles without moving_frame leaves it
+        return out
+
     def set_screening(self, mode, eps=0.0, over_horizon=False):
         """The screened pass 1 (Engine.set_screening: mode -1 | 0 | 1 | 2, ``eps`` as there); ``over_horizon``: also while
         ``update_obstacles(..., velocities=)`` has set an obstacle horizon (Engine.set_screening_horizon), which otherwise puts the
