@@ -255,6 +255,58 @@ OMDS_API int omds_point_cloud_spheres(const omds_cloud_spec* spec, const float* 
 OMDS_API int omds_set_obstacles_from_cloud(omds_ctx* ctx, const omds_cloud_spec* spec, const float* xyz, int64_t n_points,
                                            int xyz_on_device, const float* q_now, int32_t* n_spheres_out, int32_t* n_occupied_out);
 OMDS_API int omds_get_obstacles(omds_ctx* ctx, float* xyzr, int32_t* n_obs_out);
+/* SPHERE VELOCITIES FROM SUCCESSIVE CLOUDS (new work: the reference's streamers took velocities from mocap rigid bodies; a depth
+ * camera gives none).  The tracked form of the cloud call estimates one velocity per sphere from the previous tracked frame, on the
+ * device, and installs the velocities as the motion horizon (omds_set_obstacle_motion), so that a sensed scene can use the obstacle
+ * horizon, the moving frame and screening over the horizon.  Additive: no other entry point changes its launches or its bits.
+ * WHAT IT MEASURES: the NORMAL flow of a surface -- the centroid of a cell now minus the pooled centroid of the nearest previously
+ * occupied cell(s).  Motion along a surface's own tangent is invisible to it (a sliding plane occupies the same cells); an object
+ * thicker than its displacement along the motion is under-estimated (its interior cells find themselves at d2 = 0).  The normal
+ * component is the part omds_approach_rate and the moving frame consume, because the distance gradient points along it.  No temporal
+ * smoothing, no segmentation or clustering, no tangential flow: out of scope.
+ *   omds_point_cloud_flow : host only (no context, no GPU), the DEFINITION.  All fp32, every operation named one rounding, every
+ *       conversion to float round-to-nearest; all sums are integers, so the result is a function of the two SETS of points.
+ *       Per frame, for every point omds_point_cloud_spheres keeps: u_c = (p_c - origin_c) * inv, f_c = floorf(u_c), r_c = u_c - f_c
+ *       (exact), k_c = (int)(r_c * 256.0f) (the product exact, the conversion truncates: 0 .. 255); the cell's record is four uint32,
+ *       n += 1 and s_c += k_c (P <= 2^24 points: s <= 255 * 2^24 < 2^32).  The sphere list is that of omds_point_cloud_spheres(spec,
+ *       xyz_now): same occupancy (n >= min_points), same order, same error for more occupied cells than max_spheres or cap (*count_out
+ *       set, nothing else written).  Per occupied NOW cell c = (i_x, i_y, i_z) with record (n, s): the window is every cell j = c + k,
+ *       |k_c| <= reach on all axes, inside the grid, whose PREVIOUS record has n'_j >= min_points; d2 = k . k.  Empty window: vel = 0,
+ *       not matched.  Else m = min d2, T = {j : d2 = m}, t = |T|, A_c = -sum_T k_c (int32), P_c = sum_T s'_jc (uint64), N' = sum_T n'_j
+ *       (uint64), and   whole_c = (float)A_c / (float)t;   sub_c = ((float)s_c / (float)n - (float)P_c / (float)N') * 0.00390625f;
+ *       vel_c = ((whole_c + sub_c) * voxel) / dt_frame.   Ties are averaged, so no axis is favoured.  still > 0: with s2 = fmaf(v_z, v_z,
+ *       fmaf(v_y, v_y, v_x * v_x)), s2 < still * still makes all three components +0.  *matched_out counts the cells with a non-empty
+ *       window, zeroed by still or not.  xyzr_out [cap,4], vel_out [cap,3].  OMDS_ERR_INVALID_ARG before anything is written: a bad
+ *       spec, reach outside 1 .. 4, dt_frame not finite or not > 0, still not finite, null pointers, a point count outside 0 .. 2^24.
+ *   omds_set_obstacles_from_cloud_tracked : everything omds_set_obstacles_from_cloud does, in the same order, with the same final list
+ *       bit for bit (self-filter and padding included); its counting pass also sums the sub-cell offsets (records of 16 bytes per cell,
+ *       two such buffers in the context, integer atomics only), both compactions carry each sphere's cell index, and one launch (one
+ *       wave per final sphere) evaluates the definition above against the stored frame.  After the list is installed the velocities go
+ *       in through omds_set_obstacle_motion (padding spheres: 0).  THE PREVIOUS FRAME is the occupancy AS COUNTED by the last successful
+ *       tracked call: the self-filter is not applied to it, so a sphere within reach cells of where the arm was can match the arm.
+ *       There is no previous frame at the first call, after omds_cloud_track_reset, and when origin, voxel or dims are not bitwise
+ *       those of the stored frame or min_points (resolved: < 1 is 1) differs: then the frame is stored, *n_matched_out = -1 and no
+ *       horizon is set.  If every velocity of the final list is exactly 0 (a static scene; everything under still) the horizon stays
+ *       cleared and the propagate that follows is the static one: same launches, same bits.  Otherwise the context is in horizon mode
+ *       1.  *n_matched_out = final spheres (after the self-filter) with a non-empty window.  The stored frame is touched only by a
+ *       successful tracked call and by the reset: omds_set_obstacles_from_cloud and omds_set_obstacles leave it alone, and a refusal
+ *       (too many occupied cells, an argument check) leaves the scene AND the stored frame exactly as they were.
+ *   omds_cloud_track_reset : forget the stored frame.
+ *   omds_get_obstacle_motion : *have_out = 1 while a motion horizon is set, and its velocities into vel [n_obs,3] (zeros without one;
+ *       NULL: no copy); host state, no GPU work.  OMDS_ERR_NOT_INITIALISED before any scene.                                          */
+typedef struct {
+    int32_t reach;     /* search window, cells per axis each way: 1 .. 4                                    */
+    float   dt_frame;  /* seconds between the previous tracked frame and this one: finite, > 0              */
+    float   still;     /* speeds below this become exactly 0; <= 0 disables                                 */
+} omds_cloud_track_spec;
+OMDS_API int omds_point_cloud_flow(const omds_cloud_spec* spec, const omds_cloud_track_spec* track, const float* xyz_prev,
+                                   int64_t n_prev, const float* xyz_now, int64_t n_now, float* xyzr_out, float* vel_out, int32_t cap,
+                                   int32_t* count_out, int32_t* matched_out);
+OMDS_API int omds_set_obstacles_from_cloud_tracked(omds_ctx* ctx, const omds_cloud_spec* spec, const omds_cloud_track_spec* track,
+                                                   const float* xyz, int64_t n_points, int xyz_on_device, const float* q_now,
+                                                   int32_t* n_spheres_out, int32_t* n_occupied_out, int32_t* n_matched_out);
+OMDS_API int omds_cloud_track_reset(omds_ctx* ctx);
+OMDS_API int omds_get_obstacle_motion(omds_ctx* ctx, float* vel, int32_t* have_out);
 /* LinDS(q_goal) / MPPI.reset_DS / switch_DS_idx (LinDS.py:7-10, MPPI.py:76-84). */
 OMDS_API int omds_set_ds(omds_ctx* ctx, const float* q_goal);
 /* MPPI_toy's nominal DS (MPPI_toy.py:89-91): velocity = (q - q_goal) @ A, A [n,n] row-major, not

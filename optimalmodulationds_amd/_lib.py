@@ -64,6 +64,11 @@ class OmdsCloudSpec(C.Structure):
                 ("min_points", C.c_int32), ("max_spheres", C.c_int32), ("self_margin", C.c_float), ("pad", C.c_float * 4)]
 
 
+class OmdsCloudTrackSpec(C.Structure):
+    """omds_cloud_track_spec (include/omds.h): how the tracked cloud call matches a frame against the previous one."""
+    _fields_ = [("reach", C.c_int32), ("dt_frame", C.c_float), ("still", C.c_float)]
+
+
 class OmdsError(RuntimeError):
     pass
 
@@ -90,6 +95,12 @@ SIGNATURES = {
     "omds_point_cloud_spheres": (C.c_int, [C.POINTER(OmdsCloudSpec), F32P, C.c_int64, F32P, C.c_int32, I32P]),
     "omds_set_obstacles_from_cloud": (C.c_int, [C.c_void_p, C.POINTER(OmdsCloudSpec), C.c_void_p, C.c_int64, C.c_int, F32P, I32P, I32P]),
     "omds_get_obstacles": (C.c_int, [C.c_void_p, F32P, I32P]),
+    "omds_point_cloud_flow": (C.c_int, [C.POINTER(OmdsCloudSpec), C.POINTER(OmdsCloudTrackSpec), F32P, C.c_int64, F32P, C.c_int64, F32P, F32P,
+                                        C.c_int32, I32P, I32P]),
+    "omds_set_obstacles_from_cloud_tracked": (C.c_int, [C.c_void_p, C.POINTER(OmdsCloudSpec), C.POINTER(OmdsCloudTrackSpec), C.c_void_p,
+                                                        C.c_int64, C.c_int, F32P, I32P, I32P, I32P]),
+    "omds_cloud_track_reset": (C.c_int, [C.c_void_p]),
+    "omds_get_obstacle_motion": (C.c_int, [C.c_void_p, F32P, I32P]),
     "omds_set_ds": (C.c_int, [C.c_void_p, F32P]),
     "omds_set_ds_matrix": (C.c_int, [C.c_void_p, F32P, F32P]),
     "omds_set_ds_seds": (C.c_int, [C.c_void_p, F32P, C.c_int, F32P, F32P, F32P, F32P, F32P, F32P, C.c_float, C.c_float]),
@@ -186,7 +197,7 @@ HORIZON_HOOK_SIGNATURES = {
 }
 TEST_LIB_PATH = os.path.join(_HERE, "csrc", "libomds_hip_test.so")
 
-ABI_VERSION = 505      # omds_version() of the library this binding was written against
+ABI_VERSION = 506     # omds_version() of the library this binding was written against
 _libs = {}             # path -> bound CDLL
 
 

@@ -143,6 +143,17 @@ int omds_set_obstacle_motion(omds_ctx* ctx, const float* vel) {
     return OMDS_OK;
 }
 
+int omds_get_obstacle_motion(omds_ctx* ctx, float* vel, int32_t* have_out) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    REQUIRE(ctx->n_obs > 0, OMDS_ERR_NOT_INITIALISED, "omds_get_obstacle_motion: obstacles not set (omds_set_obstacles)");
+    const bool have = ctx->hz_mode == 1;
+    if (have_out) *have_out = have ? 1 : 0;
+    if (!vel) return OMDS_OK;
+    if (have) std::memcpy(vel, ctx->hz_vel.data(), (size_t)ctx->n_obs * 12);
+    else std::fill(vel, vel + (size_t)ctx->n_obs * 3, 0.f);
+    return OMDS_OK;
+}
+
 int omds_set_obstacle_horizon(omds_ctx* ctx, const float* xyzr_h, int n_obs) {
     if (!ctx) return OMDS_ERR_INVALID_ARG;
     int rc;

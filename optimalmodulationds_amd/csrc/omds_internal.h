@@ -381,6 +381,17 @@ struct omds_ctx {
     DevBuf<unsigned> d_cloudSums;     // [compaction blocks + 1] occupied items per block, scanned in place; the last word: their total
     DevBuf<float4> d_cloudCand;       // [max_spheres] candidate spheres in cell order
     DevBuf<float4> d_cloudKept;       // [max_spheres] ... and those the self-filter keeps
+    // ... tracked (omds_set_obstacles_from_cloud_tracked): per cell the record (n, s_x, s_y, s_z) of point_cloud_flow_def.h.  One of
+    // the two buffers holds the stored frame, the other is counted into; a successful tracked call makes its own the stored one
+    DevBuf<uint4> d_cloudRec[2];      // [cells rounded up to whole compaction blocks] each, allocated when first counted into
+    int cloud_stored = 0;             // which of the two is the stored frame
+    bool cloud_have_frame = false;    // a frame is stored (a tracked call succeeded since creation / omds_cloud_track_reset)
+    float cloud_frame_origin[3] = {0.f, 0.f, 0.f}, cloud_frame_voxel = 0.f;   // the grid of the stored frame, compared bitwise
+    int cloud_frame_dims[3] = {0, 0, 0};
+    unsigned cloud_frame_min_points = 0;
+    DevBuf<int> d_cloudCandCell;      // [max_spheres] cell index of every candidate, in step with d_cloudCand
+    DevBuf<int> d_cloudKeptCell;      // [max_spheres] ... and of every kept one
+    DevBuf<float4> d_cloudVel;        // [max_spheres] velocity of every final sphere; .w: 1 where its window was not empty (k_cloud_flow)
     // DS / cost
     bool have_ds = false, have_cost = false;
     float qf[OMDS_MAX_DOF] = {0};

@@ -4,8 +4,11 @@
 // candidates as its obstacle rows (the launch the shared first step of a propagate uses) and a second compaction of those it keeps.
 // The arithmetic of a cell and of its sphere is point_cloud_def.h's, shared with the host definition.  The final list goes to the host
 // (a few thousand x 16 bytes) and from there through install_obstacles, the body of omds_set_obstacles (context.hip).
+// The tracked form (omds_set_obstacles_from_cloud_tracked) counts into records of 16 bytes per cell (k_cloud_count_rec), carries each
+// candidate's cell index through both compactions, and evaluates point_cloud_flow_def.h against the records of the previous tracked
+// frame with one wave per final sphere (k_cloud_flow); the velocities then go in through omds_set_obstacle_motion.
 #include "capi_internal.h"
-#include "point_cloud_def.h"
+#include "point_cloud_flow_def.h"
 
 namespace {
 
@@ -19,6 +22,20 @@ __global__ __launch_bounds__(CLOUD_NT) void k_cloud_count(const float* __restric
     for (long long i = (long long)blockIdx.x * CLOUD_NT + threadIdx.x; i < P; i += (long long)gridDim.x * CLOUD_NT) {
         const int cell = cloud_cell(g, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]);
         if (cell >= 0) atomicAdd(&count[cell], 1u);
+    }
+}
+
+// ... of the tracked call: the same crop, and per kept point the record (n, s_x, s_y, s_z) of its cell, four integer atomics
+__global__ __launch_bounds__(CLOUD_NT) void k_cloud_count_rec(const float* __restrict__ xyz, long long P, CloudGrid g, uint4* __restrict__ rec) {
+    for (long long i = (long long)blockIdx.x * CLOUD_NT + threadIdx.x; i < P; i += (long long)gridDim.x * CLOUD_NT) {
+        unsigned k[3];
+        const int cell = cloud_cell_sub(g, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], k);
+        if (cell < 0) continue;
+        unsigned* r = reinterpret_cast<unsigned*>(rec + cell);
+        atomicAdd(r, 1u);
+        atomicAdd(r + 1, k[0]);
+        atomicAdd(r + 2, k[1]);
+        atomicAdd(r + 3, k[2]);
     }
 }
 
@@ -72,6 +89,35 @@ struct KeepSrc {            // items = candidates; d [n] their pass-1 distances 
     }
     __device__ void emit(int item, unsigned pos) const { out[pos] = cand[item]; }
 };
+// ... and those of the tracked call, which also write every kept item's cell index beside its sphere
+struct RecSrc {             // items = cells; rec is zero-padded to whole blocks like count, occupancy is its .x
+    const uint4* rec;
+    CloudGrid g;
+    float4* out;
+    int* cell;
+    __device__ unsigned flags(int base, int) const {
+        unsigned f = 0;
+        for (int j = 0; j < CLOUD_ITEMS; ++j)
+            if (rec[base + j].x >= g.min_points) f |= 1u << j;
+        return f;
+    }
+    __device__ void emit(int item, unsigned pos) const {
+        float s[4];
+        cloud_sphere(g, item, s);
+        out[pos] = make_float4(s[0], s[1], s[2], s[3]);
+        cell[pos] = item;
+    }
+};
+struct KeepCellSrc {
+    KeepSrc keep;
+    const int* candCell;
+    int* cell;
+    __device__ unsigned flags(int base, int n) const { return keep.flags(base, n); }
+    __device__ void emit(int item, unsigned pos) const {
+        keep.emit(item, pos);
+        cell[pos] = candCell[item];
+    }
+};
 
 template <class Src>
 __global__ __launch_bounds__(CLOUD_NT) void k_compact_sums(Src src, int n, unsigned* __restrict__ sums) {
@@ -115,6 +161,63 @@ __global__ __launch_bounds__(CLOUD_NT) void k_compact_emit(Src src, int n, const
         }
 }
 
+__device__ inline unsigned wave_min(unsigned v) {
+    for (int d = 32; d > 0; d >>= 1) v = min(v, (unsigned)__shfl_xor(v, d, 64));
+    return v;
+}
+template <class T>
+__device__ inline T wave_sum(T v) {
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+
+// The velocity of every final sphere (point_cloud_flow_def.h): one wave per sphere, four per workgroup, no barrier.  A first probe
+// of the sphere's own cell in the previous frame settles the common case (d2 = 0 is the unique minimum).  Otherwise the lanes stride
+// over the window clipped to the grid, x innermost; each keeps the sums of its own cells at its own smallest d2, the wave takes the
+// minimum, lanes above it drop their sums, and the rest is added up by shuffles -- integers throughout, so the schedule cannot change
+// a bit.  Lane 0 then evaluates the fp32 lines of the definition; vel[sphere].w = 1 where the window was not empty (the host counts
+// them: one counter for all spheres would serialise 30 000 atomics on one address, 0.34 ms at the scene of EXPERIMENTS R18).
+constexpr int FLOW_WAVES = CLOUD_NT / 64;
+__global__ __launch_bounds__(CLOUD_NT) void k_cloud_flow(CloudGrid g, CloudTrack tr, const uint4* __restrict__ now, const uint4* __restrict__ prev,
+                                                         const int* __restrict__ cells, int n_spheres, float4* __restrict__ vel) {
+    const int lane = threadIdx.x & 63, sphere = blockIdx.x * FLOW_WAVES + (threadIdx.x >> 6);
+    if (sphere >= n_spheres) return;   // a whole wave
+    const int cell = cells[sphere];
+    CloudFlowSums a;
+    cloud_flow_clear(a);
+    const uint4 own = prev[cell];
+    if (own.x >= g.min_points) {
+        cloud_flow_add(a, 0, 0, 0, own.x, own.y, own.z, own.w);
+    } else {
+        const int ix = cell % g.dx, iy = (cell / g.dx) % g.dy, iz = cell / (g.dx * g.dy);
+        const int x0 = max(ix - tr.reach, 0), y0 = max(iy - tr.reach, 0), z0 = max(iz - tr.reach, 0);
+        const int wx = min(ix + tr.reach, g.dx - 1) - x0 + 1, wy = min(iy + tr.reach, g.dy - 1) - y0 + 1, wz = min(iz + tr.reach, g.dz - 1) - z0 + 1;
+        for (int i = lane; i < wx * wy * wz; i += 64) {
+            const int x = x0 + i % wx, y = y0 + (i / wx) % wy, z = z0 + i / (wx * wy);
+            const uint4 p = prev[(z * g.dy + y) * g.dx + x];
+            if (p.x >= g.min_points) cloud_flow_add(a, x - ix, y - iy, z - iz, p.x, p.y, p.z, p.w);
+        }
+        const unsigned best = wave_min(a.d2);
+        if (a.d2 != best) cloud_flow_clear(a);
+        a.d2 = best;
+        a.t = wave_sum(a.t);
+        a.N = wave_sum(a.N);
+        for (int c = 0; c < 3; ++c) {
+            a.A[c] = wave_sum(a.A[c]);
+            a.P[c] = wave_sum(a.P[c]);
+        }
+    }
+    if (lane != 0) return;
+    float v[3] = {0.f, 0.f, 0.f};
+    const bool matched = a.d2 != OMDS_CLOUD_NO_MATCH;
+    if (matched) {
+        const uint4 r = now[cell];
+        const unsigned s[3] = {r.y, r.z, r.w};
+        cloud_flow_velocity(g, tr, r.x, s, a, v);
+    }
+    vel[sphere] = make_float4(v[0], v[1], v[2], matched ? 1.f : 0.f);
+}
+
 inline int compaction_blocks(int n) { return (n + CLOUD_BLOCK - 1) / CLOUD_BLOCK; }
 
 // the ordered compaction of n items of src into src.out (at most cap spheres written); *total_out = kept items.  Synchronises.
@@ -135,33 +238,35 @@ int compact(omds_ctx* ctx, const Src& src, int n, int cap, int* total_out) {
     return OMDS_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int omds_point_cloud_spheres(const omds_cloud_spec* spec, const float* xyz, int64_t n_points, float* xyzr_out, int32_t cap,
-                             int32_t* count_out) {
-    return cloud_spheres_host(spec, xyz, n_points, xyzr_out, cap, count_out, &g_create_err);
-}
-
-int omds_set_obstacles_from_cloud(omds_ctx* ctx, const omds_cloud_spec* spec, const float* xyz, int64_t n_points, int xyz_on_device,
-                                  const float* q_now, int32_t* n_spheres_out, int32_t* n_occupied_out) {
-    if (!ctx) return OMDS_ERR_INVALID_ARG;
-    CloudGrid g;
+// Both cloud entry points.  tr == nullptr is omds_set_obstacles_from_cloud: the count buffer, no cell indices, no velocities.  With tr
+// the same steps in the same order on the record buffer that is NOT the stored frame, then k_cloud_flow over the final list
+int scene_from_cloud(omds_ctx* ctx, const char* who, const omds_cloud_spec* spec, const CloudGrid& g, const CloudTrack* tr, const float* xyz,
+                     int64_t n_points, int xyz_on_device, const float* q_now, int32_t* n_spheres_out, int32_t* n_occupied_out,
+                     int32_t* n_matched_out) {
+    const std::string me(who);
     int rc;
-    if ((rc = cloud_resolve_spec(spec, &g, &ctx->err))) return rc;
     REQUIRE(n_points >= 0 && n_points <= OMDS_CLOUD_MAX_POINTS && (n_points == 0 || xyz), OMDS_ERR_INVALID_ARG,
-            "omds_set_obstacles_from_cloud: need 0 <= n_points <= 16 777 216 and a non-null xyz [P,3]");
+            me + ": need 0 <= n_points <= 16 777 216 and a non-null xyz [P,3]");
     if (q_now) {
-        REQUIRE(ctx->have_mlp, OMDS_ERR_NOT_INITIALISED, "omds_set_obstacles_from_cloud: the self-filter needs the distance network (omds_set_mlp)");
-        REQUIRE(!ctx->wide.on, OMDS_ERR_UNSUPPORTED, "omds_set_obstacles_from_cloud: no self-filter on networks wider than 256 (no obstacle tables)");
+        REQUIRE(ctx->have_mlp, OMDS_ERR_NOT_INITIALISED, me + ": the self-filter needs the distance network (omds_set_mlp)");
+        REQUIRE(!ctx->wide.on, OMDS_ERR_UNSUPPORTED, me + ": no self-filter on networks wider than 256 (no obstacle tables)");
     }
     CK(hipSetDevice(ctx->dev));
     const int nb = compaction_blocks(g.n_cells), k = ctx->cfg.n_closest;
     static_assert(CLOUD_MAX_BLOCKS * CLOUD_BLOCK == OMDS_CLOUD_MAX_CELLS, "k_compact_scan takes every grid the spec allows");
-    if (ctx->d_cloudCount.count() < (size_t)nb * CLOUD_BLOCK || ctx->d_cloudCand.count() < (size_t)g.max_spheres) {
+    const size_t n_padded = (size_t)nb * CLOUD_BLOCK;
+    DevBuf<uint4>* rec = tr ? &ctx->d_cloudRec[1 - ctx->cloud_stored] : nullptr;   // counted into; the stored frame is the other one
+    if ((tr ? rec->count() < n_padded || ctx->d_cloudVel.count() < (size_t)g.max_spheres : ctx->d_cloudCount.count() < n_padded) ||
+        ctx->d_cloudCand.count() < (size_t)g.max_spheres) {
         CK(hipStreamSynchronize(ctx->stream));
-        CK(ctx->d_cloudCount.reserve((size_t)nb * CLOUD_BLOCK));
+        if (tr) {
+            CK(rec->reserve(n_padded));
+            CK(ctx->d_cloudCandCell.reserve((size_t)g.max_spheres));
+            CK(ctx->d_cloudKeptCell.reserve((size_t)g.max_spheres));
+            CK(ctx->d_cloudVel.reserve((size_t)g.max_spheres));
+        } else {
+            CK(ctx->d_cloudCount.reserve(n_padded));
+        }
         CK(ctx->d_cloudSums.reserve((size_t)CLOUD_MAX_BLOCKS + 1));
         CK(ctx->d_cloudCand.reserve((size_t)g.max_spheres));
         CK(ctx->d_cloudKept.reserve((size_t)g.max_spheres));
@@ -176,18 +281,26 @@ int omds_set_obstacles_from_cloud(omds_ctx* ctx, const omds_cloud_spec* spec, co
         CK(hipMemcpyAsync(ctx->d_cloudXyz, xyz, (size_t)n_points * 12, hipMemcpyHostToDevice, ctx->stream));
         d_xyz = ctx->d_cloudXyz;
     }
-    CK(hipMemsetAsync(ctx->d_cloudCount, 0, (size_t)nb * CLOUD_BLOCK * 4, ctx->stream));
-    if (n_points > 0) {
-        const unsigned grid = (unsigned)std::min<long long>((n_points + CLOUD_NT - 1) / CLOUD_NT, 2048);
-        hipLaunchKernelGGL(k_cloud_count, dim3(grid), dim3(CLOUD_NT), 0, ctx->stream, d_xyz, (long long)n_points, g, ctx->d_cloudCount.get());
-    }
+    const unsigned grid = (unsigned)std::min<long long>((n_points + CLOUD_NT - 1) / CLOUD_NT, 2048);
     int occupied = 0;
-    const CellSrc cells{ctx->d_cloudCount, g, ctx->d_cloudCand};
-    if ((rc = compact(ctx, cells, g.n_cells, g.max_spheres, &occupied))) return rc;
+    if (tr) {
+        CK(hipMemsetAsync(rec->get(), 0, n_padded * 16, ctx->stream));
+        if (n_points > 0)
+            hipLaunchKernelGGL(k_cloud_count_rec, dim3(grid), dim3(CLOUD_NT), 0, ctx->stream, d_xyz, (long long)n_points, g, rec->get());
+        const RecSrc cells{rec->get(), g, ctx->d_cloudCand, ctx->d_cloudCandCell};
+        if ((rc = compact(ctx, cells, g.n_cells, g.max_spheres, &occupied))) return rc;
+    } else {
+        CK(hipMemsetAsync(ctx->d_cloudCount, 0, n_padded * 4, ctx->stream));
+        if (n_points > 0)
+            hipLaunchKernelGGL(k_cloud_count, dim3(grid), dim3(CLOUD_NT), 0, ctx->stream, d_xyz, (long long)n_points, g, ctx->d_cloudCount.get());
+        const CellSrc cells{ctx->d_cloudCount, g, ctx->d_cloudCand};
+        if ((rc = compact(ctx, cells, g.n_cells, g.max_spheres, &occupied))) return rc;
+    }
     if (n_occupied_out) *n_occupied_out = occupied;
     REQUIRE(occupied <= g.max_spheres, OMDS_ERR_INVALID_ARG,
-            "omds_set_obstacles_from_cloud: more occupied cells than max_spheres (n_occupied_out holds their number); the scene is unchanged");
+            me + ": more occupied cells than max_spheres (n_occupied_out holds their number); the scene is unchanged");
     const float4* d_list = ctx->d_cloudCand;
+    const int* d_cell = ctx->d_cloudCandCell;
     int n_list = occupied;
     if (q_now && occupied > 0) {
         // The candidates become the obstacle rows of one state.  From here on the tables of the old scene are overwritten: the context
@@ -202,17 +315,98 @@ int omds_set_obstacles_from_cloud(omds_ctx* ctx, const omds_cloud_spec* spec, co
         omds_launch_pass1(ctx->stream, ctx->mlp, ctx->d_Fq, ctx->d_Fp, ctx->d_radius, occupied, 1, ctx->prm.ignored_links, ctx->d_Dmin);
         CK(hipGetLastError());
         const KeepSrc keep{ctx->d_Dmin, d_list, spec->self_margin, ctx->d_cloudKept};
-        if ((rc = compact(ctx, keep, occupied, g.max_spheres, &n_list))) return rc;
+        if (tr) {
+            const KeepCellSrc keep_cell{keep, d_cell, ctx->d_cloudKeptCell};
+            if ((rc = compact(ctx, keep_cell, occupied, g.max_spheres, &n_list))) return rc;
+            d_cell = ctx->d_cloudKeptCell;
+        } else {
+            if ((rc = compact(ctx, keep, occupied, g.max_spheres, &n_list))) return rc;
+        }
         d_list = ctx->d_cloudKept;
     }
-    // to the host, filled up to n_closest with the spec's pad sphere, and in as omds_set_obstacles puts a list in
+    // the velocities of the final list against the stored frame, if there is one on this grid
     const int n_final = std::max(n_list, k);
+    const bool have_prev = tr && ctx->cloud_have_frame && std::memcmp(ctx->cloud_frame_origin, &g.ox, 12) == 0 &&
+                           std::memcmp(&ctx->cloud_frame_voxel, &g.voxel, 4) == 0 && ctx->cloud_frame_dims[0] == g.dx &&
+                           ctx->cloud_frame_dims[1] == g.dy && ctx->cloud_frame_dims[2] == g.dz && ctx->cloud_frame_min_points == g.min_points;
+    std::vector<float> vel4;
+    if (have_prev && n_list > 0) {
+        vel4.resize((size_t)n_list * 4);
+        hipLaunchKernelGGL(k_cloud_flow, dim3((n_list + FLOW_WAVES - 1) / FLOW_WAVES), dim3(CLOUD_NT), 0, ctx->stream, g, *tr,
+                           (const uint4*)rec->get(), (const uint4*)ctx->d_cloudRec[ctx->cloud_stored].get(), d_cell, n_list,
+                           ctx->d_cloudVel.get());
+        CK(hipGetLastError());
+        CK(hipMemcpyAsync(vel4.data(), ctx->d_cloudVel, (size_t)n_list * 16, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    // to the host, filled up to n_closest with the spec's pad sphere, and in as omds_set_obstacles puts a list in
     std::vector<float> list((size_t)n_final * 4);
     if (n_list > 0) CK(hipMemcpyAsync(list.data(), d_list, (size_t)n_list * 16, hipMemcpyDeviceToHost, ctx->stream));
     CK(hipStreamSynchronize(ctx->stream));
     for (int i = n_list; i < n_final; ++i) std::memcpy(&list[(size_t)i * 4], spec->pad, 16);
     if ((rc = install_obstacles(ctx, list.data(), n_final))) return rc;
     if (n_spheres_out) *n_spheres_out = n_list;
+    if (!tr) return OMDS_OK;
+    // a scene whose every sphere stands still keeps the cleared horizon: the propagate that follows is the static one
+    std::vector<float> vel((size_t)n_final * 3, 0.f);   // padding spheres stand still
+    int matched = 0;
+    bool moving = false;
+    for (size_t i = 0; i * 4 < vel4.size(); ++i) {
+        for (int c = 0; c < 3; ++c) {
+            vel[i * 3 + c] = vel4[i * 4 + c];
+            moving |= vel4[i * 4 + c] != 0.f;
+        }
+        matched += vel4[i * 4 + 3] != 0.f;
+    }
+    if (moving && (rc = omds_set_obstacle_motion(ctx, vel.data()))) return rc;
+    ctx->cloud_stored = 1 - ctx->cloud_stored;   // what was counted is the stored frame now
+    ctx->cloud_have_frame = true;
+    std::memcpy(ctx->cloud_frame_origin, &g.ox, 12);
+    ctx->cloud_frame_voxel = g.voxel;
+    ctx->cloud_frame_dims[0] = g.dx; ctx->cloud_frame_dims[1] = g.dy; ctx->cloud_frame_dims[2] = g.dz;
+    ctx->cloud_frame_min_points = g.min_points;
+    if (n_matched_out) *n_matched_out = have_prev ? (int32_t)matched : -1;
+    return OMDS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int omds_point_cloud_spheres(const omds_cloud_spec* spec, const float* xyz, int64_t n_points, float* xyzr_out, int32_t cap,
+                             int32_t* count_out) {
+    return cloud_spheres_host(spec, xyz, n_points, xyzr_out, cap, count_out, &g_create_err);
+}
+
+int omds_point_cloud_flow(const omds_cloud_spec* spec, const omds_cloud_track_spec* track, const float* xyz_prev, int64_t n_prev,
+                          const float* xyz_now, int64_t n_now, float* xyzr_out, float* vel_out, int32_t cap, int32_t* count_out,
+                          int32_t* matched_out) {
+    return cloud_flow_host(spec, track, xyz_prev, n_prev, xyz_now, n_now, xyzr_out, vel_out, cap, count_out, matched_out, &g_create_err);
+}
+
+int omds_set_obstacles_from_cloud(omds_ctx* ctx, const omds_cloud_spec* spec, const float* xyz, int64_t n_points, int xyz_on_device,
+                                  const float* q_now, int32_t* n_spheres_out, int32_t* n_occupied_out) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    CloudGrid g;
+    if (int rc = cloud_resolve_spec(spec, &g, &ctx->err)) return rc;
+    return scene_from_cloud(ctx, "omds_set_obstacles_from_cloud", spec, g, nullptr, xyz, n_points, xyz_on_device, q_now, n_spheres_out,
+                            n_occupied_out, nullptr);
+}
+
+int omds_set_obstacles_from_cloud_tracked(omds_ctx* ctx, const omds_cloud_spec* spec, const omds_cloud_track_spec* track, const float* xyz,
+                                          int64_t n_points, int xyz_on_device, const float* q_now, int32_t* n_spheres_out,
+                                          int32_t* n_occupied_out, int32_t* n_matched_out) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    CloudGrid g;
+    CloudTrack tr;
+    if (int rc = cloud_resolve_spec(spec, &g, &ctx->err)) return rc;
+    if (int rc = cloud_resolve_track(track, &tr, &ctx->err)) return rc;
+    return scene_from_cloud(ctx, "omds_set_obstacles_from_cloud_tracked", spec, g, &tr, xyz, n_points, xyz_on_device, q_now, n_spheres_out,
+                            n_occupied_out, n_matched_out);
+}
+
+int omds_cloud_track_reset(omds_ctx* ctx) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    ctx->cloud_have_frame = false;
     return OMDS_OK;
 }
 

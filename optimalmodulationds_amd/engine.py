@@ -80,11 +80,22 @@ class Engine:
         ``points`` [P, 3] on the device and install the spheres as the scene -> (n_spheres before padding, n_occupied cells).
         ``points``: host memory (numpy, a CPU tensor), or a float32 torch tensor on the context's device, which is passed by address.
         ``spec``: an ``OmdsCloudSpec`` (``cloud_spec`` builds one)."""
+        return self._scene_from_cloud("set_obstacles_from_cloud", points, spec, q, None)[:2]
+
+    def set_obstacles_from_cloud_tracked(self, points, spec, track, q=None):
+        """``set_obstacles_from_cloud`` with one velocity per sphere, estimated on the device from the previous tracked frame (the
+        normal flow of the surfaces: omds.h, SPHERE VELOCITIES FROM SUCCESSIVE CLOUDS) and installed as the motion horizon ->
+        (n_spheres, n_occupied, n_matched).  ``track``: an ``OmdsCloudTrackSpec`` (``cloud_track_spec`` builds one).  n_matched is -1
+        when there was no previous frame on this grid (the first call, after ``cloud_track_reset``, another grid): the frame is
+        stored and the scene stands still.  It also stands still (horizon mode 0) when every velocity came out 0."""
+        return self._scene_from_cloud("set_obstacles_from_cloud_tracked", points, spec, q, track)
+
+    def _scene_from_cloud(self, who, points, spec, q, track):
         if hasattr(points, "data_ptr") and not points.is_cuda:      # a torch tensor in host memory
             points = points.detach().numpy()
         if hasattr(points, "data_ptr"):      # a torch tensor on a device
             if points.device.index != self.device:
-                raise ValueError(f"set_obstacles_from_cloud: a tensor must live on the context's device {self.device}, got {points.device}")
+                raise ValueError(f"{who}: a tensor must live on the context's device {self.device}, got {points.device}")
             import torch
             keep = points.detach().to(torch.float32).reshape(-1, 3).contiguous()
             torch.cuda.current_stream(keep.device).synchronize()      # the library reads it on its own stream
@@ -93,8 +104,12 @@ class Engine:
             keep = L.f32(points).reshape(-1, 3)
             addr, P, on_dev = L.fptr(keep) if keep.shape[0] else None, keep.shape[0], 0
         qn = None if q is None else L.f32(q).reshape(self.n)
-        n_sph, n_occ = np.zeros(1, np.int32), np.zeros(1, np.int32)
-        rc = self.lib.omds_set_obstacles_from_cloud(self.h, C.byref(spec), addr, P, on_dev, L.fptr(qn), L.iptr(n_sph), L.iptr(n_occ))
+        n_sph, n_occ, n_match = np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32)
+        if track is None:
+            rc = self.lib.omds_set_obstacles_from_cloud(self.h, C.byref(spec), addr, P, on_dev, L.fptr(qn), L.iptr(n_sph), L.iptr(n_occ))
+        else:
+            rc = self.lib.omds_set_obstacles_from_cloud_tracked(self.h, C.byref(spec), C.byref(track), addr, P, on_dev, L.fptr(qn),
+                                                                L.iptr(n_sph), L.iptr(n_occ), L.iptr(n_match))
         n_obs = np.zeros(1, np.int32)
         self.lib.omds_get_obstacles(self.h, None, L.iptr(n_obs))      # also after a failure: the context may have dropped its scene
         self.n_obs = int(n_obs[0])
@@ -104,7 +119,20 @@ class Engine:
         except L.OmdsError as e:
             e.n_occupied = int(n_occ[0])
             raise
-        return int(n_sph[0]), int(n_occ[0])
+        return int(n_sph[0]), int(n_occ[0]), int(n_match[0])
+
+    def cloud_track_reset(self):
+        """Forget the previous tracked frame: the next ``set_obstacles_from_cloud_tracked`` stores its own and sets no velocities."""
+        self._ck(self.lib.omds_cloud_track_reset(self.h))
+
+    def get_obstacle_motion(self):
+        """(vel [n_obs, 3], have): the velocities of the motion horizon in force (``set_obstacle_motion``, or the tracked cloud call)
+        and whether there is one; zeros without (omds_get_obstacle_motion; host state of the context, no GPU work)."""
+        n_obs, have = np.zeros(1, np.int32), np.zeros(1, np.int32)
+        self._ck(self.lib.omds_get_obstacles(self.h, None, L.iptr(n_obs)))
+        vel = np.zeros((int(n_obs[0]), 3), np.float32)
+        self._ck(self.lib.omds_get_obstacle_motion(self.h, L.fptr(vel), L.iptr(have)))
+        return vel, bool(have[0])
 
     def get_obstacles(self):
         """The scene in force, [n_obs, 4] (omds_get_obstacles; host state of the context, no GPU work)."""
@@ -591,6 +619,14 @@ def cloud_spec(origin, voxel, dims, radius=0.0, min_points=1, max_spheres=4096, 
     return s
 
 
+def cloud_track_spec(reach, dt_frame, still=0.0):
+    """An ``OmdsCloudTrackSpec``: match within ``reach`` cells (1 .. 4) per axis each way, ``dt_frame`` seconds since the previous
+    tracked frame, speeds below ``still`` become exactly 0 (<= 0: off)."""
+    t = L.OmdsCloudTrackSpec()
+    t.reach, t.dt_frame, t.still = int(reach), float(dt_frame), float(still)
+    return t
+
+
 def point_cloud_spheres(points, spec, cap=None):
     """The definition on the host (omds_point_cloud_spheres, no GPU): points [P, 3] -> spheres [count, 4] of the occupied cells in
     ascending cell order.  More of them than ``spec.max_spheres`` or ``cap`` raises; the error carries ``n_occupied``."""
@@ -604,6 +640,23 @@ def point_cloud_spheres(points, spec, cap=None):
         e.n_occupied = int(cnt[0])
         raise e
     return out[:int(cnt[0])].copy()
+
+
+def point_cloud_flow(prev, now, spec, track, cap=None):
+    """The definition of the tracked cloud call on the host (omds_point_cloud_flow, no GPU): clouds ``prev`` and ``now`` [P, 3] ->
+    (spheres [count, 4] of ``point_cloud_spheres(now, spec)``, vel [count, 3], matched).  Raises like ``point_cloud_spheres``."""
+    lib = L.load()
+    a, b = L.f32(prev).reshape(-1, 3), L.f32(now).reshape(-1, 3)
+    cap = int(cap) if cap is not None else (spec.max_spheres if spec.max_spheres >= 1 else 4096)
+    out, vel = np.zeros((max(cap, 1), 4), np.float32), np.zeros((max(cap, 1), 3), np.float32)
+    cnt, matched = np.zeros(1, np.int32), np.zeros(1, np.int32)
+    rc = lib.omds_point_cloud_flow(C.byref(spec), C.byref(track), L.fptr(a) if a.shape[0] else None, a.shape[0],
+                                   L.fptr(b) if b.shape[0] else None, b.shape[0], L.fptr(out), L.fptr(vel), cap, L.iptr(cnt), L.iptr(matched))
+    if rc != 0:
+        e = L.OmdsError(f"omds_point_cloud_flow failed ({rc}): {lib.omds_last_error(None).decode()}")
+        e.n_occupied = int(cnt[0])
+        raise e
+    return out[:int(cnt[0])].copy(), vel[:int(cnt[0])].copy(), int(matched[0])
 
 
 def moving_frame_velocity(gradx, drow, vel, n_dof, softmax_k=-10.0, max_speed=1.0):

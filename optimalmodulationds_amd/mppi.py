@@ -141,13 +141,19 @@ class MPPI:
         self._engine.set_obstacle_frame(bool(moving_frame))
         return 0
 
-    def update_obstacles_from_cloud(self, points, voxel, lo, hi, radius=None, self_margin=None, min_points=1, max_spheres=4096):
+    def update_obstacles_from_cloud(self, points, voxel, lo, hi, radius=None, self_margin=None, min_points=1, max_spheres=4096,
+                                    dt_frame=None, reach=2, still=0.0, moving_frame=False):
         """The scene from a depth point cloud ``points`` [P, 3] (new here; numpy, or a torch tensor on the engine's device): cropped
         to the box ``lo`` .. ``hi``, down-sampled to one sphere per occupied ``voxel`` cell (``radius`` None: the cell's circumsphere)
         and, when ``self_margin`` is given, without the spheres the distance network places within that margin of the robot at
         ``self.q_cur`` (Engine.set_obstacles_from_cloud).  Like ``update_obstacles`` it leaves a static scene in ``self.obs``.
-        Returns (spheres before padding to n_closest, occupied cells)."""
-        from .engine import cloud_spec
+        Returns (spheres before padding to n_closest, occupied cells).
+        ``dt_frame`` (seconds since the previous such call): the tracked route (Engine.set_obstacles_from_cloud_tracked) -- one
+        velocity per sphere from the previous frame, the surfaces' normal flow, searched ``reach`` cells each way, speeds below
+        ``still`` zeroed, and installed as ``update_obstacles(obs, velocities=)`` would.  ``self.obs_velocities`` then holds them
+        ([O, 3], a CPU tensor) or None when the scene stands still (no previous frame, or every velocity 0), ``self.cloud_matched``
+        the spheres that found a previous surface (-1: no previous frame), and ``moving_frame`` acts as in ``update_obstacles``."""
+        from .engine import cloud_spec, cloud_track_spec
         lo, hi = _np(lo).reshape(3).astype(np.float32), _np(hi).reshape(3).astype(np.float32)
         dims = np.maximum(np.ceil((hi - lo) / np.float32(voxel) - 1e-4), 1).astype(np.int32)
         spec = cloud_spec(lo, voxel, dims, 0.0 if radius is None else radius, min_points, max_spheres,
@@ -155,11 +161,19 @@ class MPPI:
         q = None if self_margin is None else _np(self.q_cur).reshape(-1)
         if q is not None:
             self._push()                             # the filter takes its minimum over the links not in self.ignored_links
-        out = self._engine.set_obstacles_from_cloud(points, spec, q)
+        self.obs_velocities, self.cloud_matched = None, None
+        if dt_frame is None:
+            out = self._engine.set_obstacles_from_cloud(points, spec, q)
+        else:
+            *out, self.cloud_matched = self._engine.set_obstacles_from_cloud_tracked(points, spec, cloud_track_spec(reach, dt_frame, still), q)
+            out = tuple(out)
+            vel, have = self._engine.get_obstacle_motion()
+            if have:
+                self.obs_velocities = torch.as_tensor(vel)
         self.obs = torch.as_tensor(self._engine.get_obstacles())
         self.n_obs = self.obs.shape[0]
         self._max_obs = self._engine.max_obs
-        self._engine.set_obstacle_frame(False)       # as update_obstacles without moving_frame leaves it
+        self._engine.set_obstacle_frame(bool(moving_frame))       # as update_obstacles leaves it
         return out
 
     def set_screening(self, mode, eps=0.0, over_horizon=False):

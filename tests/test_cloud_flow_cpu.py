@@ -1,0 +1,330 @@
+"""The definition of the sphere velocities of two successive point clouds on the host (include/omds.h: omds_point_cloud_flow; no
+context, no GPU) against the numpy restatement of the header's text in tests/cloud_flow_cases.py: velocities bit for bit, the matched
+count exactly, and the sphere list that of omds_point_cloud_spheres on the second cloud.
+
+The same cases also go through a stand-alone build of the definition under AddressSanitizer + UBSan (tests/cloud_flow_host.cpp, its
+buffers allocated at exactly the sizes passed), whose output must be the library's bit for bit."""
+import ctypes as C
+import os
+import shutil
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+import cloud_flow_cases as cases
+from cloud_cases import F32, spec_of
+from cloud_flow_cases import restate_flow, track_of
+from helpers import ROOT
+
+ERR_INVALID_ARG = 1
+SENTINEL = F32(-7)
+
+
+@pytest.fixture(scope="module")
+def lib():
+    import __graft_entry__ as g
+    g.build()
+    from optimalmodulationds_amd import _lib
+    return _lib.load()
+
+
+def bits(a):
+    return np.ascontiguousarray(a, F32).view(np.uint32)
+
+
+def call(lib, spec, track, prev, now, cap=65536):
+    """(rc, count, matched, spheres, vel) of the raw entry point; a refused call must have written no sphere and no velocity"""
+    prev, now = (np.ascontiguousarray(p, F32).reshape(-1, 3) for p in (prev, now))
+    out, vel = np.full((max(cap, 1), 4), SENTINEL, F32), np.full((max(cap, 1), 3), SENTINEL, F32)
+    cnt, matched = np.full(1, -1, np.int32), np.full(1, -1, np.int32)
+    rc = lib.omds_point_cloud_flow(C.byref(spec), C.byref(track), prev.ctypes.data if prev.size else None, prev.shape[0],
+                                   now.ctypes.data if now.size else None, now.shape[0], out.ctypes.data, vel.ctypes.data, cap,
+                                   cnt.ctypes.data, matched.ctypes.data)
+    if rc != 0:
+        assert (out == SENTINEL).all() and (vel == SENTINEL).all() and matched[0] == -1, "a refused call must write nothing"
+        return rc, int(cnt[0]), -1, out[:0], vel[:0]
+    n = int(cnt[0])
+    assert (out[n:] == SENTINEL).all() and (vel[n:] == SENTINEL).all()
+    return rc, n, int(matched[0]), out[:n].copy(), vel[:n].copy()
+
+
+def check(lib, spec, track, prev, now):
+    """the definition equals the restatement; -> (spheres, vel, matched, whole of the restatement)"""
+    from optimalmodulationds_amd.engine import point_cloud_spheres
+    rc, count, matched, spheres, vel = call(lib, spec, track, prev, now)
+    occ, want_vel, want_matched, whole = restate_flow(spec, track, prev, now)
+    assert rc == 0 and count == len(occ) and matched == want_matched
+    assert np.array_equal(bits(spheres), bits(point_cloud_spheres(now, spec, cap=65536))), "the list is not omds_point_cloud_spheres(now)"
+    assert np.array_equal(bits(vel), bits(want_vel)), "velocities are not the restatement's bits"
+    return spheres, vel, matched, whole
+
+
+# ---- 1. the definition against the restatement ------------------------------------------------------------------------------------
+@pytest.mark.parametrize("reach", [1, 2, 4])
+def test_random_clouds_match_the_restatement(lib, reach):
+    spec, prev, now = cases.random_pair(3, (12, 10, 9), 700, 600, fill=0.7)
+    _, vel, matched, _ = check(lib, spec, track_of(reach, 0.1), prev, now)
+    assert 20 < matched <= len(vel) and (vel != 0).any()
+
+
+def test_non_dyadic_grid_matches_the_restatement(lib):
+    spec, prev, now = cases.random_pair(4, (14, 14, 10), 900, 900, voxel=0.05, origin=(-0.35, -0.35, -0.1), fill=0.6)
+    _, vel, matched, _ = check(lib, spec, track_of(2, 1.0 / 30.0, still=0.4), prev, now)
+    assert matched > 100 and (vel != 0).any() and (vel == 0).all(1).any()
+
+
+# ---- 2. the exact slab ------------------------------------------------------------------------------------------------------------
+def test_exact_slab(lib):
+    spec, prev, now = cases.slab()
+    assert len(prev) == 35 * 5
+    spheres, vel, matched, _ = check(lib, spec, track_of(3, 0.125), prev, now)
+    assert len(spheres) == 35 and matched == 35
+    assert np.array_equal(bits(vel), bits(np.tile(np.array([1.125, 0.0, 0.0], F32), (35, 1))))
+    spheres, vel, matched, _ = check(lib, spec, track_of(1, 0.125), prev, now)
+    assert len(spheres) == 35 and matched == 0 and np.array_equal(bits(vel), np.zeros((35, 3), np.uint32))
+
+
+# ---- 3. ties ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n", [2, 4, 8])
+def test_ties_are_averaged(lib, n):
+    spec, prev, now = cases.ties(n)
+    spheres, vel, matched, whole = check(lib, spec, track_of(2, 0.5), prev, now)
+    assert len(spheres) == 1 and matched == 1
+    tied = {2: [0], 4: [0, 1], 8: [0, 1, 2]}[n]
+    assert (whole[0, tied] == 0).all() and (vel[0, tied] == 0).all()
+    if n < 8:       # the surface came up from one cell below: one cell in half a second
+        assert whole[0, 2] == 1 and vel[0, 2] == F32(0.0625) / F32(0.5)
+
+
+# ---- 4. grid faces ----------------------------------------------------------------------------------------------------------------
+def test_corner_cells(lib):
+    spec, prev, now = cases.corners()
+    spheres, vel, matched, whole = check(lib, spec, track_of(1, 0.25), prev, now)
+    assert len(spheres) == 8 and matched == 8 and (np.abs(whole) == 1).all()       # one diagonal cell outward on every axis
+
+
+def test_flat_grid(lib):
+    spec, prev, now = cases.random_pair(5, (37, 29, 1), 400, 400, shift=(1.6, -0.7, 0.0), fill=0.8)
+    _, vel, matched, _ = check(lib, spec, track_of(3, 0.1), prev, now)
+    assert matched > 100 and (vel[:, 2] != 0).any(), "in a grid one cell high the z flow is the change of the in-cell height alone"
+
+
+def test_reach_wider_than_the_grid(lib):
+    spec, prev, now = cases.random_pair(6, (3, 2, 5), 12, 25, shift=(0.0, 0.0, 0.0))
+    _, _, matched, _ = check(lib, spec, track_of(4, 0.1), prev, now)
+    assert matched > 10
+
+
+# ---- 5. robustness ----------------------------------------------------------------------------------------------------------------
+def test_order_of_the_points_changes_nothing(lib):
+    spec, prev, now = cases.random_pair(3, (12, 10, 9), 700, 600, fill=0.7)
+    tr = track_of(2, 0.1)
+    want = call(lib, spec, tr, prev, now)
+    rng = np.random.RandomState(9)
+    for a, b in ((prev[rng.permutation(len(prev))], now), (prev, now[rng.permutation(len(now))])):
+        got = call(lib, spec, tr, a, b)
+        assert got[:3] == want[:3] and np.array_equal(bits(got[3]), bits(want[3])) and np.array_equal(bits(got[4]), bits(want[4]))
+
+
+def test_min_points_applies_to_the_previous_frame(lib):
+    spec = spec_of((0.0, 0.0, 0.0), 0.0625, (8, 8, 8), min_points=3)
+    off = np.array([[0.25, 0.5, 0.5], [0.5, 0.5, 0.5], [0.75, 0.25, 0.5]])
+    now = cases.cell_points(spec, (3, 3, 3), off)
+    thin = cases.cell_points(spec, (4, 3, 3), off[:2])                       # two points: not occupied at min_points 3
+    far = cases.cell_points(spec, (3, 5, 3), off)
+    spheres, vel, matched, whole = check(lib, spec, track_of(2, 0.1), np.concatenate([thin, far]), now)
+    assert len(spheres) == 1 and matched == 1 and list(whole[0]) == [0, -2, 0]
+    assert check(lib, spec, track_of(2, 0.1), thin, now)[2] == 0
+
+
+def test_duplicates_count(lib):
+    spec = spec_of((0.0, 0.0, 0.0), 0.0625, (8, 8, 8), min_points=2)
+    p = cases.cell_points(spec, (2, 2, 2), [[0.25, 0.25, 0.25]])
+    q = cases.cell_points(spec, (2, 3, 2), [[0.75, 0.25, 0.25]])
+    spheres, vel, matched, _ = check(lib, spec, track_of(1, 1.0), np.concatenate([q, q, q]), np.concatenate([p, p]))
+    assert len(spheres) == 1 and matched == 1 and np.array_equal(vel[0], np.array([-0.5, -1.0, 0.0], F32) * F32(0.0625))
+    assert check(lib, spec, track_of(1, 1.0), np.concatenate([q, q, q]), p)[0].shape[0] == 0
+
+
+def test_empty_clouds(lib):
+    spec, prev, now = cases.few_spheres(3)
+    none = np.zeros((0, 3), F32)
+    spheres, vel, matched, _ = check(lib, spec, track_of(2, 0.1), none, now)
+    assert len(spheres) == 3 and matched == 0 and not vel.any()
+    assert call(lib, spec, track_of(2, 0.1), prev, none)[:3] == (0, 0, 0)
+    assert call(lib, spec, track_of(2, 0.1), none, none, cap=0)[:3] == (0, 0, 0)
+
+
+def test_non_finite_points_are_dropped_in_both_frames(lib):
+    spec, prev, now = cases.few_spheres(3)
+    bad = np.array([[np.nan, 0.1, 0.1], [0.1, np.inf, 0.1], [0.1, 0.1, -np.inf], [1e30, 0.1, 0.1], [-1.0, 0.1, 0.1]], F32)
+    tr = track_of(2, 0.1)
+    want = call(lib, spec, tr, prev, now)
+    got = call(lib, spec, tr, np.concatenate([bad, prev]), np.concatenate([now, bad]))
+    assert got[:3] == want[:3] == (0, 3, 3) and np.array_equal(bits(got[4]), bits(want[4]))
+    check(lib, spec, tr, np.concatenate([bad, prev]), np.concatenate([now, bad]))
+
+
+# ---- 6. still ---------------------------------------------------------------------------------------------------------------------
+def test_still_zeroes_just_below_and_keeps_just_above(lib):
+    spec, prev, now = cases.few_spheres(1)
+    _, vel, matched, _ = check(lib, spec, track_of(2, 0.1), prev, now)
+    v = vel[0]
+    assert matched == 1 and (v != 0).all()
+    s2 = cases.fmaf(v[2], v[2], cases.fmaf(v[1], v[1], v[0] * v[0]))
+    above = np.sqrt(s2)                                   # the smallest threshold whose square exceeds s2 ...
+    while above * above > s2:
+        above = np.nextafter(above, F32(0))
+    while not above * above > s2:
+        above = np.nextafter(above, F32(np.inf))
+    below = np.nextafter(above, F32(0))                   # ... and the largest one whose square does not
+    assert above.dtype == F32 and below * below <= s2 < above * above
+    _, vel, matched, _ = check(lib, spec, track_of(2, 0.1, still=above), prev, now)
+    assert matched == 1 and np.array_equal(bits(vel[0]), np.zeros(3, np.uint32)), "a zeroed cell still counts as matched, and is +0"
+    _, vel, matched, _ = check(lib, spec, track_of(2, 0.1, still=below), prev, now)
+    assert matched == 1 and np.array_equal(bits(vel[0]), bits(v))
+    for off in (0.0, -1.0):
+        assert np.array_equal(bits(check(lib, spec, track_of(2, 0.1, still=off), prev, now)[1][0]), bits(v))
+
+
+# ---- 7. one heavy cell ------------------------------------------------------------------------------------------------------------
+def test_heavy_cell_sums_round_like_the_restatement(lib):
+    spec, prev, now = cases.heavy()
+    rec_now, rec_prev = cases.records(spec, now), cases.records(spec, prev)
+    assert rec_now[21].tolist() == [70000, 17850000, 17850000, 17850000] and rec_now[21, 1] > 2 ** 24
+    total = int(rec_prev[22, 1] + rec_prev[25, 1])
+    assert total > 2 ** 24 and int(F32(total)) != total, "the pooled sum must not be a float32"
+    spheres, vel, matched, whole = check(lib, spec, track_of(1, 0.1), prev, now)
+    assert len(spheres) == 1 and matched == 1 and list(whole[0]) == [-0.5, -0.5, 0]
+
+
+# ---- 8. errors --------------------------------------------------------------------------------------------------------------------
+def test_errors(lib):
+    spec, prev, now = cases.few_spheres(5)
+    good = track_of(2, 0.1)
+    assert call(lib, spec, good, prev, now)[:3] == (0, 5, 5)
+    for reach in (0, 5, -1):
+        assert call(lib, spec, track_of(reach, 0.1), prev, now)[0] == ERR_INVALID_ARG
+    assert b"reach" in lib.omds_last_error(None)
+    for dt in (0.0, -0.1, np.nan, np.inf, -np.inf):
+        assert call(lib, spec, track_of(2, dt), prev, now)[0] == ERR_INVALID_ARG
+    for still in (np.nan, np.inf, -np.inf):
+        assert call(lib, spec, track_of(2, 0.1, still), prev, now)[0] == ERR_INVALID_ARG
+    assert call(lib, spec_of((0, 0, 0), 0.0, (4, 4, 4)), good, prev, now)[0] == ERR_INVALID_ARG
+    rc, count, _, _, _ = call(lib, spec, good, prev, now, cap=4)                     # a too-small cap: the count comes back, as from
+    assert rc == ERR_INVALID_ARG and count == 5                                     # omds_point_cloud_spheres, and nothing else
+    small = spec_of((0.0, 0.0, 0.0), 0.0625, (8, 8, 8), max_spheres=4)
+    assert call(lib, small, good, prev, now)[:2] == (ERR_INVALID_ARG, 5)
+    assert call(lib, spec, good, prev, now, cap=5)[:3] == (0, 5, 5)
+    # null pointers and point counts
+    out, vel, cnt, mt = np.full((8, 4), SENTINEL, F32), np.full((8, 3), SENTINEL, F32), np.full(1, -1, np.int32), np.full(1, -1, np.int32)
+    args = [C.byref(spec), C.byref(good), prev.ctypes.data, len(prev), now.ctypes.data, len(now), out.ctypes.data, vel.ctypes.data, 8,
+            cnt.ctypes.data, mt.ctypes.data]
+    assert lib.omds_point_cloud_flow(*args) == 0 and cnt[0] == 5
+    out[:], vel[:], cnt[:], mt[:] = SENTINEL, SENTINEL, -1, -1
+    for i in (0, 1, 2, 4, 6, 7, 9, 10):
+        bad = list(args)
+        bad[i] = None
+        assert lib.omds_point_cloud_flow(*bad) == ERR_INVALID_ARG, i
+        assert (out == SENTINEL).all() and (vel == SENTINEL).all() and mt[0] == -1 and cnt[0] == -1, i
+    for i, v in ((3, -1), (5, -1), (3, 2 ** 24 + 1), (8, -1)):
+        bad = list(args)
+        bad[i] = v
+        assert lib.omds_point_cloud_flow(*bad) == ERR_INVALID_ARG, (i, v)
+        assert (out == SENTINEL).all() and (vel == SENTINEL).all() and mt[0] == -1 and cnt[0] == -1, (i, v)
+
+
+def test_python_wrapper(lib):
+    from optimalmodulationds_amd import _lib
+    from optimalmodulationds_amd.engine import point_cloud_flow
+    spec, prev, now = cases.slab()
+    spheres, vel, matched = point_cloud_flow(prev, now, spec, track_of(3, 0.125))
+    assert spheres.shape == (35, 4) and vel.shape == (35, 3) and matched == 35 and (vel == F32([1.125, 0, 0])).all()
+    with pytest.raises(_lib.OmdsError) as e:
+        point_cloud_flow(prev, now, spec, track_of(3, 0.125), cap=10)
+    assert e.value.n_occupied == 35
+
+
+def test_context_entry_points_are_bound_and_refuse_a_null_context(lib):
+    import inspect
+    from optimalmodulationds_amd import MPPI
+    from optimalmodulationds_amd.engine import Engine
+    spec, track = spec_of((0.0, 0.0, 0.0), 0.0625, (4, 4, 4)), track_of(2, 0.1)
+    assert lib.omds_set_obstacles_from_cloud_tracked(None, C.byref(spec), C.byref(track), None, 0, 0, None, None, None, None) == ERR_INVALID_ARG
+    assert lib.omds_cloud_track_reset(None) == ERR_INVALID_ARG and lib.omds_get_obstacle_motion(None, None, None) == ERR_INVALID_ARG
+    assert list(inspect.signature(Engine.set_obstacles_from_cloud_tracked).parameters) == ["self", "points", "spec", "track", "q"]
+    assert hasattr(Engine, "get_obstacle_motion") and hasattr(Engine, "cloud_track_reset")
+    p = inspect.signature(MPPI.update_obstacles_from_cloud).parameters
+    assert [(k, p[k].default) for k in ("dt_frame", "reach", "still", "moving_frame")] == [("dt_frame", None), ("reach", 2), ("still", 0.0),
+                                                                                          ("moving_frame", False)]
+    assert list(p)[:9] == ["self", "points", "voxel", "lo", "hi", "radius", "self_margin", "min_points", "max_spheres"]
+
+
+# ---- 9. the definition under the sanitizers ---------------------------------------------------------------------------------------
+def _pack_case(spec, track, prev, now, cap, null_mask=0):
+    prev, now = (np.ascontiguousarray(p, F32).reshape(-1, 3) for p in (prev, now))
+    return bytes(spec) + bytes(track) + struct.pack("<qqii", prev.shape[0], now.shape[0], cap, null_mask) + prev.tobytes() + now.tobytes()
+
+
+def test_definition_under_address_and_ub_sanitizer(lib, tmp_path):
+    """tests/cloud_flow_host.cpp, a stand-alone program around the header both the library and its kernels include, built with
+    -fsanitize=address,undefined and run on the cases above: a clean exit, and the library's bits."""
+    if shutil.which("g++") is None:
+        pytest.fail("g++ is needed to build tests/cloud_flow_host.cpp")
+    exe = str(tmp_path / "cloud_flow_host")
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-static-libasan", "-static-libubsan",       # the runtimes inside the program: no demand on what is loaded before it
+                    "-fno-omit-frame-pointer", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cloud_flow_host.cpp"),
+                    "-o", exe], check=True)
+    none = np.zeros((0, 3), F32)
+    bad = np.array([[np.nan, 0.1, 0.1], [0.1, np.inf, 0.1], [0.1, 0.1, -np.inf], [1e30, 0.1, 0.1], [-1e30, 0.1, 0.1]], F32)
+    todo = []
+
+    def add(spec, track, prev, now, cap=None, mask=0):
+        todo.append((spec, track, prev, now, len(restate_flow(spec, track, prev, now)[0]) if cap is None else cap, mask))     # exactly cap: the last row ends both buffers
+
+    add(*cases.slab()[:1], track_of(3, 0.125), *cases.slab()[1:])
+    add(*cases.slab()[:1], track_of(1, 0.125), *cases.slab()[1:])
+    for n in (2, 4, 8):
+        s, p, q = cases.ties(n)
+        add(s, track_of(2, 0.5), p, q)
+    s, p, q = cases.corners()
+    add(s, track_of(1, 0.25), p, q)
+    add(s, track_of(4, 0.25), p, q)
+    s, p, q = cases.random_pair(5, (37, 29, 1), 400, 400, shift=(1.6, -0.7, 0.0), fill=0.8)
+    add(s, track_of(3, 0.1), p, q)
+    s, p, q = cases.random_pair(6, (3, 2, 5), 12, 25, shift=(0.0, 0.0, 0.0))
+    add(s, track_of(4, 0.1), p, q)
+    s, p, q = cases.random_pair(3, (12, 10, 9), 700, 600, fill=0.7, min_points=2)
+    add(s, track_of(2, 0.1, still=0.3), p[::-1], np.concatenate([q, q[:50], bad]))          # shuffled, duplicates, non-finite, still
+    add(s, track_of(2, 0.1), none, q)
+    add(s, track_of(2, 0.1), p, none)
+    add(s, track_of(2, 0.1), p, q, cap=7)                                                   # too many cells: nothing written
+    s, p, q = cases.heavy()
+    add(s, track_of(1, 0.1), p, q)
+    s, p, q = cases.few_spheres(3)
+    for mask in (1, 2, 4, 8, 16, 32, 64, 128):
+        add(s, track_of(2, 0.1), p, q, cap=3, mask=mask)
+    add(s, track_of(5, 0.1), p, q, cap=3)
+    add(s, track_of(2, np.nan), p, q, cap=3)
+    fin, fout = tmp_path / "cases.bin", tmp_path / "out.bin"
+    fin.write_bytes(struct.pack("<i", len(todo)) + b"".join(_pack_case(*c) for c in todo))
+    r = subprocess.run([exe, str(fin), str(fout)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "cloud_flow_host: done" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+    raw, off = fout.read_bytes(), 0
+    for spec, track, prev, now, cap, mask in todo:
+        rc, count, matched, written = struct.unpack_from("<iiii", raw, off)
+        off += 16
+        got = np.frombuffer(raw, F32, written * 4, off).reshape(-1, 4)
+        off += written * 16
+        got_vel = np.frombuffer(raw, F32, written * 3, off).reshape(-1, 3)
+        off += written * 12
+        if mask:
+            assert rc == ERR_INVALID_ARG
+            continue
+        want_rc, want_count, want_matched, want, want_vel = call(lib, spec, track, prev, now, cap)
+        assert (rc, count, matched) == (want_rc, want_count, want_matched)
+        assert np.array_equal(bits(got), bits(want)) and np.array_equal(bits(got_vel), bits(want_vel))
+    assert off == len(raw)
