@@ -307,6 +307,63 @@ OMDS_API int omds_set_obstacles_from_cloud_tracked(omds_ctx* ctx, const omds_clo
                                                    int32_t* n_spheres_out, int32_t* n_occupied_out, int32_t* n_matched_out);
 OMDS_API int omds_cloud_track_reset(omds_ctx* ctx);
 OMDS_API int omds_get_obstacle_motion(omds_ctx* ctx, float* vel, int32_t* have_out);
+/* OBJECT VELOCITIES FROM SUCCESSIVE CLOUDS.  The tracked call above measures the normal flow per cell: it is blind to motion
+ * along a surface and under-estimates an object thicker than its displacement.  The objects form segments the final sphere list into
+ * connected components, matches the components of successive frames by their centroids, and gives every sphere of a matched object the
+ * velocity of the object's centroid; everywhere else the sphere keeps the tracked call's velocity, so this route is never worse.
+ * Additive: no other entry point changes its launches or its bits.
+ * WHAT IT MEASURES: the rigid TRANSLATION of an object, from the displacement of the centroid of its visible points.  Rotation shows up
+ * as the centroid's motion alone; two objects that touch (within link cells) are one object; an object entering the view, or being
+ * uncovered, shifts its visible centroid and so reports a velocity it does not have; no temporal smoothing.
+ *   omds_point_cloud_object_flow : host only (no context, no GPU), the DEFINITION.  Records, occupancy and spheres are those of
+ *       omds_point_cloud_flow.  keep_prev / keep_now: one uint8 per OCCUPIED cell of that frame in ascending cell order, NULL = keep all;
+ *       they stand for the self-filter.  The output lists the occupied NOW cells with keep_now != 0 in cell order; *count_out = occupied
+ *       NOW cells BEFORE the mask; more of them than max_spheres or cap: OMDS_ERR_INVALID_ARG with *count_out set, nothing else written.
+ *       COMPONENTS, per frame over that frame's kept cells: two cells are linked when max_c |i_c - j_c| <= link; a component is a
+ *       connected set; its label is the smallest cell index in it (a function of the set of cells).  Its record, all integers: m = cells
+ *       (uint32), N = sum n (uint64), Q_c = sum (256 i_c n + s_c) (uint64, < 2^54): the sum of the points' coordinates in 1/256 cell.
+ *       OBJECTS: a NOW component with m >= min_cells; *n_objects_out counts them.  Centroids in fp64, each operation one rounding,
+ *       conversions round-to-nearest: cen_c = (double)Q_c / (double)N.  The candidate of a NOW object is, over all PREVIOUS components
+ *       with m' >= min_cells, the one with the smallest d2 = (dx dx + dy dy) + dz dz (d = cen - cen', three products, two sums), ties to
+ *       the smaller label.  It is accepted when d2 <= (256.0 * reach)^2 (the centroid moved at most reach cells) and 2 min(m, m') >=
+ *       max(m, m') in integers (the guard against merges and splits).  Then per axis g = (float)((cen_c - cen'_c) * 0.00390625) and
+ *       vel_c = (g * voxel) / dt_frame in fp32, followed by the still rule of omds_point_cloud_flow.  PER SPHERE: in an accepted object
+ *       vel_out is the object's velocity and object_out = 1; everywhere else (small components, objects without a candidate, rejected
+ *       matches, no previous cloud) vel_out is bit for bit omds_point_cloud_flow's for that cell against the UNMASKED previous records and
+ *       object_out = 0.  label_out = the component's label.  *matched_out counts the spheres with object_out = 1, or with a non-empty
+ *       window; *n_objects_matched_out the accepted objects (NULL = skip, and so for n_objects_out).  xyzr_out [cap,4], vel_out [cap,3],
+ *       label_out, object_out [cap].  OMDS_ERR_INVALID_ARG before anything is written: what omds_point_cloud_flow refuses, link outside
+ *       1 .. 2, a null obj, a null label_out or object_out with cap > 0.
+ *   omds_set_obstacles_from_cloud_objects : everything omds_set_obstacles_from_cloud_tracked does, in the same order, with the same final
+ *       list bit for bit (self-filter and padding included) and the same stored record frame; its velocity launch runs unchanged and
+ *       supplies the fallback.  Between it and the install, a fixed number of launches: a slot map (cell -> list index), a lock-free
+ *       union-find over the lower half of every sphere's window (the larger root hooks under the smaller, compare-and-swap; no launch
+ *       waits on another wave), a flatten to labels, the component sums (equal roots are combined inside the wave and the workgroup before
+ *       the 64-bit integer atomics), an ordered compaction of the roots into the component table, one wave per NOW component for the match, and
+ *       one pass that overwrites the velocity of every sphere of an accepted object.  Padding spheres: velocity 0, label -1, object 0.
+ *       THE PREVIOUS TABLE is the component table of the FINAL list (after the self-filter: the arm is not in it) of the last successful
+ *       objects call.  There is none at the first objects call, after omds_cloud_track_reset, when there is no previous record frame on
+ *       this grid (origin, voxel, dims, min_points as for the tracked call), when link or min_cells (resolved: < 1 is 1) differ from
+ *       the stored table's, and after a plain tracked call, which stores its records but invalidates the table.  Without one every
+ *       sphere takes the fallback, *n_objects_matched_out = -1, and the table is stored.  omds_set_obstacles_from_cloud and
+ *       omds_set_obstacles leave records and table alone; a refusal (too many occupied cells, an argument check) leaves the scene, the
+ *       record frame and the table exactly as they were.  A scene whose velocities are all exactly 0 keeps the static propagate.
+ *   omds_get_cloud_objects : label [n_obs] and object [n_obs] of the scene in force (NULL: no copy), *n_objects_out its objects; host
+ *       state, no GPU work.  OMDS_ERR_NOT_INITIALISED unless the scene in force was installed by the objects call.                    */
+typedef struct {
+    int32_t link;       /* cells are neighbours when their Chebyshev distance is <= link: 1 .. 2 */
+    int32_t min_cells;  /* a component of fewer cells is no object; < 1 -> 1                     */
+} omds_cloud_object_spec;
+OMDS_API int omds_point_cloud_object_flow(const omds_cloud_spec* spec, const omds_cloud_track_spec* track, const omds_cloud_object_spec* obj,
+                                          const float* xyz_prev, int64_t n_prev, const uint8_t* keep_prev, const float* xyz_now,
+                                          int64_t n_now, const uint8_t* keep_now, float* xyzr_out, float* vel_out, int32_t* label_out,
+                                          int32_t* object_out, int32_t cap, int32_t* count_out, int32_t* matched_out,
+                                          int32_t* n_objects_out, int32_t* n_objects_matched_out);
+OMDS_API int omds_set_obstacles_from_cloud_objects(omds_ctx* ctx, const omds_cloud_spec* spec, const omds_cloud_track_spec* track,
+                                                   const omds_cloud_object_spec* obj, const float* xyz, int64_t n_points,
+                                                   int xyz_on_device, const float* q_now, int32_t* n_spheres_out, int32_t* n_occupied_out,
+                                                   int32_t* n_matched_out, int32_t* n_objects_out, int32_t* n_objects_matched_out);
+OMDS_API int omds_get_cloud_objects(omds_ctx* ctx, int32_t* label, int32_t* object, int32_t* n_objects_out);
 /* LinDS(q_goal) / MPPI.reset_DS / switch_DS_idx (LinDS.py:7-10, MPPI.py:76-84). */
 OMDS_API int omds_set_ds(omds_ctx* ctx, const float* q_goal);
 /* MPPI_toy's nominal DS (MPPI_toy.py:89-91): velocity = (q - q_goal) @ A, A [n,n] row-major, not

@@ -69,6 +69,11 @@ class OmdsCloudTrackSpec(C.Structure):
     _fields_ = [("reach", C.c_int32), ("dt_frame", C.c_float), ("still", C.c_float)]
 
 
+class OmdsCloudObjectSpec(C.Structure):
+    """omds_cloud_object_spec (include/omds.h): how the objects cloud call segments the sphere list into components."""
+    _fields_ = [("link", C.c_int32), ("min_cells", C.c_int32)]
+
+
 class OmdsError(RuntimeError):
     pass
 
@@ -101,6 +106,13 @@ SIGNATURES = {
                                                         C.c_int64, C.c_int, F32P, I32P, I32P, I32P]),
     "omds_cloud_track_reset": (C.c_int, [C.c_void_p]),
     "omds_get_obstacle_motion": (C.c_int, [C.c_void_p, F32P, I32P]),
+    "omds_point_cloud_object_flow": (C.c_int, [C.POINTER(OmdsCloudSpec), C.POINTER(OmdsCloudTrackSpec), C.POINTER(OmdsCloudObjectSpec), F32P,
+                                               C.c_int64, C.c_void_p, F32P, C.c_int64, C.c_void_p, F32P, F32P, I32P, I32P, C.c_int32, I32P,
+                                               I32P, I32P, I32P]),
+    "omds_set_obstacles_from_cloud_objects": (C.c_int, [C.c_void_p, C.POINTER(OmdsCloudSpec), C.POINTER(OmdsCloudTrackSpec),
+                                                        C.POINTER(OmdsCloudObjectSpec), C.c_void_p, C.c_int64, C.c_int, F32P, I32P, I32P,
+                                                        I32P, I32P, I32P]),
+    "omds_get_cloud_objects": (C.c_int, [C.c_void_p, I32P, I32P, I32P]),
     "omds_set_ds": (C.c_int, [C.c_void_p, F32P]),
     "omds_set_ds_matrix": (C.c_int, [C.c_void_p, F32P, F32P]),
     "omds_set_ds_seds": (C.c_int, [C.c_void_p, F32P, C.c_int, F32P, F32P, F32P, F32P, F32P, F32P, C.c_float, C.c_float]),
@@ -197,7 +209,7 @@ HORIZON_HOOK_SIGNATURES = {
 }
 TEST_LIB_PATH = os.path.join(_HERE, "csrc", "libomds_hip_test.so")
 
-ABI_VERSION = 506     # omds_version() of the library this binding was written against
+ABI_VERSION = 507     # omds_version() of the library this binding was written against
 _libs = {}             # path -> bound CDLL
 
 

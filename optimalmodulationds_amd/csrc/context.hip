@@ -8,7 +8,7 @@ thread_local std::string g_create_err;
 
 extern "C" {
 
-int omds_version(void) { return 506; }
+int omds_version(void) { return 507; }
 
 int omds_device_count(int32_t* count) {
     if (!count) return OMDS_ERR_INVALID_ARG;
@@ -255,6 +255,8 @@ int install_obstacles(omds_ctx* ctx, const float* xyzr, int n_obs) {
     ctx->n_obs = n_obs;
     ctx->scr.scene_changed(xyzr, n_obs);
     ctx->obs_now.assign(xyzr, xyzr + (size_t)n_obs * 4);
+    ctx->cloud_obj_label.clear();   // the labels of a scene belong to the objects call that installed it (point_cloud.hip puts them back)
+    ctx->cloud_obj_flag.clear();
     if (ctx->have_mlp && !ctx->wide.on) {
         omds_launch_obstacle_features(ctx->stream, ctx->mlp, ctx->d_obs, n_obs, ctx->d_Fp, ctx->d_radius, ctx->d_FpH, ctx->cfg.max_obs);
         CK(hipGetLastError());

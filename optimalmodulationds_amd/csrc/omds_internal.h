@@ -392,6 +392,23 @@ struct omds_ctx {
     DevBuf<int> d_cloudCandCell;      // [max_spheres] cell index of every candidate, in step with d_cloudCand
     DevBuf<int> d_cloudKeptCell;      // [max_spheres] ... and of every kept one
     DevBuf<float4> d_cloudVel;        // [max_spheres] velocity of every final sphere; .w: 1 where its window was not empty (k_cloud_flow)
+    // ... objects (omds_set_obstacles_from_cloud_objects): the components of the final list, point_cloud_objects_def.h.  The component
+    // tables are 40-byte CloudComp records (kept as bytes here: the type is point_cloud.hip's); one of the two is the stored table
+    DevBuf<int> d_cloudSlot;          // [cells rounded up to whole compaction blocks] list index of every final sphere's cell, else -1
+    DevBuf<int> d_cloudParent;        // [max_spheres] the union-find; after the flatten the root (list index) of every sphere
+    DevBuf<int> d_cloudLabel;         // [max_spheres] label (smallest cell of the component) of every sphere
+    DevBuf<int> d_cloudObject;        // [max_spheres] 1 where the sphere's component is an accepted object
+    DevBuf<int> d_cloudCompOf;        // [max_spheres] at a root: the row of its component in the table
+    DevBuf<unsigned long long> d_cloudAcc;   // [max_spheres][5] at a root: m, N, Q_x, Q_y, Q_z of its component
+    DevBuf<unsigned char> d_cloudTable[2];   // [max_spheres] CloudComp each, ascending labels
+    DevBuf<float4> d_cloudObjVel;     // [max_spheres] per component: the object's velocity; .w: 0 no object, 1 object, 2 accepted
+    int cloud_table_stored = 0;       // which of the two tables is the stored one
+    bool cloud_have_table = false;    // a table is stored: an objects call succeeded and no reset / plain tracked call came after it
+    int cloud_table_n = 0;            // components in the stored table
+    int cloud_table_link = 0;         // the object spec it was built under
+    unsigned cloud_table_min_cells = 0;
+    std::vector<int32_t> cloud_obj_label, cloud_obj_flag;   // [n_obs] of the scene in force when the objects call installed it, else empty
+    int cloud_obj_count = 0;          // its objects
     // DS / cost
     bool have_ds = false, have_cost = false;
     float qf[OMDS_MAX_DOF] = {0};

@@ -7,8 +7,11 @@
 // The tracked form (omds_set_obstacles_from_cloud_tracked) counts into records of 16 bytes per cell (k_cloud_count_rec), carries each
 // candidate's cell index through both compactions, and evaluates point_cloud_flow_def.h against the records of the previous tracked
 // frame with one wave per final sphere (k_cloud_flow); the velocities then go in through omds_set_obstacle_motion.
+// The objects form (omds_set_obstacles_from_cloud_objects) is the tracked one with the launches of point_cloud_objects_def.h between
+// k_cloud_flow and the install: slot map, union-find, flatten, component sums, the component table by the same ordered compaction, one
+// wave per component for the match against the stored table, and the object velocities over k_cloud_flow's.
 #include "capi_internal.h"
-#include "point_cloud_flow_def.h"
+#include "point_cloud_objects_def.h"
 
 namespace {
 
@@ -218,6 +221,211 @@ __global__ __launch_bounds__(CLOUD_NT) void k_cloud_flow(CloudGrid g, CloudTrack
     vel[sphere] = make_float4(v[0], v[1], v[2], matched ? 1.f : 0.f);
 }
 
+// ---- the objects of the final list (point_cloud_objects_def.h) ---------------------------------------------------------------------
+// slot[cell] = list index of the final sphere in that cell (the rest of the grid was cleared to -1), and every sphere its own root
+__global__ __launch_bounds__(CLOUD_NT) void k_obj_slot(const int* __restrict__ cells, int n, int* __restrict__ slot, int* __restrict__ parent) {
+    const int i = blockIdx.x * CLOUD_NT + threadIdx.x;
+    if (i >= n) return;
+    slot[cells[i]] = i;
+    parent[i] = i;
+}
+
+// The union-find.  Invariants: parent[x] <= x, and an entry that has stopped being a root (parent[x] != x) never becomes one again.
+// Loads and stores are relaxed device-scope atomics, so that no lane works on a cached copy of another workgroup's hook.
+__device__ inline int uf_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ inline void uf_store(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// the root of x as far as this lane can see; x strictly decreases, so the loop ends after at most x steps.  Path halving: the
+// grandparent of a non-root is one of its ancestors and stays one, whatever is hooked meanwhile (hooks only act on roots)
+__device__ inline int uf_find(int* parent, int x) {
+    for (;;) {
+        const int p = uf_load(parent + x);
+        if (p == x) return x;
+        const int gp = uf_load(parent + p);
+        if (gp != p) uf_store(parent + x, gp);
+        x = p;
+    }
+}
+
+// Unite the components of a and b: hook the larger root under the smaller by compare-and-swap.  A swap that fails means another
+// lane has hooked that root in the meantime; the search resumes from there, and max(a, b) is strictly smaller than before: the loop
+// ends on this lane's own progress and waits for nobody.  Returns the root both are under now
+__device__ inline int uf_unite(int* parent, int a, int b) {
+    for (;;) {
+        a = uf_find(parent, a);
+        b = uf_find(parent, b);
+        if (a == b) return a;
+        if (a < b) { const int t = a; a = b; b = t; }
+        if (atomicCAS(parent + a, a, b) == a) return b;
+    }
+}
+
+// one lane per sphere: unite with every final sphere in the lower half of its window (the upper half is the other sphere's).  The
+// list is in cell order, so hooking larger under smaller leaves the component's smallest cell as its root
+__global__ __launch_bounds__(CLOUD_NT) void k_obj_union(CloudGrid g, int link, const int* __restrict__ cells, int n, const int* __restrict__ slot,
+                                                        int* parent) {
+    const int i = blockIdx.x * CLOUD_NT + threadIdx.x;
+    if (i >= n) return;
+    int mine = i;   // an ancestor of i: where the next search for its root starts
+    cloud_lower_neighbours(g, link, cells[i], [&](int cell, bool implied) {
+        const int j = slot[cell];
+        if (j < 0) return false;
+        if (!implied) mine = uf_unite(parent, mine, j);
+        return true;
+    });
+}
+
+// the root of x by a walk that stores nothing
+__device__ inline int uf_root(const int* parent, int x) {
+    for (;;) {
+        const int p = uf_load(parent + x);
+        if (p == x) return x;
+        x = p;
+    }
+}
+
+// parent[i] = root of i, label[i] = the root's cell.  INVARIANT: in this launch entry i is stored to by lane i alone, once, and the
+// value is the root -- the searches here halve no path (a halving store of another lane, landing late, could put a mere ancestor
+// back over the root).  A concurrent walk reads either the old ancestor or the root at i: both lead to the root.  After this launch
+// parent[] IS the root of every sphere, which is what k_obj_sums, RootSrc and k_obj_apply take it for
+__global__ __launch_bounds__(CLOUD_NT) void k_obj_flatten(const int* __restrict__ cells, int n, int* parent, int* __restrict__ label) {
+    const int i = blockIdx.x * CLOUD_NT + threadIdx.x;
+    if (i >= n) return;
+    const int r = uf_root(parent, i);
+    if (r != i) uf_store(parent + i, r);
+    label[i] = cells[r];
+}
+
+// The component sums m, N, Q[3] at acc[root][5], all uint64.  A dense scene is one or two huge components: every sphere's five atomics
+// would land on the same five words, and atomics from different waves on one word cost 80 ns and more each (EXPERIMENTS R19).  So
+// equal roots are combined before memory is touched, in three steps: the list is in cell order, so every run of equal roots inside a
+// wave is added up by a segmented shuffle scan; the runs of the wave's DOMINANT root (that of its first lane: the huge component,
+// whose runs small components interrupt) are added up by a shuffle sum; and the dominant sums of the sixteen waves of the workgroup
+// meet in LDS, from where each distinct root goes to memory once.  What is left for the atomics is one set per workgroup for a huge
+// component and one per run for the small ones.  Integers throughout: no order can change a bit
+constexpr int OBJ_ACC = 5;
+constexpr int SUMS_NT = 1024, SUMS_WAVES = SUMS_NT / 64;
+__global__ __launch_bounds__(SUMS_NT) void k_obj_sums(CloudGrid g, const uint4* __restrict__ now, const int* __restrict__ cells,
+                                                      const int* __restrict__ root, int n, unsigned long long* __restrict__ acc) {
+    __shared__ int key[SUMS_WAVES];
+    __shared__ unsigned long long part[SUMS_WAVES][OBJ_ACC];
+    const int i = blockIdx.x * SUMS_NT + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int r = -1;
+    unsigned long long v[OBJ_ACC] = {0ull, 0ull, 0ull, 0ull, 0ull};
+    if (i < n) {
+        r = root[i];
+        const int cell = cells[i];
+        const uint4 rec = now[cell];
+        v[0] = 1ull;
+        v[1] = rec.x;
+        v[2] = cloud_comp_q(cell % g.dx, rec.x, rec.y);
+        v[3] = cloud_comp_q((cell / g.dx) % g.dy, rec.x, rec.z);
+        v[4] = cloud_comp_q(cell / (g.dx * g.dy), rec.x, rec.w);
+    }
+    const int before = __shfl_up(r, 1, 64);
+    const bool head = lane == 0 || before != r;
+    const unsigned long long heads = __ballot(head);
+    const unsigned long long above = lane == 63 ? 0ull : heads >> (lane + 1);
+    const int run_end = above ? lane + __ffsll((long long)above) : 64;   // the next head, exclusive end of this lane's run
+    for (int d = 1; d < 64; d <<= 1)
+        for (int k = 0; k < OBJ_ACC; ++k) {
+            const unsigned long long o = __shfl_down(v[k], d, 64);
+            if (lane + d < run_end) v[k] += o;
+        }
+    const int dominant = __shfl(r, 0, 64);   // -1: the whole wave lies past the list
+    const bool first = head && r >= 0, joins = first && r == dominant;
+    for (int k = 0; k < OBJ_ACC; ++k) {
+        const unsigned long long d = wave_sum(joins ? v[k] : 0ull);
+        if (lane == 0) part[wave][k] = d;
+    }
+    if (lane == 0) key[wave] = dominant;
+    if (first && !joins)
+        for (int k = 0; k < OBJ_ACC; ++k) atomicAdd(acc + (size_t)r * OBJ_ACC + k, v[k]);
+    __syncthreads();
+    if (threadIdx.x >= SUMS_WAVES || key[threadIdx.x] < 0) return;
+    const int mine = key[threadIdx.x];
+    for (int w = 0; w < (int)threadIdx.x; ++w)
+        if (key[w] == mine) return;   // an earlier wave speaks for this root
+    for (int k = 0; k < OBJ_ACC; ++k) {
+        unsigned long long s = 0ull;
+        for (int w = threadIdx.x; w < SUMS_WAVES; ++w)
+            if (key[w] == mine) s += part[w][k];
+        atomicAdd(acc + (size_t)mine * OBJ_ACC + k, s);
+    }
+}
+
+// the roots as a third item space of the ordered compaction: the component table in ascending label order
+struct RootSrc {
+    const int* root;
+    const int* cells;
+    const unsigned long long* acc;
+    CloudComp* table;
+    int* compOf;
+    __device__ unsigned flags(int base, int n) const {
+        unsigned f = 0;
+        for (int j = 0; j < CLOUD_ITEMS; ++j)
+            if (base + j < n && root[base + j] == base + j) f |= 1u << j;
+        return f;
+    }
+    __device__ void emit(int item, unsigned pos) const {
+        const unsigned long long* a = acc + (size_t)item * OBJ_ACC;
+        table[pos] = CloudComp{cells[item], (unsigned)a[0], a[1], {a[2], a[3], a[4]}};
+        compOf[item] = (int)pos;
+    }
+};
+
+// One wave per NOW component.  A component of fewer than min_cells cells is no object (.w = 0).  Else the lanes stride over the
+// previous table in the definition's fp64 statements, the wave takes the minimum of (d2, label), and lane 0 applies the gates and the
+// velocity lines: .w = 2 with the object's velocity when accepted, else .w = 1
+__global__ __launch_bounds__(CLOUD_NT) void k_obj_match(CloudGrid g, CloudTrack tr, CloudObjects ob, const CloudComp* __restrict__ now, int n_now,
+                                                        const CloudComp* __restrict__ prev, int n_prev, float4* __restrict__ objVel) {
+    const int lane = threadIdx.x & 63, comp = blockIdx.x * FLOW_WAVES + (threadIdx.x >> 6);
+    if (comp >= n_now) return;   // a whole wave
+    const CloudComp c = now[comp];
+    if (c.m < ob.min_cells) {
+        if (lane == 0) objVel[comp] = make_float4(0.f, 0.f, 0.f, 0.f);
+        return;
+    }
+    double cn[3], cp[3], best_d2 = 0.0;
+    int best = -1, best_label = 0;
+    cloud_comp_centroid(c, cn);
+    for (int j = lane; j < n_prev; j += 64) {
+        const CloudComp p = prev[j];
+        if (p.m < ob.min_cells) continue;
+        cloud_comp_centroid(p, cp);
+        const double d2 = cloud_object_d2(cn, cp);
+        if (best < 0 || cloud_object_closer(d2, p.label, best_d2, best_label)) { best = j; best_d2 = d2; best_label = p.label; }
+    }
+    for (int d = 32; d > 0; d >>= 1) {
+        const double o_d2 = __shfl_xor(best_d2, d, 64);
+        const int o_best = __shfl_xor(best, d, 64), o_label = __shfl_xor(best_label, d, 64);
+        if (o_best >= 0 && (best < 0 || cloud_object_closer(o_d2, o_label, best_d2, best_label))) { best = o_best; best_d2 = o_d2; best_label = o_label; }
+    }
+    if (lane != 0) return;
+    float v[3] = {0.f, 0.f, 0.f};
+    float state = 1.f;
+    if (best >= 0) {
+        const CloudComp p = prev[best];
+        if (cloud_object_accept(tr, c.m, p.m, best_d2)) {
+            cloud_comp_centroid(p, cp);
+            cloud_object_velocity(g, tr, cn, cp, v);
+            state = 2.f;
+        }
+    }
+    objVel[comp] = make_float4(v[0], v[1], v[2], state);
+}
+
+// every sphere of an accepted object takes the object's velocity over k_cloud_flow's and counts as matched
+__global__ __launch_bounds__(CLOUD_NT) void k_obj_apply(const int* __restrict__ root, const int* __restrict__ compOf, const float4* __restrict__ objVel,
+                                                        int n, float4* __restrict__ vel, int* __restrict__ object) {
+    const int i = blockIdx.x * CLOUD_NT + threadIdx.x;
+    if (i >= n) return;
+    const float4 o = objVel[compOf[root[i]]];
+    const bool accepted = o.w == 2.f;
+    if (accepted) vel[i] = make_float4(o.x, o.y, o.z, 1.f);
+    object[i] = accepted ? 1 : 0;
+}
+
 inline int compaction_blocks(int n) { return (n + CLOUD_BLOCK - 1) / CLOUD_BLOCK; }
 
 // the ordered compaction of n items of src into src.out (at most cap spheres written); *total_out = kept items.  Synchronises.
@@ -238,11 +446,19 @@ int compact(omds_ctx* ctx, const Src& src, int n, int cap, int* total_out) {
     return OMDS_OK;
 }
 
-// Both cloud entry points.  tr == nullptr is omds_set_obstacles_from_cloud: the count buffer, no cell indices, no velocities.  With tr
-// the same steps in the same order on the record buffer that is NOT the stored frame, then k_cloud_flow over the final list
+// What the objects call adds to the tracked one: its spec, and where its two counts go
+struct ObjectsCall {
+    CloudObjects ob;
+    int32_t* n_objects_out;
+    int32_t* n_objects_matched_out;
+};
+
+// The cloud entry points.  tr == nullptr is omds_set_obstacles_from_cloud: the count buffer, no cell indices, no velocities.  With tr
+// the same steps in the same order on the record buffer that is NOT the stored frame, then k_cloud_flow over the final list; with oc
+// (which needs tr) the components of the final list, into the table that is NOT the stored one, and the object velocities
 int scene_from_cloud(omds_ctx* ctx, const char* who, const omds_cloud_spec* spec, const CloudGrid& g, const CloudTrack* tr, const float* xyz,
                      int64_t n_points, int xyz_on_device, const float* q_now, int32_t* n_spheres_out, int32_t* n_occupied_out,
-                     int32_t* n_matched_out) {
+                     int32_t* n_matched_out, const ObjectsCall* oc = nullptr) {
     const std::string me(who);
     int rc;
     REQUIRE(n_points >= 0 && n_points <= OMDS_CLOUD_MAX_POINTS && (n_points == 0 || xyz), OMDS_ERR_INVALID_ARG,
@@ -270,6 +486,19 @@ int scene_from_cloud(omds_ctx* ctx, const char* who, const omds_cloud_spec* spec
         CK(ctx->d_cloudSums.reserve((size_t)CLOUD_MAX_BLOCKS + 1));
         CK(ctx->d_cloudCand.reserve((size_t)g.max_spheres));
         CK(ctx->d_cloudKept.reserve((size_t)g.max_spheres));
+    }
+    DevBuf<unsigned char>* table = oc ? &ctx->d_cloudTable[1 - ctx->cloud_table_stored] : nullptr;   // written; the stored table is the other one
+    if (oc && (ctx->d_cloudSlot.count() < n_padded || ctx->d_cloudParent.count() < (size_t)g.max_spheres ||
+               table->count() < (size_t)g.max_spheres * sizeof(CloudComp))) {
+        CK(hipStreamSynchronize(ctx->stream));
+        CK(ctx->d_cloudSlot.reserve(n_padded));
+        CK(ctx->d_cloudParent.reserve((size_t)g.max_spheres));
+        CK(ctx->d_cloudLabel.reserve((size_t)g.max_spheres));
+        CK(ctx->d_cloudObject.reserve((size_t)g.max_spheres));
+        CK(ctx->d_cloudCompOf.reserve((size_t)g.max_spheres));
+        CK(ctx->d_cloudAcc.reserve((size_t)g.max_spheres * OBJ_ACC));
+        CK(ctx->d_cloudObjVel.reserve((size_t)g.max_spheres));
+        CK(table->reserve((size_t)g.max_spheres * sizeof(CloudComp)));
     }
     // the points: the caller's device array as it is, a host array through a staging buffer of the context
     const float* d_xyz = xyz;
@@ -336,8 +565,43 @@ int scene_from_cloud(omds_ctx* ctx, const char* who, const omds_cloud_spec* spec
                            (const uint4*)rec->get(), (const uint4*)ctx->d_cloudRec[ctx->cloud_stored].get(), d_cell, n_list,
                            ctx->d_cloudVel.get());
         CK(hipGetLastError());
-        CK(hipMemcpyAsync(vel4.data(), ctx->d_cloudVel, (size_t)n_list * 16, hipMemcpyDeviceToHost, ctx->stream));
     }
+    // the components of the final list, their match against the stored table and the velocities of the accepted objects
+    const bool have_table = oc && have_prev && ctx->cloud_have_table && ctx->cloud_table_link == oc->ob.link &&
+                            ctx->cloud_table_min_cells == oc->ob.min_cells;
+    int n_comp = 0;
+    std::vector<int32_t> label((size_t)n_final, -1), object((size_t)n_final, 0);   // padding spheres: label -1, no object
+    std::vector<float> obj_vel;
+    if (oc && n_list > 0) {
+        const int blocks = (n_list + CLOUD_NT - 1) / CLOUD_NT;
+        CloudComp* d_table = reinterpret_cast<CloudComp*>(table->get());
+        CK(hipMemsetAsync(ctx->d_cloudSlot, 0xff, n_padded * 4, ctx->stream));   // -1
+        CK(hipMemsetAsync(ctx->d_cloudAcc, 0, (size_t)n_list * OBJ_ACC * 8, ctx->stream));
+        hipLaunchKernelGGL(k_obj_slot, dim3(blocks), dim3(CLOUD_NT), 0, ctx->stream, d_cell, n_list, ctx->d_cloudSlot.get(), ctx->d_cloudParent.get());
+        hipLaunchKernelGGL(k_obj_union, dim3(blocks), dim3(CLOUD_NT), 0, ctx->stream, g, oc->ob.link, d_cell, n_list,
+                           (const int*)ctx->d_cloudSlot.get(), ctx->d_cloudParent.get());
+        hipLaunchKernelGGL(k_obj_flatten, dim3(blocks), dim3(CLOUD_NT), 0, ctx->stream, d_cell, n_list, ctx->d_cloudParent.get(), ctx->d_cloudLabel.get());
+        hipLaunchKernelGGL(k_obj_sums, dim3((n_list + SUMS_NT - 1) / SUMS_NT), dim3(SUMS_NT), 0, ctx->stream, g, (const uint4*)rec->get(), d_cell,
+                           (const int*)ctx->d_cloudParent.get(), n_list, ctx->d_cloudAcc.get());
+        CK(hipGetLastError());
+        const RootSrc roots{ctx->d_cloudParent, d_cell, ctx->d_cloudAcc, d_table, ctx->d_cloudCompOf};
+        if ((rc = compact(ctx, roots, n_list, g.max_spheres, &n_comp))) return rc;
+        hipLaunchKernelGGL(k_obj_match, dim3((n_comp + FLOW_WAVES - 1) / FLOW_WAVES), dim3(CLOUD_NT), 0, ctx->stream, g, *tr, oc->ob,
+                           (const CloudComp*)d_table, n_comp,
+                           (const CloudComp*)reinterpret_cast<const CloudComp*>(ctx->d_cloudTable[ctx->cloud_table_stored].get()),
+                           have_table ? ctx->cloud_table_n : 0, ctx->d_cloudObjVel.get());
+        if (have_table) {
+            hipLaunchKernelGGL(k_obj_apply, dim3(blocks), dim3(CLOUD_NT), 0, ctx->stream, (const int*)ctx->d_cloudParent.get(),
+                               (const int*)ctx->d_cloudCompOf.get(), (const float4*)ctx->d_cloudObjVel.get(), n_list, ctx->d_cloudVel.get(),
+                               ctx->d_cloudObject.get());
+            CK(hipMemcpyAsync(object.data(), ctx->d_cloudObject, (size_t)n_list * 4, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        CK(hipGetLastError());
+        obj_vel.resize((size_t)n_comp * 4);
+        CK(hipMemcpyAsync(obj_vel.data(), ctx->d_cloudObjVel, (size_t)n_comp * 16, hipMemcpyDeviceToHost, ctx->stream));
+        CK(hipMemcpyAsync(label.data(), ctx->d_cloudLabel, (size_t)n_list * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (!vel4.empty()) CK(hipMemcpyAsync(vel4.data(), ctx->d_cloudVel, (size_t)n_list * 16, hipMemcpyDeviceToHost, ctx->stream));
     // to the host, filled up to n_closest with the spec's pad sphere, and in as omds_set_obstacles puts a list in
     std::vector<float> list((size_t)n_final * 4);
     if (n_list > 0) CK(hipMemcpyAsync(list.data(), d_list, (size_t)n_list * 16, hipMemcpyDeviceToHost, ctx->stream));
@@ -365,6 +629,23 @@ int scene_from_cloud(omds_ctx* ctx, const char* who, const omds_cloud_spec* spec
     ctx->cloud_frame_dims[0] = g.dx; ctx->cloud_frame_dims[1] = g.dy; ctx->cloud_frame_dims[2] = g.dz;
     ctx->cloud_frame_min_points = g.min_points;
     if (n_matched_out) *n_matched_out = have_prev ? (int32_t)matched : -1;
+    ctx->cloud_have_table = false;   // a plain tracked call stores its records and no table: the next objects call has nothing to match
+    if (!oc) return OMDS_OK;
+    int32_t n_objects = 0, n_accepted = 0;
+    for (int c = 0; c < n_comp; ++c) {
+        n_objects += obj_vel[(size_t)c * 4 + 3] >= 1.f;
+        n_accepted += obj_vel[(size_t)c * 4 + 3] == 2.f;
+    }
+    ctx->cloud_table_stored = 1 - ctx->cloud_table_stored;   // what was written is the stored table now
+    ctx->cloud_have_table = true;
+    ctx->cloud_table_n = n_comp;
+    ctx->cloud_table_link = oc->ob.link;
+    ctx->cloud_table_min_cells = oc->ob.min_cells;
+    ctx->cloud_obj_label = std::move(label);
+    ctx->cloud_obj_flag = std::move(object);
+    ctx->cloud_obj_count = n_objects;
+    if (oc->n_objects_out) *oc->n_objects_out = n_objects;
+    if (oc->n_objects_matched_out) *oc->n_objects_matched_out = have_table ? n_accepted : -1;
     return OMDS_OK;
 }
 
@@ -404,9 +685,43 @@ int omds_set_obstacles_from_cloud_tracked(omds_ctx* ctx, const omds_cloud_spec* 
                             n_occupied_out, n_matched_out);
 }
 
+int omds_point_cloud_object_flow(const omds_cloud_spec* spec, const omds_cloud_track_spec* track, const omds_cloud_object_spec* obj,
+                                 const float* xyz_prev, int64_t n_prev, const uint8_t* keep_prev, const float* xyz_now, int64_t n_now,
+                                 const uint8_t* keep_now, float* xyzr_out, float* vel_out, int32_t* label_out, int32_t* object_out, int32_t cap,
+                                 int32_t* count_out, int32_t* matched_out, int32_t* n_objects_out, int32_t* n_objects_matched_out) {
+    return cloud_objects_host(spec, track, obj, xyz_prev, n_prev, keep_prev, xyz_now, n_now, keep_now, xyzr_out, vel_out, label_out, object_out,
+                              cap, count_out, matched_out, n_objects_out, n_objects_matched_out, &g_create_err);
+}
+
+int omds_set_obstacles_from_cloud_objects(omds_ctx* ctx, const omds_cloud_spec* spec, const omds_cloud_track_spec* track,
+                                          const omds_cloud_object_spec* obj, const float* xyz, int64_t n_points, int xyz_on_device,
+                                          const float* q_now, int32_t* n_spheres_out, int32_t* n_occupied_out, int32_t* n_matched_out,
+                                          int32_t* n_objects_out, int32_t* n_objects_matched_out) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    CloudGrid g;
+    CloudTrack tr;
+    ObjectsCall oc{{0, 0u}, n_objects_out, n_objects_matched_out};
+    if (int rc = cloud_resolve_spec(spec, &g, &ctx->err)) return rc;
+    if (int rc = cloud_resolve_track(track, &tr, &ctx->err)) return rc;
+    if (int rc = cloud_resolve_objects(obj, &oc.ob, &ctx->err)) return rc;
+    return scene_from_cloud(ctx, "omds_set_obstacles_from_cloud_objects", spec, g, &tr, xyz, n_points, xyz_on_device, q_now, n_spheres_out,
+                            n_occupied_out, n_matched_out, &oc);
+}
+
+int omds_get_cloud_objects(omds_ctx* ctx, int32_t* label, int32_t* object, int32_t* n_objects_out) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    REQUIRE(ctx->n_obs > 0 && ctx->cloud_obj_label.size() == (size_t)ctx->n_obs, OMDS_ERR_NOT_INITIALISED,
+            "omds_get_cloud_objects: the scene in force was not installed by omds_set_obstacles_from_cloud_objects");
+    if (label) std::memcpy(label, ctx->cloud_obj_label.data(), (size_t)ctx->n_obs * 4);
+    if (object) std::memcpy(object, ctx->cloud_obj_flag.data(), (size_t)ctx->n_obs * 4);
+    if (n_objects_out) *n_objects_out = ctx->cloud_obj_count;
+    return OMDS_OK;
+}
+
 int omds_cloud_track_reset(omds_ctx* ctx) {
     if (!ctx) return OMDS_ERR_INVALID_ARG;
     ctx->cloud_have_frame = false;
+    ctx->cloud_have_table = false;
     return OMDS_OK;
 }
 

@@ -71,6 +71,16 @@ OMDS_CLOUD_FN void cloud_flow_add(CloudFlowSums& a, int kx, int ky, int kz, unsi
     a.N += n;
 }
 
+// the `still` rule on a finished velocity (shared with point_cloud_objects_def.h): a speed below the bar is exactly +0
+OMDS_CLOUD_FN void cloud_flow_still(const CloudTrack& tr, float* v) {
+    if (tr.still > 0.f) {
+        const float xx = v[0] * v[0];
+        const float s2 = fmaf(v[2], v[2], fmaf(v[1], v[1], xx));
+        const float bar = tr.still * tr.still;
+        if (s2 < bar) v[0] = v[1] = v[2] = 0.f;
+    }
+}
+
 // the fp32 lines of the definition: the NOW record (n, s) and the sums of a non-empty window -> vel[3]
 OMDS_CLOUD_FN void cloud_flow_velocity(const CloudGrid& g, const CloudTrack& tr, unsigned n, const unsigned* s, const CloudFlowSums& a,
                                        float* vel) {
@@ -85,12 +95,7 @@ OMDS_CLOUD_FN void cloud_flow_velocity(const CloudGrid& g, const CloudTrack& tr,
         const float metres = cells * g.voxel;
         v[c] = metres / tr.dt_frame;
     }
-    if (tr.still > 0.f) {
-        const float xx = v[0] * v[0];
-        const float s2 = fmaf(v[2], v[2], fmaf(v[1], v[1], xx));
-        const float bar = tr.still * tr.still;
-        if (s2 < bar) v[0] = v[1] = v[2] = 0.f;
-    }
+    cloud_flow_still(tr, v);
     vel[0] = v[0]; vel[1] = v[1]; vel[2] = v[2];
 }
 
@@ -104,6 +109,25 @@ inline void cloud_records_host(const CloudGrid& g, const float* xyz, int64_t n_p
         uint32_t* r = &rec[(size_t)cell * 4];
         r[0] += 1u; r[1] += k[0]; r[2] += k[1]; r[3] += k[2];
     }
+}
+
+// the velocity of the occupied NOW cell c with record r against the PREVIOUS records: true when its window was not empty, else vel = 0
+inline bool cloud_flow_cell_host(const CloudGrid& g, const CloudTrack& tr, const uint32_t* r, const std::vector<uint32_t>& prev, int c, float* vel) {
+    const int ix = c % g.dx, iy = (c / g.dx) % g.dy, iz = c / (g.dx * g.dy);
+    CloudFlowSums a;
+    cloud_flow_clear(a);
+    for (int z = std::max(iz - tr.reach, 0); z <= std::min(iz + tr.reach, g.dz - 1); ++z)
+        for (int y = std::max(iy - tr.reach, 0); y <= std::min(iy + tr.reach, g.dy - 1); ++y)
+            for (int x = std::max(ix - tr.reach, 0); x <= std::min(ix + tr.reach, g.dx - 1); ++x) {
+                const uint32_t* p = &prev[((size_t)(z * g.dy + y) * g.dx + x) * 4];
+                if (p[0] >= g.min_points) cloud_flow_add(a, x - ix, y - iy, z - iz, p[0], p[1], p[2], p[3]);
+            }
+    if (a.d2 == OMDS_CLOUD_NO_MATCH) {
+        vel[0] = vel[1] = vel[2] = 0.f;
+        return false;
+    }
+    cloud_flow_velocity(g, tr, r[0], r + 1, a, vel);
+    return true;
 }
 
 // omds_point_cloud_flow without its argument messages
@@ -131,22 +155,7 @@ inline int cloud_flow_host(const omds_cloud_spec* spec, const omds_cloud_track_s
         const uint32_t* r = &now[(size_t)c * 4];
         if (r[0] < g.min_points) continue;
         cloud_sphere(g, c, xyzr_out + (size_t)4 * w);
-        float* vel = vel_out + (size_t)3 * w++;
-        const int ix = c % g.dx, iy = (c / g.dx) % g.dy, iz = c / (g.dx * g.dy);
-        CloudFlowSums a;
-        cloud_flow_clear(a);
-        for (int z = std::max(iz - tr.reach, 0); z <= std::min(iz + tr.reach, g.dz - 1); ++z)
-            for (int y = std::max(iy - tr.reach, 0); y <= std::min(iy + tr.reach, g.dy - 1); ++y)
-                for (int x = std::max(ix - tr.reach, 0); x <= std::min(ix + tr.reach, g.dx - 1); ++x) {
-                    const uint32_t* p = &prev[((size_t)(z * g.dy + y) * g.dx + x) * 4];
-                    if (p[0] >= g.min_points) cloud_flow_add(a, x - ix, y - iy, z - iz, p[0], p[1], p[2], p[3]);
-                }
-        if (a.d2 == OMDS_CLOUD_NO_MATCH) {
-            vel[0] = vel[1] = vel[2] = 0.f;
-            continue;
-        }
-        ++matched;
-        cloud_flow_velocity(g, tr, r[0], r + 1, a, vel);
+        matched += cloud_flow_cell_host(g, tr, r, prev, c, vel_out + (size_t)3 * w++);
     }
     *matched_out = matched;
     return OMDS_OK;

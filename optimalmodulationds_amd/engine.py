@@ -90,7 +90,26 @@ class Engine:
         stored and the scene stands still.  It also stands still (horizon mode 0) when every velocity came out 0."""
         return self._scene_from_cloud("set_obstacles_from_cloud_tracked", points, spec, q, track)
 
-    def _scene_from_cloud(self, who, points, spec, q, track):
+    def set_obstacles_from_cloud_objects(self, points, spec, track, obj, q=None):
+        """``set_obstacles_from_cloud_tracked`` with one velocity per OBJECT where one can be had (omds.h, OBJECT VELOCITIES FROM
+        SUCCESSIVE CLOUDS): the final list is segmented into connected components on the device, the components are matched with those
+        of the previous objects call by their centroids, and every sphere of a matched object takes the centroid's velocity; the
+        other spheres keep the tracked call's -> (n_spheres, n_occupied, n_matched, n_objects, n_objects_matched).  ``obj``: an
+        ``OmdsCloudObjectSpec`` (``cloud_object_spec`` builds one).  n_objects_matched is -1 when there was no previous component
+        table (the first call, after ``cloud_track_reset``, another grid or object spec, a plain tracked call in between)."""
+        return self._scene_from_cloud("set_obstacles_from_cloud_objects", points, spec, q, track, obj)
+
+    def cloud_objects(self):
+        """(label [n_obs], object [n_obs], n_objects) of the scene the objects cloud call installed: per sphere the label of its
+        component (its smallest cell index; padding: -1) and whether it moves with a matched object (omds_get_cloud_objects; host
+        state of the context, no GPU work)."""
+        n_obs, n_objects = np.zeros(1, np.int32), np.zeros(1, np.int32)
+        self._ck(self.lib.omds_get_obstacles(self.h, None, L.iptr(n_obs)))
+        label, flag = np.zeros(max(int(n_obs[0]), 1), np.int32), np.zeros(max(int(n_obs[0]), 1), np.int32)
+        self._ck(self.lib.omds_get_cloud_objects(self.h, L.iptr(label), L.iptr(flag), L.iptr(n_objects)))
+        return label[:int(n_obs[0])], flag[:int(n_obs[0])], int(n_objects[0])
+
+    def _scene_from_cloud(self, who, points, spec, q, track, obj=None):
         if hasattr(points, "data_ptr") and not points.is_cuda:      # a torch tensor in host memory
             points = points.detach().numpy()
         if hasattr(points, "data_ptr"):      # a torch tensor on a device
@@ -105,7 +124,12 @@ class Engine:
             addr, P, on_dev = L.fptr(keep) if keep.shape[0] else None, keep.shape[0], 0
         qn = None if q is None else L.f32(q).reshape(self.n)
         n_sph, n_occ, n_match = np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32)
-        if track is None:
+        n_objects, n_objects_matched = np.zeros(1, np.int32), np.zeros(1, np.int32)
+        if obj is not None:
+            rc = self.lib.omds_set_obstacles_from_cloud_objects(self.h, C.byref(spec), C.byref(track), C.byref(obj), addr, P, on_dev, L.fptr(qn),
+                                                                L.iptr(n_sph), L.iptr(n_occ), L.iptr(n_match), L.iptr(n_objects),
+                                                                L.iptr(n_objects_matched))
+        elif track is None:
             rc = self.lib.omds_set_obstacles_from_cloud(self.h, C.byref(spec), addr, P, on_dev, L.fptr(qn), L.iptr(n_sph), L.iptr(n_occ))
         else:
             rc = self.lib.omds_set_obstacles_from_cloud_tracked(self.h, C.byref(spec), C.byref(track), addr, P, on_dev, L.fptr(qn),
@@ -119,6 +143,8 @@ class Engine:
         except L.OmdsError as e:
             e.n_occupied = int(n_occ[0])
             raise
+        if obj is not None:
+            return int(n_sph[0]), int(n_occ[0]), int(n_match[0]), int(n_objects[0]), int(n_objects_matched[0])
         return int(n_sph[0]), int(n_occ[0]), int(n_match[0])
 
     def cloud_track_reset(self):
@@ -627,6 +653,14 @@ def cloud_track_spec(reach, dt_frame, still=0.0):
     return t
 
 
+def cloud_object_spec(link=1, min_cells=4):
+    """An ``OmdsCloudObjectSpec``: spheres whose cells are at most ``link`` cells apart (1 .. 2, Chebyshev) belong to one component; a
+    component of fewer than ``min_cells`` cells is no object."""
+    o = L.OmdsCloudObjectSpec()
+    o.link, o.min_cells = int(link), int(min_cells)
+    return o
+
+
 def point_cloud_spheres(points, spec, cap=None):
     """The definition on the host (omds_point_cloud_spheres, no GPU): points [P, 3] -> spheres [count, 4] of the occupied cells in
     ascending cell order.  More of them than ``spec.max_spheres`` or ``cap`` raises; the error carries ``n_occupied``."""
@@ -657,6 +691,34 @@ def point_cloud_flow(prev, now, spec, track, cap=None):
         e.n_occupied = int(cnt[0])
         raise e
     return out[:int(cnt[0])].copy(), vel[:int(cnt[0])].copy(), int(matched[0])
+
+
+def point_cloud_object_flow(prev, now, spec, track, obj, keep_prev=None, keep_now=None, cap=None):
+    """The definition of the objects cloud call on the host (omds_point_cloud_object_flow, no GPU): clouds ``prev`` and ``now`` [P, 3],
+    ``keep_prev`` / ``keep_now`` one flag per occupied cell of that frame in cell order (None: keep all; they stand for the
+    self-filter) -> (spheres [kept, 4], vel [kept, 3], label [kept], object [kept], matched, n_objects, n_objects_matched).  Raises
+    like ``point_cloud_spheres``."""
+    lib = L.load()
+    a, b = L.f32(prev).reshape(-1, 3), L.f32(now).reshape(-1, 3)
+    kp = None if keep_prev is None else np.ascontiguousarray(np.asarray(keep_prev) != 0, np.uint8)
+    kn = None if keep_now is None else np.ascontiguousarray(np.asarray(keep_now) != 0, np.uint8)
+    cap = int(cap) if cap is not None else (spec.max_spheres if spec.max_spheres >= 1 else 4096)
+    out, vel = np.zeros((max(cap, 1), 4), np.float32), np.zeros((max(cap, 1), 3), np.float32)
+    label, flag = np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.int32)
+    cnt, matched, n_obj, n_acc = (np.zeros(1, np.int32) for _ in range(4))
+    for k, pts, what in ((kp, a, "keep_prev"), (kn, b, "keep_now")):
+        if k is not None and k.size != len(point_cloud_spheres(pts, spec, cap=65536)):
+            raise ValueError(f"point_cloud_object_flow: {what} needs one entry per occupied cell")
+    rc = lib.omds_point_cloud_object_flow(C.byref(spec), C.byref(track), C.byref(obj), L.fptr(a) if a.shape[0] else None, a.shape[0],
+                                          None if kp is None or not kp.size else kp.ctypes.data, L.fptr(b) if b.shape[0] else None, b.shape[0],
+                                          None if kn is None or not kn.size else kn.ctypes.data, L.fptr(out), L.fptr(vel), L.iptr(label),
+                                          L.iptr(flag), cap, L.iptr(cnt), L.iptr(matched), L.iptr(n_obj), L.iptr(n_acc))
+    if rc != 0:
+        e = L.OmdsError(f"omds_point_cloud_object_flow failed ({rc}): {lib.omds_last_error(None).decode()}")
+        e.n_occupied = int(cnt[0])
+        raise e
+    n = int(cnt[0]) if kn is None else int(kn.sum())
+    return out[:n].copy(), vel[:n].copy(), label[:n].copy(), flag[:n].copy(), int(matched[0]), int(n_obj[0]), int(n_acc[0])
 
 
 def moving_frame_velocity(gradx, drow, vel, n_dof, softmax_k=-10.0, max_speed=1.0):

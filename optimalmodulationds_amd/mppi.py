@@ -142,7 +142,7 @@ class MPPI:
         return 0
 
     def update_obstacles_from_cloud(self, points, voxel, lo, hi, radius=None, self_margin=None, min_points=1, max_spheres=4096,
-                                    dt_frame=None, reach=2, still=0.0, moving_frame=False):
+                                    dt_frame=None, reach=2, still=0.0, moving_frame=False, objects=False, link=1, min_cells=4):
         """The scene from a depth point cloud ``points`` [P, 3] (new here; numpy, or a torch tensor on the engine's device): cropped
         to the box ``lo`` .. ``hi``, down-sampled to one sphere per occupied ``voxel`` cell (``radius`` None: the cell's circumsphere)
         and, when ``self_margin`` is given, without the spheres the distance network places within that margin of the robot at
@@ -152,8 +152,15 @@ class MPPI:
         velocity per sphere from the previous frame, the surfaces' normal flow, searched ``reach`` cells each way, speeds below
         ``still`` zeroed, and installed as ``update_obstacles(obs, velocities=)`` would.  ``self.obs_velocities`` then holds them
         ([O, 3], a CPU tensor) or None when the scene stands still (no previous frame, or every velocity 0), ``self.cloud_matched``
-        the spheres that found a previous surface (-1: no previous frame), and ``moving_frame`` acts as in ``update_obstacles``."""
-        from .engine import cloud_spec, cloud_track_spec
+        the spheres that found a previous surface (-1: no previous frame), and ``moving_frame`` acts as in ``update_obstacles``.
+        ``objects`` (needs ``dt_frame``): the objects route (Engine.set_obstacles_from_cloud_objects) -- the spheres are segmented into
+        connected components (cells at most ``link`` apart), a component of at least ``min_cells`` cells that is matched with one of
+        the previous such call moves as a rigid body with its centroid, the other spheres keep the tracked velocities.
+        ``self.cloud_objects`` then holds the objects of the scene and ``self.cloud_objects_matched`` those that were matched (-1: no
+        previous component table); both are None on the other routes."""
+        from .engine import cloud_object_spec, cloud_spec, cloud_track_spec
+        if objects and dt_frame is None:
+            raise ValueError("update_obstacles_from_cloud: objects=True needs dt_frame (the objects route is a tracked one)")
         lo, hi = _np(lo).reshape(3).astype(np.float32), _np(hi).reshape(3).astype(np.float32)
         dims = np.maximum(np.ceil((hi - lo) / np.float32(voxel) - 1e-4), 1).astype(np.int32)
         spec = cloud_spec(lo, voxel, dims, 0.0 if radius is None else radius, min_points, max_spheres,
@@ -162,10 +169,16 @@ class MPPI:
         if q is not None:
             self._push()                             # the filter takes its minimum over the links not in self.ignored_links
         self.obs_velocities, self.cloud_matched = None, None
+        self.cloud_objects, self.cloud_objects_matched = None, None
         if dt_frame is None:
             out = self._engine.set_obstacles_from_cloud(points, spec, q)
         else:
-            *out, self.cloud_matched = self._engine.set_obstacles_from_cloud_tracked(points, spec, cloud_track_spec(reach, dt_frame, still), q)
+            track = cloud_track_spec(reach, dt_frame, still)
+            if objects:
+                *out, self.cloud_matched, self.cloud_objects, self.cloud_objects_matched = self._engine.set_obstacles_from_cloud_objects(
+                    points, spec, track, cloud_object_spec(link, min_cells), q)
+            else:
+                *out, self.cloud_matched = self._engine.set_obstacles_from_cloud_tracked(points, spec, track, q)
             out = tuple(out)
             vel, have = self._engine.get_obstacle_motion()
             if have:
