@@ -364,6 +364,57 @@ OMDS_API int omds_set_obstacles_from_cloud_objects(omds_ctx* ctx, const omds_clo
                                                    int xyz_on_device, const float* q_now, int32_t* n_spheres_out, int32_t* n_occupied_out,
                                                    int32_t* n_matched_out, int32_t* n_objects_out, int32_t* n_objects_matched_out);
 OMDS_API int omds_get_cloud_objects(omds_ctx* ctx, int32_t* label, int32_t* object, int32_t* n_objects_out);
+/* THE SCENE STRAIGHT FROM DEPTH IMAGES, SEVERAL CAMERAS.  The three cloud calls above start from xyz [P,3] in the frame of the voxel
+ * grid; a depth camera delivers a uint16 (or float32) image, intrinsics and a pose, and a cell around an arm has two or three of them.
+ * The depth call deprojects inside the counting pass, without ever writing a point: everything after that pass is integer sums and
+ * ordered compactions, a function of the SET of points.  Additive: no other entry point changes its launches or its bits.
+ * OUT OF SCOPE: lens distortion (the image is taken as rectified), range-type depth (z is depth along the optical axis), depth-noise
+ * filtering, registration of the cameras against each other (the poses are taken as given), temporal smoothing.
+ *   omds_depth_points : host only (no context, no GPU), the DEFINITION.  All fp32, every operation named one rounding.  Once per
+ *       camera: ifx = 1.0f / fx, ify = 1.0f / fy.  The visited pixels are columns u and rows v in 0, step, 2 step, ... (step < 1 is 1),
+ *       in row-major order, ceil(H / step) * ceil(W / step) of them; the raw value is d = image[v * pitch + u] (pitch in ELEMENTS, 0 is
+ *       width).  OMDS_DEPTH_U16: d == 0 drops the pixel (no return), else z = (float)d * depth_scale.  OMDS_DEPTH_F32: z = d.  The pixel
+ *       is kept only if z >= z_min && z <= z_max (NaN, +-inf, negative values and -0 fail by the comparison).  Then
+ *       a = ((float)u - cx) * ifx;  b = ((float)v - cy) * ify;  xc = a * z;  yc = b * z;  and for r = 0, 1, 2
+ *       w_r = fmaf(pose[4r], xc, fmaf(pose[4r+1], yc, fmaf(pose[4r+2], z, pose[4r+3]))).   z is depth along the optical axis, not
+ *       range; no distortion model; R is not checked for orthonormality.  xyz_out [cap_points,3] takes one row per visited pixel, a
+ *       dropped one as three NaNs (omds_point_cloud_spheres drops those); *n_valid_out = kept pixels.  OMDS_ERR_INVALID_ARG before
+ *       anything is written: a camera outside the ranges of the struct (cx, cy must be finite too), null pointers, cap_points smaller
+ *       than the visited count.
+ *   omds_set_obstacles_from_depth : THE CONTRACT -- every effect of the call (status, every out value, the installed scene and its
+ *       padding, velocities and horizon mode, labels and object flags, the stored record frame and component table) is that of
+ *       omds_set_obstacles_from_cloud (track == NULL, obj == NULL) / _tracked (track) / _objects (track and obj) on the concatenation, in
+ *       camera order, of omds_depth_points of each image, bit for bit.  The depth call and the cloud calls share the one stored frame
+ *       and the one stored table: frames may alternate between them.  cams [n_cams], images [n_cams] (images[i]: uint16 or float
+ *       elements as cams[i].format says, at least (H - 1) pitch + W of them); 1 <= n_cams <= OMDS_DEPTH_MAX_CAMERAS; the visited pixels
+ *       of all cameras together at most 16 777 216 (2^24, the bound the record sums rest on), checked from the shapes before anything is
+ *       read; obj without track is an argument error.  images_on_device = 0: host images, each through a staging buffer of the context
+ *       by one asynchronous copy; 1: device memory on the context's device that the caller has finished writing and leaves alone until
+ *       the call returns, read in place -- any base aligned to the element size and any pitch (a sliced view with an odd element offset
+ *       included).  ONE launch counts all cameras (the camera table travels by value in the kernel arguments): a lane takes a run of 4
+ *       consecutive visited pixels of a row, deprojects them with the functions of the definition and adds to the cell counters (the
+ *       records when tracked) of the cloud calls -- equal cells are combined inside the lane and, for at most 8 rounds, across the wave
+ *       before the integer atomics, which changes no bit; from there on the call IS the cloud call.  Argument refusals and the too-many-cells
+ *       refusal leave the scene, the stored frame and the stored table exactly as they were.  Synchronous.                           */
+#define OMDS_DEPTH_U16 0
+#define OMDS_DEPTH_F32 1
+#define OMDS_DEPTH_MAX_CAMERAS 8
+typedef struct {
+    int32_t width, height;   /* pixels, each >= 1                                                         */
+    int32_t pitch;           /* ELEMENTS between row starts; 0 -> width; else >= width                    */
+    int32_t format;          /* OMDS_DEPTH_U16: raw units, 0 = no return;  OMDS_DEPTH_F32: metres         */
+    int32_t step;            /* visit rows and columns 0, step, 2 step, ...; < 1 -> 1                     */
+    float   fx, fy, cx, cy;  /* pinhole intrinsics of the (rectified) image; fx, fy finite and != 0        */
+    float   depth_scale;     /* metres per raw unit (U16 only; finite, > 0)                               */
+    float   z_min, z_max;    /* range gate along the optical axis: 0 < z_min <= z_max, finite             */
+    float   pose[12];        /* row-major [R | t], camera -> the frame of the voxel grid; finite          */
+} omds_depth_camera;
+OMDS_API int omds_depth_points(const omds_depth_camera* cam, const void* image, float* xyz_out, int64_t cap_points, int64_t* n_valid_out);
+OMDS_API int omds_set_obstacles_from_depth(omds_ctx* ctx, const omds_cloud_spec* spec, const omds_cloud_track_spec* track,
+                                           const omds_cloud_object_spec* obj, const omds_depth_camera* cams, const void* const* images,
+                                           int32_t n_cams, int images_on_device, const float* q_now, int32_t* n_spheres_out,
+                                           int32_t* n_occupied_out, int32_t* n_matched_out, int32_t* n_objects_out,
+                                           int32_t* n_objects_matched_out);
 /* LinDS(q_goal) / MPPI.reset_DS / switch_DS_idx (LinDS.py:7-10, MPPI.py:76-84). */
 OMDS_API int omds_set_ds(omds_ctx* ctx, const float* q_goal);
 /* MPPI_toy's nominal DS (MPPI_toy.py:89-91): velocity = (q - q_goal) @ A, A [n,n] row-major, not

@@ -74,6 +74,16 @@ class OmdsCloudObjectSpec(C.Structure):
     _fields_ = [("link", C.c_int32), ("min_cells", C.c_int32)]
 
 
+DEPTH_U16, DEPTH_F32, DEPTH_MAX_CAMERAS = 0, 1, 8     # omds_depth_camera.format; cameras per omds_set_obstacles_from_depth
+
+
+class OmdsDepthCamera(C.Structure):
+    """omds_depth_camera (include/omds.h): one depth image's shape, intrinsics, range gate and pose."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("pitch", C.c_int32), ("format", C.c_int32), ("step", C.c_int32),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("depth_scale", C.c_float),
+                ("z_min", C.c_float), ("z_max", C.c_float), ("pose", C.c_float * 12)]
+
+
 class OmdsError(RuntimeError):
     pass
 
@@ -113,6 +123,10 @@ SIGNATURES = {
                                                         C.POINTER(OmdsCloudObjectSpec), C.c_void_p, C.c_int64, C.c_int, F32P, I32P, I32P,
                                                         I32P, I32P, I32P]),
     "omds_get_cloud_objects": (C.c_int, [C.c_void_p, I32P, I32P, I32P]),
+    "omds_depth_points": (C.c_int, [C.POINTER(OmdsDepthCamera), C.c_void_p, F32P, C.c_int64, C.POINTER(C.c_int64)]),
+    "omds_set_obstacles_from_depth": (C.c_int, [C.c_void_p, C.POINTER(OmdsCloudSpec), C.POINTER(OmdsCloudTrackSpec),
+                                                C.POINTER(OmdsCloudObjectSpec), C.POINTER(OmdsDepthCamera), C.POINTER(C.c_void_p), C.c_int32,
+                                                C.c_int, F32P, I32P, I32P, I32P, I32P, I32P]),
     "omds_set_ds": (C.c_int, [C.c_void_p, F32P]),
     "omds_set_ds_matrix": (C.c_int, [C.c_void_p, F32P, F32P]),
     "omds_set_ds_seds": (C.c_int, [C.c_void_p, F32P, C.c_int, F32P, F32P, F32P, F32P, F32P, F32P, C.c_float, C.c_float]),
@@ -209,7 +223,7 @@ HORIZON_HOOK_SIGNATURES = {
 }
 TEST_LIB_PATH = os.path.join(_HERE, "csrc", "libomds_hip_test.so")
 
-ABI_VERSION = 507     # omds_version() of the library this binding was written against
+ABI_VERSION = 508     # omds_version() of the library this binding was written against
 _libs = {}             # path -> bound CDLL
 
 

@@ -377,6 +377,7 @@ struct omds_ctx {
     DevBuf<float> d_frameOut;    // [n_traj][1 + n] omds_approach_rate: rate, then qo (allocated at the first call)
     // the scene from a point cloud (point_cloud.hip; all allocated at the first omds_set_obstacles_from_cloud, grown with the spec)
     DevBuf<float> d_cloudXyz;         // [P][3] the points of a host cloud
+    DevBuf<unsigned char> d_depthImg; // the host images of a depth call, one after the other, each from a multiple of 16 bytes on
     DevBuf<unsigned> d_cloudCount;    // [cells rounded up to whole compaction blocks] points per cell
     DevBuf<unsigned> d_cloudSums;     // [compaction blocks + 1] occupied items per block, scanned in place; the last word: their total
     DevBuf<float4> d_cloudCand;       // [max_spheres] candidate spheres in cell order

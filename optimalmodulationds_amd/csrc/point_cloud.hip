@@ -10,7 +10,10 @@
 // The objects form (omds_set_obstacles_from_cloud_objects) is the tracked one with the launches of point_cloud_objects_def.h between
 // k_cloud_flow and the install: slot map, union-find, flatten, component sums, the component table by the same ordered compaction, one
 // wave per component for the match against the stored table, and the object velocities over k_cloud_flow's.
+// The depth form (omds_set_obstacles_from_depth) is any of the three with another POINT SOURCE: the counting pass deprojects the
+// pixels of up to eight depth images itself (depth_def.h; k_depth_count, k_depth_count_rec) and no point is ever written.
 #include "capi_internal.h"
+#include "depth_def.h"
 #include "point_cloud_objects_def.h"
 
 namespace {
@@ -172,6 +175,148 @@ template <class T>
 __device__ inline T wave_sum(T v) {
     for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
     return v;
+}
+
+// ---- the counting pass over depth images (depth_def.h) -----------------------------------------------------------------------------
+// ONE launch for all cameras: the table goes by value in the kernel arguments, blockIdx.y is the camera (so every index into the table
+// is uniform over the workgroup) and blockIdx.x strides over that camera's items.  An ITEM is a run of DEPTH_RUN consecutive visited
+// pixels of one visited row: with step 1 a lane's loads are 8 bytes of a U16 row (two dwords where the run's address is a multiple of
+// 4, else four shorts: a base aligned to the element size only, an odd pitch) or 16 bytes of an F32 row.  The loop bound is the same
+// for all lanes of a workgroup, so every wave reaches the cross-lane steps below whole.
+constexpr int DEPTH_RUN = 4;
+constexpr int DEPTH_ROUNDS = 8;       // wave rounds before the lanes that are left issue their own atomics
+constexpr unsigned DEPTH_MAX_BLOCKS = 2048;
+
+struct DepthCamDev {
+    DepthCam c;
+    const void* image;     // device memory, element (0, 0)
+    int runs;              // items per visited row: ceil(nu / DEPTH_RUN)
+    long long items;       // runs * nv
+};
+struct DepthTable {
+    DepthCamDev cam[OMDS_DEPTH_MAX_CAMERAS];
+};
+
+// the cells of item `item` of camera d: cell[t] (-1: no point) and, when REC, k[t][3] of cloud_cell_sub
+template <bool REC>
+__device__ inline void depth_item_cells(const DepthCamDev& d, const CloudGrid& g, long long item, int* cell, unsigned (*k)[3]) {
+    const DepthCam& c = d.c;
+    const int iv = (int)(item / d.runs), j0 = (int)(item % d.runs) * DEPTH_RUN;
+    const int v = iv * c.step;
+    const long long first = (long long)v * c.pitch + (long long)j0 * c.step;
+    const bool whole = c.step == 1 && j0 + DEPTH_RUN <= c.nu;
+    float z[DEPTH_RUN];
+    bool have[DEPTH_RUN];
+    if (c.format == OMDS_DEPTH_U16) {
+        const uint16_t* p = static_cast<const uint16_t*>(d.image) + first;
+        unsigned raw[DEPTH_RUN] = {0u, 0u, 0u, 0u};
+        if (whole && (reinterpret_cast<uintptr_t>(p) & 3u) == 0) {
+            const unsigned* q = reinterpret_cast<const unsigned*>(p);
+            const unsigned w0 = q[0], w1 = q[1];
+            raw[0] = w0 & 0xffffu; raw[1] = w0 >> 16; raw[2] = w1 & 0xffffu; raw[3] = w1 >> 16;
+        } else {
+            for (int t = 0; t < DEPTH_RUN; ++t)
+                if (j0 + t < c.nu) raw[t] = p[(long long)t * c.step];
+        }
+        for (int t = 0; t < DEPTH_RUN; ++t) {
+            z[t] = 0.f;
+            have[t] = depth_z_u16(c, raw[t], &z[t]);   // a column past the row holds raw 0: no return
+        }
+    } else {
+        const float* p = static_cast<const float*>(d.image) + first;
+        if (whole && (reinterpret_cast<uintptr_t>(p) & 15u) == 0) {
+            const float4 w = *reinterpret_cast<const float4*>(p);
+            z[0] = w.x; z[1] = w.y; z[2] = w.z; z[3] = w.w;
+            for (int t = 0; t < DEPTH_RUN; ++t) have[t] = true;
+        } else {
+            for (int t = 0; t < DEPTH_RUN; ++t) {
+                have[t] = j0 + t < c.nu;
+                z[t] = have[t] ? p[(long long)t * c.step] : 0.f;
+            }
+        }
+    }
+    for (int t = 0; t < DEPTH_RUN; ++t) {
+        cell[t] = -1;
+        if (!have[t] || !depth_gate(c, z[t])) continue;
+        float w[3];
+        depth_point(c, (j0 + t) * c.step, v, z[t], w);
+        if (REC) cell[t] = cloud_cell_sub(g, w[0], w[1], w[2], k[t]);
+        else cell[t] = cloud_cell(g, w[0], w[1], w[2]);
+    }
+}
+
+// what one lane adds to a cell: the count alone, or the record (n, s_x, s_y, s_z) packed in 16-bit fields.  A wave's sum of one cell
+// is at most 64 lanes x DEPTH_RUN pixels = 256 points and 255 x 256 = 65 280 per offset sum: no field carries into the next
+template <bool REC> struct DepthAcc;
+template <> struct DepthAcc<false> {
+    typedef unsigned T;
+    __device__ static T one(const unsigned*) { return 1u; }
+    __device__ static void add(void* buf, int cell, T v) { atomicAdd(static_cast<unsigned*>(buf) + cell, v); }
+};
+template <> struct DepthAcc<true> {
+    typedef unsigned long long T;
+    __device__ static T one(const unsigned* k) {
+        return 1ull | (unsigned long long)k[0] << 16 | (unsigned long long)k[1] << 32 | (unsigned long long)k[2] << 48;
+    }
+    __device__ static void add(void* buf, int cell, T v) {
+        unsigned* r = reinterpret_cast<unsigned*>(static_cast<uint4*>(buf) + cell);
+        atomicAdd(r, (unsigned)(v & 0xffffu));
+        atomicAdd(r + 1, (unsigned)(v >> 16 & 0xffffu));
+        atomicAdd(r + 2, (unsigned)(v >> 32 & 0xffffu));
+        atomicAdd(r + 3, (unsigned)(v >> 48));
+    }
+};
+
+// The lane first merges equal cells of its run in registers; then the wave merges across lanes -- the first lane that still holds a
+// cell names it, the lanes that hold the same cell hand their sums to a wave reduction (zeros from the others) and drop it, the naming
+// lane issues the one atomic (four when REC) -- for at most DEPTH_ROUNDS rounds; what is left after that goes out lane by lane, so an
+// image in which every lane holds other cells does not serialise 64 rounds.  Integer sums: no order can change a bit.  No atomic
+// returns a value and nothing waits for one.  (The plain form, one atomic per kept pixel, was 0.02-0.06 ms slower per tracked call
+// at 640 x 480: EXPERIMENTS R20.)
+template <bool REC>
+__device__ inline void depth_count(const DepthTable& tab, const CloudGrid& g, void* buf) {
+    typedef DepthAcc<REC> Acc;
+    typedef typename Acc::T T;
+    const DepthCamDev& d = tab.cam[blockIdx.y];
+    const int lane = threadIdx.x & 63;
+    for (long long base = (long long)blockIdx.x * CLOUD_NT; base < d.items; base += (long long)gridDim.x * CLOUD_NT) {
+        const long long item = base + threadIdx.x;
+        int cell[DEPTH_RUN] = {-1, -1, -1, -1};
+        unsigned k[DEPTH_RUN][3] = {};
+        if (item < d.items) depth_item_cells<REC>(d, g, item, cell, k);
+        T acc[DEPTH_RUN];
+        for (int t = 0; t < DEPTH_RUN; ++t) acc[t] = Acc::one(k[t]);
+        for (int t = 1; t < DEPTH_RUN; ++t)
+            for (int s = 0; s < t; ++s)
+                if (cell[t] >= 0 && cell[t] == cell[s]) {
+                    acc[s] += acc[t];
+                    cell[t] = -1;
+                }
+        for (int round = 0; round < DEPTH_ROUNDS; ++round) {
+            const int mine = cell[0] >= 0 ? cell[0] : cell[1] >= 0 ? cell[1] : cell[2] >= 0 ? cell[2] : cell[3];
+            const unsigned long long pending = __ballot(mine >= 0);
+            if (!pending) break;   // the same for every lane of the wave
+            const int namer = __ffsll((long long)pending) - 1;
+            const int named = __shfl(mine, namer, 64);
+            T part = 0;
+            for (int t = 0; t < DEPTH_RUN; ++t)
+                if (cell[t] == named) {
+                    part = acc[t];
+                    cell[t] = -1;
+                }
+            const T sum = wave_sum(part);
+            if (lane == namer) Acc::add(buf, named, sum);
+        }
+        for (int t = 0; t < DEPTH_RUN; ++t)
+            if (cell[t] >= 0) Acc::add(buf, cell[t], acc[t]);
+    }
+}
+
+__global__ __launch_bounds__(CLOUD_NT) void k_depth_count(DepthTable tab, CloudGrid g, unsigned* __restrict__ count) {
+    depth_count<false>(tab, g, count);
+}
+__global__ __launch_bounds__(CLOUD_NT) void k_depth_count_rec(DepthTable tab, CloudGrid g, uint4* __restrict__ rec) {
+    depth_count<true>(tab, g, rec);
 }
 
 // The velocity of every final sphere (point_cloud_flow_def.h): one wave per sphere, four per workgroup, no barrier.  A first probe
@@ -453,15 +598,63 @@ struct ObjectsCall {
     int32_t* n_objects_matched_out;
 };
 
+// Where the points of a call come from: an array xyz [n_points][3] (host or device), or the depth images of up to eight cameras
+struct DepthSource {
+    DepthCam cam[OMDS_DEPTH_MAX_CAMERAS];   // behind their checks
+    const void* const* images;
+    int n_cams;
+    int on_device;
+};
+struct PointSource {
+    const float* xyz;
+    int64_t n_points;
+    int xyz_on_device;
+    const DepthSource* depth;   // != nullptr: the images, and the three fields above are unused
+};
+
+// the kernel's camera table and its grid; host images go to the context's staging buffer, one asynchronous copy each
+int stage_depth(omds_ctx* ctx, const DepthSource& src, DepthTable* tab, dim3* grid) {
+    size_t offset[OMDS_DEPTH_MAX_CAMERAS], total = 0;
+    long long most = 1;
+    for (int i = 0; i < src.n_cams; ++i) {
+        const size_t bytes = (size_t)depth_extent(src.cam[i]) * (src.cam[i].format == OMDS_DEPTH_U16 ? 2 : 4);
+        offset[i] = total;
+        total += (bytes + 15) & ~(size_t)15;
+    }
+    if (!src.on_device && ctx->d_depthImg.count() < total) {
+        CK(hipStreamSynchronize(ctx->stream));
+        CK(ctx->d_depthImg.alloc(total));
+    }
+    std::memset(static_cast<void*>(tab), 0, sizeof(*tab));
+    for (int i = 0; i < src.n_cams; ++i) {
+        DepthCamDev& d = tab->cam[i];
+        d.c = src.cam[i];
+        d.image = src.images[i];
+        if (!src.on_device) {
+            const size_t bytes = (size_t)depth_extent(d.c) * (d.c.format == OMDS_DEPTH_U16 ? 2 : 4);
+            CK(hipMemcpyAsync(ctx->d_depthImg.get() + offset[i], src.images[i], bytes, hipMemcpyHostToDevice, ctx->stream));
+            d.image = ctx->d_depthImg.get() + offset[i];
+        }
+        d.runs = (d.c.nu + DEPTH_RUN - 1) / DEPTH_RUN;
+        d.items = (long long)d.runs * d.c.nv;
+        most = std::max(most, d.items);
+    }
+    const unsigned per_camera = std::max(DEPTH_MAX_BLOCKS / (unsigned)src.n_cams, 1u);
+    *grid = dim3((unsigned)std::min<long long>((most + CLOUD_NT - 1) / CLOUD_NT, per_camera), (unsigned)src.n_cams);
+    return OMDS_OK;
+}
+
 // The cloud entry points.  tr == nullptr is omds_set_obstacles_from_cloud: the count buffer, no cell indices, no velocities.  With tr
 // the same steps in the same order on the record buffer that is NOT the stored frame, then k_cloud_flow over the final list; with oc
 // (which needs tr) the components of the final list, into the table that is NOT the stored one, and the object velocities
-int scene_from_cloud(omds_ctx* ctx, const char* who, const omds_cloud_spec* spec, const CloudGrid& g, const CloudTrack* tr, const float* xyz,
-                     int64_t n_points, int xyz_on_device, const float* q_now, int32_t* n_spheres_out, int32_t* n_occupied_out,
-                     int32_t* n_matched_out, const ObjectsCall* oc = nullptr) {
+int scene_from_cloud(omds_ctx* ctx, const char* who, const omds_cloud_spec* spec, const CloudGrid& g, const CloudTrack* tr, const PointSource& src,
+                     const float* q_now, int32_t* n_spheres_out, int32_t* n_occupied_out, int32_t* n_matched_out,
+                     const ObjectsCall* oc = nullptr) {
     const std::string me(who);
     int rc;
-    REQUIRE(n_points >= 0 && n_points <= OMDS_CLOUD_MAX_POINTS && (n_points == 0 || xyz), OMDS_ERR_INVALID_ARG,
+    const float* xyz = src.xyz;
+    const int64_t n_points = src.n_points;
+    REQUIRE(src.depth || (n_points >= 0 && n_points <= OMDS_CLOUD_MAX_POINTS && (n_points == 0 || xyz)), OMDS_ERR_INVALID_ARG,
             me + ": need 0 <= n_points <= 16 777 216 and a non-null xyz [P,3]");
     if (q_now) {
         REQUIRE(ctx->have_mlp, OMDS_ERR_NOT_INITIALISED, me + ": the self-filter needs the distance network (omds_set_mlp)");
@@ -502,7 +695,11 @@ int scene_from_cloud(omds_ctx* ctx, const char* who, const omds_cloud_spec* spec
     }
     // the points: the caller's device array as it is, a host array through a staging buffer of the context
     const float* d_xyz = xyz;
-    if (!xyz_on_device && n_points > 0) {
+    DepthTable depth_table;
+    dim3 depth_grid;
+    if (src.depth) {
+        if ((rc = stage_depth(ctx, *src.depth, &depth_table, &depth_grid))) return rc;
+    } else if (!src.xyz_on_device && n_points > 0) {
         if (ctx->d_cloudXyz.count() < (size_t)n_points * 3) {
             CK(hipStreamSynchronize(ctx->stream));
             CK(ctx->d_cloudXyz.alloc((size_t)n_points * 3));
@@ -514,13 +711,17 @@ int scene_from_cloud(omds_ctx* ctx, const char* who, const omds_cloud_spec* spec
     int occupied = 0;
     if (tr) {
         CK(hipMemsetAsync(rec->get(), 0, n_padded * 16, ctx->stream));
-        if (n_points > 0)
+        if (src.depth)
+            hipLaunchKernelGGL(k_depth_count_rec, depth_grid, dim3(CLOUD_NT), 0, ctx->stream, depth_table, g, rec->get());
+        else if (n_points > 0)
             hipLaunchKernelGGL(k_cloud_count_rec, dim3(grid), dim3(CLOUD_NT), 0, ctx->stream, d_xyz, (long long)n_points, g, rec->get());
         const RecSrc cells{rec->get(), g, ctx->d_cloudCand, ctx->d_cloudCandCell};
         if ((rc = compact(ctx, cells, g.n_cells, g.max_spheres, &occupied))) return rc;
     } else {
         CK(hipMemsetAsync(ctx->d_cloudCount, 0, n_padded * 4, ctx->stream));
-        if (n_points > 0)
+        if (src.depth)
+            hipLaunchKernelGGL(k_depth_count, depth_grid, dim3(CLOUD_NT), 0, ctx->stream, depth_table, g, ctx->d_cloudCount.get());
+        else if (n_points > 0)
             hipLaunchKernelGGL(k_cloud_count, dim3(grid), dim3(CLOUD_NT), 0, ctx->stream, d_xyz, (long long)n_points, g, ctx->d_cloudCount.get());
         const CellSrc cells{ctx->d_cloudCount, g, ctx->d_cloudCand};
         if ((rc = compact(ctx, cells, g.n_cells, g.max_spheres, &occupied))) return rc;
@@ -669,8 +870,8 @@ int omds_set_obstacles_from_cloud(omds_ctx* ctx, const omds_cloud_spec* spec, co
     if (!ctx) return OMDS_ERR_INVALID_ARG;
     CloudGrid g;
     if (int rc = cloud_resolve_spec(spec, &g, &ctx->err)) return rc;
-    return scene_from_cloud(ctx, "omds_set_obstacles_from_cloud", spec, g, nullptr, xyz, n_points, xyz_on_device, q_now, n_spheres_out,
-                            n_occupied_out, nullptr);
+    return scene_from_cloud(ctx, "omds_set_obstacles_from_cloud", spec, g, nullptr, PointSource{xyz, n_points, xyz_on_device, nullptr}, q_now,
+                            n_spheres_out, n_occupied_out, nullptr);
 }
 
 int omds_set_obstacles_from_cloud_tracked(omds_ctx* ctx, const omds_cloud_spec* spec, const omds_cloud_track_spec* track, const float* xyz,
@@ -681,8 +882,8 @@ int omds_set_obstacles_from_cloud_tracked(omds_ctx* ctx, const omds_cloud_spec* 
     CloudTrack tr;
     if (int rc = cloud_resolve_spec(spec, &g, &ctx->err)) return rc;
     if (int rc = cloud_resolve_track(track, &tr, &ctx->err)) return rc;
-    return scene_from_cloud(ctx, "omds_set_obstacles_from_cloud_tracked", spec, g, &tr, xyz, n_points, xyz_on_device, q_now, n_spheres_out,
-                            n_occupied_out, n_matched_out);
+    return scene_from_cloud(ctx, "omds_set_obstacles_from_cloud_tracked", spec, g, &tr, PointSource{xyz, n_points, xyz_on_device, nullptr}, q_now,
+                            n_spheres_out, n_occupied_out, n_matched_out);
 }
 
 int omds_point_cloud_object_flow(const omds_cloud_spec* spec, const omds_cloud_track_spec* track, const omds_cloud_object_spec* obj,
@@ -704,8 +905,44 @@ int omds_set_obstacles_from_cloud_objects(omds_ctx* ctx, const omds_cloud_spec* 
     if (int rc = cloud_resolve_spec(spec, &g, &ctx->err)) return rc;
     if (int rc = cloud_resolve_track(track, &tr, &ctx->err)) return rc;
     if (int rc = cloud_resolve_objects(obj, &oc.ob, &ctx->err)) return rc;
-    return scene_from_cloud(ctx, "omds_set_obstacles_from_cloud_objects", spec, g, &tr, xyz, n_points, xyz_on_device, q_now, n_spheres_out,
-                            n_occupied_out, n_matched_out, &oc);
+    return scene_from_cloud(ctx, "omds_set_obstacles_from_cloud_objects", spec, g, &tr, PointSource{xyz, n_points, xyz_on_device, nullptr}, q_now,
+                            n_spheres_out, n_occupied_out, n_matched_out, &oc);
+}
+
+int omds_depth_points(const omds_depth_camera* cam, const void* image, float* xyz_out, int64_t cap_points, int64_t* n_valid_out) {
+    return depth_points_host(cam, image, xyz_out, cap_points, n_valid_out, &g_create_err);
+}
+
+int omds_set_obstacles_from_depth(omds_ctx* ctx, const omds_cloud_spec* spec, const omds_cloud_track_spec* track,
+                                  const omds_cloud_object_spec* obj, const omds_depth_camera* cams, const void* const* images, int32_t n_cams,
+                                  int images_on_device, const float* q_now, int32_t* n_spheres_out, int32_t* n_occupied_out,
+                                  int32_t* n_matched_out, int32_t* n_objects_out, int32_t* n_objects_matched_out) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    const char* me = "omds_set_obstacles_from_depth";
+    CloudGrid g;
+    CloudTrack tr;
+    ObjectsCall oc{{0, 0u}, n_objects_out, n_objects_matched_out};
+    if (int rc = cloud_resolve_spec(spec, &g, &ctx->err)) return rc;
+    REQUIRE(!obj || track, OMDS_ERR_INVALID_ARG, std::string(me) + ": an object spec needs a track spec (the objects route is a tracked one)");
+    if (track)
+        if (int rc = cloud_resolve_track(track, &tr, &ctx->err)) return rc;
+    if (obj)
+        if (int rc = cloud_resolve_objects(obj, &oc.ob, &ctx->err)) return rc;
+    REQUIRE(n_cams >= 1 && n_cams <= OMDS_DEPTH_MAX_CAMERAS && cams && images, OMDS_ERR_INVALID_ARG,
+            std::string(me) + ": need 1 <= n_cams <= 8 and non-null cams, images [n_cams]");
+    DepthSource depth;
+    depth.images = images;
+    depth.n_cams = n_cams;
+    depth.on_device = images_on_device;
+    int64_t visited = 0;
+    for (int i = 0; i < n_cams; ++i) {
+        if (int rc = depth_resolve_camera(cams + i, &depth.cam[i], &ctx->err)) return rc;
+        REQUIRE(images[i], OMDS_ERR_INVALID_ARG, std::string(me) + ": a null image");
+        visited += depth_visited(depth.cam[i]);   // each < 2^62 / 8: no overflow
+    }
+    REQUIRE(visited <= OMDS_CLOUD_MAX_POINTS, OMDS_ERR_INVALID_ARG, std::string(me) + ": more than 16 777 216 visited pixels in all");
+    return scene_from_cloud(ctx, me, spec, g, track ? &tr : nullptr, PointSource{nullptr, 0, 0, &depth}, q_now, n_spheres_out, n_occupied_out,
+                            n_matched_out, obj ? &oc : nullptr);
 }
 
 int omds_get_cloud_objects(omds_ctx* ctx, int32_t* label, int32_t* object, int32_t* n_objects_out) {

@@ -134,6 +134,10 @@ class Engine:
         else:
             rc = self.lib.omds_set_obstacles_from_cloud_tracked(self.h, C.byref(spec), C.byref(track), addr, P, on_dev, L.fptr(qn),
                                                                 L.iptr(n_sph), L.iptr(n_occ), L.iptr(n_match))
+        return self._scene_call_done(rc, qn, obj, n_sph, n_occ, n_match, n_objects, n_objects_matched)
+
+    def _scene_call_done(self, rc, qn, obj, n_sph, n_occ, n_match, n_objects, n_objects_matched):
+        """what follows every cloud / depth scene call: the wrapper's view of the scene, the error with its count, the counts"""
         n_obs = np.zeros(1, np.int32)
         self.lib.omds_get_obstacles(self.h, None, L.iptr(n_obs))      # also after a failure: the context may have dropped its scene
         self.n_obs = int(n_obs[0])
@@ -146,6 +150,48 @@ class Engine:
         if obj is not None:
             return int(n_sph[0]), int(n_occ[0]), int(n_match[0]), int(n_objects[0]), int(n_objects_matched[0])
         return int(n_sph[0]), int(n_occ[0]), int(n_match[0])
+
+    def set_obstacles_from_depth(self, images, cams, spec, q=None, track=None, obj=None):
+        """The scene straight from depth images (omds.h: THE SCENE STRAIGHT FROM DEPTH IMAGES): every effect is that of
+        ``set_obstacles_from_cloud`` (``track`` None) / ``_tracked`` (``track``) / ``_objects`` (``track`` and ``obj``) on the
+        concatenation of ``depth_points`` of each image, bit for bit, and so is what is returned (2, 3 or 5 counts).  ``images``: one
+        per camera (a single image and camera may be passed bare), all numpy ``uint16`` / ``float32`` arrays [H, W], or all torch
+        tensors on the engine's device (``uint16``; ``int16``, reinterpreted; ``float32``), which are read in place -- rows need not
+        be contiguous as long as the last dimension has stride 1 (the camera's ``pitch`` is then taken from the row stride).  ``cams``:
+        ``OmdsDepthCamera`` s (``depth_camera`` builds one); shape and format must be the image's."""
+        if isinstance(cams, L.OmdsDepthCamera):
+            images, cams = [images], [cams]
+        images, cams = list(images), list(cams)
+        if len(images) != len(cams):
+            raise ValueError(f"set_obstacles_from_depth: {len(images)} images but {len(cams)} cameras")
+        n = len(cams)
+        table = (L.OmdsDepthCamera * max(n, 1))()
+        addrs = (C.c_void_p * max(n, 1))()
+        on_dev = [hasattr(im, "data_ptr") and im.is_cuda for im in images]
+        if n and any(on_dev) != all(on_dev):
+            raise ValueError("set_obstacles_from_depth: the images must all be on the host or all on the engine's device")
+        keep = []
+        for i, (im, cam) in enumerate(zip(images, cams)):
+            C.memmove(C.byref(table[i]), C.byref(cam), C.sizeof(L.OmdsDepthCamera))
+            if im is None:
+                continue                      # a null image: the library refuses the call
+            im, addr, pitch = _depth_image(im, cam, self.device)
+            keep.append(im)
+            addrs[i] = addr
+            if pitch is not None:
+                table[i].pitch = pitch
+        if n and all(on_dev):
+            import torch
+            torch.cuda.current_stream(self.device).synchronize()      # the library reads the images on its own stream
+        qn = None if q is None else L.f32(q).reshape(self.n)
+        n_sph, n_occ, n_match = np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32)
+        n_objects, n_objects_matched = np.zeros(1, np.int32), np.zeros(1, np.int32)
+        rc = self.lib.omds_set_obstacles_from_depth(self.h, C.byref(spec), None if track is None else C.byref(track),
+                                                    None if obj is None else C.byref(obj), table, addrs, n, 1 if n and all(on_dev) else 0,
+                                                    L.fptr(qn), L.iptr(n_sph), L.iptr(n_occ), L.iptr(n_match), L.iptr(n_objects),
+                                                    L.iptr(n_objects_matched))
+        out = self._scene_call_done(rc, qn, obj, n_sph, n_occ, n_match, n_objects, n_objects_matched)
+        return out[:2] if track is None else out
 
     def cloud_track_reset(self):
         """Forget the previous tracked frame: the next ``set_obstacles_from_cloud_tracked`` stores its own and sets no velocities."""
@@ -659,6 +705,72 @@ def cloud_object_spec(link=1, min_cells=4):
     o = L.OmdsCloudObjectSpec()
     o.link, o.min_cells = int(link), int(min_cells)
     return o
+
+
+def depth_camera(width, height, fx, fy, cx, cy, pose=None, format=L.DEPTH_U16, depth_scale=0.001, z_min=0.1, z_max=10.0, step=1, pitch=0):
+    """An ``OmdsDepthCamera``: a ``width`` x ``height`` depth image (``format``: ``DEPTH_U16`` raw units of ``depth_scale`` metres, 0 = no
+    return, or ``DEPTH_F32`` metres) of a pinhole camera (``fx``, ``fy``, ``cx``, ``cy``), range-gated to ``z_min`` .. ``z_max`` along the
+    optical axis, of which rows and columns 0, ``step``, 2 ``step``, ... are visited.  ``pose``: camera -> the frame of the voxel grid,
+    a 3 x 4 or 4 x 4 matrix [R | t] (None: the identity).  ``pitch``: elements between row starts (0: ``width``)."""
+    c = L.OmdsDepthCamera()
+    c.width, c.height, c.pitch, c.format, c.step = int(width), int(height), int(pitch), int(format), int(step)
+    c.fx, c.fy, c.cx, c.cy = float(fx), float(fy), float(cx), float(cy)
+    c.depth_scale, c.z_min, c.z_max = float(depth_scale), float(z_min), float(z_max)
+    m = np.eye(4, dtype=np.float32)[:3] if pose is None else np.asarray(pose, np.float32)
+    if m.shape not in ((3, 4), (4, 4)):
+        raise ValueError(f"depth_camera: pose must be a 3 x 4 or 4 x 4 matrix, got {m.shape}")
+    c.pose[:] = [float(v) for v in m[:3].reshape(-1)]
+    return c
+
+
+_DEPTH_NUMPY = {L.DEPTH_U16: (np.uint16,), L.DEPTH_F32: (np.float32,)}
+
+
+def _depth_image(im, cam, device=None):
+    """(object to keep alive, address of element (0, 0), pitch in elements or None: the camera's) of one depth image"""
+    if hasattr(im, "data_ptr") and not im.is_cuda:
+        im = im.detach().numpy()
+    shape = (int(cam.height), int(cam.width))
+    if hasattr(im, "data_ptr"):      # a torch tensor on a device: read in place
+        import torch
+        if im.device.index != device:
+            raise ValueError(f"depth image: a tensor must live on the context's device {device}, got {im.device}")
+        u16 = tuple(t for t in (getattr(torch, "uint16", None), torch.int16) if t is not None)      # int16: the same bits, reinterpreted
+        want = u16 if cam.format == L.DEPTH_U16 else (torch.float32,)
+        if im.dtype not in want or tuple(im.shape) != shape:
+            raise ValueError(f"depth image: need a tensor {shape} of {want}, got {tuple(im.shape)} of {im.dtype}")
+        if shape[1] > 1 and im.stride(1) != 1:
+            raise ValueError("depth image: the last dimension must have stride 1")
+        return im, im.data_ptr(), (int(im.stride(0)) if shape[0] > 1 else shape[1])
+    im = np.asarray(im)
+    if im.dtype not in _DEPTH_NUMPY.get(int(cam.format), ()):
+        raise ValueError(f"depth image: format {cam.format} needs dtype {_DEPTH_NUMPY.get(int(cam.format))}, got {im.dtype}")
+    if im.shape == shape and (shape[1] == 1 or im.strides[1] == im.itemsize) and (shape[0] == 1 or (im.strides[0] > 0 and im.strides[0] % im.itemsize == 0)):
+        return im, im.ctypes.data, (im.strides[0] // im.itemsize if shape[0] > 1 else shape[1])
+    flat = np.ascontiguousarray(im).reshape(-1)      # a flat buffer laid out by the camera's own pitch
+    pitch = int(cam.pitch) if cam.pitch else shape[1]
+    if flat.size < (shape[0] - 1) * pitch + shape[1]:
+        raise ValueError(f"depth image: {flat.size} elements, the camera needs {(shape[0] - 1) * pitch + shape[1]}")
+    return flat, flat.ctypes.data, None
+
+
+def depth_points(image, cam):
+    """The definition on the host (omds_depth_points, no GPU): one depth image (numpy ``uint16`` / ``float32``) -> (xyz [visited, 3],
+    n_valid): the visited pixels in row-major order as points in the frame of the voxel grid, a dropped pixel as three NaNs (which
+    the cloud calls drop), and how many were kept."""
+    lib = L.load()
+    c = L.OmdsDepthCamera()
+    C.memmove(C.byref(c), C.byref(cam), C.sizeof(L.OmdsDepthCamera))
+    keep, addr, pitch = _depth_image(image, c)
+    if pitch is not None:
+        c.pitch = pitch
+    step = max(int(c.step), 1)
+    visited = max(-(-int(c.height) // step), 0) * max(-(-int(c.width) // step), 0)
+    out, n_valid = np.zeros((max(visited, 1), 3), np.float32), C.c_int64(0)
+    rc = lib.omds_depth_points(C.byref(c), addr, L.fptr(out), visited, C.byref(n_valid))
+    if rc != 0:
+        raise L.OmdsError(f"omds_depth_points failed ({rc}): {lib.omds_last_error(None).decode()}")
+    return out[:visited], int(n_valid.value)
 
 
 def point_cloud_spheres(points, spec, cap=None):

@@ -158,9 +158,30 @@ class MPPI:
         the previous such call moves as a rigid body with its centroid, the other spheres keep the tracked velocities.
         ``self.cloud_objects`` then holds the objects of the scene and ``self.cloud_objects_matched`` those that were matched (-1: no
         previous component table); both are None on the other routes."""
+        return self._update_obstacles_sensed("update_obstacles_from_cloud", lambda e, spec, q, track, obj: (
+            e.set_obstacles_from_cloud(points, spec, q) if track is None else
+            e.set_obstacles_from_cloud_tracked(points, spec, track, q) if obj is None else
+            e.set_obstacles_from_cloud_objects(points, spec, track, obj, q)),
+            voxel, lo, hi, radius, self_margin, min_points, max_spheres, dt_frame, reach, still, moving_frame, objects, link, min_cells)
+
+    def update_obstacles_from_depth(self, images, cameras, voxel, lo, hi, radius=None, self_margin=None, min_points=1, max_spheres=4096,
+                                    dt_frame=None, reach=2, still=0.0, moving_frame=False, objects=False, link=1, min_cells=4):
+        """``update_obstacles_from_cloud`` straight from depth images (new here): ``images`` [H, W] one per camera (numpy ``uint16`` /
+        ``float32``, or torch tensors on the engine's device, read in place) and ``cameras`` their ``OmdsDepthCamera`` s
+        (``engine.depth_camera``: intrinsics, range gate, pose in the frame of ``lo`` .. ``hi``).  The pixels are deprojected inside the
+        counting pass on the device (Engine.set_obstacles_from_depth); everything else -- arguments, routes, return value and the
+        attributes set -- is ``update_obstacles_from_cloud`` on the points of the images, bit for bit."""
+        return self._update_obstacles_sensed("update_obstacles_from_depth", lambda e, spec, q, track, obj: (
+            e.set_obstacles_from_depth(images, cameras, spec, q, track, obj)),
+            voxel, lo, hi, radius, self_margin, min_points, max_spheres, dt_frame, reach, still, moving_frame, objects, link, min_cells)
+
+    def _update_obstacles_sensed(self, who, install, voxel, lo, hi, radius, self_margin, min_points, max_spheres, dt_frame, reach, still,
+                                 moving_frame, objects, link, min_cells):
+        """what ``update_obstacles_from_cloud`` and ``update_obstacles_from_depth`` share: the specs, ``install(engine, spec, q, track,
+        obj)`` (the engine call of the route; its counts come back), and the attributes the facade keeps of the sensed scene"""
         from .engine import cloud_object_spec, cloud_spec, cloud_track_spec
         if objects and dt_frame is None:
-            raise ValueError("update_obstacles_from_cloud: objects=True needs dt_frame (the objects route is a tracked one)")
+            raise ValueError(f"{who}: objects=True needs dt_frame (the objects route is a tracked one)")
         lo, hi = _np(lo).reshape(3).astype(np.float32), _np(hi).reshape(3).astype(np.float32)
         dims = np.maximum(np.ceil((hi - lo) / np.float32(voxel) - 1e-4), 1).astype(np.int32)
         spec = cloud_spec(lo, voxel, dims, 0.0 if radius is None else radius, min_points, max_spheres,
@@ -171,14 +192,14 @@ class MPPI:
         self.obs_velocities, self.cloud_matched = None, None
         self.cloud_objects, self.cloud_objects_matched = None, None
         if dt_frame is None:
-            out = self._engine.set_obstacles_from_cloud(points, spec, q)
+            out = install(self._engine, spec, q, None, None)
         else:
             track = cloud_track_spec(reach, dt_frame, still)
             if objects:
-                *out, self.cloud_matched, self.cloud_objects, self.cloud_objects_matched = self._engine.set_obstacles_from_cloud_objects(
-                    points, spec, track, cloud_object_spec(link, min_cells), q)
+                *out, self.cloud_matched, self.cloud_objects, self.cloud_objects_matched = install(
+                    self._engine, spec, q, track, cloud_object_spec(link, min_cells))
             else:
-                *out, self.cloud_matched = self._engine.set_obstacles_from_cloud_tracked(points, spec, track, q)
+                *out, self.cloud_matched = install(self._engine, spec, q, track, None)
             out = tuple(out)
             vel, have = self._engine.get_obstacle_motion()
             if have:
