@@ -1,6 +1,5 @@
 // Host-only declarations shared by the translation units of the C ABI (include/omds.h): context.hip, mlp_pack.hip, network.hip,
-// screening.hip, propagate.hip, update.hip, sdf_data.hip, obstacle_horizon.hip and point_cloud.hip (the one of them that also holds
-// kernels, those of the voxel grid).  No other kernel file includes this header.
+// screening.hip, propagate.hip, update.hip, sdf_data.hip, obstacle_horizon.hip and scene_cloud.hip.  No kernel file includes this header.
 #pragma once
 #include <algorithm>
 #include <cmath>

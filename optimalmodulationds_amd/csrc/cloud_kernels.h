@@ -1,0 +1,61 @@
+// What the host stages of the scene from a point cloud or from depth images (scene_cloud.hip) need of cloud_kernels.hip: the sizes
+// they reserve buffers by, the camera table of the depth counting pass, and the launchers.  A launcher takes a stream and raw
+// pointers, enqueues, and waits for nothing.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "depth_def.h"
+#include "point_cloud_objects_def.h"
+
+constexpr int CLOUD_NT = 256;                          // lanes of every workgroup here
+constexpr int CLOUD_ITEMS = 4;                         // consecutive items per lane of a compaction block
+constexpr int CLOUD_BLOCK = CLOUD_NT * CLOUD_ITEMS;    // items per compaction block
+constexpr int CLOUD_MAX_BLOCKS = (int)(OMDS_CLOUD_MAX_CELLS / CLOUD_BLOCK);   // 4096: what the one workgroup of k_compact_scan takes
+static_assert(CLOUD_MAX_BLOCKS * CLOUD_BLOCK == OMDS_CLOUD_MAX_CELLS, "k_compact_scan takes every grid the spec allows");
+constexpr int OBJ_ACC = 5;                             // uint64 words of a component's sums: m, N, Q[3]
+
+inline int cloud_compaction_blocks(int n) { return (n + CLOUD_BLOCK - 1) / CLOUD_BLOCK; }
+// the cells of a grid rounded up to whole compaction blocks: what the per-cell buffers (counts, records, slots) hold
+inline size_t cloud_padded_cells(const CloudGrid& g) { return (size_t)cloud_compaction_blocks(g.n_cells) * CLOUD_BLOCK; }
+
+struct DepthCamDev {
+    DepthCam c;
+    const void* image;     // device memory, element (0, 0)
+    int runs;              // items per visited row: ceil(nu / DEPTH_RUN)       (these two are the launcher's to fill)
+    long long items;       // runs * nv
+};
+struct DepthTable {
+    DepthCamDev cam[OMDS_DEPTH_MAX_CAMERAS];
+};
+
+// The counting pass, from P points xyz [P][3] or from the images of tab.cam[0 .. n_cams), into counts [cells] or into records [cells]
+// (both cleared by the caller)
+void omds_launch_cloud_count(hipStream_t s, const float* xyz, long long P, const CloudGrid& g, unsigned* count);
+void omds_launch_cloud_count(hipStream_t s, const float* xyz, long long P, const CloudGrid& g, uint4* rec);
+void omds_launch_cloud_count(hipStream_t s, DepthTable tab, int n_cams, const CloudGrid& g, unsigned* count);
+void omds_launch_cloud_count(hipStream_t s, DepthTable tab, int n_cams, const CloudGrid& g, uint4* rec);
+
+// The ordered compactions, one per item space: the kept items to out (and what goes with them) in item order, at most cap of them
+// written; sums [blocks of the item space + 1] is scratch, and sums[cloud_compaction_blocks(n)] holds the number of kept items after.
+// ... the cells of g with min_points points and more (count / rec padded with zeros to cloud_padded_cells): their spheres, cap = g.max_spheres
+void omds_launch_cloud_compact_cells(hipStream_t s, const unsigned* count, const CloudGrid& g, float4* out, unsigned* sums);
+void omds_launch_cloud_compact_cells(hipStream_t s, const uint4* rec, const CloudGrid& g, float4* out, int* cell, unsigned* sums);
+// ... the n candidates the self-filter keeps at their pass-1 distances d [n]; with candCell their cell indices go to cell beside them
+void omds_launch_cloud_compact_kept(hipStream_t s, const float* d, const float4* cand, const int* candCell, int n, float margin, int cap,
+                                    float4* out, int* cell, unsigned* sums);
+// ... the roots among the n spheres (root, acc: what omds_launch_cloud_components left): the component table, compOf[root] = its row
+void omds_launch_cloud_compact_roots(hipStream_t s, const int* root, const int* cells, const unsigned long long* acc, int n, int cap,
+                                     CloudComp* table, int* compOf, unsigned* sums);
+
+// vel [n]: the velocity of every final sphere (its cell in cells) from the records of this frame and the previous one
+void omds_launch_cloud_flow(hipStream_t s, const CloudGrid& g, const CloudTrack& tr, const uint4* now, const uint4* prev, const int* cells, int n,
+                            float4* vel);
+// the components of the n final spheres: slot [cloud_padded_cells] and acc [n][OBJ_ACC] are cleared here; after it parent [n] is
+// every sphere's root, label [n] its component's label and acc the sums at the roots
+void omds_launch_cloud_components(hipStream_t s, const CloudGrid& g, int link, const uint4* now, const int* cells, int n, int* slot, int* parent,
+                                  int* label, unsigned long long* acc);
+// objVel [n_now]: every component of the table now against the table prev (n_prev = 0: nothing to match)
+void omds_launch_cloud_match(hipStream_t s, const CloudGrid& g, const CloudTrack& tr, const CloudObjects& ob, const CloudComp* now, int n_now,
+                             const CloudComp* prev, int n_prev, float4* objVel);
+// the velocities of the accepted objects over vel [n], object [n] = 1 on their spheres
+void omds_launch_cloud_apply(hipStream_t s, const int* root, const int* compOf, const float4* objVel, int n, float4* vel, int* object);

@@ -1,27 +1,20 @@
-// The scene from a depth point cloud (omds.h: omds_point_cloud_spheres, omds_set_obstacles_from_cloud): the workspace crop and the
-// voxel down-sample as one counting pass over the points (k_cloud_count, integer atomics) and an ordered compaction of the occupied
-// cells (k_compact_sums -> k_compact_scan -> k_compact_emit), the robot self-filter as ONE fp32 pass-1 launch over one state with the
-// candidates as its obstacle rows (the launch the shared first step of a propagate uses) and a second compaction of those it keeps.
-// The arithmetic of a cell and of its sphere is point_cloud_def.h's, shared with the host definition.  The final list goes to the host
-// (a few thousand x 16 bytes) and from there through install_obstacles, the body of omds_set_obstacles (context.hip).
-// The tracked form (omds_set_obstacles_from_cloud_tracked) counts into records of 16 bytes per cell (k_cloud_count_rec), carries each
-// candidate's cell index through both compactions, and evaluates point_cloud_flow_def.h against the records of the previous tracked
-// frame with one wave per final sphere (k_cloud_flow); the velocities then go in through omds_set_obstacle_motion.
-// The objects form (omds_set_obstacles_from_cloud_objects) is the tracked one with the launches of point_cloud_objects_def.h between
-// k_cloud_flow and the install: slot map, union-find, flatten, component sums, the component table by the same ordered compaction, one
-// wave per component for the match against the stored table, and the object velocities over k_cloud_flow's.
-// The depth form (omds_set_obstacles_from_depth) is any of the three with another POINT SOURCE: the counting pass deprojects the
-// pixels of up to eight depth images itself (depth_def.h; k_depth_count, k_depth_count_rec) and no point is ever written.
-#include "capi_internal.h"
-#include "depth_def.h"
-#include "point_cloud_objects_def.h"
+// The kernels of the scene from a depth point cloud or from depth images (the host stages: scene_cloud.hip).  The workspace crop and
+// the voxel down-sample are one counting pass over the points (k_cloud_count, integer atomics) and an ordered compaction of the
+// occupied cells (k_compact_sums -> k_compact_scan -> k_compact_emit); the same compaction keeps the candidates the self-filter lets
+// through.  The arithmetic of a cell and of its sphere is point_cloud_def.h's, shared with the host definition.
+// The tracked form counts into records of 16 bytes per cell (k_cloud_count_rec), carries each candidate's cell index through both
+// compactions, and evaluates point_cloud_flow_def.h against the records of the previous tracked frame with one wave per final sphere
+// (k_cloud_flow).
+// The objects form adds the launches of point_cloud_objects_def.h: slot map, union-find, flatten, component sums, the component table
+// by the same ordered compaction, one wave per component for the match against the stored table, and the object velocities over
+// k_cloud_flow's.
+// The depth form is another POINT SOURCE of the counting pass: it deprojects the pixels of up to eight depth images itself
+// (depth_def.h; k_depth_count, k_depth_count_rec) and no point is ever written.
+#include <algorithm>
+
+#include "cloud_kernels.h"
 
 namespace {
-
-constexpr int CLOUD_NT = 256;                          // lanes of every workgroup here
-constexpr int CLOUD_ITEMS = 4;                         // consecutive items per lane of a compaction block
-constexpr int CLOUD_BLOCK = CLOUD_NT * CLOUD_ITEMS;    // items per compaction block
-constexpr int CLOUD_MAX_BLOCKS = (int)(OMDS_CLOUD_MAX_CELLS / CLOUD_BLOCK);   // 4096: what the one workgroup of k_compact_scan takes
 
 // one pass over the points: the crop is cloud_cell's range test, the down-sample the count per cell
 __global__ __launch_bounds__(CLOUD_NT) void k_cloud_count(const float* __restrict__ xyz, long long P, CloudGrid g, unsigned* __restrict__ count) {
@@ -186,16 +179,6 @@ __device__ inline T wave_sum(T v) {
 constexpr int DEPTH_RUN = 4;
 constexpr int DEPTH_ROUNDS = 8;       // wave rounds before the lanes that are left issue their own atomics
 constexpr unsigned DEPTH_MAX_BLOCKS = 2048;
-
-struct DepthCamDev {
-    DepthCam c;
-    const void* image;     // device memory, element (0, 0)
-    int runs;              // items per visited row: ceil(nu / DEPTH_RUN)
-    long long items;       // runs * nv
-};
-struct DepthTable {
-    DepthCamDev cam[OMDS_DEPTH_MAX_CAMERAS];
-};
 
 // the cells of item `item` of camera d: cell[t] (-1: no point) and, when REC, k[t][3] of cloud_cell_sub
 template <bool REC>
@@ -448,7 +431,6 @@ __global__ __launch_bounds__(CLOUD_NT) void k_obj_flatten(const int* __restrict_
 // whose runs small components interrupt) are added up by a shuffle sum; and the dominant sums of the sixteen waves of the workgroup
 // meet in LDS, from where each distinct root goes to memory once.  What is left for the atomics is one set per workgroup for a huge
 // component and one per run for the small ones.  Integers throughout: no order can change a bit
-constexpr int OBJ_ACC = 5;
 constexpr int SUMS_NT = 1024, SUMS_WAVES = SUMS_NT / 64;
 __global__ __launch_bounds__(SUMS_NT) void k_obj_sums(CloudGrid g, const uint4* __restrict__ now, const int* __restrict__ cells,
                                                       const int* __restrict__ root, int n, unsigned long long* __restrict__ acc) {
@@ -571,395 +553,86 @@ __global__ __launch_bounds__(CLOUD_NT) void k_obj_apply(const int* __restrict__ 
     object[i] = accepted ? 1 : 0;
 }
 
-inline int compaction_blocks(int n) { return (n + CLOUD_BLOCK - 1) / CLOUD_BLOCK; }
-
-// the ordered compaction of n items of src into src.out (at most cap spheres written); *total_out = kept items.  Synchronises.
+// the ordered compaction of n items of src (at most cap written); the number of kept items is left at sums[blocks of n]
 template <class Src>
-int compact(omds_ctx* ctx, const Src& src, int n, int cap, int* total_out) {
-    *total_out = 0;
-    if (n <= 0) return OMDS_OK;
-    const int nb = compaction_blocks(n);
-    unsigned* sums = ctx->d_cloudSums;
-    hipLaunchKernelGGL((k_compact_sums<Src>), dim3(nb), dim3(CLOUD_NT), 0, ctx->stream, src, n, sums);
-    hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(CLOUD_NT), 0, ctx->stream, sums, nb);
-    hipLaunchKernelGGL((k_compact_emit<Src>), dim3(nb), dim3(CLOUD_NT), 0, ctx->stream, src, n, sums, (unsigned)cap);
-    CK(hipGetLastError());
-    unsigned total = 0;
-    CK(hipMemcpyAsync(&total, sums + nb, 4, hipMemcpyDeviceToHost, ctx->stream));
-    CK(hipStreamSynchronize(ctx->stream));
-    *total_out = (int)total;
-    return OMDS_OK;
+void compact(hipStream_t s, const Src& src, int n, int cap, unsigned* sums) {
+    if (n <= 0) return;
+    const int nb = cloud_compaction_blocks(n);
+    hipLaunchKernelGGL((k_compact_sums<Src>), dim3(nb), dim3(CLOUD_NT), 0, s, src, n, sums);
+    hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(CLOUD_NT), 0, s, sums, nb);
+    hipLaunchKernelGGL((k_compact_emit<Src>), dim3(nb), dim3(CLOUD_NT), 0, s, src, n, sums, (unsigned)cap);
 }
 
-// What the objects call adds to the tracked one: its spec, and where its two counts go
-struct ObjectsCall {
-    CloudObjects ob;
-    int32_t* n_objects_out;
-    int32_t* n_objects_matched_out;
-};
+inline dim3 point_blocks(long long P) { return dim3((unsigned)std::min<long long>((P + CLOUD_NT - 1) / CLOUD_NT, 2048)); }
 
-// Where the points of a call come from: an array xyz [n_points][3] (host or device), or the depth images of up to eight cameras
-struct DepthSource {
-    DepthCam cam[OMDS_DEPTH_MAX_CAMERAS];   // behind their checks
-    const void* const* images;
-    int n_cams;
-    int on_device;
-};
-struct PointSource {
-    const float* xyz;
-    int64_t n_points;
-    int xyz_on_device;
-    const DepthSource* depth;   // != nullptr: the images, and the three fields above are unused
-};
-
-// the kernel's camera table and its grid; host images go to the context's staging buffer, one asynchronous copy each
-int stage_depth(omds_ctx* ctx, const DepthSource& src, DepthTable* tab, dim3* grid) {
-    size_t offset[OMDS_DEPTH_MAX_CAMERAS], total = 0;
+// the items of every camera into the table; the grid: blockIdx.y the camera, DEPTH_MAX_BLOCKS workgroups over all of them
+dim3 depth_blocks(DepthTable& tab, int n_cams) {
     long long most = 1;
-    for (int i = 0; i < src.n_cams; ++i) {
-        const size_t bytes = (size_t)depth_extent(src.cam[i]) * (src.cam[i].format == OMDS_DEPTH_U16 ? 2 : 4);
-        offset[i] = total;
-        total += (bytes + 15) & ~(size_t)15;
-    }
-    if (!src.on_device && ctx->d_depthImg.count() < total) {
-        CK(hipStreamSynchronize(ctx->stream));
-        CK(ctx->d_depthImg.alloc(total));
-    }
-    std::memset(static_cast<void*>(tab), 0, sizeof(*tab));
-    for (int i = 0; i < src.n_cams; ++i) {
-        DepthCamDev& d = tab->cam[i];
-        d.c = src.cam[i];
-        d.image = src.images[i];
-        if (!src.on_device) {
-            const size_t bytes = (size_t)depth_extent(d.c) * (d.c.format == OMDS_DEPTH_U16 ? 2 : 4);
-            CK(hipMemcpyAsync(ctx->d_depthImg.get() + offset[i], src.images[i], bytes, hipMemcpyHostToDevice, ctx->stream));
-            d.image = ctx->d_depthImg.get() + offset[i];
-        }
+    for (int i = 0; i < n_cams; ++i) {
+        DepthCamDev& d = tab.cam[i];
         d.runs = (d.c.nu + DEPTH_RUN - 1) / DEPTH_RUN;
         d.items = (long long)d.runs * d.c.nv;
         most = std::max(most, d.items);
     }
-    const unsigned per_camera = std::max(DEPTH_MAX_BLOCKS / (unsigned)src.n_cams, 1u);
-    *grid = dim3((unsigned)std::min<long long>((most + CLOUD_NT - 1) / CLOUD_NT, per_camera), (unsigned)src.n_cams);
-    return OMDS_OK;
-}
-
-// The cloud entry points.  tr == nullptr is omds_set_obstacles_from_cloud: the count buffer, no cell indices, no velocities.  With tr
-// the same steps in the same order on the record buffer that is NOT the stored frame, then k_cloud_flow over the final list; with oc
-// (which needs tr) the components of the final list, into the table that is NOT the stored one, and the object velocities
-int scene_from_cloud(omds_ctx* ctx, const char* who, const omds_cloud_spec* spec, const CloudGrid& g, const CloudTrack* tr, const PointSource& src,
-                     const float* q_now, int32_t* n_spheres_out, int32_t* n_occupied_out, int32_t* n_matched_out,
-                     const ObjectsCall* oc = nullptr) {
-    const std::string me(who);
-    int rc;
-    const float* xyz = src.xyz;
-    const int64_t n_points = src.n_points;
-    REQUIRE(src.depth || (n_points >= 0 && n_points <= OMDS_CLOUD_MAX_POINTS && (n_points == 0 || xyz)), OMDS_ERR_INVALID_ARG,
-            me + ": need 0 <= n_points <= 16 777 216 and a non-null xyz [P,3]");
-    if (q_now) {
-        REQUIRE(ctx->have_mlp, OMDS_ERR_NOT_INITIALISED, me + ": the self-filter needs the distance network (omds_set_mlp)");
-        REQUIRE(!ctx->wide.on, OMDS_ERR_UNSUPPORTED, me + ": no self-filter on networks wider than 256 (no obstacle tables)");
-    }
-    CK(hipSetDevice(ctx->dev));
-    const int nb = compaction_blocks(g.n_cells), k = ctx->cfg.n_closest;
-    static_assert(CLOUD_MAX_BLOCKS * CLOUD_BLOCK == OMDS_CLOUD_MAX_CELLS, "k_compact_scan takes every grid the spec allows");
-    const size_t n_padded = (size_t)nb * CLOUD_BLOCK;
-    DevBuf<uint4>* rec = tr ? &ctx->d_cloudRec[1 - ctx->cloud_stored] : nullptr;   // counted into; the stored frame is the other one
-    if ((tr ? rec->count() < n_padded || ctx->d_cloudVel.count() < (size_t)g.max_spheres : ctx->d_cloudCount.count() < n_padded) ||
-        ctx->d_cloudCand.count() < (size_t)g.max_spheres) {
-        CK(hipStreamSynchronize(ctx->stream));
-        if (tr) {
-            CK(rec->reserve(n_padded));
-            CK(ctx->d_cloudCandCell.reserve((size_t)g.max_spheres));
-            CK(ctx->d_cloudKeptCell.reserve((size_t)g.max_spheres));
-            CK(ctx->d_cloudVel.reserve((size_t)g.max_spheres));
-        } else {
-            CK(ctx->d_cloudCount.reserve(n_padded));
-        }
-        CK(ctx->d_cloudSums.reserve((size_t)CLOUD_MAX_BLOCKS + 1));
-        CK(ctx->d_cloudCand.reserve((size_t)g.max_spheres));
-        CK(ctx->d_cloudKept.reserve((size_t)g.max_spheres));
-    }
-    DevBuf<unsigned char>* table = oc ? &ctx->d_cloudTable[1 - ctx->cloud_table_stored] : nullptr;   // written; the stored table is the other one
-    if (oc && (ctx->d_cloudSlot.count() < n_padded || ctx->d_cloudParent.count() < (size_t)g.max_spheres ||
-               table->count() < (size_t)g.max_spheres * sizeof(CloudComp))) {
-        CK(hipStreamSynchronize(ctx->stream));
-        CK(ctx->d_cloudSlot.reserve(n_padded));
-        CK(ctx->d_cloudParent.reserve((size_t)g.max_spheres));
-        CK(ctx->d_cloudLabel.reserve((size_t)g.max_spheres));
-        CK(ctx->d_cloudObject.reserve((size_t)g.max_spheres));
-        CK(ctx->d_cloudCompOf.reserve((size_t)g.max_spheres));
-        CK(ctx->d_cloudAcc.reserve((size_t)g.max_spheres * OBJ_ACC));
-        CK(ctx->d_cloudObjVel.reserve((size_t)g.max_spheres));
-        CK(table->reserve((size_t)g.max_spheres * sizeof(CloudComp)));
-    }
-    // the points: the caller's device array as it is, a host array through a staging buffer of the context
-    const float* d_xyz = xyz;
-    DepthTable depth_table;
-    dim3 depth_grid;
-    if (src.depth) {
-        if ((rc = stage_depth(ctx, *src.depth, &depth_table, &depth_grid))) return rc;
-    } else if (!src.xyz_on_device && n_points > 0) {
-        if (ctx->d_cloudXyz.count() < (size_t)n_points * 3) {
-            CK(hipStreamSynchronize(ctx->stream));
-            CK(ctx->d_cloudXyz.alloc((size_t)n_points * 3));
-        }
-        CK(hipMemcpyAsync(ctx->d_cloudXyz, xyz, (size_t)n_points * 12, hipMemcpyHostToDevice, ctx->stream));
-        d_xyz = ctx->d_cloudXyz;
-    }
-    const unsigned grid = (unsigned)std::min<long long>((n_points + CLOUD_NT - 1) / CLOUD_NT, 2048);
-    int occupied = 0;
-    if (tr) {
-        CK(hipMemsetAsync(rec->get(), 0, n_padded * 16, ctx->stream));
-        if (src.depth)
-            hipLaunchKernelGGL(k_depth_count_rec, depth_grid, dim3(CLOUD_NT), 0, ctx->stream, depth_table, g, rec->get());
-        else if (n_points > 0)
-            hipLaunchKernelGGL(k_cloud_count_rec, dim3(grid), dim3(CLOUD_NT), 0, ctx->stream, d_xyz, (long long)n_points, g, rec->get());
-        const RecSrc cells{rec->get(), g, ctx->d_cloudCand, ctx->d_cloudCandCell};
-        if ((rc = compact(ctx, cells, g.n_cells, g.max_spheres, &occupied))) return rc;
-    } else {
-        CK(hipMemsetAsync(ctx->d_cloudCount, 0, n_padded * 4, ctx->stream));
-        if (src.depth)
-            hipLaunchKernelGGL(k_depth_count, depth_grid, dim3(CLOUD_NT), 0, ctx->stream, depth_table, g, ctx->d_cloudCount.get());
-        else if (n_points > 0)
-            hipLaunchKernelGGL(k_cloud_count, dim3(grid), dim3(CLOUD_NT), 0, ctx->stream, d_xyz, (long long)n_points, g, ctx->d_cloudCount.get());
-        const CellSrc cells{ctx->d_cloudCount, g, ctx->d_cloudCand};
-        if ((rc = compact(ctx, cells, g.n_cells, g.max_spheres, &occupied))) return rc;
-    }
-    if (n_occupied_out) *n_occupied_out = occupied;
-    REQUIRE(occupied <= g.max_spheres, OMDS_ERR_INVALID_ARG,
-            me + ": more occupied cells than max_spheres (n_occupied_out holds their number); the scene is unchanged");
-    const float4* d_list = ctx->d_cloudCand;
-    const int* d_cell = ctx->d_cloudCandCell;
-    int n_list = occupied;
-    if (q_now && occupied > 0) {
-        // The candidates become the obstacle rows of one state.  From here on the tables of the old scene are overwritten: the context
-        // holds no scene, and no horizon of one, until install_obstacles below has put the new one in
-        const int n = ctx->cfg.n_dof;
-        if ((rc = reserve_obstacle_capacity(ctx, occupied))) return rc;
-        ctx->n_obs = 0;
-        clear_obstacle_horizon(ctx);
-        CK(hipMemcpyAsync(ctx->d_qcur, q_now, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-        omds_launch_rollout_features(ctx->stream, ctx->mlp, ctx->d_qcur, 1, 1, ctx->d_Fq);
-        omds_launch_obstacle_features(ctx->stream, ctx->mlp, reinterpret_cast<const float*>(d_list), occupied, ctx->d_Fp, ctx->d_radius);
-        omds_launch_pass1(ctx->stream, ctx->mlp, ctx->d_Fq, ctx->d_Fp, ctx->d_radius, occupied, 1, ctx->prm.ignored_links, ctx->d_Dmin);
-        CK(hipGetLastError());
-        const KeepSrc keep{ctx->d_Dmin, d_list, spec->self_margin, ctx->d_cloudKept};
-        if (tr) {
-            const KeepCellSrc keep_cell{keep, d_cell, ctx->d_cloudKeptCell};
-            if ((rc = compact(ctx, keep_cell, occupied, g.max_spheres, &n_list))) return rc;
-            d_cell = ctx->d_cloudKeptCell;
-        } else {
-            if ((rc = compact(ctx, keep, occupied, g.max_spheres, &n_list))) return rc;
-        }
-        d_list = ctx->d_cloudKept;
-    }
-    // the velocities of the final list against the stored frame, if there is one on this grid
-    const int n_final = std::max(n_list, k);
-    const bool have_prev = tr && ctx->cloud_have_frame && std::memcmp(ctx->cloud_frame_origin, &g.ox, 12) == 0 &&
-                           std::memcmp(&ctx->cloud_frame_voxel, &g.voxel, 4) == 0 && ctx->cloud_frame_dims[0] == g.dx &&
-                           ctx->cloud_frame_dims[1] == g.dy && ctx->cloud_frame_dims[2] == g.dz && ctx->cloud_frame_min_points == g.min_points;
-    std::vector<float> vel4;
-    if (have_prev && n_list > 0) {
-        vel4.resize((size_t)n_list * 4);
-        hipLaunchKernelGGL(k_cloud_flow, dim3((n_list + FLOW_WAVES - 1) / FLOW_WAVES), dim3(CLOUD_NT), 0, ctx->stream, g, *tr,
-                           (const uint4*)rec->get(), (const uint4*)ctx->d_cloudRec[ctx->cloud_stored].get(), d_cell, n_list,
-                           ctx->d_cloudVel.get());
-        CK(hipGetLastError());
-    }
-    // the components of the final list, their match against the stored table and the velocities of the accepted objects
-    const bool have_table = oc && have_prev && ctx->cloud_have_table && ctx->cloud_table_link == oc->ob.link &&
-                            ctx->cloud_table_min_cells == oc->ob.min_cells;
-    int n_comp = 0;
-    std::vector<int32_t> label((size_t)n_final, -1), object((size_t)n_final, 0);   // padding spheres: label -1, no object
-    std::vector<float> obj_vel;
-    if (oc && n_list > 0) {
-        const int blocks = (n_list + CLOUD_NT - 1) / CLOUD_NT;
-        CloudComp* d_table = reinterpret_cast<CloudComp*>(table->get());
-        CK(hipMemsetAsync(ctx->d_cloudSlot, 0xff, n_padded * 4, ctx->stream));   // -1
-        CK(hipMemsetAsync(ctx->d_cloudAcc, 0, (size_t)n_list * OBJ_ACC * 8, ctx->stream));
-        hipLaunchKernelGGL(k_obj_slot, dim3(blocks), dim3(CLOUD_NT), 0, ctx->stream, d_cell, n_list, ctx->d_cloudSlot.get(), ctx->d_cloudParent.get());
-        hipLaunchKernelGGL(k_obj_union, dim3(blocks), dim3(CLOUD_NT), 0, ctx->stream, g, oc->ob.link, d_cell, n_list,
-                           (const int*)ctx->d_cloudSlot.get(), ctx->d_cloudParent.get());
-        hipLaunchKernelGGL(k_obj_flatten, dim3(blocks), dim3(CLOUD_NT), 0, ctx->stream, d_cell, n_list, ctx->d_cloudParent.get(), ctx->d_cloudLabel.get());
-        hipLaunchKernelGGL(k_obj_sums, dim3((n_list + SUMS_NT - 1) / SUMS_NT), dim3(SUMS_NT), 0, ctx->stream, g, (const uint4*)rec->get(), d_cell,
-                           (const int*)ctx->d_cloudParent.get(), n_list, ctx->d_cloudAcc.get());
-        CK(hipGetLastError());
-        const RootSrc roots{ctx->d_cloudParent, d_cell, ctx->d_cloudAcc, d_table, ctx->d_cloudCompOf};
-        if ((rc = compact(ctx, roots, n_list, g.max_spheres, &n_comp))) return rc;
-        hipLaunchKernelGGL(k_obj_match, dim3((n_comp + FLOW_WAVES - 1) / FLOW_WAVES), dim3(CLOUD_NT), 0, ctx->stream, g, *tr, oc->ob,
-                           (const CloudComp*)d_table, n_comp,
-                           (const CloudComp*)reinterpret_cast<const CloudComp*>(ctx->d_cloudTable[ctx->cloud_table_stored].get()),
-                           have_table ? ctx->cloud_table_n : 0, ctx->d_cloudObjVel.get());
-        if (have_table) {
-            hipLaunchKernelGGL(k_obj_apply, dim3(blocks), dim3(CLOUD_NT), 0, ctx->stream, (const int*)ctx->d_cloudParent.get(),
-                               (const int*)ctx->d_cloudCompOf.get(), (const float4*)ctx->d_cloudObjVel.get(), n_list, ctx->d_cloudVel.get(),
-                               ctx->d_cloudObject.get());
-            CK(hipMemcpyAsync(object.data(), ctx->d_cloudObject, (size_t)n_list * 4, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        CK(hipGetLastError());
-        obj_vel.resize((size_t)n_comp * 4);
-        CK(hipMemcpyAsync(obj_vel.data(), ctx->d_cloudObjVel, (size_t)n_comp * 16, hipMemcpyDeviceToHost, ctx->stream));
-        CK(hipMemcpyAsync(label.data(), ctx->d_cloudLabel, (size_t)n_list * 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    if (!vel4.empty()) CK(hipMemcpyAsync(vel4.data(), ctx->d_cloudVel, (size_t)n_list * 16, hipMemcpyDeviceToHost, ctx->stream));
-    // to the host, filled up to n_closest with the spec's pad sphere, and in as omds_set_obstacles puts a list in
-    std::vector<float> list((size_t)n_final * 4);
-    if (n_list > 0) CK(hipMemcpyAsync(list.data(), d_list, (size_t)n_list * 16, hipMemcpyDeviceToHost, ctx->stream));
-    CK(hipStreamSynchronize(ctx->stream));
-    for (int i = n_list; i < n_final; ++i) std::memcpy(&list[(size_t)i * 4], spec->pad, 16);
-    if ((rc = install_obstacles(ctx, list.data(), n_final))) return rc;
-    if (n_spheres_out) *n_spheres_out = n_list;
-    if (!tr) return OMDS_OK;
-    // a scene whose every sphere stands still keeps the cleared horizon: the propagate that follows is the static one
-    std::vector<float> vel((size_t)n_final * 3, 0.f);   // padding spheres stand still
-    int matched = 0;
-    bool moving = false;
-    for (size_t i = 0; i * 4 < vel4.size(); ++i) {
-        for (int c = 0; c < 3; ++c) {
-            vel[i * 3 + c] = vel4[i * 4 + c];
-            moving |= vel4[i * 4 + c] != 0.f;
-        }
-        matched += vel4[i * 4 + 3] != 0.f;
-    }
-    if (moving && (rc = omds_set_obstacle_motion(ctx, vel.data()))) return rc;
-    ctx->cloud_stored = 1 - ctx->cloud_stored;   // what was counted is the stored frame now
-    ctx->cloud_have_frame = true;
-    std::memcpy(ctx->cloud_frame_origin, &g.ox, 12);
-    ctx->cloud_frame_voxel = g.voxel;
-    ctx->cloud_frame_dims[0] = g.dx; ctx->cloud_frame_dims[1] = g.dy; ctx->cloud_frame_dims[2] = g.dz;
-    ctx->cloud_frame_min_points = g.min_points;
-    if (n_matched_out) *n_matched_out = have_prev ? (int32_t)matched : -1;
-    ctx->cloud_have_table = false;   // a plain tracked call stores its records and no table: the next objects call has nothing to match
-    if (!oc) return OMDS_OK;
-    int32_t n_objects = 0, n_accepted = 0;
-    for (int c = 0; c < n_comp; ++c) {
-        n_objects += obj_vel[(size_t)c * 4 + 3] >= 1.f;
-        n_accepted += obj_vel[(size_t)c * 4 + 3] == 2.f;
-    }
-    ctx->cloud_table_stored = 1 - ctx->cloud_table_stored;   // what was written is the stored table now
-    ctx->cloud_have_table = true;
-    ctx->cloud_table_n = n_comp;
-    ctx->cloud_table_link = oc->ob.link;
-    ctx->cloud_table_min_cells = oc->ob.min_cells;
-    ctx->cloud_obj_label = std::move(label);
-    ctx->cloud_obj_flag = std::move(object);
-    ctx->cloud_obj_count = n_objects;
-    if (oc->n_objects_out) *oc->n_objects_out = n_objects;
-    if (oc->n_objects_matched_out) *oc->n_objects_matched_out = have_table ? n_accepted : -1;
-    return OMDS_OK;
+    const unsigned per_camera = std::max(DEPTH_MAX_BLOCKS / (unsigned)n_cams, 1u);
+    return dim3((unsigned)std::min<long long>((most + CLOUD_NT - 1) / CLOUD_NT, per_camera), (unsigned)n_cams);
 }
 
 }  // namespace
 
-extern "C" {
-
-int omds_point_cloud_spheres(const omds_cloud_spec* spec, const float* xyz, int64_t n_points, float* xyzr_out, int32_t cap,
-                             int32_t* count_out) {
-    return cloud_spheres_host(spec, xyz, n_points, xyzr_out, cap, count_out, &g_create_err);
+void omds_launch_cloud_count(hipStream_t s, const float* xyz, long long P, const CloudGrid& g, unsigned* count) {
+    if (P > 0) hipLaunchKernelGGL(k_cloud_count, point_blocks(P), dim3(CLOUD_NT), 0, s, xyz, P, g, count);
+}
+void omds_launch_cloud_count(hipStream_t s, const float* xyz, long long P, const CloudGrid& g, uint4* rec) {
+    if (P > 0) hipLaunchKernelGGL(k_cloud_count_rec, point_blocks(P), dim3(CLOUD_NT), 0, s, xyz, P, g, rec);
+}
+void omds_launch_cloud_count(hipStream_t s, DepthTable tab, int n_cams, const CloudGrid& g, unsigned* count) {
+    const dim3 grid = depth_blocks(tab, n_cams);
+    hipLaunchKernelGGL(k_depth_count, grid, dim3(CLOUD_NT), 0, s, tab, g, count);
+}
+void omds_launch_cloud_count(hipStream_t s, DepthTable tab, int n_cams, const CloudGrid& g, uint4* rec) {
+    const dim3 grid = depth_blocks(tab, n_cams);
+    hipLaunchKernelGGL(k_depth_count_rec, grid, dim3(CLOUD_NT), 0, s, tab, g, rec);
 }
 
-int omds_point_cloud_flow(const omds_cloud_spec* spec, const omds_cloud_track_spec* track, const float* xyz_prev, int64_t n_prev,
-                          const float* xyz_now, int64_t n_now, float* xyzr_out, float* vel_out, int32_t cap, int32_t* count_out,
-                          int32_t* matched_out) {
-    return cloud_flow_host(spec, track, xyz_prev, n_prev, xyz_now, n_now, xyzr_out, vel_out, cap, count_out, matched_out, &g_create_err);
+void omds_launch_cloud_compact_cells(hipStream_t s, const unsigned* count, const CloudGrid& g, float4* out, unsigned* sums) {
+    compact(s, CellSrc{count, g, out}, g.n_cells, g.max_spheres, sums);
+}
+void omds_launch_cloud_compact_cells(hipStream_t s, const uint4* rec, const CloudGrid& g, float4* out, int* cell, unsigned* sums) {
+    compact(s, RecSrc{rec, g, out, cell}, g.n_cells, g.max_spheres, sums);
+}
+void omds_launch_cloud_compact_kept(hipStream_t s, const float* d, const float4* cand, const int* candCell, int n, float margin, int cap,
+                                    float4* out, int* cell, unsigned* sums) {
+    const KeepSrc keep{d, cand, margin, out};
+    if (candCell) compact(s, KeepCellSrc{keep, candCell, cell}, n, cap, sums);
+    else compact(s, keep, n, cap, sums);
+}
+void omds_launch_cloud_compact_roots(hipStream_t s, const int* root, const int* cells, const unsigned long long* acc, int n, int cap,
+                                     CloudComp* table, int* compOf, unsigned* sums) {
+    compact(s, RootSrc{root, cells, acc, table, compOf}, n, cap, sums);
 }
 
-int omds_set_obstacles_from_cloud(omds_ctx* ctx, const omds_cloud_spec* spec, const float* xyz, int64_t n_points, int xyz_on_device,
-                                  const float* q_now, int32_t* n_spheres_out, int32_t* n_occupied_out) {
-    if (!ctx) return OMDS_ERR_INVALID_ARG;
-    CloudGrid g;
-    if (int rc = cloud_resolve_spec(spec, &g, &ctx->err)) return rc;
-    return scene_from_cloud(ctx, "omds_set_obstacles_from_cloud", spec, g, nullptr, PointSource{xyz, n_points, xyz_on_device, nullptr}, q_now,
-                            n_spheres_out, n_occupied_out, nullptr);
+void omds_launch_cloud_flow(hipStream_t s, const CloudGrid& g, const CloudTrack& tr, const uint4* now, const uint4* prev, const int* cells, int n,
+                            float4* vel) {
+    hipLaunchKernelGGL(k_cloud_flow, dim3((n + FLOW_WAVES - 1) / FLOW_WAVES), dim3(CLOUD_NT), 0, s, g, tr, now, prev, cells, n, vel);
 }
 
-int omds_set_obstacles_from_cloud_tracked(omds_ctx* ctx, const omds_cloud_spec* spec, const omds_cloud_track_spec* track, const float* xyz,
-                                          int64_t n_points, int xyz_on_device, const float* q_now, int32_t* n_spheres_out,
-                                          int32_t* n_occupied_out, int32_t* n_matched_out) {
-    if (!ctx) return OMDS_ERR_INVALID_ARG;
-    CloudGrid g;
-    CloudTrack tr;
-    if (int rc = cloud_resolve_spec(spec, &g, &ctx->err)) return rc;
-    if (int rc = cloud_resolve_track(track, &tr, &ctx->err)) return rc;
-    return scene_from_cloud(ctx, "omds_set_obstacles_from_cloud_tracked", spec, g, &tr, PointSource{xyz, n_points, xyz_on_device, nullptr}, q_now,
-                            n_spheres_out, n_occupied_out, n_matched_out);
+void omds_launch_cloud_components(hipStream_t s, const CloudGrid& g, int link, const uint4* now, const int* cells, int n, int* slot, int* parent,
+                                  int* label, unsigned long long* acc) {
+    const int blocks = (n + CLOUD_NT - 1) / CLOUD_NT;
+    (void)hipMemsetAsync(slot, 0xff, cloud_padded_cells(g) * 4, s);   // -1.  (A failure is the caller's hipGetLastError, like a launch's)
+    (void)hipMemsetAsync(acc, 0, (size_t)n * OBJ_ACC * 8, s);
+    hipLaunchKernelGGL(k_obj_slot, dim3(blocks), dim3(CLOUD_NT), 0, s, cells, n, slot, parent);
+    hipLaunchKernelGGL(k_obj_union, dim3(blocks), dim3(CLOUD_NT), 0, s, g, link, cells, n, (const int*)slot, parent);
+    hipLaunchKernelGGL(k_obj_flatten, dim3(blocks), dim3(CLOUD_NT), 0, s, cells, n, parent, label);
+    hipLaunchKernelGGL(k_obj_sums, dim3((n + SUMS_NT - 1) / SUMS_NT), dim3(SUMS_NT), 0, s, g, now, cells, (const int*)parent, n, acc);
 }
 
-int omds_point_cloud_object_flow(const omds_cloud_spec* spec, const omds_cloud_track_spec* track, const omds_cloud_object_spec* obj,
-                                 const float* xyz_prev, int64_t n_prev, const uint8_t* keep_prev, const float* xyz_now, int64_t n_now,
-                                 const uint8_t* keep_now, float* xyzr_out, float* vel_out, int32_t* label_out, int32_t* object_out, int32_t cap,
-                                 int32_t* count_out, int32_t* matched_out, int32_t* n_objects_out, int32_t* n_objects_matched_out) {
-    return cloud_objects_host(spec, track, obj, xyz_prev, n_prev, keep_prev, xyz_now, n_now, keep_now, xyzr_out, vel_out, label_out, object_out,
-                              cap, count_out, matched_out, n_objects_out, n_objects_matched_out, &g_create_err);
+void omds_launch_cloud_match(hipStream_t s, const CloudGrid& g, const CloudTrack& tr, const CloudObjects& ob, const CloudComp* now, int n_now,
+                             const CloudComp* prev, int n_prev, float4* objVel) {
+    hipLaunchKernelGGL(k_obj_match, dim3((n_now + FLOW_WAVES - 1) / FLOW_WAVES), dim3(CLOUD_NT), 0, s, g, tr, ob, now, n_now, prev, n_prev, objVel);
 }
 
-int omds_set_obstacles_from_cloud_objects(omds_ctx* ctx, const omds_cloud_spec* spec, const omds_cloud_track_spec* track,
-                                          const omds_cloud_object_spec* obj, const float* xyz, int64_t n_points, int xyz_on_device,
-                                          const float* q_now, int32_t* n_spheres_out, int32_t* n_occupied_out, int32_t* n_matched_out,
-                                          int32_t* n_objects_out, int32_t* n_objects_matched_out) {
-    if (!ctx) return OMDS_ERR_INVALID_ARG;
-    CloudGrid g;
-    CloudTrack tr;
-    ObjectsCall oc{{0, 0u}, n_objects_out, n_objects_matched_out};
-    if (int rc = cloud_resolve_spec(spec, &g, &ctx->err)) return rc;
-    if (int rc = cloud_resolve_track(track, &tr, &ctx->err)) return rc;
-    if (int rc = cloud_resolve_objects(obj, &oc.ob, &ctx->err)) return rc;
-    return scene_from_cloud(ctx, "omds_set_obstacles_from_cloud_objects", spec, g, &tr, PointSource{xyz, n_points, xyz_on_device, nullptr}, q_now,
-                            n_spheres_out, n_occupied_out, n_matched_out, &oc);
+void omds_launch_cloud_apply(hipStream_t s, const int* root, const int* compOf, const float4* objVel, int n, float4* vel, int* object) {
+    hipLaunchKernelGGL(k_obj_apply, dim3((n + CLOUD_NT - 1) / CLOUD_NT), dim3(CLOUD_NT), 0, s, root, compOf, objVel, n, vel, object);
 }
-
-int omds_depth_points(const omds_depth_camera* cam, const void* image, float* xyz_out, int64_t cap_points, int64_t* n_valid_out) {
-    return depth_points_host(cam, image, xyz_out, cap_points, n_valid_out, &g_create_err);
-}
-
-int omds_set_obstacles_from_depth(omds_ctx* ctx, const omds_cloud_spec* spec, const omds_cloud_track_spec* track,
-                                  const omds_cloud_object_spec* obj, const omds_depth_camera* cams, const void* const* images, int32_t n_cams,
-                                  int images_on_device, const float* q_now, int32_t* n_spheres_out, int32_t* n_occupied_out,
-                                  int32_t* n_matched_out, int32_t* n_objects_out, int32_t* n_objects_matched_out) {
-    if (!ctx) return OMDS_ERR_INVALID_ARG;
-    const char* me = "omds_set_obstacles_from_depth";
-    CloudGrid g;
-    CloudTrack tr;
-    ObjectsCall oc{{0, 0u}, n_objects_out, n_objects_matched_out};
-    if (int rc = cloud_resolve_spec(spec, &g, &ctx->err)) return rc;
-    REQUIRE(!obj || track, OMDS_ERR_INVALID_ARG, std::string(me) + ": an object spec needs a track spec (the objects route is a tracked one)");
-    if (track)
-        if (int rc = cloud_resolve_track(track, &tr, &ctx->err)) return rc;
-    if (obj)
-        if (int rc = cloud_resolve_objects(obj, &oc.ob, &ctx->err)) return rc;
-    REQUIRE(n_cams >= 1 && n_cams <= OMDS_DEPTH_MAX_CAMERAS && cams && images, OMDS_ERR_INVALID_ARG,
-            std::string(me) + ": need 1 <= n_cams <= 8 and non-null cams, images [n_cams]");
-    DepthSource depth;
-    depth.images = images;
-    depth.n_cams = n_cams;
-    depth.on_device = images_on_device;
-    int64_t visited = 0;
-    for (int i = 0; i < n_cams; ++i) {
-        if (int rc = depth_resolve_camera(cams + i, &depth.cam[i], &ctx->err)) return rc;
-        REQUIRE(images[i], OMDS_ERR_INVALID_ARG, std::string(me) + ": a null image");
-        visited += depth_visited(depth.cam[i]);   // each < 2^62 / 8: no overflow
-    }
-    REQUIRE(visited <= OMDS_CLOUD_MAX_POINTS, OMDS_ERR_INVALID_ARG, std::string(me) + ": more than 16 777 216 visited pixels in all");
-    return scene_from_cloud(ctx, me, spec, g, track ? &tr : nullptr, PointSource{nullptr, 0, 0, &depth}, q_now, n_spheres_out, n_occupied_out,
-                            n_matched_out, obj ? &oc : nullptr);
-}
-
-int omds_get_cloud_objects(omds_ctx* ctx, int32_t* label, int32_t* object, int32_t* n_objects_out) {
-    if (!ctx) return OMDS_ERR_INVALID_ARG;
-    REQUIRE(ctx->n_obs > 0 && ctx->cloud_obj_label.size() == (size_t)ctx->n_obs, OMDS_ERR_NOT_INITIALISED,
-            "omds_get_cloud_objects: the scene in force was not installed by omds_set_obstacles_from_cloud_objects");
-    if (label) std::memcpy(label, ctx->cloud_obj_label.data(), (size_t)ctx->n_obs * 4);
-    if (object) std::memcpy(object, ctx->cloud_obj_flag.data(), (size_t)ctx->n_obs * 4);
-    if (n_objects_out) *n_objects_out = ctx->cloud_obj_count;
-    return OMDS_OK;
-}
-
-int omds_cloud_track_reset(omds_ctx* ctx) {
-    if (!ctx) return OMDS_ERR_INVALID_ARG;
-    ctx->cloud_have_frame = false;
-    ctx->cloud_have_table = false;
-    return OMDS_OK;
-}
-
-}  // extern "C"

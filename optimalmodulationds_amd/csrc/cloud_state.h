@@ -1,0 +1,76 @@
+// What a context keeps for the scene from a point cloud or from depth images (scene_cloud.hip): omds_ctx::cloud.  Included by
+// omds_internal.h behind DevBuf.  Every buffer is allocated at the first call of the route that needs it and grown with the spec.
+#pragma once
+#include <cstring>
+
+#include "point_cloud_objects_def.h"
+
+// Two buffers, one of which holds what the last successful call stored while the other is written; commit() swaps them
+template <class T>
+struct Flip {
+    DevBuf<T> buf[2];
+    int stored = 0;
+    DevBuf<T>& kept() { return buf[stored]; }
+    DevBuf<T>& next() { return buf[1 - stored]; }
+    void commit() { stored = 1 - stored; }
+};
+
+// the grid of the stored frame; the floats are compared bitwise
+struct CloudFrameKey {
+    bool have = false;            // a frame is stored (a tracked call succeeded since creation / omds_cloud_track_reset)
+    float origin[3] = {0.f, 0.f, 0.f}, voxel = 0.f;
+    int dims[3] = {0, 0, 0};
+    unsigned min_points = 0;
+    bool same(const CloudGrid& g) const {
+        return have && std::memcmp(origin, &g.ox, 12) == 0 && std::memcmp(&voxel, &g.voxel, 4) == 0 && dims[0] == g.dx && dims[1] == g.dy &&
+               dims[2] == g.dz && min_points == g.min_points;
+    }
+    void set(const CloudGrid& g) {
+        have = true;
+        std::memcpy(origin, &g.ox, 12);
+        voxel = g.voxel;
+        dims[0] = g.dx; dims[1] = g.dy; dims[2] = g.dz;
+        min_points = g.min_points;
+    }
+};
+
+// the object spec the stored component table was built under, and its rows
+struct CloudTableKey {
+    bool have = false;            // a table is stored: an objects call succeeded and no reset / plain tracked call came after it
+    int link = 0;
+    unsigned min_cells = 0;
+    int n = 0;                    // components in the stored table
+    bool same(const CloudObjects& ob) const { return have && link == ob.link && min_cells == ob.min_cells; }
+    void set(const CloudObjects& ob, int n_comp) { have = true; link = ob.link; min_cells = ob.min_cells; n = n_comp; }
+};
+
+struct CloudState {
+    DevBuf<float> xyz;                // [P][3] the points of a host cloud
+    DevBuf<unsigned char> depthImg;   // the host images of a depth call, one after the other, each from a multiple of 16 bytes on
+    DevBuf<unsigned> count;           // [cells rounded up to whole compaction blocks] points per cell
+    DevBuf<unsigned> sums;            // [compaction blocks + 1] occupied items per block, scanned in place; the last word: their total
+    DevBuf<float4> cand;              // [max_spheres] candidate spheres in cell order
+    DevBuf<float4> kept;              // [max_spheres] ... and those the self-filter keeps
+    // ... tracked (omds_set_obstacles_from_cloud_tracked): per cell the record (n, s_x, s_y, s_z) of point_cloud_flow_def.h.  One of
+    // the two buffers holds the stored frame, the other is counted into; a successful tracked call makes its own the stored one
+    Flip<uint4> rec;                  // [cells rounded up to whole compaction blocks] each, allocated when first counted into
+    CloudFrameKey frame;
+    DevBuf<int> candCell;             // [max_spheres] cell index of every candidate, in step with cand
+    DevBuf<int> keptCell;             // [max_spheres] ... and of every kept one
+    DevBuf<float4> vel;               // [max_spheres] velocity of every final sphere; .w: 1 where its window was not empty (k_cloud_flow)
+    // ... objects (omds_set_obstacles_from_cloud_objects): the components of the final list, point_cloud_objects_def.h
+    DevBuf<int> slot;                 // [cells rounded up to whole compaction blocks] list index of every final sphere's cell, else -1
+    DevBuf<int> parent;               // [max_spheres] the union-find; after the flatten the root (list index) of every sphere
+    DevBuf<int> label;                // [max_spheres] label (smallest cell of the component) of every sphere
+    DevBuf<int> object;               // [max_spheres] 1 where the sphere's component is an accepted object
+    DevBuf<int> compOf;               // [max_spheres] at a root: the row of its component in the table
+    DevBuf<unsigned long long> acc;   // [max_spheres][5] at a root: m, N, Q_x, Q_y, Q_z of its component
+    Flip<CloudComp> table;            // [max_spheres] each, ascending labels; one of the two is the stored table
+    CloudTableKey tab;
+    DevBuf<float4> objVel;            // [max_spheres] per component: the object's velocity; .w: 0 no object, 1 object, 2 accepted
+    std::vector<int32_t> obj_label, obj_flag;   // [n_obs] of the scene in force when the objects call installed it, else empty
+    int obj_count = 0;                // its objects
+
+    void forget_tracking() { frame.have = false; tab.have = false; }          // omds_cloud_track_reset
+    void forget_labels() { obj_label.clear(); obj_flag.clear(); }             // another setter installed the scene in force
+};

@@ -245,7 +245,7 @@ int reserve_obstacle_capacity(omds_ctx* ctx, int n_obs) {
 }
 
 // What omds_set_obstacles does with a checked list xyzr [n_obs][4] in host memory (n_obs >= n_closest): omds_set_obstacles_from_cloud
-// ends in the same body (point_cloud.hip)
+// ends in the same body (scene_cloud.hip)
 int install_obstacles(omds_ctx* ctx, const float* xyzr, int n_obs) {
     CK(hipSetDevice(ctx->dev));
     int rc;
@@ -255,8 +255,7 @@ int install_obstacles(omds_ctx* ctx, const float* xyzr, int n_obs) {
     ctx->n_obs = n_obs;
     ctx->scr.scene_changed(xyzr, n_obs);
     ctx->obs_now.assign(xyzr, xyzr + (size_t)n_obs * 4);
-    ctx->cloud_obj_label.clear();   // the labels of a scene belong to the objects call that installed it (point_cloud.hip puts them back)
-    ctx->cloud_obj_flag.clear();
+    ctx->cloud.forget_labels();   // the labels of a scene belong to the objects call that installed it (scene_cloud.hip puts them back)
     if (ctx->have_mlp && !ctx->wide.on) {
         omds_launch_obstacle_features(ctx->stream, ctx->mlp, ctx->d_obs, n_obs, ctx->d_Fp, ctx->d_radius, ctx->d_FpH, ctx->cfg.max_obs);
         CK(hipGetLastError());

@@ -312,6 +312,8 @@ struct ScreenHost {
     void reset_stats() { rows = 0.0; steps = 0.0; audit_rows = 0.0; }   // omds_prof_reset
 };
 
+#include "cloud_state.h"
+
 struct omds_ctx {
     omds_config cfg{};
     omds_params prm{};
@@ -375,41 +377,7 @@ struct omds_ctx {
     bool frame_on = false;
     float frame_max = 1.f;       // clamp of the approach speed (the unit speed rollout velocities are normalised to)
     DevBuf<float> d_frameOut;    // [n_traj][1 + n] omds_approach_rate: rate, then qo (allocated at the first call)
-    // the scene from a point cloud (point_cloud.hip; all allocated at the first omds_set_obstacles_from_cloud, grown with the spec)
-    DevBuf<float> d_cloudXyz;         // [P][3] the points of a host cloud
-    DevBuf<unsigned char> d_depthImg; // the host images of a depth call, one after the other, each from a multiple of 16 bytes on
-    DevBuf<unsigned> d_cloudCount;    // [cells rounded up to whole compaction blocks] points per cell
-    DevBuf<unsigned> d_cloudSums;     // [compaction blocks + 1] occupied items per block, scanned in place; the last word: their total
-    DevBuf<float4> d_cloudCand;       // [max_spheres] candidate spheres in cell order
-    DevBuf<float4> d_cloudKept;       // [max_spheres] ... and those the self-filter keeps
-    // ... tracked (omds_set_obstacles_from_cloud_tracked): per cell the record (n, s_x, s_y, s_z) of point_cloud_flow_def.h.  One of
-    // the two buffers holds the stored frame, the other is counted into; a successful tracked call makes its own the stored one
-    DevBuf<uint4> d_cloudRec[2];      // [cells rounded up to whole compaction blocks] each, allocated when first counted into
-    int cloud_stored = 0;             // which of the two is the stored frame
-    bool cloud_have_frame = false;    // a frame is stored (a tracked call succeeded since creation / omds_cloud_track_reset)
-    float cloud_frame_origin[3] = {0.f, 0.f, 0.f}, cloud_frame_voxel = 0.f;   // the grid of the stored frame, compared bitwise
-    int cloud_frame_dims[3] = {0, 0, 0};
-    unsigned cloud_frame_min_points = 0;
-    DevBuf<int> d_cloudCandCell;      // [max_spheres] cell index of every candidate, in step with d_cloudCand
-    DevBuf<int> d_cloudKeptCell;      // [max_spheres] ... and of every kept one
-    DevBuf<float4> d_cloudVel;        // [max_spheres] velocity of every final sphere; .w: 1 where its window was not empty (k_cloud_flow)
-    // ... objects (omds_set_obstacles_from_cloud_objects): the components of the final list, point_cloud_objects_def.h.  The component
-    // tables are 40-byte CloudComp records (kept as bytes here: the type is point_cloud.hip's); one of the two is the stored table
-    DevBuf<int> d_cloudSlot;          // [cells rounded up to whole compaction blocks] list index of every final sphere's cell, else -1
-    DevBuf<int> d_cloudParent;        // [max_spheres] the union-find; after the flatten the root (list index) of every sphere
-    DevBuf<int> d_cloudLabel;         // [max_spheres] label (smallest cell of the component) of every sphere
-    DevBuf<int> d_cloudObject;        // [max_spheres] 1 where the sphere's component is an accepted object
-    DevBuf<int> d_cloudCompOf;        // [max_spheres] at a root: the row of its component in the table
-    DevBuf<unsigned long long> d_cloudAcc;   // [max_spheres][5] at a root: m, N, Q_x, Q_y, Q_z of its component
-    DevBuf<unsigned char> d_cloudTable[2];   // [max_spheres] CloudComp each, ascending labels
-    DevBuf<float4> d_cloudObjVel;     // [max_spheres] per component: the object's velocity; .w: 0 no object, 1 object, 2 accepted
-    int cloud_table_stored = 0;       // which of the two tables is the stored one
-    bool cloud_have_table = false;    // a table is stored: an objects call succeeded and no reset / plain tracked call came after it
-    int cloud_table_n = 0;            // components in the stored table
-    int cloud_table_link = 0;         // the object spec it was built under
-    unsigned cloud_table_min_cells = 0;
-    std::vector<int32_t> cloud_obj_label, cloud_obj_flag;   // [n_obs] of the scene in force when the objects call installed it, else empty
-    int cloud_obj_count = 0;          // its objects
+    CloudState cloud;            // the scene from a point cloud or from depth images (cloud_state.h; scene_cloud.hip)
     // DS / cost
     bool have_ds = false, have_cost = false;
     float qf[OMDS_MAX_DOF] = {0};

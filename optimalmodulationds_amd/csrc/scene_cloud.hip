@@ -1,0 +1,435 @@
+// The scene from a depth point cloud or from depth images (omds.h: omds_set_obstacles_from_cloud[_tracked|_objects],
+// omds_set_obstacles_from_depth), as host stages over the launchers of cloud_kernels.h; the state between calls is omds_ctx::cloud
+// (cloud_state.h).  One body, scene_from_cloud, for every route.  A route is a choice of three things (CloudCall): tracked or not,
+// objects or not (objects need tracked), and where the points come from.
+//   plain   : count per cell -> ordered compaction of the occupied cells -> the robot self-filter as ONE fp32 pass-1 launch over one
+//             state with the candidates as its obstacle rows, and a second compaction of those it keeps -> the final list to the host
+//             (a few thousand x 16 bytes) and in through install_obstacles, the body of omds_set_obstacles (context.hip)
+//   tracked : the same steps in the same order on the record buffer that is NOT the stored frame, the cell indices carried through both
+//             compactions, then the velocities of the final list against the stored frame, in through omds_set_obstacle_motion
+//   objects : the tracked one with the components of the final list, into the table that is NOT the stored one, their match against
+//             the stored table and the object velocities over the spheres', between the velocities and the install
+//   depth   : any of the three with the images of up to eight cameras as the point source: no point is ever written
+#include "capi_internal.h"
+#include "cloud_kernels.h"
+
+namespace {
+
+// Where the points of a call come from: an array xyz [n_points][3] (host or device), or the depth images of up to eight cameras
+struct DepthSource {
+    DepthCam cam[OMDS_DEPTH_MAX_CAMERAS];   // behind their checks
+    const void* const* images;
+    int n_cams;
+    int on_device;
+};
+struct PointSource {
+    const float* xyz;
+    int64_t n_points;
+    int xyz_on_device;
+    const DepthSource* depth;   // != nullptr: the images, and the three fields above are unused
+};
+
+// the five counts a call may return; a route leaves those of the routes above it alone
+struct CloudOuts {
+    int32_t *n_spheres, *n_occupied, *n_matched, *n_objects, *n_objects_matched;
+};
+
+// One call behind the checks of its specs: the route and the caller's pointers
+struct CloudCall {
+    const char* who;
+    const omds_cloud_spec* spec;
+    CloudGrid g;
+    bool tracked, objects;
+    CloudTrack tr;      // while tracked
+    CloudObjects ob;    // while objects
+    PointSource src;
+    const float* q_now;
+    CloudOuts out;
+};
+
+// What the stages of one call hand on
+struct CloudWork {
+    const float* d_xyz = nullptr;   // the points on the device, or
+    DepthTable depth;               // ... the camera table of a depth call
+    int occupied = 0;               // cells with min_points points and more
+    const float4* d_list = nullptr; // the final list so far: the candidates, behind the self-filter those it keeps
+    const int* d_cell = nullptr;    // tracked: the cell of every sphere of d_list, else nullptr
+    int n_list = 0, n_final = 0;    // spheres of d_list; of the installed scene (filled up to n_closest)
+    bool have_prev = false, have_table = false;   // there is a stored frame on this grid; and a stored table under this object spec
+    int n_comp = 0, matched = 0;
+    std::vector<float> vel4, obj_vel;             // [n_list][4] of cloud.vel, [n_comp][4] of cloud.objVel
+    std::vector<int32_t> label, object;           // [n_final]
+};
+
+// spec, then track when the route is tracked, then obj when it has objects: each behind its checks, in that order
+int resolve_call(omds_ctx* ctx, const char* who, const omds_cloud_spec* spec, bool tracked, const omds_cloud_track_spec* track, bool objects,
+                 const omds_cloud_object_spec* obj, CloudCall* c) {
+    *c = CloudCall{who, spec, CloudGrid{}, tracked, objects};
+    if (int rc = cloud_resolve_spec(spec, &c->g, &ctx->err)) return rc;
+    REQUIRE(!objects || tracked, OMDS_ERR_INVALID_ARG, std::string(who) + ": an object spec needs a track spec (the objects route is a tracked one)");
+    if (tracked)
+        if (int rc = cloud_resolve_track(track, &c->tr, &ctx->err)) return rc;
+    if (objects)
+        if (int rc = cloud_resolve_objects(obj, &c->ob, &ctx->err)) return rc;
+    return OMDS_OK;
+}
+
+// ---- reserve: one function per group of buffers.  A group that has a buffer too small synchronises the stream first (enqueued work
+// may still read what a reallocation frees); reserve() leaves a buffer that is large enough alone
+int reserve_base(omds_ctx* ctx, const CloudCall& c) {
+    CloudState& s = ctx->cloud;
+    const size_t cells = c.tracked ? 0 : cloud_padded_cells(c.g), m = (size_t)c.g.max_spheres;   // a tracked call counts into records
+    if (s.count.count() < cells || s.sums.count() < (size_t)CLOUD_MAX_BLOCKS + 1 || s.cand.count() < m || s.kept.count() < m)
+        CK(hipStreamSynchronize(ctx->stream));
+    CK(s.count.reserve(cells));
+    CK(s.sums.reserve((size_t)CLOUD_MAX_BLOCKS + 1));
+    CK(s.cand.reserve(m));
+    CK(s.kept.reserve(m));
+    return OMDS_OK;
+}
+int reserve_tracked(omds_ctx* ctx, const CloudCall& c) {
+    CloudState& s = ctx->cloud;
+    const size_t cells = cloud_padded_cells(c.g), m = (size_t)c.g.max_spheres;
+    if (s.rec.next().count() < cells || s.candCell.count() < m || s.keptCell.count() < m || s.vel.count() < m)
+        CK(hipStreamSynchronize(ctx->stream));
+    CK(s.rec.next().reserve(cells));   // counted into; the stored frame is the other one
+    CK(s.candCell.reserve(m));
+    CK(s.keptCell.reserve(m));
+    CK(s.vel.reserve(m));
+    return OMDS_OK;
+}
+int reserve_objects(omds_ctx* ctx, const CloudCall& c) {
+    CloudState& s = ctx->cloud;
+    const size_t cells = cloud_padded_cells(c.g), m = (size_t)c.g.max_spheres;
+    if (s.slot.count() < cells || s.parent.count() < m || s.label.count() < m || s.object.count() < m || s.compOf.count() < m ||
+        s.acc.count() < m * OBJ_ACC || s.objVel.count() < m || s.table.next().count() < m)
+        CK(hipStreamSynchronize(ctx->stream));
+    CK(s.slot.reserve(cells));
+    CK(s.parent.reserve(m));
+    CK(s.label.reserve(m));
+    CK(s.object.reserve(m));
+    CK(s.compOf.reserve(m));
+    CK(s.acc.reserve(m * OBJ_ACC));
+    CK(s.objVel.reserve(m));
+    CK(s.table.next().reserve(m));     // written; the stored table is the other one
+    return OMDS_OK;
+}
+
+// ---- stage the points: the caller's device memory as it is, host memory through a staging buffer of the context (a host array by
+// one asynchronous copy, host images by one each)
+int stage_points(omds_ctx* ctx, const CloudCall& c, CloudWork& w) {
+    CloudState& s = ctx->cloud;
+    if (!c.src.depth) {
+        const size_t n = (size_t)c.src.n_points;
+        w.d_xyz = c.src.xyz;
+        if (c.src.xyz_on_device || n == 0) return OMDS_OK;
+        if (s.xyz.count() < n * 3) {
+            CK(hipStreamSynchronize(ctx->stream));
+            CK(s.xyz.alloc(n * 3));
+        }
+        CK(hipMemcpyAsync(s.xyz, c.src.xyz, n * 12, hipMemcpyHostToDevice, ctx->stream));
+        w.d_xyz = s.xyz;
+        return OMDS_OK;
+    }
+    const DepthSource& src = *c.src.depth;
+    size_t offset[OMDS_DEPTH_MAX_CAMERAS], bytes[OMDS_DEPTH_MAX_CAMERAS], total = 0;
+    for (int i = 0; i < src.n_cams; ++i) {
+        bytes[i] = (size_t)depth_extent(src.cam[i]) * (src.cam[i].format == OMDS_DEPTH_U16 ? 2 : 4);
+        offset[i] = total;
+        total += (bytes[i] + 15) & ~(size_t)15;
+    }
+    if (!src.on_device && s.depthImg.count() < total) {
+        CK(hipStreamSynchronize(ctx->stream));
+        CK(s.depthImg.alloc(total));
+    }
+    std::memset(static_cast<void*>(&w.depth), 0, sizeof(w.depth));
+    for (int i = 0; i < src.n_cams; ++i) {
+        DepthCamDev& d = w.depth.cam[i];
+        d.c = src.cam[i];
+        d.image = src.images[i];
+        if (src.on_device) continue;
+        CK(hipMemcpyAsync(s.depthImg.get() + offset[i], src.images[i], bytes[i], hipMemcpyHostToDevice, ctx->stream));
+        d.image = s.depthImg.get() + offset[i];
+    }
+    return OMDS_OK;
+}
+
+// the number of items the compaction of n items that was just enqueued kept.  Synchronises.
+int compaction_total(omds_ctx* ctx, int n, int* total_out) {
+    *total_out = 0;
+    if (n <= 0) return OMDS_OK;
+    CK(hipGetLastError());
+    unsigned total = 0;
+    CK(hipMemcpyAsync(&total, ctx->cloud.sums + cloud_compaction_blocks(n), 4, hipMemcpyDeviceToHost, ctx->stream));
+    CK(hipStreamSynchronize(ctx->stream));
+    *total_out = (int)total;
+    return OMDS_OK;
+}
+
+// ---- count and compact the cells: the candidates in cell order, their cell indices when tracked, and w.occupied
+template <class T>   // unsigned: counts, uint4: records
+void enqueue_count(omds_ctx* ctx, const CloudCall& c, const CloudWork& w, T* into) {
+    if (c.src.depth) omds_launch_cloud_count(ctx->stream, w.depth, c.src.depth->n_cams, c.g, into);
+    else omds_launch_cloud_count(ctx->stream, w.d_xyz, (long long)c.src.n_points, c.g, into);
+}
+int count_cells(omds_ctx* ctx, const CloudCall& c, CloudWork& w) {
+    CloudState& s = ctx->cloud;
+    const size_t cells = cloud_padded_cells(c.g);
+    if (c.tracked) {
+        uint4* rec = s.rec.next();
+        CK(hipMemsetAsync(rec, 0, cells * 16, ctx->stream));
+        enqueue_count(ctx, c, w, rec);
+        omds_launch_cloud_compact_cells(ctx->stream, rec, c.g, s.cand, s.candCell, s.sums);
+        w.d_cell = s.candCell;
+    } else {
+        CK(hipMemsetAsync(s.count, 0, cells * 4, ctx->stream));
+        enqueue_count(ctx, c, w, s.count.get());
+        omds_launch_cloud_compact_cells(ctx->stream, s.count, c.g, s.cand, s.sums);
+    }
+    w.d_list = s.cand;
+    return compaction_total(ctx, c.g.n_cells, &w.occupied);
+}
+
+// ---- self-filter: the candidates become the obstacle rows of one state.  From here on the tables of the old scene are overwritten:
+// the context holds no scene, and no horizon of one, until install_scene has put the new one in
+int self_filter(omds_ctx* ctx, const CloudCall& c, CloudWork& w) {
+    CloudState& s = ctx->cloud;
+    const int n = ctx->cfg.n_dof, occupied = w.occupied;
+    if (int rc = reserve_obstacle_capacity(ctx, occupied)) return rc;
+    ctx->n_obs = 0;
+    clear_obstacle_horizon(ctx);
+    CK(hipMemcpyAsync(ctx->d_qcur, c.q_now, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    omds_launch_rollout_features(ctx->stream, ctx->mlp, ctx->d_qcur, 1, 1, ctx->d_Fq);
+    omds_launch_obstacle_features(ctx->stream, ctx->mlp, reinterpret_cast<const float*>(w.d_list), occupied, ctx->d_Fp, ctx->d_radius);
+    omds_launch_pass1(ctx->stream, ctx->mlp, ctx->d_Fq, ctx->d_Fp, ctx->d_radius, occupied, 1, ctx->prm.ignored_links, ctx->d_Dmin);
+    CK(hipGetLastError());
+    omds_launch_cloud_compact_kept(ctx->stream, ctx->d_Dmin, w.d_list, w.d_cell, occupied, c.spec->self_margin, c.g.max_spheres, s.kept, s.keptCell,
+                                   s.sums);
+    w.d_list = s.kept;
+    if (w.d_cell) w.d_cell = s.keptCell;
+    return compaction_total(ctx, occupied, &w.n_list);
+}
+
+// ---- sphere velocities: the final list against the stored frame, if there is one on this grid
+int sphere_velocities(omds_ctx* ctx, const CloudCall& c, CloudWork& w) {
+    CloudState& s = ctx->cloud;
+    w.have_prev = s.frame.same(c.g);
+    if (!w.have_prev || w.n_list == 0) return OMDS_OK;
+    w.vel4.resize((size_t)w.n_list * 4);
+    omds_launch_cloud_flow(ctx->stream, c.g, c.tr, s.rec.next(), s.rec.kept(), w.d_cell, w.n_list, s.vel);
+    CK(hipGetLastError());
+    return OMDS_OK;
+}
+
+// ---- objects: the components of the final list, their match against the stored table and the velocities of the accepted objects
+int object_velocities(omds_ctx* ctx, const CloudCall& c, CloudWork& w) {
+    CloudState& s = ctx->cloud;
+    const int n = w.n_list;
+    w.have_table = w.have_prev && s.tab.same(c.ob);
+    w.label.assign((size_t)w.n_final, -1);   // padding spheres: label -1, no object
+    w.object.assign((size_t)w.n_final, 0);
+    if (n == 0) return OMDS_OK;
+    omds_launch_cloud_components(ctx->stream, c.g, c.ob.link, s.rec.next(), w.d_cell, n, s.slot, s.parent, s.label, s.acc);
+    CK(hipGetLastError());
+    omds_launch_cloud_compact_roots(ctx->stream, s.parent, w.d_cell, s.acc, n, c.g.max_spheres, s.table.next(), s.compOf, s.sums);
+    if (int rc = compaction_total(ctx, n, &w.n_comp)) return rc;
+    omds_launch_cloud_match(ctx->stream, c.g, c.tr, c.ob, s.table.next(), w.n_comp, s.table.kept(), w.have_table ? s.tab.n : 0, s.objVel);
+    if (w.have_table) {
+        omds_launch_cloud_apply(ctx->stream, s.parent, s.compOf, s.objVel, n, s.vel, s.object);
+        CK(hipMemcpyAsync(w.object.data(), s.object, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    CK(hipGetLastError());
+    w.obj_vel.resize((size_t)w.n_comp * 4);
+    CK(hipMemcpyAsync(w.obj_vel.data(), s.objVel, (size_t)w.n_comp * 16, hipMemcpyDeviceToHost, ctx->stream));
+    CK(hipMemcpyAsync(w.label.data(), s.label, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    return OMDS_OK;
+}
+
+// ---- install: the list to the host, filled up to n_closest with the spec's pad sphere, and in as omds_set_obstacles puts a list in;
+// then the velocities, if any sphere moves: a scene whose every sphere stands still keeps the cleared horizon, and the propagate that
+// follows is the static one
+int install_scene(omds_ctx* ctx, const CloudCall& c, CloudWork& w) {
+    const int n_list = w.n_list, n_final = w.n_final;
+    if (!w.vel4.empty()) CK(hipMemcpyAsync(w.vel4.data(), ctx->cloud.vel, (size_t)n_list * 16, hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<float> list((size_t)n_final * 4);
+    if (n_list > 0) CK(hipMemcpyAsync(list.data(), w.d_list, (size_t)n_list * 16, hipMemcpyDeviceToHost, ctx->stream));
+    CK(hipStreamSynchronize(ctx->stream));
+    for (int i = n_list; i < n_final; ++i) std::memcpy(&list[(size_t)i * 4], c.spec->pad, 16);
+    if (int rc = install_obstacles(ctx, list.data(), n_final)) return rc;
+    if (c.out.n_spheres) *c.out.n_spheres = n_list;
+    if (w.vel4.empty()) return OMDS_OK;
+    std::vector<float> vel((size_t)n_final * 3, 0.f);   // padding spheres stand still
+    bool moving = false;
+    for (size_t i = 0; i * 4 < w.vel4.size(); ++i) {
+        for (int k = 0; k < 3; ++k) {
+            vel[i * 3 + k] = w.vel4[i * 4 + k];
+            moving |= w.vel4[i * 4 + k] != 0.f;
+        }
+        w.matched += w.vel4[i * 4 + 3] != 0.f;
+    }
+    return moving ? omds_set_obstacle_motion(ctx, vel.data()) : OMDS_OK;
+}
+
+// ---- commit, behind everything that can fail: what was counted is the stored frame now ...
+void commit_frame(omds_ctx* ctx, const CloudCall& c, const CloudWork& w) {
+    CloudState& s = ctx->cloud;
+    s.rec.commit();
+    s.frame.set(c.g);
+    s.tab.have = false;   // a plain tracked call stores its records and no table: the next objects call has nothing to match
+    if (c.out.n_matched) *c.out.n_matched = w.have_prev ? (int32_t)w.matched : -1;
+}
+// ... and what was written the stored table, with the labels of the scene in force
+void commit_objects(omds_ctx* ctx, const CloudCall& c, CloudWork& w) {
+    CloudState& s = ctx->cloud;
+    int32_t n_objects = 0, n_accepted = 0;
+    for (int i = 0; i < w.n_comp; ++i) {
+        n_objects += w.obj_vel[(size_t)i * 4 + 3] >= 1.f;
+        n_accepted += w.obj_vel[(size_t)i * 4 + 3] == 2.f;
+    }
+    s.table.commit();
+    s.tab.set(c.ob, w.n_comp);
+    s.obj_label = std::move(w.label);
+    s.obj_flag = std::move(w.object);
+    s.obj_count = n_objects;
+    if (c.out.n_objects) *c.out.n_objects = n_objects;
+    if (c.out.n_objects_matched) *c.out.n_objects_matched = w.have_table ? n_accepted : -1;
+}
+
+int scene_from_cloud(omds_ctx* ctx, const CloudCall& c) {
+    const std::string me(c.who);
+    int rc;
+    REQUIRE(c.src.depth || (c.src.n_points >= 0 && c.src.n_points <= OMDS_CLOUD_MAX_POINTS && (c.src.n_points == 0 || c.src.xyz)),
+            OMDS_ERR_INVALID_ARG, me + ": need 0 <= n_points <= 16 777 216 and a non-null xyz [P,3]");
+    if (c.q_now) {
+        REQUIRE(ctx->have_mlp, OMDS_ERR_NOT_INITIALISED, me + ": the self-filter needs the distance network (omds_set_mlp)");
+        REQUIRE(!ctx->wide.on, OMDS_ERR_UNSUPPORTED, me + ": no self-filter on networks wider than 256 (no obstacle tables)");
+    }
+    CK(hipSetDevice(ctx->dev));
+    CloudWork w;
+    if ((rc = reserve_base(ctx, c))) return rc;
+    if (c.tracked && (rc = reserve_tracked(ctx, c))) return rc;
+    if (c.objects && (rc = reserve_objects(ctx, c))) return rc;
+    if ((rc = stage_points(ctx, c, w))) return rc;
+    if ((rc = count_cells(ctx, c, w))) return rc;
+    if (c.out.n_occupied) *c.out.n_occupied = w.occupied;
+    REQUIRE(w.occupied <= c.g.max_spheres, OMDS_ERR_INVALID_ARG,
+            me + ": more occupied cells than max_spheres (n_occupied_out holds their number); the scene is unchanged");
+    w.n_list = w.occupied;
+    if (c.q_now && w.occupied > 0 && (rc = self_filter(ctx, c, w))) return rc;
+    w.n_final = std::max(w.n_list, ctx->cfg.n_closest);
+    if (c.tracked && (rc = sphere_velocities(ctx, c, w))) return rc;
+    if (c.objects && (rc = object_velocities(ctx, c, w))) return rc;
+    if ((rc = install_scene(ctx, c, w))) return rc;
+    if (c.tracked) commit_frame(ctx, c, w);
+    if (c.objects) commit_objects(ctx, c, w);
+    return OMDS_OK;
+}
+
+// a cloud entry point behind resolve_call: the caller's array as the point source
+int scene_from_points(omds_ctx* ctx, CloudCall& c, const float* xyz, int64_t n_points, int xyz_on_device, const float* q_now, const CloudOuts& out) {
+    c.src = PointSource{xyz, n_points, xyz_on_device, nullptr};
+    c.q_now = q_now;
+    c.out = out;
+    return scene_from_cloud(ctx, c);
+}
+
+}  // namespace
+
+extern "C" {
+
+int omds_point_cloud_spheres(const omds_cloud_spec* spec, const float* xyz, int64_t n_points, float* xyzr_out, int32_t cap,
+                             int32_t* count_out) {
+    return cloud_spheres_host(spec, xyz, n_points, xyzr_out, cap, count_out, &g_create_err);
+}
+
+int omds_point_cloud_flow(const omds_cloud_spec* spec, const omds_cloud_track_spec* track, const float* xyz_prev, int64_t n_prev,
+                          const float* xyz_now, int64_t n_now, float* xyzr_out, float* vel_out, int32_t cap, int32_t* count_out,
+                          int32_t* matched_out) {
+    return cloud_flow_host(spec, track, xyz_prev, n_prev, xyz_now, n_now, xyzr_out, vel_out, cap, count_out, matched_out, &g_create_err);
+}
+
+int omds_point_cloud_object_flow(const omds_cloud_spec* spec, const omds_cloud_track_spec* track, const omds_cloud_object_spec* obj,
+                                 const float* xyz_prev, int64_t n_prev, const uint8_t* keep_prev, const float* xyz_now, int64_t n_now,
+                                 const uint8_t* keep_now, float* xyzr_out, float* vel_out, int32_t* label_out, int32_t* object_out, int32_t cap,
+                                 int32_t* count_out, int32_t* matched_out, int32_t* n_objects_out, int32_t* n_objects_matched_out) {
+    return cloud_objects_host(spec, track, obj, xyz_prev, n_prev, keep_prev, xyz_now, n_now, keep_now, xyzr_out, vel_out, label_out, object_out,
+                              cap, count_out, matched_out, n_objects_out, n_objects_matched_out, &g_create_err);
+}
+
+int omds_depth_points(const omds_depth_camera* cam, const void* image, float* xyz_out, int64_t cap_points, int64_t* n_valid_out) {
+    return depth_points_host(cam, image, xyz_out, cap_points, n_valid_out, &g_create_err);
+}
+
+int omds_set_obstacles_from_cloud(omds_ctx* ctx, const omds_cloud_spec* spec, const float* xyz, int64_t n_points, int xyz_on_device,
+                                  const float* q_now, int32_t* n_spheres_out, int32_t* n_occupied_out) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    CloudCall c;
+    if (int rc = resolve_call(ctx, "omds_set_obstacles_from_cloud", spec, false, nullptr, false, nullptr, &c)) return rc;
+    return scene_from_points(ctx, c, xyz, n_points, xyz_on_device, q_now, {n_spheres_out, n_occupied_out, nullptr, nullptr, nullptr});
+}
+
+int omds_set_obstacles_from_cloud_tracked(omds_ctx* ctx, const omds_cloud_spec* spec, const omds_cloud_track_spec* track, const float* xyz,
+                                          int64_t n_points, int xyz_on_device, const float* q_now, int32_t* n_spheres_out,
+                                          int32_t* n_occupied_out, int32_t* n_matched_out) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    CloudCall c;
+    if (int rc = resolve_call(ctx, "omds_set_obstacles_from_cloud_tracked", spec, true, track, false, nullptr, &c)) return rc;
+    return scene_from_points(ctx, c, xyz, n_points, xyz_on_device, q_now, {n_spheres_out, n_occupied_out, n_matched_out, nullptr, nullptr});
+}
+
+int omds_set_obstacles_from_cloud_objects(omds_ctx* ctx, const omds_cloud_spec* spec, const omds_cloud_track_spec* track,
+                                          const omds_cloud_object_spec* obj, const float* xyz, int64_t n_points, int xyz_on_device,
+                                          const float* q_now, int32_t* n_spheres_out, int32_t* n_occupied_out, int32_t* n_matched_out,
+                                          int32_t* n_objects_out, int32_t* n_objects_matched_out) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    CloudCall c;
+    if (int rc = resolve_call(ctx, "omds_set_obstacles_from_cloud_objects", spec, true, track, true, obj, &c)) return rc;
+    return scene_from_points(ctx, c, xyz, n_points, xyz_on_device, q_now,
+                             {n_spheres_out, n_occupied_out, n_matched_out, n_objects_out, n_objects_matched_out});
+}
+
+int omds_set_obstacles_from_depth(omds_ctx* ctx, const omds_cloud_spec* spec, const omds_cloud_track_spec* track,
+                                  const omds_cloud_object_spec* obj, const omds_depth_camera* cams, const void* const* images, int32_t n_cams,
+                                  int images_on_device, const float* q_now, int32_t* n_spheres_out, int32_t* n_occupied_out,
+                                  int32_t* n_matched_out, int32_t* n_objects_out, int32_t* n_objects_matched_out) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    const char* me = "omds_set_obstacles_from_depth";
+    CloudCall c;
+    if (int rc = resolve_call(ctx, me, spec, track != nullptr, track, obj != nullptr, obj, &c)) return rc;
+    REQUIRE(n_cams >= 1 && n_cams <= OMDS_DEPTH_MAX_CAMERAS && cams && images, OMDS_ERR_INVALID_ARG,
+            std::string(me) + ": need 1 <= n_cams <= 8 and non-null cams, images [n_cams]");
+    DepthSource depth;
+    depth.images = images;
+    depth.n_cams = n_cams;
+    depth.on_device = images_on_device;
+    int64_t visited = 0;
+    for (int i = 0; i < n_cams; ++i) {
+        if (int rc = depth_resolve_camera(cams + i, &depth.cam[i], &ctx->err)) return rc;
+        REQUIRE(images[i], OMDS_ERR_INVALID_ARG, std::string(me) + ": a null image");
+        visited += depth_visited(depth.cam[i]);   // each < 2^62 / 8: no overflow
+    }
+    REQUIRE(visited <= OMDS_CLOUD_MAX_POINTS, OMDS_ERR_INVALID_ARG, std::string(me) + ": more than 16 777 216 visited pixels in all");
+    c.src = PointSource{nullptr, 0, 0, &depth};
+    c.q_now = q_now;
+    c.out = CloudOuts{n_spheres_out, n_occupied_out, n_matched_out, n_objects_out, n_objects_matched_out};
+    return scene_from_cloud(ctx, c);
+}
+
+int omds_get_cloud_objects(omds_ctx* ctx, int32_t* label, int32_t* object, int32_t* n_objects_out) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    const CloudState& s = ctx->cloud;
+    REQUIRE(ctx->n_obs > 0 && s.obj_label.size() == (size_t)ctx->n_obs, OMDS_ERR_NOT_INITIALISED,
+            "omds_get_cloud_objects: the scene in force was not installed by omds_set_obstacles_from_cloud_objects");
+    if (label) std::memcpy(label, s.obj_label.data(), (size_t)ctx->n_obs * 4);
+    if (object) std::memcpy(object, s.obj_flag.data(), (size_t)ctx->n_obs * 4);
+    if (n_objects_out) *n_objects_out = s.obj_count;
+    return OMDS_OK;
+}
+
+int omds_cloud_track_reset(omds_ctx* ctx) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    ctx->cloud.forget_tracking();
+    return OMDS_OK;
+}
+
+}  // extern "C"

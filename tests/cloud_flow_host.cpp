@@ -8,9 +8,7 @@
 // OUT: per case: int32 rc, int32 count, int32 matched, int32 written, float xyzr[written][4], float vel[written][3]
 //      (written = count when rc == 0, else 0)
 // Every array is allocated at exactly the size passed, so that a write or read past one is the sanitizer's to report.
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
+#include "host_io.h"
 
 #include "../optimalmodulationds_amd/csrc/point_cloud_flow_def.h"
 
@@ -21,30 +19,19 @@ extern "C" int omds_point_cloud_flow(const omds_cloud_spec* spec, const omds_clo
     return cloud_flow_host(spec, track, xyz_prev, n_prev, xyz_now, n_now, xyzr_out, vel_out, cap, count_out, matched_out, &err);
 }
 
-template <typename T>
-static bool get(FILE* f, T* v, size_t n = 1) { return fread(v, sizeof(T), n, f) == n; }
-
-static float* exactly(size_t bytes) { return static_cast<float*>(malloc(bytes + 1)); }
-
 int main(int argc, char** argv) {
-    if (argc != 3) return 2;
-    FILE* in = fopen(argv[1], "rb");
-    FILE* out = fopen(argv[2], "wb");
-    if (!in || !out) return 2;
-    int32_t n_cases = 0;
-    if (!get(in, &n_cases)) return 2;
-    for (int32_t c = 0; c < n_cases; ++c) {
+    return run_cases(argc, argv, "cloud_flow_host", [](FILE* in, FILE* out) {
         omds_cloud_spec spec;
         omds_cloud_track_spec track;
         int64_t n_prev = 0, n_now = 0;
         int32_t cap = 0, null_mask = 0;
-        if (!get(in, &spec) || !get(in, &track) || !get(in, &n_prev) || !get(in, &n_now) || !get(in, &cap) || !get(in, &null_mask)) return 2;
+        if (!get(in, &spec) || !get(in, &track) || !get(in, &n_prev) || !get(in, &n_now) || !get(in, &cap) || !get(in, &null_mask)) return false;
         const size_t sp = n_prev > 0 ? (size_t)n_prev : 0, sn = n_now > 0 ? (size_t)n_now : 0, sc = cap > 0 ? (size_t)cap : 0;
-        float* prev = exactly(sp * 12);
-        float* now = exactly(sn * 12);
-        float* xyzr = exactly(sc * 16);
-        float* vel = exactly(sc * 12);
-        if ((sp && !get(in, prev, sp * 3)) || (sn && !get(in, now, sn * 3))) return 2;
+        float* prev = exactly<float>(sp * 3);
+        float* now = exactly<float>(sn * 3);
+        float* xyzr = exactly<float>(sc * 4);
+        float* vel = exactly<float>(sc * 3);
+        if ((sp && !get(in, prev, sp * 3)) || (sn && !get(in, now, sn * 3))) return false;
         int32_t count = -1, matched = -1;
         const int rc = omds_point_cloud_flow((null_mask & 1) ? nullptr : &spec, (null_mask & 2) ? nullptr : &track, (null_mask & 4) ? nullptr : prev,
                                              n_prev, (null_mask & 8) ? nullptr : now, n_now, (null_mask & 16) ? nullptr : xyzr,
@@ -60,9 +47,6 @@ int main(int argc, char** argv) {
         free(now);
         free(xyzr);
         free(vel);
-    }
-    fclose(in);
-    fclose(out);
-    puts("cloud_flow_host: done");
-    return 0;
+        return true;
+    });
 }

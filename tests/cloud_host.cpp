@@ -7,9 +7,7 @@
 // OUT: per case: int32 rc, int32 count, int32 written, float xyzr[written][4]   (written = count when rc == 0, else 0)
 // The output array is allocated at exactly cap spheres and the points at exactly n_points, so that a write or read past either is
 // the sanitizer's to report.
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
+#include "host_io.h"
 
 #include "../optimalmodulationds_amd/csrc/point_cloud_def.h"
 
@@ -19,25 +17,16 @@ extern "C" int omds_point_cloud_spheres(const omds_cloud_spec* spec, const float
     return cloud_spheres_host(spec, xyz, n_points, xyzr_out, cap, count_out, &err);
 }
 
-template <typename T>
-static bool get(FILE* f, T* v, size_t n = 1) { return fread(v, sizeof(T), n, f) == n; }
-
 int main(int argc, char** argv) {
-    if (argc != 3) return 2;
-    FILE* in = fopen(argv[1], "rb");
-    FILE* out = fopen(argv[2], "wb");
-    if (!in || !out) return 2;
-    int32_t n_cases = 0;
-    if (!get(in, &n_cases)) return 2;
-    for (int32_t c = 0; c < n_cases; ++c) {
+    return run_cases(argc, argv, "cloud_host", [](FILE* in, FILE* out) {
         omds_cloud_spec spec;
         int64_t n_points = 0;
         int32_t cap = 0, null_mask = 0;
-        if (!get(in, &spec) || !get(in, &n_points) || !get(in, &cap) || !get(in, &null_mask)) return 2;
+        if (!get(in, &spec) || !get(in, &n_points) || !get(in, &cap) || !get(in, &null_mask)) return false;
         const size_t stored = n_points > 0 ? (size_t)n_points : 0;
-        float* xyz = static_cast<float*>(malloc(stored * 12 + 1));
-        float* xyzr = static_cast<float*>(malloc((cap > 0 ? (size_t)cap : 0) * 16 + 1));
-        if (stored && !get(in, xyz, stored * 3)) return 2;
+        float* xyz = exactly<float>(stored * 3);
+        float* xyzr = exactly<float>((cap > 0 ? (size_t)cap : 0) * 4);
+        if (stored && !get(in, xyz, stored * 3)) return false;
         int32_t count = -1;
         const int rc = omds_point_cloud_spheres((null_mask & 1) ? nullptr : &spec, (null_mask & 2) ? nullptr : xyz, n_points,
                                                 (null_mask & 4) ? nullptr : xyzr, cap, (null_mask & 8) ? nullptr : &count);
@@ -46,9 +35,6 @@ int main(int argc, char** argv) {
         if (head[2] > 0) fwrite(xyzr, 16, (size_t)head[2], out);
         free(xyz);
         free(xyzr);
-    }
-    fclose(in);
-    fclose(out);
-    puts("cloud_host: done");
-    return 0;
+        return true;
+    });
 }

@@ -9,27 +9,12 @@
 // OUT: per case: int32 rc, count, matched, n_objects, n_objects_matched, written, float xyzr[written][4], float vel[written][3],
 //      int32 label[written], int32 object[written]   (written = kept cells when rc == 0, else 0)
 // Every array is allocated at exactly the size passed, so that a write or read past one is the sanitizer's to report.
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
+#include "host_io.h"
 
 #include "../optimalmodulationds_amd/csrc/point_cloud_objects_def.h"
 
-template <typename T>
-static bool get(FILE* f, T* v, size_t n = 1) { return fread(v, sizeof(T), n, f) == n; }
-
-// count elements and not a byte more (one element for an empty array, so that the pointer is not null)
-template <typename T>
-static T* exactly(size_t count) { return static_cast<T*>(malloc((count ? count : 1) * sizeof(T))); }
-
 int main(int argc, char** argv) {
-    if (argc != 3) return 2;
-    FILE* in = fopen(argv[1], "rb");
-    FILE* out = fopen(argv[2], "wb");
-    if (!in || !out) return 2;
-    int32_t n_cases = 0;
-    if (!get(in, &n_cases)) return 2;
-    for (int32_t c = 0; c < n_cases; ++c) {
+    return run_cases(argc, argv, "cloud_objects_host", [](FILE* in, FILE* out) {
         omds_cloud_spec spec;
         omds_cloud_track_spec track;
         omds_cloud_object_spec obj;
@@ -37,7 +22,7 @@ int main(int argc, char** argv) {
         int32_t cap = 0, mask = 0;
         if (!get(in, &spec) || !get(in, &track) || !get(in, &obj) || !get(in, &n_prev) || !get(in, &n_now) || !get(in, &n_kp) || !get(in, &n_kn) ||
             !get(in, &cap) || !get(in, &mask))
-            return 2;
+            return false;
         const size_t sp = n_prev > 0 ? (size_t)n_prev : 0, sn = n_now > 0 ? (size_t)n_now : 0, sc = cap > 0 ? (size_t)cap : 0;
         float* prev = exactly<float>(sp * 3);
         float* now = exactly<float>(sn * 3);
@@ -48,7 +33,7 @@ int main(int argc, char** argv) {
         int32_t* label = exactly<int32_t>(sc);
         int32_t* object = exactly<int32_t>(sc);
         if ((sp && !get(in, prev, sp * 3)) || (sn && !get(in, now, sn * 3)) || (kp && !get(in, kp, (size_t)n_kp)) || (kn && !get(in, kn, (size_t)n_kn)))
-            return 2;
+            return false;
         int32_t count = -1, matched = -1, n_objects = -1, n_accepted = -1;
         auto nul = [&](int bit) { return (mask >> bit & 1) != 0; };
         std::string err;
@@ -73,9 +58,6 @@ int main(int argc, char** argv) {
             fwrite(object, 4, (size_t)written, out);
         }
         free(prev); free(now); free(kp); free(kn); free(xyzr); free(vel); free(label); free(object);
-    }
-    fclose(in);
-    fclose(out);
-    puts("cloud_objects_host: done");
-    return 0;
+        return true;
+    });
 }

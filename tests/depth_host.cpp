@@ -7,8 +7,7 @@
 // OUT: per case: int32 rc, int64 n_valid, int64 written, float xyz[written][3]   (written = cap_points when rc == 0, else 0)
 // The image is allocated at exactly n_elems elements and the output at exactly cap_points points, so that a read or write past
 // either is the sanitizer's to report.
-#include <cstdio>
-#include <cstdlib>
+#include "host_io.h"
 
 #include "../optimalmodulationds_amd/csrc/depth_def.h"
 
@@ -17,27 +16,18 @@ extern "C" int omds_depth_points(const omds_depth_camera* cam, const void* image
     return depth_points_host(cam, image, xyz_out, cap_points, n_valid_out, &err);
 }
 
-template <typename T>
-static bool get(FILE* f, T* v, size_t n = 1) { return fread(v, sizeof(T), n, f) == n; }
-
 int main(int argc, char** argv) {
-    if (argc != 3) return 2;
-    FILE* in = fopen(argv[1], "rb");
-    FILE* out = fopen(argv[2], "wb");
-    if (!in || !out) return 2;
-    int32_t n_cases = 0;
-    if (!get(in, &n_cases)) return 2;
-    for (int32_t c = 0; c < n_cases; ++c) {
+    return run_cases(argc, argv, "depth_host", [](FILE* in, FILE* out) {
         omds_depth_camera cam;
         int64_t cap = 0, n_elems = 0;
         int32_t null_mask = 0, elem_bytes = 0;
-        if (!get(in, &cam) || !get(in, &cap) || !get(in, &null_mask) || !get(in, &elem_bytes) || !get(in, &n_elems)) return 2;
-        if (n_elems < 0 || elem_bytes < 1 || elem_bytes > 4) return 2;
-        const size_t image_bytes = (size_t)n_elems * (size_t)elem_bytes, out_bytes = (cap > 0 ? (size_t)cap : 0) * 12;
-        unsigned char* image = static_cast<unsigned char*>(malloc(image_bytes ? image_bytes : 1));   // malloc: aligned for either element
-        float* xyz = static_cast<float*>(malloc(out_bytes ? out_bytes : 1));
-        if (!image || !xyz) return 2;
-        if (image_bytes && !get(in, image, image_bytes)) return 2;
+        if (!get(in, &cam) || !get(in, &cap) || !get(in, &null_mask) || !get(in, &elem_bytes) || !get(in, &n_elems)) return false;
+        if (n_elems < 0 || elem_bytes < 1 || elem_bytes > 4) return false;
+        const size_t image_bytes = (size_t)n_elems * (size_t)elem_bytes;
+        unsigned char* image = exactly<unsigned char>(image_bytes);   // malloc: aligned for either element
+        float* xyz = exactly<float>((cap > 0 ? (size_t)cap : 0) * 3);
+        if (!image || !xyz) return false;
+        if (image_bytes && !get(in, image, image_bytes)) return false;
         int64_t n_valid = -1;
         const int rc = omds_depth_points((null_mask & 1) ? nullptr : &cam, (null_mask & 2) ? nullptr : image, (null_mask & 4) ? nullptr : xyz, cap,
                                          (null_mask & 8) ? nullptr : &n_valid);
@@ -48,9 +38,6 @@ int main(int argc, char** argv) {
         if (written > 0) fwrite(xyz, 12, (size_t)written, out);
         free(image);
         free(xyz);
-    }
-    fclose(in);
-    fclose(out);
-    puts("depth_host: done");
-    return 0;
+        return true;
+    });
 }

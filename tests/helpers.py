@@ -113,6 +113,23 @@ def log_plain_bar(family, what, against, counts):
         pass
 
 
+def sanitized_host_program(name, tmp_path):
+    """tests/<name>.cpp, a stand-alone program (its own main) around a header the library and its kernels include, built by g++ under
+    AddressSanitizer + UBSan into ``tmp_path``.  The runtimes are linked into the program: no demand on what is loaded before it.
+    Fails the test when there is no g++.  Returns the path of the executable."""
+    import shutil
+    import subprocess
+
+    import pytest
+    if shutil.which("g++") is None:
+        pytest.fail(f"g++ is needed to build tests/{name}.cpp")
+    exe = str(tmp_path / name)
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-static-libasan", "-static-libubsan", "-fno-omit-frame-pointer", "-I", os.path.join(ROOT, "include"),
+                    os.path.join(ROOT, "tests", name + ".cpp"), "-o", exe], check=True)
+    return exe
+
+
 _TRIG_HOST = None
 
 

@@ -13,8 +13,6 @@ float32 centre must lie within 1 float32 ulp of it.
 The same edge cases also go through a stand-alone build of the definition under AddressSanitizer + UBSan (tests/cloud_host.cpp, its
 buffers allocated at exactly the sizes passed), whose output must be the library's bit for bit."""
 import ctypes as C
-import os
-import shutil
 import struct
 import subprocess
 
@@ -22,7 +20,7 @@ import numpy as np
 import pytest
 
 from cloud_cases import F32, cells_of, edge_points, lattice_cloud, restate, spec_of
-from helpers import ROOT
+from helpers import sanitized_host_program
 
 ERR_INVALID_ARG = 1
 
@@ -165,13 +163,7 @@ def _pack_case(spec, pts, cap, null_mask=0):
 def test_definition_under_address_and_ub_sanitizer(lib, tmp_path):
     """tests/cloud_host.cpp, a stand-alone program around the header both the library and its kernels include, built with
     -fsanitize=address,undefined and run on the edge cases above: a clean exit, and the library's bits."""
-    if shutil.which("g++") is None:
-        pytest.fail("g++ is needed to build tests/cloud_host.cpp")
-    exe = str(tmp_path / "cloud_host")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-static-libasan", "-static-libubsan",       # the runtimes inside the program: no demand on what is loaded before it
-                    "-fno-omit-frame-pointer", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cloud_host.cpp"), "-o", exe],
-                   check=True)
+    exe = sanitized_host_program("cloud_host", tmp_path)
     cases = []
     for dims in ((6, 5, 4), (37, 29, 1)):
         for mp in (1, 3):

@@ -5,8 +5,6 @@ count exactly, and the sphere list that of omds_point_cloud_spheres on the secon
 The same cases also go through a stand-alone build of the definition under AddressSanitizer + UBSan (tests/cloud_flow_host.cpp, its
 buffers allocated at exactly the sizes passed), whose output must be the library's bit for bit."""
 import ctypes as C
-import os
-import shutil
 import struct
 import subprocess
 
@@ -16,7 +14,7 @@ import pytest
 import cloud_flow_cases as cases
 from cloud_cases import F32, spec_of
 from cloud_flow_cases import restate_flow, track_of
-from helpers import ROOT
+from helpers import sanitized_host_program
 
 ERR_INVALID_ARG = 1
 SENTINEL = F32(-7)
@@ -271,13 +269,7 @@ def _pack_case(spec, track, prev, now, cap, null_mask=0):
 def test_definition_under_address_and_ub_sanitizer(lib, tmp_path):
     """tests/cloud_flow_host.cpp, a stand-alone program around the header both the library and its kernels include, built with
     -fsanitize=address,undefined and run on the cases above: a clean exit, and the library's bits."""
-    if shutil.which("g++") is None:
-        pytest.fail("g++ is needed to build tests/cloud_flow_host.cpp")
-    exe = str(tmp_path / "cloud_flow_host")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-static-libasan", "-static-libubsan",       # the runtimes inside the program: no demand on what is loaded before it
-                    "-fno-omit-frame-pointer", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cloud_flow_host.cpp"),
-                    "-o", exe], check=True)
+    exe = sanitized_host_program("cloud_flow_host", tmp_path)
     none = np.zeros((0, 3), F32)
     bad = np.array([[np.nan, 0.1, 0.1], [0.1, np.inf, 0.1], [0.1, 0.1, -np.inf], [1e30, 0.1, 0.1], [-1e30, 0.1, 0.1]], F32)
     todo = []

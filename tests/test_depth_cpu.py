@@ -16,8 +16,6 @@ The same edge cases also go through a stand-alone build of the definition under 
 image allocated at exactly (H - 1) pitch + W elements and the output at exactly the visited count), whose output must be the
 library's bit for bit."""
 import ctypes as C
-import os
-import shutil
 import struct
 import subprocess
 
@@ -27,7 +25,7 @@ import pytest
 import depth_cases as dc
 from cloud_cases import cells_of, restate as cloud_restate, spec_of
 from depth_cases import F32, F64, FLT, U16
-from helpers import ROOT
+from helpers import sanitized_host_program
 
 ERR_INVALID_ARG = 1
 SENTINEL = F32(-7.0)
@@ -258,13 +256,7 @@ def test_definition_under_address_and_ub_sanitizer(lib, tmp_path):
     """tests/depth_host.cpp, a stand-alone program around the header both the library and its kernels include, built with
     -fsanitize=address,undefined: the image at exactly (H - 1) pitch + W elements, the output at exactly the visited count; a clean
     exit, and the library's bits."""
-    if shutil.which("g++") is None:
-        pytest.fail("g++ is needed to build tests/depth_host.cpp")
-    exe = str(tmp_path / "depth_host")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-static-libasan", "-static-libubsan",       # the runtimes inside the program: no demand on what is loaded before it
-                    "-fno-omit-frame-pointer", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "depth_host.cpp"), "-o", exe],
-                   check=True)
+    exe = sanitized_host_program("depth_host", tmp_path)
     cases = []
     for step in (1, 2, 3, 20):
         for pitch in (0, 16):

@@ -1,4 +1,4 @@
-"""The scene from a depth point cloud on the device (include/omds.h: omds_set_obstacles_from_cloud, csrc/point_cloud.hip) against
+"""The scene from a depth point cloud on the device (include/omds.h: omds_set_obstacles_from_cloud, csrc/cloud_kernels.hip) against
 its host definition (omds_point_cloud_spheres, checked on its own in tests/test_cloud_cpu.py) and, for the self-filter, against the
 CPU oracle's pass-1 distances -- all bit for bit: the voxel arithmetic is one source for host and kernels, the compaction is ordered
 by construction, and the device's pass-1 values are the oracle's bits.
