@@ -415,6 +415,65 @@ OMDS_API int omds_set_obstacles_from_depth(omds_ctx* ctx, const omds_cloud_spec*
                                            int32_t n_cams, int images_on_device, const float* q_now, int32_t* n_spheres_out,
                                            int32_t* n_occupied_out, int32_t* n_matched_out, int32_t* n_objects_out,
                                            int32_t* n_objects_matched_out);
+/* THE OBSTACLE FOCUS (new work).  A sensed scene has thousands of spheres; everything behind pass 1 uses the n_closest nearest per
+ * (rollout, step).  A focus call evaluates the distance of every sphere of the scene at ONE joint state, selects the near ones and
+ * installs them as the scene in force, on the device; the full scene (the MASTER) is kept, so that the next call selects from it again
+ * -- at every planner iteration, without a new camera frame.  Additive: without a focus call every entry point keeps its launches and
+ * its bits.
+ *   omds_obstacle_focus_select : host only (no context, no GPU), the DEFINITION.  All fp32, every operation named one rounding.
+ *       REACH: with vel == NULL r_o = d_o; else s2 = fmaf(v_z, v_z, fmaf(v_y, v_y, v_x * v_x)), speed = sqrtf(s2),
+ *       r_o = fmaf(-speed, lookahead, d_o).  A NaN r_o counts as -inf (such a sphere is always kept, like the self-filter's "a NaN
+ *       distance keeps the sphere").  ORDER: by (r_o, o) -- the fp32 comparison decides, -0 equals +0, ties go to the smaller index.
+ *       THRESHOLD: t = the reach of the n_closest-th sphere of that order.  PASSING: with margin == +inf every sphere passes; else
+ *       bar = t + margin and a sphere passes when r_o <= bar; P of them (>= n_closest).  KEPT: M = min(P, max_keep), or P without a cap;
+ *       the first M spheres of the order, listed in idx_out in ASCENDING INDEX; *kept_out = M, *passed_out = P.  A function of the
+ *       values only.  OMDS_ERR_INVALID_ARG before anything is written: a bad spec, n_obs < n_closest, n_closest < 1, null pointers
+ *       (vel may be NULL).  cap < M: OMDS_ERR_INVALID_ARG with both counts set and idx_out untouched.
+ *   omds_focus_obstacles : THE MASTER is the scene in force with its motion velocities (horizon mode 1) when no focus is in force, else
+ *       the one already stored; it lives on the device (spheres, velocities) and on the host (with the labels and flags of an objects
+ *       scene).  d_o is pass 1's value at (q, master sphere o): the fp32 pass-1 kernel over one state with the master as its obstacle
+ *       rows, bit for bit the mindist row of omds_dist_grad(q, 1) on the master.  It needs a network (else OMDS_ERR_NOT_INITIALISED) of
+ *       hidden width <= 256 (else OMDS_ERR_UNSUPPORTED) and a scene (else OMDS_ERR_NOT_INITIALISED) of at most 2^30 spheres;
+ *       planar-point networks take v_z = 0, as the horizon does.  The selection: integer keys that carry the order of the reaches
+ *       (NaN as -inf, -0 as +0), an exact k-th-smallest run twice on them (n_closest, then M) by ONE workgroup of 1024 lanes -- a
+ *       radix select over 256-bin LDS histograms, the keys read from global memory in every pass, so any count takes the same path --
+ *       and the ordered compaction of the cloud calls, which emits the kept spheres in ascending index with their master indices and
+ *       velocities; the group of keys equal to the last kept one is cut by index.  Integer adds only: nothing depends on scheduling.
+ *       Only the M kept items travel to the host.  The kept list goes in through the body of omds_set_obstacles (buffers, the cleared
+ *       horizon, the screening notification as for any setter; the capacity stays at the master's); the kept velocities through the
+ *       body of omds_set_obstacle_motion when the master is in mode 1 AND some kept component is non-zero, else the horizon stays
+ *       cleared and the propagate that follows is the static one (the cloud calls' rule).  The labels and flags of an objects master
+ *       are gathered: omds_get_cloud_objects, omds_get_obstacles and omds_get_obstacle_motion answer for the scene in force
+ *       (*n_objects_out stays the master's).  kept_out, passed_out: M and P (NULL = skip).  Synchronous.
+ *       THE CONTRACT: after a successful call every entry point behaves as on a context that was given omds_set_obstacles(master[idx])
+ *       and, where motion is installed, omds_set_obstacle_motion(vel[idx]) -- propagate on every route, omds_dist_grad, cost, update,
+ *       bit for bit.  The call says NOTHING about whether that equals the propagate on the full master: equality holds exactly when no
+ *       dropped sphere would have entered a (rollout, step)'s n_closest; margin is the caller's bet on how much a distance can change
+ *       over (H - 1) dt of joint motion (lookahead: the seconds a moving sphere is given to approach); it is measured by
+ *       tools/studies/obstacle_focus_cost.py (EXPERIMENTS R22), not proven.
+ *       STATE: any scene setter (omds_set_obstacles, the three cloud calls, the depth call) ends the focus; its scene is the next
+ *       master.  While a focus is in force omds_set_obstacle_motion and omds_set_obstacle_horizon return OMDS_ERR_UNSUPPORTED for every
+ *       argument, NULL included (they would address the subset and be lost at the next focus; omds_clear_obstacle_focus first).  A
+ *       master with an explicit horizon table (mode 2): OMDS_ERR_UNSUPPORTED, the scene stays as it was.  The stored cloud frame, the
+ *       component table and the moving-frame preference are untouched.  Argument refusals leave the scene, the master and the focus
+ *       exactly as they were; a HIP failure later in the call leaves the context without a scene.
+ *       SCREENING: a focus that changes the sphere count discards a measured calibration, as any setter does (a calibration every
+ *       planner iteration costs more than the focus saves): a caller who screens sets a fixed eps > 0 (omds_set_screening).
+ *   omds_get_obstacle_focus : the master index of every sphere in force into idx [n_obs] (NULL: no copy; untouched without a focus);
+ *       *n_master_out = the master's size, 0 when no focus is in force; *n_kept_out = n_obs.  Host state, no GPU work.
+ *   omds_clear_obstacle_focus : puts the master and its motion (and labels) back; a no-op without a focus.                            */
+typedef struct {
+    float   margin;     /* >= 0, or +inf (every sphere passes); NaN or negative: OMDS_ERR_INVALID_ARG        */
+    float   lookahead;  /* seconds a moving sphere is given to approach; >= 0 and finite                    */
+    int32_t max_keep;   /* at most this many spheres; < 1: no cap; else >= n_closest, or OMDS_ERR_INVALID_ARG */
+} omds_obstacle_focus_spec;
+OMDS_API int omds_obstacle_focus_select(const omds_obstacle_focus_spec* spec, const float* d, const float* vel /* [O,3] or NULL */,
+                                        int n_obs, int n_closest, int32_t* idx_out /* [cap] */, int32_t cap, int32_t* kept_out,
+                                        int32_t* passed_out);
+OMDS_API int omds_focus_obstacles(omds_ctx* ctx, const omds_obstacle_focus_spec* spec, const float* q /* [n_dof] */, int32_t* kept_out,
+                                  int32_t* passed_out);
+OMDS_API int omds_get_obstacle_focus(omds_ctx* ctx, int32_t* idx /* [n_obs] or NULL */, int32_t* n_master_out, int32_t* n_kept_out);
+OMDS_API int omds_clear_obstacle_focus(omds_ctx* ctx);
 /* LinDS(q_goal) / MPPI.reset_DS / switch_DS_idx (LinDS.py:7-10, MPPI.py:76-84). */
 OMDS_API int omds_set_ds(omds_ctx* ctx, const float* q_goal);
 /* MPPI_toy's nominal DS (MPPI_toy.py:89-91): velocity = (q - q_goal) @ A, A [n,n] row-major, not

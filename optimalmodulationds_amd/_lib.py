@@ -84,6 +84,11 @@ class OmdsDepthCamera(C.Structure):
                 ("z_min", C.c_float), ("z_max", C.c_float), ("pose", C.c_float * 12)]
 
 
+class OmdsObstacleFocusSpec(C.Structure):
+    """omds_obstacle_focus_spec (include/omds.h): which spheres of a large scene an obstacle focus keeps."""
+    _fields_ = [("margin", C.c_float), ("lookahead", C.c_float), ("max_keep", C.c_int32)]
+
+
 class OmdsError(RuntimeError):
     pass
 
@@ -127,6 +132,10 @@ SIGNATURES = {
     "omds_set_obstacles_from_depth": (C.c_int, [C.c_void_p, C.POINTER(OmdsCloudSpec), C.POINTER(OmdsCloudTrackSpec),
                                                 C.POINTER(OmdsCloudObjectSpec), C.POINTER(OmdsDepthCamera), C.POINTER(C.c_void_p), C.c_int32,
                                                 C.c_int, F32P, I32P, I32P, I32P, I32P, I32P]),
+    "omds_obstacle_focus_select": (C.c_int, [C.POINTER(OmdsObstacleFocusSpec), F32P, F32P, C.c_int, C.c_int, I32P, C.c_int32, I32P, I32P]),
+    "omds_focus_obstacles": (C.c_int, [C.c_void_p, C.POINTER(OmdsObstacleFocusSpec), F32P, I32P, I32P]),
+    "omds_get_obstacle_focus": (C.c_int, [C.c_void_p, I32P, I32P, I32P]),
+    "omds_clear_obstacle_focus": (C.c_int, [C.c_void_p]),
     "omds_set_ds": (C.c_int, [C.c_void_p, F32P]),
     "omds_set_ds_matrix": (C.c_int, [C.c_void_p, F32P, F32P]),
     "omds_set_ds_seds": (C.c_int, [C.c_void_p, F32P, C.c_int, F32P, F32P, F32P, F32P, F32P, F32P, C.c_float, C.c_float]),
@@ -223,7 +232,7 @@ HORIZON_HOOK_SIGNATURES = {
 }
 TEST_LIB_PATH = os.path.join(_HERE, "csrc", "libomds_hip_test.so")
 
-ABI_VERSION = 508     # omds_version() of the library this binding was written against
+ABI_VERSION = 509     # omds_version() of the library this binding was written against
 _libs = {}             # path -> bound CDLL
 
 

@@ -1,5 +1,5 @@
 // Host-only declarations shared by the translation units of the C ABI (include/omds.h): context.hip, mlp_pack.hip, network.hip,
-// screening.hip, propagate.hip, update.hip, sdf_data.hip, obstacle_horizon.hip and scene_cloud.hip.  No kernel file includes this header.
+// screening.hip, propagate.hip, update.hip, sdf_data.hip, obstacle_horizon.hip, scene_cloud.hip and obstacle_focus.hip.  No kernel file includes this header.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -174,10 +174,13 @@ int alloc_obstacle_horizon(omds_ctx* ctx);             // the tables for cfg.hor
 void clear_obstacle_horizon(omds_ctx* ctx);            // omds_set_obstacles: back to the static scene
 void obstacle_horizon_network_changed(omds_ctx* ctx);  // omds_set_mlp*: the feature slabs are derived again at the next propagate
 int prepare_obstacle_horizon(omds_ctx* ctx);           // omds_propagate: rebuilds the tables when they are dirty (one launch)
+int install_obstacle_motion(omds_ctx* ctx, const float* vel);   // the body of omds_set_obstacle_motion behind its focus check
 
 // ---- context.hip: the scene ----------------------------------------------------------------------------------------------------
 int reserve_obstacle_capacity(omds_ctx* ctx, int n_obs);             // grows the obstacle buffers when n_obs exceeds max_obs (the scene is then gone)
 int install_obstacles(omds_ctx* ctx, const float* xyzr, int n_obs);   // the body of omds_set_obstacles behind its argument checks
+// an obstacle focus is in force (obstacle_focus.hip): the scene is a subset of omds_ctx::focus's master.  install_obstacles ends it
+inline bool obstacle_focus_active(const omds_ctx* ctx) { return ctx->focus.on && ctx->n_obs > 0; }
 
 // ---- network.hip ------------------------------------------------------------------------------------------------------------
 void release_network(omds_ctx* ctx);   // frees omds_ctx::mlp_allocs (omds_destroy; every install starts with it)

@@ -47,6 +47,16 @@ void omds_launch_cloud_compact_kept(hipStream_t s, const float* d, const float4*
 void omds_launch_cloud_compact_roots(hipStream_t s, const int* root, const int* cells, const unsigned long long* acc, int n, int cap,
                                      CloudComp* table, int* compOf, unsigned* sums);
 
+// ... the spheres of a master scene the obstacle focus keeps (keys [n], res [4]: what omds_launch_focus_select left), in ascending
+// master index: the sphere to out, its index to idx, and with vel [n][3] its velocity to velOut [cap][3]
+void omds_launch_focus_compact(hipStream_t s, const unsigned* keys, const unsigned* res, const float4* master, const float* vel, int n, int cap,
+                               float4* out, int* idx, float* velOut, unsigned* sums);
+// The obstacle focus (obstacle_focus_kernels.hip).  keys [n]: the keys (obstacle_focus_def.h) of the reaches of distances d [n] and
+// velocities vel [n][3] (nullptr: the distances themselves; dims < 3: v_z = 0)
+void omds_launch_focus_keys(hipStream_t s, const float* d, const float* vel, int dims, float lookahead, int n, unsigned* keys);
+// res [4]: kept, passing, the key of the last kept sphere of the order, the index up to which a sphere with that key is kept.  One workgroup
+void omds_launch_focus_select(hipStream_t s, const unsigned* keys, int n, int n_closest, float margin, bool all_pass, int max_keep, unsigned* res);
+
 // vel [n]: the velocity of every final sphere (its cell in cells) from the records of this frame and the previous one
 void omds_launch_cloud_flow(hipStream_t s, const CloudGrid& g, const CloudTrack& tr, const uint4* now, const uint4* prev, const int* cells, int n,
                             float4* vel);

@@ -553,6 +553,34 @@ __global__ __launch_bounds__(CLOUD_NT) void k_obj_apply(const int* __restrict__ 
     object[i] = accepted ? 1 : 0;
 }
 
+// the spheres of a master scene as a fourth item space (the obstacle focus, obstacle_focus_kernels.hip): kept are the keys below
+// res[2] and, of the keys equal to it, those at indices up to res[3]; each goes out with its master index and its velocity
+struct FocusSrc {
+    const unsigned* keys;
+    const unsigned* res;
+    const float4* master;
+    const float* vel;       // [n][3] or nullptr
+    float4* out;
+    int* idx;
+    float* velOut;          // [cap][3], written when vel is given
+    __device__ unsigned flags(int base, int n) const {
+        const unsigned last = res[2], cut = res[3];
+        unsigned f = 0;
+        for (int j = 0; j < CLOUD_ITEMS; ++j)
+            if (base + j < n) {
+                const unsigned key = keys[base + j];
+                if (key < last || (key == last && (unsigned)(base + j) <= cut)) f |= 1u << j;
+            }
+        return f;
+    }
+    __device__ void emit(int item, unsigned pos) const {
+        out[pos] = master[item];
+        idx[pos] = item;
+        if (vel)
+            for (int c = 0; c < 3; ++c) velOut[3 * (size_t)pos + c] = vel[3 * (size_t)item + c];
+    }
+};
+
 // the ordered compaction of n items of src (at most cap written); the number of kept items is left at sums[blocks of n]
 template <class Src>
 void compact(hipStream_t s, const Src& src, int n, int cap, unsigned* sums) {
@@ -610,6 +638,11 @@ void omds_launch_cloud_compact_kept(hipStream_t s, const float* d, const float4*
 void omds_launch_cloud_compact_roots(hipStream_t s, const int* root, const int* cells, const unsigned long long* acc, int n, int cap,
                                      CloudComp* table, int* compOf, unsigned* sums) {
     compact(s, RootSrc{root, cells, acc, table, compOf}, n, cap, sums);
+}
+
+void omds_launch_focus_compact(hipStream_t s, const unsigned* keys, const unsigned* res, const float4* master, const float* vel, int n, int cap,
+                               float4* out, int* idx, float* velOut, unsigned* sums) {
+    compact(s, FocusSrc{keys, res, master, vel, out, idx, velOut}, n, cap, sums);
 }
 
 void omds_launch_cloud_flow(hipStream_t s, const CloudGrid& g, const CloudTrack& tr, const uint4* now, const uint4* prev, const int* cells, int n,

@@ -1,4 +1,5 @@
-// What a context keeps for the scene from a point cloud or from depth images (scene_cloud.hip): omds_ctx::cloud.  Included by
+// What a context keeps for the scene from a point cloud or from depth images (scene_cloud.hip): omds_ctx::cloud, and for the obstacle
+// focus (obstacle_focus.hip): omds_ctx::focus.  Included by
 // omds_internal.h behind DevBuf.  Every buffer is allocated at the first call of the route that needs it and grown with the spec.
 #pragma once
 #include <cstring>
@@ -42,6 +43,25 @@ struct CloudTableKey {
     int n = 0;                    // components in the stored table
     bool same(const CloudObjects& ob) const { return have && link == ob.link && min_cells == ob.min_cells; }
     void set(const CloudObjects& ob, int n_comp) { have = true; link = ob.link; min_cells = ob.min_cells; n = n_comp; }
+};
+
+// What a context keeps for the obstacle focus (obstacle_focus.hip): omds_ctx::focus.  While `on`, the scene in force is a subset of the
+// MASTER stored here, and idx says which.  Every buffer is allocated at the first focus call and grown with the master.
+struct FocusState {
+    bool on = false;                  // set by omds_focus_obstacles, cleared by install_obstacles (every scene setter ends in it)
+    int n_master = 0;
+    bool moving = false;              // the master carried motion velocities (horizon mode 1)
+    bool labelled = false;            // ... and the labels of an objects call
+    DevBuf<float4> master;            // [n_master]
+    DevBuf<float> vel;                // [n_master][3] while moving
+    std::vector<float> h_master, h_vel;          // the same on the host (what omds_clear_obstacle_focus installs again)
+    std::vector<int32_t> label, flag;            // [n_master] while labelled
+    int obj_count = 0;
+    std::vector<int32_t> idx;                    // [n_obs] master index of every sphere in force, ascending
+    DevBuf<unsigned> keys, sums, res;            // [n_master], [compaction blocks + 1], [4]
+    DevBuf<float4> kept;                         // [n_master] the emission: spheres,
+    DevBuf<int> keptIdx;                         // ... their master indices
+    DevBuf<float> keptVel;                       // ... and [n_master][3] their velocities
 };
 
 struct CloudState {

@@ -8,7 +8,7 @@ thread_local std::string g_create_err;
 
 extern "C" {
 
-int omds_version(void) { return 508; }
+int omds_version(void) { return 509; }
 
 int omds_device_count(int32_t* count) {
     if (!count) return OMDS_ERR_INVALID_ARG;
@@ -250,6 +250,7 @@ int install_obstacles(omds_ctx* ctx, const float* xyzr, int n_obs) {
     CK(hipSetDevice(ctx->dev));
     int rc;
     clear_obstacle_horizon(ctx);   // the new scene stands still until the caller says otherwise (omds_set_obstacle_motion / _horizon)
+    ctx->focus.on = false;         // ... and is nobody's subset: any setter ends an obstacle focus (omds_focus_obstacles switches it on again)
     if (n_obs > ctx->cfg.max_obs && (rc = grow_obstacle_capacity(ctx, n_obs))) return rc;
     CK(hipMemcpyAsync(ctx->d_obs, xyzr, (size_t)n_obs * 16, hipMemcpyHostToDevice, ctx->stream));
     ctx->n_obs = n_obs;

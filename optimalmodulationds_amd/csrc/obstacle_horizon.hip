@@ -115,6 +115,24 @@ static int horizon_ready(omds_ctx* ctx, const char* who) {
     return OMDS_OK;
 }
 
+// while a focus is in force the motion and horizon setters would address the subset and be lost at the next focus
+static std::string focus_refusal(const char* who) {
+    return std::string(who) + ": an obstacle focus is in force (the call would address the kept subset and be lost at the next focus); "
+                              "omds_clear_obstacle_focus first";
+}
+
+// the body of omds_set_obstacle_motion behind its focus check: the obstacle focus installs the kept velocities through it
+int install_obstacle_motion(omds_ctx* ctx, const float* vel) {
+    int rc;
+    if ((rc = horizon_ready(ctx, "omds_set_obstacle_motion"))) return rc;
+    clear_obstacle_horizon(ctx);
+    if (!vel) return OMDS_OK;
+    ctx->hz_vel.assign(vel, vel + (size_t)ctx->n_obs * 3);
+    ctx->hz_mode = 1;
+    ctx->hz_dirty = true;
+    return OMDS_OK;
+}
+
 extern "C" {
 
 int omds_obstacle_horizon_predict(const float* xyzr, const float* vel, int n_obs, int horizon, float dt, float* out) {
@@ -133,14 +151,8 @@ int omds_obstacle_horizon_predict(const float* xyzr, const float* vel, int n_obs
 
 int omds_set_obstacle_motion(omds_ctx* ctx, const float* vel) {
     if (!ctx) return OMDS_ERR_INVALID_ARG;
-    int rc;
-    if ((rc = horizon_ready(ctx, "omds_set_obstacle_motion"))) return rc;
-    clear_obstacle_horizon(ctx);
-    if (!vel) return OMDS_OK;
-    ctx->hz_vel.assign(vel, vel + (size_t)ctx->n_obs * 3);
-    ctx->hz_mode = 1;
-    ctx->hz_dirty = true;
-    return OMDS_OK;
+    REQUIRE(!obstacle_focus_active(ctx), OMDS_ERR_UNSUPPORTED, focus_refusal("omds_set_obstacle_motion"));
+    return install_obstacle_motion(ctx, vel);
 }
 
 int omds_get_obstacle_motion(omds_ctx* ctx, float* vel, int32_t* have_out) {
@@ -157,6 +169,7 @@ int omds_get_obstacle_motion(omds_ctx* ctx, float* vel, int32_t* have_out) {
 int omds_set_obstacle_horizon(omds_ctx* ctx, const float* xyzr_h, int n_obs) {
     if (!ctx) return OMDS_ERR_INVALID_ARG;
     int rc;
+    REQUIRE(!obstacle_focus_active(ctx), OMDS_ERR_UNSUPPORTED, focus_refusal("omds_set_obstacle_horizon"));
     if ((rc = horizon_ready(ctx, "omds_set_obstacle_horizon"))) return rc;
     if (!xyzr_h) { clear_obstacle_horizon(ctx); return OMDS_OK; }
     REQUIRE(n_obs == ctx->n_obs, OMDS_ERR_INVALID_ARG, "omds_set_obstacle_horizon: n_obs differs from the scene's (omds_set_obstacles)");

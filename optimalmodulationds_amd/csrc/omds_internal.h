@@ -378,6 +378,7 @@ struct omds_ctx {
     float frame_max = 1.f;       // clamp of the approach speed (the unit speed rollout velocities are normalised to)
     DevBuf<float> d_frameOut;    // [n_traj][1 + n] omds_approach_rate: rate, then qo (allocated at the first call)
     CloudState cloud;            // the scene from a point cloud or from depth images (cloud_state.h; scene_cloud.hip)
+    FocusState focus;            // the obstacle focus: the master scene and which of it is in force (cloud_state.h; obstacle_focus.hip)
     // DS / cost
     bool have_ds = false, have_cost = false;
     float qf[OMDS_MAX_DOF] = {0};

@@ -214,6 +214,37 @@ class Engine:
         self._ck(self.lib.omds_get_obstacles(self.h, L.fptr(out), None))
         return out
 
+    # ---- the obstacle focus: the spheres of a large scene near one joint state as the scene in force (omds.h) ---------------------
+    def focus_obstacles(self, q, margin, max_keep=0, lookahead=0.0):
+        """Select, on the device, the spheres of the MASTER scene (the scene in force at the first call; kept for the next) that are
+        near joint state ``q`` [n] and install them as the scene in force -> (kept, passed).  Kept are the ``n_closest`` nearest and
+        every sphere within ``margin`` metres of the farthest of those (``np.inf``: all), at most ``max_keep`` (0: no cap); a moving
+        sphere is given ``lookahead`` seconds to approach.  Every scene setter ends the focus; ``set_obstacle_motion`` and
+        ``set_obstacle_horizon`` raise while one is in force."""
+        qn = L.f32(q).reshape(self.n)
+        spec = obstacle_focus_spec(margin, max_keep, lookahead)
+        kept, passed = np.zeros(1, np.int32), np.zeros(1, np.int32)
+        self._ck(self.lib.omds_focus_obstacles(self.h, C.byref(spec), L.fptr(qn), L.iptr(kept), L.iptr(passed)))
+        self.n_obs = int(kept[0])
+        return int(kept[0]), int(passed[0])
+
+    def obstacle_focus(self):
+        """The master index of every sphere in force (ascending, int32 [n_obs]), or None when no focus is in force."""
+        n_master, n_kept = np.zeros(1, np.int32), np.zeros(1, np.int32)
+        self._ck(self.lib.omds_get_obstacle_focus(self.h, None, L.iptr(n_master), L.iptr(n_kept)))
+        if int(n_master[0]) == 0:
+            return None
+        idx = np.zeros(int(n_kept[0]), np.int32)
+        self._ck(self.lib.omds_get_obstacle_focus(self.h, L.iptr(idx), None, None))
+        return idx
+
+    def clear_obstacle_focus(self):
+        """Put the master scene and its motion back (a no-op without a focus)."""
+        self._ck(self.lib.omds_clear_obstacle_focus(self.h))
+        n_obs = np.zeros(1, np.int32)
+        self._ck(self.lib.omds_get_obstacles(self.h, None, L.iptr(n_obs)))
+        self.n_obs = int(n_obs[0])
+
     # ---- obstacle horizon: step i of a propagate sees slab i - 1 of a table [H, O, 4] (omds.h) ---------------------------------
     def set_obstacle_motion(self, vel):
         """Constant velocities ``vel`` [O, 3] of the spheres of the last ``set_obstacles``: step i of ``propagate`` sees them moved by
@@ -705,6 +736,32 @@ def cloud_object_spec(link=1, min_cells=4):
     o = L.OmdsCloudObjectSpec()
     o.link, o.min_cells = int(link), int(min_cells)
     return o
+
+
+def obstacle_focus_spec(margin, max_keep=0, lookahead=0.0):
+    """An ``OmdsObstacleFocusSpec``: keep the spheres within ``margin`` metres (>= 0, ``np.inf``: all) of the n_closest-th nearest, at
+    most ``max_keep`` of them (< 1: no cap), a moving sphere given ``lookahead`` seconds to approach."""
+    s = L.OmdsObstacleFocusSpec()
+    s.margin, s.lookahead, s.max_keep = float(margin), float(lookahead), int(max_keep)
+    return s
+
+
+def obstacle_focus_select(d, n_closest, margin, max_keep=0, lookahead=0.0, vel=None, cap=None):
+    """The definition of the obstacle focus on the host (omds_obstacle_focus_select; no context, no GPU): distances ``d`` [O] and
+    optional velocities ``vel`` [O, 3] -> (idx, passed): the kept indices in ascending order (int32) and the number that passed."""
+    lib = L.load()
+    d = L.f32(d).reshape(-1)
+    v = None if vel is None else L.f32(vel).reshape(-1, 3)
+    if v is not None and v.shape[0] != d.shape[0]:
+        raise ValueError(f"obstacle_focus_select: velocities must be [{d.shape[0]}, 3], got {v.shape}")
+    cap = d.shape[0] if cap is None else int(cap)
+    spec = obstacle_focus_spec(margin, max_keep, lookahead)
+    idx, kept, passed = np.zeros(max(cap, 1), np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32)
+    rc = lib.omds_obstacle_focus_select(C.byref(spec), L.fptr(d), L.fptr(v), d.shape[0], int(n_closest), L.iptr(idx), cap, L.iptr(kept),
+                                        L.iptr(passed))
+    if rc != 0:
+        raise L.OmdsError(f"omds_obstacle_focus_select failed ({rc}): {lib.omds_last_error(None).decode()}")
+    return idx[:int(kept[0])].copy(), int(passed[0])
 
 
 def depth_camera(width, height, fx, fy, cx, cy, pose=None, format=L.DEPTH_U16, depth_scale=0.001, z_min=0.1, z_max=10.0, step=1, pitch=0):

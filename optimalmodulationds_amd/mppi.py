@@ -94,6 +94,7 @@ class MPPI:
                                        rollout_offset=rollout_offset)
         self.Policy._owner = self
         self.Cost = Cost(self.qf, self.dh_params, owner=self)
+        self.obs_focus = None         # focus_obstacles: the master index of every sphere of self.obs, else None
         self.cur_cost = None
         self._cache = {}
         self._generation = 0          # propagate() calls so far (LazyRollout tensors belong to one of them)
@@ -135,6 +136,7 @@ class MPPI:
         # the reference takes any obstacle count at any time: the context grows its own obstacle buffers (omds_set_obstacles),
         # so the handle -- network, samples, RCCL communicator, screening state -- survives
         self._engine.set_obstacles(self.obs.numpy())
+        self.obs_focus = None                        # (and ended an obstacle focus)
         self._max_obs = self._engine.max_obs
         if vel is not None:                          # (set_obstacles cleared the previous motion)
             self._engine.set_obstacle_motion(vel)
@@ -191,6 +193,7 @@ class MPPI:
             self._push()                             # the filter takes its minimum over the links not in self.ignored_links
         self.obs_velocities, self.cloud_matched = None, None
         self.cloud_objects, self.cloud_objects_matched = None, None
+        self.obs_focus = None                        # a scene setter ends an obstacle focus
         if dt_frame is None:
             out = install(self._engine, spec, q, None, None)
         else:
@@ -209,6 +212,33 @@ class MPPI:
         self._max_obs = self._engine.max_obs
         self._engine.set_obstacle_frame(bool(moving_frame))       # as update_obstacles leaves it
         return out
+
+    def focus_obstacles(self, margin, max_keep=0, q=None):
+        """Narrow a large scene to the spheres near the robot, on the device (new here; Engine.focus_obstacles): of the MASTER -- the
+        scene the last ``update_obstacles*`` call installed, kept for the next call -- the ``n_closest_obs`` spheres nearest to ``q``
+        (None: ``self.q_cur``) and every sphere within ``margin`` metres of the farthest of those stay in force, at most ``max_keep``
+        (0: no cap); a moving sphere is given the horizon, (dt_H - 1) dt seconds, to approach.  Meant for every planner iteration,
+        before ``propagate``.  ``self.obs``, ``self.n_obs`` and ``self.obs_velocities`` then describe the scene in force and
+        ``self.obs_focus`` holds the master index of each of its spheres.  Returns (kept, passed).  Whether the propagate equals the one
+        on the full scene is the caller's bet on ``margin`` (omds.h: THE OBSTACLE FOCUS)."""
+        self._push()                                 # the distances take their minimum over the links not in self.ignored_links
+        q = _np(self.q_cur if q is None else q).reshape(-1)
+        out = self._engine.focus_obstacles(q, margin, max_keep, (self.dt_H - 1) * float(self.dt))
+        self._focus_refresh()
+        return out
+
+    def clear_obstacle_focus(self):
+        """Put the master scene and its velocities back in force (a no-op without a focus)."""
+        self._engine.clear_obstacle_focus()
+        self._focus_refresh()
+
+    def _focus_refresh(self):
+        self.obs = torch.as_tensor(self._engine.get_obstacles())
+        self.n_obs = self.obs.shape[0]
+        vel, have = self._engine.get_obstacle_motion()
+        self.obs_velocities = torch.as_tensor(vel) if have else None
+        idx = self._engine.obstacle_focus()
+        self.obs_focus = None if idx is None else torch.as_tensor(idx)
 
     def set_screening(self, mode, eps=0.0, over_horizon=False):
         """The screened pass 1 (Engine.set_screening: mode -1 | 0 | 1 | 2, ``eps`` as there); ``over_horizon``: also while
