@@ -501,7 +501,11 @@ OMDS_API int omds_set_policy_samples(omds_ctx* ctx, const float* mu, const float
                                      int n_kernels);
 /* TensorPolicyMPPI.sample_policy on the device (Philox4x32-10 + Box-Muller): theta_tmp =
  * N(0, theta_s) + theta_c; mean arrays are [K,n], [K], [K,n].  rollout_offset = global index
- * of this shard's rollout 0 (the global rollout 0 gets alpha_tmp = alpha_c, policy.py:74). */
+ * of this shard's rollout 0 (the global rollout 0 gets alpha_tmp = alpha_c, policy.py:74).
+ * Draws: Philox4x32-10, key (seed lo, seed hi), counter (g lo, g hi, kernel, block c) with g = rollout_offset + rollout as 64 bits,
+ * so a sample depends on (seed, g, kernel) only.  Block c gives the normals z[4c .. 4c+3] = r cos t, r sin t of words (0, 1), then of
+ * words (2, 3), with r = sqrt(-2 ln((w_a + 1) 2^-32)), t = 2 pi w_b 2^-32; mu_j takes z[j], sigma z[n], alpha_j z[n+1+j]
+ * (tests/philox_ref.py restates it, tests/test_gpu_random_draws.py holds the device to it). */
 OMDS_API int omds_sample_policy(omds_ctx* ctx, const float* mu_c, const float* sigma_c, const float* alpha_c,
                                 float mu_s, float sigma_s, float alpha_s, int n_kernels, uint64_t seed,
                                 int64_t rollout_offset);

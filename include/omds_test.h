@@ -1,8 +1,9 @@
 /*
  * omds_test.h -- test hooks of the MI355X-native MPPI rollout path.  NOT part of the product ABI: libomds_hip.so does not export
  * them.  They exist in libomds_hip_test.so (`make test-lib`: the same objects except mlp_pack, screening, tail_kernel and train, which are compiled
- * with -DOMDS_TEST_HOOKS; the sin / cos hooks live beside k_encode in train.hip), which tests/ load explicitly
- * (optimalmodulationds_amd._lib.load_test_hooks()).  Neither library reads experiment environment variables.
+ * with -DOMDS_TEST_HOOKS; the sin / cos hooks live beside k_encode in train.hip; the raw Philox hook is csrc/philox_test.hip, a file
+ * that only the test library links), which tests/ load explicitly (optimalmodulationds_amd._lib.load_test_hooks()).  Neither
+ * library reads experiment environment variables.
  */
 #ifndef OMDS_TEST_H
 #define OMDS_TEST_H
@@ -41,6 +42,10 @@ OMDS_API int omds_test_pack_mlp(int n_dof, int n_linear, const int32_t* in_dims,
  * of splitmix64(bits(x) << 32 | bits(f(x))) for f = sin / cos -- order-independent, the sum oracle/chain_arith.c computes.   */
 OMDS_API int omds_test_trig(const float* x, float* s, float* c, int64_t n);
 OMDS_API int omds_test_trig_sweep(uint32_t lo, uint64_t hi, uint64_t* digests);
+/* The generator behind both random kernels (csrc/philox_device.h: philox4x32_10, what k_sample and k_sdf_data inline) on the current
+ * device, for tests/test_gpu_random_draws.py: out[i] = the four words of counter ctr[i] under key key[i], for n <= 2^28 host rows
+ * (copied to the device and back).                                                                                             */
+OMDS_API int omds_test_philox(const uint32_t* ctr /*[n][4]*/, const uint32_t* key /*[n][2]*/, uint32_t* out /*[n][4]*/, int64_t n);
 
 #ifdef __cplusplus
 }

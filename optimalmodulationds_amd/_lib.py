@@ -219,6 +219,7 @@ TEST_HOOK_SIGNATURES = {
                                      C.POINTER(C.c_uint64), C.POINTER(C.c_int64)]),
     "omds_test_trig": (C.c_int, [F32P, F32P, F32P, C.c_int64]),
     "omds_test_trig_sweep": (C.c_int, [C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "omds_test_philox": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
 }
 # include/omds_test_tiles.h: the hooks of the block-ordered pass 1, in the test library likewise
 TILE_HOOK_SIGNATURES = {
@@ -286,7 +287,8 @@ def load(path=None, extra_signatures=None):
 
 def load_test_hooks():
     """libomds_hip_test.so: the product's objects plus the hooks of include/omds_test.h (damage the screening inputs, force a tile
-    shape, the trainer's general GEMM, the host half of omds_set_mlp_ex, the encoding's sin / cos).  For tests only:
+    shape, the trainer's general GEMM, the host half of omds_set_mlp_ex, the encoding's sin / cos, the raw words of the device's
+    Philox4x32-10: omds_test_philox(ctr [n, 4] uint32, key [n, 2] uint32, out [n, 4] uint32, n)).  For tests only:
     ``Engine(..., lib=load_test_hooks())``."""
     return load(TEST_LIB_PATH, dict(TEST_HOOK_SIGNATURES, **TILE_HOOK_SIGNATURES, **HORIZON_HOOK_SIGNATURES))
 
