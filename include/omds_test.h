@@ -1,8 +1,8 @@
 /*
  * omds_test.h -- test hooks of the MI355X-native MPPI rollout path.  NOT part of the product ABI: libomds_hip.so does not export
  * them.  They exist in libomds_hip_test.so (`make test-lib`: the same objects except mlp_pack, screening, tail_kernel and train, which are compiled
- * with -DOMDS_TEST_HOOKS; the sin / cos hooks live beside k_encode in train.hip; the raw Philox hook is csrc/philox_test.hip, a file
- * that only the test library links), which tests/ load explicitly (optimalmodulationds_amd._lib.load_test_hooks()).  Neither
+ * with -DOMDS_TEST_HOOKS; the sin / cos hooks live beside k_encode in train.hip; the raw Philox hook is csrc/philox_test.hip and the top-k hook
+ * csrc/select_test.hip, files that only the test library links), which tests/ load explicitly (optimalmodulationds_amd._lib.load_test_hooks()).  Neither
  * library reads experiment environment variables.
  */
 #ifndef OMDS_TEST_H
@@ -46,6 +46,11 @@ OMDS_API int omds_test_trig_sweep(uint32_t lo, uint64_t hi, uint64_t* digests);
  * device, for tests/test_gpu_random_draws.py: out[i] = the four words of counter ctr[i] under key key[i], for n <= 2^28 host rows
  * (copied to the device and back).                                                                                             */
 OMDS_API int omds_test_philox(const uint32_t* ctr /*[n][4]*/, const uint32_t* key /*[n][2]*/, uint32_t* out /*[n][4]*/, int64_t n);
+/* The selection of the k closest obstacles (csrc/topk_device.h: topk_row, both of its paths) on the current device, for
+ * tests/test_gpu_topk.py: the host rows are copied to the device, the production launcher (k_topk, one wave per row) runs on them
+ * as it does on the pass-1 matrix, and idx_out[b][j] = the index of the j-th smallest entry of row b under the rule at the top of
+ * topk_device.h.  1 <= k <= O.  (csrc/select_test.hip, a file that only the test library links.)                                */
+OMDS_API int omds_test_topk(const float* rows /*[B][O]*/, int B, int O, int k, int32_t* idx_out /*[B][k]*/);
 
 #ifdef __cplusplus
 }

@@ -220,6 +220,7 @@ TEST_HOOK_SIGNATURES = {
     "omds_test_trig": (C.c_int, [F32P, F32P, F32P, C.c_int64]),
     "omds_test_trig_sweep": (C.c_int, [C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64)]),
     "omds_test_philox": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "omds_test_topk": (C.c_int, [F32P, C.c_int, C.c_int, C.c_int, I32P]),
 }
 # include/omds_test_tiles.h: the hooks of the block-ordered pass 1, in the test library likewise
 TILE_HOOK_SIGNATURES = {
@@ -288,9 +289,22 @@ def load(path=None, extra_signatures=None):
 def load_test_hooks():
     """libomds_hip_test.so: the product's objects plus the hooks of include/omds_test.h (damage the screening inputs, force a tile
     shape, the trainer's general GEMM, the host half of omds_set_mlp_ex, the encoding's sin / cos, the raw words of the device's
-    Philox4x32-10: omds_test_philox(ctr [n, 4] uint32, key [n, 2] uint32, out [n, 4] uint32, n)).  For tests only:
+    Philox4x32-10: omds_test_philox(ctr [n, 4] uint32, key [n, 2] uint32, out [n, 4] uint32, n), the top-k selection on given rows:
+    ``select_topk`` below).  For tests only:
     ``Engine(..., lib=load_test_hooks())``."""
     return load(TEST_LIB_PATH, dict(TEST_HOOK_SIGNATURES, **TILE_HOOK_SIGNATURES, **HORIZON_HOOK_SIGNATURES))
+
+
+def select_topk(rows, k):
+    """omds_test_topk (include/omds_test.h): rows [B, O] float32 -> int32 [B, k], the indices of each row's k smallest entries as the
+    production top-k kernel selects them.  Needs no context; loads the test library."""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    assert rows.ndim == 2
+    idx = np.full((rows.shape[0], int(k)), -2, np.int32)
+    rc = load_test_hooks().omds_test_topk(rows.ctypes.data, rows.shape[0], rows.shape[1], int(k), idx.ctypes.data)
+    if rc != 0:
+        raise OmdsError(f"omds_test_topk failed ({rc})")
+    return idx
 
 
 def f32(a, shape=None):

@@ -1,15 +1,16 @@
-// The k smallest entries of a row, one wave per row, on 64-bit keys and a DPP wave minimum.  Included by mlp_kernels.hip (k_topk)
-// and tail_kernel.hip.
+// The k smallest entries of a row, one wave per row.  Included by mlp_kernels.hip (k_topk) and tail_kernel.hip.
 #pragma once
 
-// k smallest entries of row[0..O) in ascending order (ties by lower index), one wave per row.
-// emit(j, index) is called by lane 0.  Rows of up to 512 entries are held in registers.
-// In-register rows: every entry becomes ONE 64-bit key, (order-preserving image of the value) << 32 | index, so that "smaller value,
-// then lower index" is an unsigned comparison, "after the previous pick" is key > previous key, and a round is a local minimum over
-// the lane's keys + a wave minimum on DPP row operations (quad xor 1 / 2, half-row and row mirror, row broadcasts 15 / 31: no LDS
-// crossbar in the chain) -- a third of the cycles of the (value, index) butterfly of ds_bpermutes it replaces.  -0 counts as +0
-// (they compare equal, the index decides); a NaN is never picked (its key is the "nothing" key); rows with fewer than k pickable
-// entries repeat index 0, as before.
+// k smallest entries of row[0..O) in ascending order, one wave per row; emit(j, index) is called by lane 0.  The rule, for rows of
+// every length (tests/test_gpu_topk.py holds both paths to it): entries are ordered by (value, index) -- ties go to the lower
+// index, and -0 counts as +0 (they compare equal, the index decides); a NaN is never picked; +inf and -inf are ordinary values;
+// once a row has no pickable entry left (fewer than k entries that are not NaN) every further position holds index 0.
+// Rows of up to 512 entries are held in registers: every entry becomes ONE 64-bit key, (order-preserving image of the value) << 32
+// | index, so that "smaller value, then lower index" is an unsigned comparison, "after the previous pick" is key > previous key
+// (a NaN's key is the "nothing" key), and a round is a local minimum over the lane's keys + a wave minimum on DPP row operations
+// (quad xor 1 / 2, half-row and row mirror, row broadcasts 15 / 31: no LDS crossbar in the chain) -- a third of the cycles of the
+// (value, index) butterfly of ds_bpermutes it replaces.  Longer rows are read again in every round, with a float comparison and a
+// __shfl_xor butterfly; a round that finds nothing leaves (+inf, INT_MAX) as the previous pick, behind which no entry comes.
 __device__ __forceinline__ unsigned long long omds_dpp_min_u64(unsigned long long v, unsigned long long o) { return o < v ? o : v; }
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ unsigned long long omds_dpp_step_min_u64(unsigned long long v) {
@@ -78,9 +79,8 @@ __device__ __forceinline__ void topk_row(const float* __restrict__ row, int O, i
             const int oi = __shfl_xor(bi, off);
             if ((ov < bv) || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
         }
-        if (bi == 0x7fffffff) bi = 0;
-        if (lane == 0) emit(j, bi);
-        pv = bv;
+        if (lane == 0) emit(j, bi == 0x7fffffff ? 0 : bi);
+        pv = bv;   // a dry round leaves (+inf, INT_MAX): a +inf entry of the row does not come "after" it, so the row stays dry
         pi = bi;
     }
 }
