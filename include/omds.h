@@ -415,6 +415,65 @@ OMDS_API int omds_set_obstacles_from_depth(omds_ctx* ctx, const omds_cloud_spec*
                                            int32_t n_cams, int images_on_device, const float* q_now, int32_t* n_spheres_out,
                                            int32_t* n_occupied_out, int32_t* n_matched_out, int32_t* n_objects_out,
                                            int32_t* n_objects_matched_out);
+/* THE SCENE MEMORY OF THE DEPTH ROUTE: KEEP OCCLUDED OBSTACLES, CLEAR CELLS SEEN THROUGH (new work).  Every call above is memoryless
+ * about occupancy: a cell that got no points this frame is gone, whether a camera looked through it or the arm, a dropout (raw 0) or
+ * the edge of a frustum kept every camera from telling.  This route keeps one word per cell between calls and asks the cameras.
+ * Additive: no other entry point changes its launches or its bits.
+ * OUT OF SCOPE: memory on the tracked / objects routes (velocities of remembered cells: remembered spheres stand still, this route
+ * installs a static scene), the plain cloud route (no cameras, so no visibility), per-cell occupancy probabilities or log-odds,
+ * sub-voxel footprints that follow the cell's projected size, motion compensation of the memory when the grid frame moves.
+ *   THE WORD: m[c] (uint32) per grid cell; 0 = empty, k >= 1 = occupied and last counted k - 1 calls ago.
+ *   omds_depth_scene_memory : host only (no context, no GPU), the DEFINITION.  All fp32, every operation named one rounding.  n[c] are
+ *       the counts of the depth route's counting pass (omds_depth_points of every image, cloud_cell), unchanged.  mem_in [cells] (NULL =
+ *       all empty) -> mem_out [cells] (may be the same array), per cell:
+ *       1. n[c] >= min_points: m' = 1, SEEN.   2. else m[c] == 0: m' = 0.   3. else every camera i = 0 .. n_cams - 1 gives a verdict on
+ *       the cell centre p (the three fmaf of the cell's sphere): d_r = p_r - pose[4r+3];  xc = fmaf(pose[0], d_0, fmaf(pose[4], d_1,
+ *       pose[8] * d_2)), yc with pose[1], [5], [9], zc with pose[2], [6], [10] -- R taken as orthonormal and applied transposed, NOT
+ *       checked;  !(zc >= z_min && zc <= z_max): SILENT;  iz = 1.0f / zc (IEEE-rounded);  uf = fmaf(xc * iz, fx, cx), vf = fmaf(yc * iz,
+ *       fy, cy);  ju = rintf(uf * istep), jv = rintf(vf * istep) with istep = 1.0f / (float)step taken once (ties to even);
+ *       !(ju >= 0 && ju < nu && jv >= 0 && jv < nv), compared as floats before any conversion: SILENT;  lim = zc + clear_margin;  every
+ *       visited pixel (ju + a, jv + b), |a|, |b| <= footprint, inside [0, nu) x [0, nv) reads the raw element at column (ju + a) step,
+ *       row (jv + b) step: U16 with d == 0: SILENT, else z_pix = (float)d * depth_scale; F32: z_pix = the element;
+ *       !(fabsf(z_pix) <= FLT_MAX && z_pix > lim): SILENT.  The range gate is deliberately not applied to z_pix: a return beyond z_max
+ *       is still a return from behind the cell.  All window pixels passed: FREE.   4. any camera FREE: m' = 0, CLEARED.   5. else m' =
+ *       m + 1 saturating at 0xFFFFFFFF; max_age >= 1 && m' > (uint32)max_age + 1: m' = 0, EXPIRED; else REMEMBERED -- a cell survives
+ *       exactly max_age unseen calls.  counts_out [4] = cells seen, remembered, cleared, expired (NULL = skip).  No self-filter here.
+ *       OMDS_ERR_INVALID_ARG before anything is written: a bad cloud spec or camera, footprint outside 0 .. 3, NaN clear_margin, null
+ *       mem_spec, cams, images, an image or mem_out, n_cams outside 1 .. 8, more than 2^24 visited pixels.
+ *   omds_set_obstacles_from_depth_memory : THE CONTRACT -- the candidates are the cells with m' != 0 in ascending cell order, as their
+ *       spheres; with q_now the self-filter of omds_set_obstacles_from_cloud runs on them, and a candidate it drops sets m'[cell] = 0
+ *       (SELF-FORGOTTEN: otherwise the arm's own past poses would haunt the scene wherever no camera can see).  The installed scene and
+ *       its padding are those of omds_set_obstacles on the spheres of the final m'; the stored memory afterwards is the final m'; both
+ *       are bit for bit the definition iterated from the stored memory.  The memory is keyed by origin, voxel, dims (bitwise), the
+ *       resolved min_points and the resolved memory spec (clear_margin bitwise): a call on another key starts from empty memory.
+ *       seen + remembered > max_spheres: OMDS_ERR_INVALID_ARG with counts_out filled ([4] = 0), scene and stored memory exactly as they
+ *       were (the call writes the buffer that is not the stored one and commits behind everything that can fail); so do the argument
+ *       checks.  Like every scene setter it ends an obstacle focus and clears a motion horizon.  The stored record frame and component
+ *       table of the tracked / objects routes are left alone.  counts_out [5] = the four above and the self-forgotten cells (NULL =
+ *       skip); *n_spheres_out = spheres before padding.  On the device: the counting pass as it is; ONE launch maps (counts, stored
+ *       words) to the new words, 4 consecutive cells per lane by 16-byte loads and one 16-byte store -- a lane whose four stored words
+ *       are 0 (nearly all of them) projects nothing and reads no image; the others loop the camera table, which travels by value;
+ *       integer counters, reduced per wave.  Then the ordered compaction on m' != 0 with the cell indices, the self-filter, one launch
+ *       that zeroes the dropped cells, one that gathers the ages.  Synchronous.
+ *   omds_scene_memory_reset : forgets the stored memory; the next memory call starts from empty.
+ *   omds_get_scene_memory : age [n_obs] of the scene in force: m' - 1 of every sphere's cell (0: seen in the installing call), -1 for a
+ *       padding sphere and for every sphere when another setter (an obstacle focus included) installed the scene; grid [cells] = the
+ *       stored words (NULL: no copy; untouched without a stored memory); *n_cells_out = cells of the stored memory, 0 without one.    */
+typedef struct {
+    int32_t max_age;       /* a cell unseen for more calls than this is dropped; < 1: never                          */
+    float   clear_margin;  /* a return must be farther than the cell's depth + this to clear it; <= 0: the sphere radius; not NaN */
+    int32_t footprint;     /* the window of a verdict is (2 footprint + 1)^2 visited pixels: 0 .. 3                   */
+} omds_scene_memory_spec;
+OMDS_API int omds_depth_scene_memory(const omds_cloud_spec* spec, const omds_scene_memory_spec* mem_spec, const omds_depth_camera* cams,
+                                     const void* const* images, int32_t n_cams, const uint32_t* mem_in /* [cells] or NULL = empty */,
+                                     uint32_t* mem_out /* [cells] */, int32_t counts_out[4] /* seen, remembered, cleared, expired */);
+OMDS_API int omds_set_obstacles_from_depth_memory(omds_ctx* ctx, const omds_cloud_spec* spec, const omds_scene_memory_spec* mem_spec,
+                                                  const omds_depth_camera* cams, const void* const* images, int32_t n_cams,
+                                                  int images_on_device, const float* q_now, int32_t* n_spheres_out,
+                                                  int32_t counts_out[5] /* the four above + self-forgotten */);
+OMDS_API int omds_scene_memory_reset(omds_ctx* ctx);
+OMDS_API int omds_get_scene_memory(omds_ctx* ctx, int32_t* age /* [n_obs] or NULL */, uint32_t* grid /* [cells] or NULL */,
+                                   int32_t* n_cells_out);
 /* THE OBSTACLE FOCUS (new work).  A sensed scene has thousands of spheres; everything behind pass 1 uses the n_closest nearest per
  * (rollout, step).  A focus call evaluates the distance of every sphere of the scene at ONE joint state, selects the near ones and
  * installs them as the scene in force, on the device; the full scene (the MASTER) is kept, so that the next call selects from it again

@@ -84,6 +84,11 @@ class OmdsDepthCamera(C.Structure):
                 ("z_min", C.c_float), ("z_max", C.c_float), ("pose", C.c_float * 12)]
 
 
+class OmdsSceneMemorySpec(C.Structure):
+    """omds_scene_memory_spec (include/omds.h): how the depth route's scene memory ages and clears an unseen cell."""
+    _fields_ = [("max_age", C.c_int32), ("clear_margin", C.c_float), ("footprint", C.c_int32)]
+
+
 class OmdsObstacleFocusSpec(C.Structure):
     """omds_obstacle_focus_spec (include/omds.h): which spheres of a large scene an obstacle focus keeps."""
     _fields_ = [("margin", C.c_float), ("lookahead", C.c_float), ("max_keep", C.c_int32)]
@@ -132,6 +137,12 @@ SIGNATURES = {
     "omds_set_obstacles_from_depth": (C.c_int, [C.c_void_p, C.POINTER(OmdsCloudSpec), C.POINTER(OmdsCloudTrackSpec),
                                                 C.POINTER(OmdsCloudObjectSpec), C.POINTER(OmdsDepthCamera), C.POINTER(C.c_void_p), C.c_int32,
                                                 C.c_int, F32P, I32P, I32P, I32P, I32P, I32P]),
+    "omds_depth_scene_memory": (C.c_int, [C.POINTER(OmdsCloudSpec), C.POINTER(OmdsSceneMemorySpec), C.POINTER(OmdsDepthCamera),
+                                          C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.c_void_p, I32P]),
+    "omds_set_obstacles_from_depth_memory": (C.c_int, [C.c_void_p, C.POINTER(OmdsCloudSpec), C.POINTER(OmdsSceneMemorySpec),
+                                                       C.POINTER(OmdsDepthCamera), C.POINTER(C.c_void_p), C.c_int32, C.c_int, F32P, I32P, I32P]),
+    "omds_scene_memory_reset": (C.c_int, [C.c_void_p]),
+    "omds_get_scene_memory": (C.c_int, [C.c_void_p, I32P, C.c_void_p, I32P]),
     "omds_obstacle_focus_select": (C.c_int, [C.POINTER(OmdsObstacleFocusSpec), F32P, F32P, C.c_int, C.c_int, I32P, C.c_int32, I32P, I32P]),
     "omds_focus_obstacles": (C.c_int, [C.c_void_p, C.POINTER(OmdsObstacleFocusSpec), F32P, I32P, I32P]),
     "omds_get_obstacle_focus": (C.c_int, [C.c_void_p, I32P, I32P, I32P]),
@@ -234,7 +245,7 @@ HORIZON_HOOK_SIGNATURES = {
 }
 TEST_LIB_PATH = os.path.join(_HERE, "csrc", "libomds_hip_test.so")
 
-ABI_VERSION = 509     # omds_version() of the library this binding was written against
+ABI_VERSION = 510     # omds_version() of the library this binding was written against
 _libs = {}             # path -> bound CDLL
 
 

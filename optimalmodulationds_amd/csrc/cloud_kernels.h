@@ -6,6 +6,7 @@
 
 #include "depth_def.h"
 #include "point_cloud_objects_def.h"
+#include "scene_memory_def.h"
 
 constexpr int CLOUD_NT = 256;                          // lanes of every workgroup here
 constexpr int CLOUD_ITEMS = 4;                         // consecutive items per lane of a compaction block
@@ -40,6 +41,8 @@ void omds_launch_cloud_count(hipStream_t s, DepthTable tab, int n_cams, const Cl
 // ... the cells of g with min_points points and more (count / rec padded with zeros to cloud_padded_cells): their spheres, cap = g.max_spheres
 void omds_launch_cloud_compact_cells(hipStream_t s, const unsigned* count, const CloudGrid& g, float4* out, unsigned* sums);
 void omds_launch_cloud_compact_cells(hipStream_t s, const uint4* rec, const CloudGrid& g, float4* out, int* cell, unsigned* sums);
+// ... the cells of g whose scene-memory word is not 0 (mem padded with zeros like count): their spheres and their cell indices
+void omds_launch_cloud_compact_cells(hipStream_t s, const unsigned* mem, const CloudGrid& g, float4* out, int* cell, unsigned* sums);
 // ... the n candidates the self-filter keeps at their pass-1 distances d [n]; with candCell their cell indices go to cell beside them
 void omds_launch_cloud_compact_kept(hipStream_t s, const float* d, const float4* cand, const int* candCell, int n, float margin, int cap,
                                     float4* out, int* cell, unsigned* sums);
@@ -56,6 +59,16 @@ void omds_launch_focus_compact(hipStream_t s, const unsigned* keys, const unsign
 void omds_launch_focus_keys(hipStream_t s, const float* d, const float* vel, int dims, float lookahead, int n, unsigned* keys);
 // res [4]: kept, passing, the key of the last kept sphere of the order, the index up to which a sphere with that key is kept.  One workgroup
 void omds_launch_focus_select(hipStream_t s, const unsigned* keys, int n, int n_closest, float margin, bool all_pass, int max_keep, unsigned* res);
+
+// The scene memory (scene_memory_def.h).  mem_out [cloud_padded_cells]: the words of this call from the counts count and the stored
+// words mem_in (both padded with zeros; mem_in == nullptr: all empty); counters [SCENE_MEM_COUNTS], cleared by the caller, takes the
+// seen, remembered, cleared and expired cells
+void omds_launch_scene_memory(hipStream_t s, DepthTable tab, const SceneMemCams& ks, int n_cams, const CloudGrid& g, const SceneMem& sm,
+                              const unsigned* count, const unsigned* mem_in, unsigned* mem_out, unsigned* counters);
+// ... mem[cell[i]] = 0 for every candidate i of n the self-filter drops at its pass-1 distance d[i]; counters[SCENE_MEM_FORGOTTEN] += them
+void omds_launch_scene_memory_forget(hipStream_t s, const float* d, const int* cell, int n, float margin, unsigned* mem, unsigned* counters);
+// ... age[i] = mem[cell[i]] - 1 for the n final spheres
+void omds_launch_scene_memory_age(hipStream_t s, const unsigned* mem, const int* cell, int n, int* age);
 
 // vel [n]: the velocity of every final sphere (its cell in cells) from the records of this frame and the previous one
 void omds_launch_cloud_flow(hipStream_t s, const CloudGrid& g, const CloudTrack& tr, const uint4* now, const uint4* prev, const int* cells, int n,

@@ -10,6 +10,8 @@
 // k_cloud_flow's.
 // The depth form is another POINT SOURCE of the counting pass: it deprojects the pixels of up to eight depth images itself
 // (depth_def.h; k_depth_count, k_depth_count_rec) and no point is ever written.
+// The scene memory of the depth route (scene_memory_def.h) is one more pass over the cells behind that counting pass (k_scene_memory),
+// a fifth item space of the compaction (MemSrc) and two small launches over the candidates (k_scene_memory_forget, k_scene_memory_age).
 #include <algorithm>
 
 #include "cloud_kernels.h"
@@ -99,6 +101,22 @@ struct RecSrc {             // items = cells; rec is zero-padded to whole blocks
         for (int j = 0; j < CLOUD_ITEMS; ++j)
             if (rec[base + j].x >= g.min_points) f |= 1u << j;
         return f;
+    }
+    __device__ void emit(int item, unsigned pos) const {
+        float s[4];
+        cloud_sphere(g, item, s);
+        out[pos] = make_float4(s[0], s[1], s[2], s[3]);
+        cell[pos] = item;
+    }
+};
+struct MemSrc {             // items = cells; mem is zero-padded to whole blocks like count, kept are the words that are not 0
+    const unsigned* mem;
+    CloudGrid g;
+    float4* out;
+    int* cell;
+    __device__ unsigned flags(int base, int) const {
+        const uint4 m = *reinterpret_cast<const uint4*>(mem + base);
+        return (m.x ? 1u : 0u) | (m.y ? 2u : 0u) | (m.z ? 4u : 0u) | (m.w ? 8u : 0u);
     }
     __device__ void emit(int item, unsigned pos) const {
         float s[4];
@@ -300,6 +318,66 @@ __global__ __launch_bounds__(CLOUD_NT) void k_depth_count(DepthTable tab, CloudG
 }
 __global__ __launch_bounds__(CLOUD_NT) void k_depth_count_rec(DepthTable tab, CloudGrid g, uint4* __restrict__ rec) {
     depth_count<true>(tab, g, rec);
+}
+
+// ---- the scene memory of the depth route (scene_memory_def.h) ----------------------------------------------------------------------
+// One pass over the cells behind the counting pass: a lane owns 4 consecutive cells (one 16-byte load of the counts, one of the stored
+// words, one 16-byte store of the new words) and the workgroups stride over the padded cells, so the padding comes out 0 too.  A lane
+// whose four stored words are 0 -- nearly every lane of a large grid -- projects nothing and reads no image.  The others ask the
+// cameras of the table, which travels by value like the counting pass's; every camera is asked, so the table index stays uniform.
+// The lanes of a wave diverge there (accepted: a few thousand remembered cells against millions of empty ones).  A streaming kernel:
+// no LDS, no barrier.  The counters are integers, reduced per wave before one atomic each: no order can change them
+struct TableCams {
+    const DepthTable& t;
+    __device__ const DepthCam& cam(int i) const { return t.cam[i].c; }
+    __device__ const void* image(int i) const { return t.cam[i].image; }
+};
+constexpr unsigned MEM_MAX_BLOCKS = 2048;
+__global__ __launch_bounds__(CLOUD_NT) void k_scene_memory(DepthTable tab, SceneMemCams ks, int n_cams, CloudGrid g, SceneMem sm,
+                                                           const unsigned* __restrict__ count, const unsigned* __restrict__ mem_in,
+                                                           unsigned* __restrict__ mem_out, int groups, unsigned* __restrict__ counters) {
+    const TableCams cams{tab};
+    unsigned tally[4] = {0u, 0u, 0u, 0u};
+    for (int i = blockIdx.x * CLOUD_NT + threadIdx.x; i < groups; i += gridDim.x * CLOUD_NT) {
+        const int base = i * CLOUD_ITEMS;
+        const uint4 n4 = *reinterpret_cast<const uint4*>(count + base);
+        const uint4 m4 = mem_in ? *reinterpret_cast<const uint4*>(mem_in + base) : make_uint4(0u, 0u, 0u, 0u);
+        const unsigned n[CLOUD_ITEMS] = {n4.x, n4.y, n4.z, n4.w}, m[CLOUD_ITEMS] = {m4.x, m4.y, m4.z, m4.w};
+        unsigned out[CLOUD_ITEMS];
+        if ((m4.x | m4.y | m4.z | m4.w) == 0u) {
+            for (int j = 0; j < CLOUD_ITEMS; ++j) {
+                out[j] = (base + j < g.n_cells && n[j] >= g.min_points) ? 1u : 0u;
+                tally[SCENE_MEM_SEEN] += out[j];
+            }
+        } else {
+            for (int j = 0; j < CLOUD_ITEMS; ++j) {
+                int what = -1;
+                out[j] = base + j < g.n_cells ? scene_memory_cell(g, sm, cams, ks, n_cams, base + j, n[j], m[j], &what) : 0u;
+                for (int k = 0; k < 4; ++k) tally[k] += what == k ? 1u : 0u;
+            }
+        }
+        *reinterpret_cast<uint4*>(mem_out + base) = make_uint4(out[0], out[1], out[2], out[3]);
+    }
+    for (int k = 0; k < 4; ++k) {
+        const unsigned sum = wave_sum(tally[k]);
+        if ((threadIdx.x & 63) == 0 && sum) atomicAdd(counters + k, sum);
+    }
+}
+
+// the candidates the self-filter drops (cloud_keep's rule at the same distances the second compaction reads) leave the memory
+__global__ __launch_bounds__(CLOUD_NT) void k_scene_memory_forget(const float* __restrict__ d, const int* __restrict__ cell, int n, float margin,
+                                                                  unsigned* __restrict__ mem, unsigned* __restrict__ counters) {
+    const int i = blockIdx.x * CLOUD_NT + threadIdx.x;
+    const bool drop = i < n && !cloud_keep(d[i], margin);
+    if (drop) mem[cell[i]] = 0u;
+    const unsigned sum = wave_sum(drop ? 1u : 0u);
+    if ((threadIdx.x & 63) == 0 && sum) atomicAdd(counters + SCENE_MEM_FORGOTTEN, sum);
+}
+
+__global__ __launch_bounds__(CLOUD_NT) void k_scene_memory_age(const unsigned* __restrict__ mem, const int* __restrict__ cell, int n,
+                                                               int* __restrict__ age) {
+    const int i = blockIdx.x * CLOUD_NT + threadIdx.x;
+    if (i < n) age[i] = (int)(mem[cell[i]] - 1u);
 }
 
 // The velocity of every final sphere (point_cloud_flow_def.h): one wave per sphere, four per workgroup, no barrier.  A first probe
@@ -629,6 +707,23 @@ void omds_launch_cloud_compact_cells(hipStream_t s, const unsigned* count, const
 void omds_launch_cloud_compact_cells(hipStream_t s, const uint4* rec, const CloudGrid& g, float4* out, int* cell, unsigned* sums) {
     compact(s, RecSrc{rec, g, out, cell}, g.n_cells, g.max_spheres, sums);
 }
+void omds_launch_cloud_compact_cells(hipStream_t s, const unsigned* mem, const CloudGrid& g, float4* out, int* cell, unsigned* sums) {
+    compact(s, MemSrc{mem, g, out, cell}, g.n_cells, g.max_spheres, sums);
+}
+
+void omds_launch_scene_memory(hipStream_t s, DepthTable tab, const SceneMemCams& ks, int n_cams, const CloudGrid& g, const SceneMem& sm,
+                              const unsigned* count, const unsigned* mem_in, unsigned* mem_out, unsigned* counters) {
+    const int groups = (int)(cloud_padded_cells(g) / CLOUD_ITEMS);   // a multiple of CLOUD_NT
+    const unsigned blocks = std::min((unsigned)(groups / CLOUD_NT), MEM_MAX_BLOCKS);
+    hipLaunchKernelGGL(k_scene_memory, dim3(blocks), dim3(CLOUD_NT), 0, s, tab, ks, n_cams, g, sm, count, mem_in, mem_out, groups, counters);
+}
+void omds_launch_scene_memory_forget(hipStream_t s, const float* d, const int* cell, int n, float margin, unsigned* mem, unsigned* counters) {
+    if (n > 0) hipLaunchKernelGGL(k_scene_memory_forget, dim3((n + CLOUD_NT - 1) / CLOUD_NT), dim3(CLOUD_NT), 0, s, d, cell, n, margin, mem, counters);
+}
+void omds_launch_scene_memory_age(hipStream_t s, const unsigned* mem, const int* cell, int n, int* age) {
+    if (n > 0) hipLaunchKernelGGL(k_scene_memory_age, dim3((n + CLOUD_NT - 1) / CLOUD_NT), dim3(CLOUD_NT), 0, s, mem, cell, n, age);
+}
+
 void omds_launch_cloud_compact_kept(hipStream_t s, const float* d, const float4* cand, const int* candCell, int n, float margin, int cap,
                                     float4* out, int* cell, unsigned* sums) {
     const KeepSrc keep{d, cand, margin, out};

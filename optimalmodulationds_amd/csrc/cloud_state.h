@@ -5,6 +5,7 @@
 #include <cstring>
 
 #include "point_cloud_objects_def.h"
+#include "scene_memory_def.h"
 
 // Two buffers, one of which holds what the last successful call stored while the other is written; commit() swaps them
 template <class T>
@@ -43,6 +44,22 @@ struct CloudTableKey {
     int n = 0;                    // components in the stored table
     bool same(const CloudObjects& ob) const { return have && link == ob.link && min_cells == ob.min_cells; }
     void set(const CloudObjects& ob, int n_comp) { have = true; link = ob.link; min_cells = ob.min_cells; n = n_comp; }
+};
+
+// the grid and the memory spec the stored scene memory was built under (omds_set_obstacles_from_depth_memory); floats bitwise
+struct SceneMemKey {
+    CloudFrameKey grid;           // grid.have: a memory is stored (a memory call succeeded since creation / omds_scene_memory_reset)
+    int max_age = 0, footprint = 0;
+    float clear_margin = 0.f;
+    int n_cells = 0;
+    bool same(const CloudGrid& g, const SceneMem& sm) const {
+        return grid.same(g) && max_age == sm.max_age && footprint == sm.footprint && std::memcmp(&clear_margin, &sm.clear_margin, 4) == 0;
+    }
+    void set(const CloudGrid& g, const SceneMem& sm) {
+        grid.set(g);
+        max_age = sm.max_age; footprint = sm.footprint; clear_margin = sm.clear_margin;
+        n_cells = g.n_cells;
+    }
 };
 
 // What a context keeps for the obstacle focus (obstacle_focus.hip): omds_ctx::focus.  While `on`, the scene in force is a subset of the
@@ -90,7 +107,14 @@ struct CloudState {
     DevBuf<float4> objVel;            // [max_spheres] per component: the object's velocity; .w: 0 no object, 1 object, 2 accepted
     std::vector<int32_t> obj_label, obj_flag;   // [n_obs] of the scene in force when the objects call installed it, else empty
     int obj_count = 0;                // its objects
+    // ... scene memory (omds_set_obstacles_from_depth_memory): per cell the word of scene_memory_def.h.  One of the two buffers holds
+    // the stored memory, the other is written; a successful memory call makes its own the stored one
+    Flip<unsigned> mem;               // [cells rounded up to whole compaction blocks] each, allocated when first written
+    SceneMemKey memKey;
+    DevBuf<int> age;                  // [max_spheres] m' - 1 of every final sphere's cell
+    DevBuf<unsigned> memCounts;       // [SCENE_MEM_COUNTS] seen, remembered, cleared, expired, self-forgotten of the call under way
+    std::vector<int32_t> mem_age;     // [n_obs] of the scene in force when the memory call installed it (padding: -1), else empty
 
     void forget_tracking() { frame.have = false; tab.have = false; }          // omds_cloud_track_reset
-    void forget_labels() { obj_label.clear(); obj_flag.clear(); }             // another setter installed the scene in force
+    void forget_labels() { obj_label.clear(); obj_flag.clear(); mem_age.clear(); }   // another setter installed the scene in force
 };

@@ -1,5 +1,5 @@
 // The scene from a depth point cloud or from depth images (omds.h: omds_set_obstacles_from_cloud[_tracked|_objects],
-// omds_set_obstacles_from_depth), as host stages over the launchers of cloud_kernels.h; the state between calls is omds_ctx::cloud
+// omds_set_obstacles_from_depth[_memory]), as host stages over the launchers of cloud_kernels.h; the state between calls is omds_ctx::cloud
 // (cloud_state.h).  One body, scene_from_cloud, for every route.  A route is a choice of three things (CloudCall): tracked or not,
 // objects or not (objects need tracked), and where the points come from.
 //   plain   : count per cell -> ordered compaction of the occupied cells -> the robot self-filter as ONE fp32 pass-1 launch over one
@@ -10,6 +10,8 @@
 //   objects : the tracked one with the components of the final list, into the table that is NOT the stored one, their match against
 //             the stored table and the object velocities over the spheres', between the velocities and the install
 //   depth   : any of the three with the images of up to eight cameras as the point source: no point is ever written
+//   memory  : the plain depth route with one word per cell kept between calls (scene_from_depth_memory, a stage sequence of its own
+//             over the same stages): occluded cells stay, cells a camera looked through leave
 #include "capi_internal.h"
 #include "cloud_kernels.h"
 
@@ -333,6 +335,90 @@ int scene_from_points(omds_ctx* ctx, CloudCall& c, const float* xyz, int64_t n_p
     return scene_from_cloud(ctx, c);
 }
 
+// the checks of a depth call's cameras and images, into depth (whose images, n_cams and on_device the caller has set)
+int resolve_depth_source(omds_ctx* ctx, const char* me, const omds_depth_camera* cams, DepthSource& depth) {
+    REQUIRE(depth.n_cams >= 1 && depth.n_cams <= OMDS_DEPTH_MAX_CAMERAS && cams && depth.images, OMDS_ERR_INVALID_ARG,
+            std::string(me) + ": need 1 <= n_cams <= 8 and non-null cams, images [n_cams]");
+    int64_t visited = 0;
+    for (int i = 0; i < depth.n_cams; ++i) {
+        if (int rc = depth_resolve_camera(cams + i, &depth.cam[i], &ctx->err)) return rc;
+        REQUIRE(depth.images[i], OMDS_ERR_INVALID_ARG, std::string(me) + ": a null image");
+        visited += depth_visited(depth.cam[i]);   // each < 2^62 / 8: no overflow
+    }
+    REQUIRE(visited <= OMDS_CLOUD_MAX_POINTS, OMDS_ERR_INVALID_ARG, std::string(me) + ": more than 16 777 216 visited pixels in all");
+    return OMDS_OK;
+}
+
+// ---- the depth route with the scene memory (omds_set_obstacles_from_depth_memory): a stage sequence of its own beside
+// scene_from_cloud, over the same stages -- count -> k_scene_memory into the buffer that is NOT the stored memory -> compaction of the
+// words that are not 0, with their cells -> the refusal check -> self-filter, and the cells it drops leave the memory -> ages ->
+// install -> commit, behind everything that can fail
+int reserve_memory(omds_ctx* ctx, const CloudCall& c) {
+    CloudState& s = ctx->cloud;
+    const size_t cells = cloud_padded_cells(c.g), m = (size_t)c.g.max_spheres;
+    if (s.mem.next().count() < cells || s.candCell.count() < m || s.keptCell.count() < m || s.age.count() < m || s.memCounts.count() < SCENE_MEM_COUNTS)
+        CK(hipStreamSynchronize(ctx->stream));
+    CK(s.mem.next().reserve(cells));   // written; the stored memory is the other one
+    CK(s.candCell.reserve(m));
+    CK(s.keptCell.reserve(m));
+    CK(s.age.reserve(m));
+    CK(s.memCounts.reserve(SCENE_MEM_COUNTS));
+    return OMDS_OK;
+}
+
+int scene_from_depth_memory(omds_ctx* ctx, const CloudCall& c, const SceneMem& sm, const SceneMemCams& ks, int32_t* counts_out) {
+    const std::string me(c.who);
+    CloudState& s = ctx->cloud;
+    int rc;
+    if (c.q_now) {
+        REQUIRE(ctx->have_mlp, OMDS_ERR_NOT_INITIALISED, me + ": the self-filter needs the distance network (omds_set_mlp)");
+        REQUIRE(!ctx->wide.on, OMDS_ERR_UNSUPPORTED, me + ": no self-filter on networks wider than 256 (no obstacle tables)");
+    }
+    CK(hipSetDevice(ctx->dev));
+    CloudWork w;
+    if ((rc = reserve_base(ctx, c))) return rc;
+    if ((rc = reserve_memory(ctx, c))) return rc;
+    if ((rc = stage_points(ctx, c, w))) return rc;
+    const bool have = s.memKey.same(c.g, sm);   // else: from empty memory, whatever is stored stays until the commit
+    unsigned* next = s.mem.next();
+    CK(hipMemsetAsync(s.count, 0, cloud_padded_cells(c.g) * 4, ctx->stream));
+    CK(hipMemsetAsync(s.memCounts, 0, SCENE_MEM_COUNTS * 4, ctx->stream));
+    enqueue_count(ctx, c, w, s.count.get());
+    if ((rc = prof_begin(ctx))) return rc;   // omds_prof_enable: this route's dominant kernel is k_scene_memory
+    omds_launch_scene_memory(ctx->stream, w.depth, ks, c.src.depth->n_cams, c.g, sm, s.count, have ? s.mem.kept().get() : nullptr, next, s.memCounts);
+    if ((rc = prof_end(ctx, c.g.n_cells, 0.0, "k_scene_memory"))) return rc;
+    omds_launch_cloud_compact_cells(ctx->stream, next, c.g, s.cand, s.candCell, s.sums);
+    unsigned counts[SCENE_MEM_COUNTS] = {0u, 0u, 0u, 0u, 0u};
+    CK(hipMemcpyAsync(counts, s.memCounts, 4 * 4, hipMemcpyDeviceToHost, ctx->stream));
+    w.d_list = s.cand;
+    w.d_cell = s.candCell;
+    if ((rc = compaction_total(ctx, c.g.n_cells, &w.occupied))) return rc;   // = seen + remembered
+    if (counts_out)
+        for (int k = 0; k < SCENE_MEM_COUNTS; ++k) counts_out[k] = (int32_t)counts[k];
+    REQUIRE(w.occupied <= c.g.max_spheres, OMDS_ERR_INVALID_ARG,
+            me + ": more seen and remembered cells than max_spheres (counts_out holds their numbers); the scene and the memory are unchanged");
+    w.n_list = w.occupied;
+    if (c.q_now && w.occupied > 0) {
+        if ((rc = self_filter(ctx, c, w))) return rc;
+        omds_launch_scene_memory_forget(ctx->stream, ctx->d_Dmin, s.candCell, w.occupied, c.spec->self_margin, next, s.memCounts);
+        CK(hipGetLastError());
+        CK(hipMemcpyAsync(counts + SCENE_MEM_FORGOTTEN, s.memCounts + SCENE_MEM_FORGOTTEN, 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    w.n_final = std::max(w.n_list, ctx->cfg.n_closest);
+    std::vector<int32_t> age((size_t)w.n_final, -1);   // padding spheres: -1
+    if (w.n_list > 0) {
+        omds_launch_scene_memory_age(ctx->stream, next, w.d_cell, w.n_list, s.age);
+        CK(hipGetLastError());
+        CK(hipMemcpyAsync(age.data(), s.age, (size_t)w.n_list * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if ((rc = install_scene(ctx, c, w))) return rc;   // synchronises
+    if (counts_out) counts_out[SCENE_MEM_FORGOTTEN] = (int32_t)counts[SCENE_MEM_FORGOTTEN];
+    s.mem_age = std::move(age);
+    s.mem.commit();
+    s.memKey.set(c.g, sm);
+    return OMDS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -396,23 +482,66 @@ int omds_set_obstacles_from_depth(omds_ctx* ctx, const omds_cloud_spec* spec, co
     const char* me = "omds_set_obstacles_from_depth";
     CloudCall c;
     if (int rc = resolve_call(ctx, me, spec, track != nullptr, track, obj != nullptr, obj, &c)) return rc;
-    REQUIRE(n_cams >= 1 && n_cams <= OMDS_DEPTH_MAX_CAMERAS && cams && images, OMDS_ERR_INVALID_ARG,
-            std::string(me) + ": need 1 <= n_cams <= 8 and non-null cams, images [n_cams]");
     DepthSource depth;
     depth.images = images;
     depth.n_cams = n_cams;
     depth.on_device = images_on_device;
-    int64_t visited = 0;
-    for (int i = 0; i < n_cams; ++i) {
-        if (int rc = depth_resolve_camera(cams + i, &depth.cam[i], &ctx->err)) return rc;
-        REQUIRE(images[i], OMDS_ERR_INVALID_ARG, std::string(me) + ": a null image");
-        visited += depth_visited(depth.cam[i]);   // each < 2^62 / 8: no overflow
-    }
-    REQUIRE(visited <= OMDS_CLOUD_MAX_POINTS, OMDS_ERR_INVALID_ARG, std::string(me) + ": more than 16 777 216 visited pixels in all");
+    if (int rc = resolve_depth_source(ctx, me, cams, depth)) return rc;
     c.src = PointSource{nullptr, 0, 0, &depth};
     c.q_now = q_now;
     c.out = CloudOuts{n_spheres_out, n_occupied_out, n_matched_out, n_objects_out, n_objects_matched_out};
     return scene_from_cloud(ctx, c);
+}
+
+int omds_depth_scene_memory(const omds_cloud_spec* spec, const omds_scene_memory_spec* mem_spec, const omds_depth_camera* cams,
+                            const void* const* images, int32_t n_cams, const uint32_t* mem_in, uint32_t* mem_out, int32_t counts_out[4]) {
+    return scene_memory_host(spec, mem_spec, cams, images, n_cams, mem_in, mem_out, counts_out, &g_create_err);
+}
+
+int omds_set_obstacles_from_depth_memory(omds_ctx* ctx, const omds_cloud_spec* spec, const omds_scene_memory_spec* mem_spec,
+                                         const omds_depth_camera* cams, const void* const* images, int32_t n_cams, int images_on_device,
+                                         const float* q_now, int32_t* n_spheres_out, int32_t counts_out[5]) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    const char* me = "omds_set_obstacles_from_depth_memory";
+    CloudCall c;
+    SceneMem sm;
+    if (int rc = resolve_call(ctx, me, spec, false, nullptr, false, nullptr, &c)) return rc;
+    if (int rc = scene_memory_resolve(mem_spec, c.g, &sm, &ctx->err)) return rc;
+    DepthSource depth;
+    depth.images = images;
+    depth.n_cams = n_cams;
+    depth.on_device = images_on_device;
+    if (int rc = resolve_depth_source(ctx, me, cams, depth)) return rc;
+    SceneMemCams ks;
+    std::memset(static_cast<void*>(&ks), 0, sizeof(ks));
+    for (int i = 0; i < n_cams; ++i) ks.k[i] = scene_memory_camera(cams[i], depth.cam[i]);
+    c.src = PointSource{nullptr, 0, 0, &depth};
+    c.q_now = q_now;
+    c.out = CloudOuts{n_spheres_out, nullptr, nullptr, nullptr, nullptr};
+    return scene_from_depth_memory(ctx, c, sm, ks, counts_out);
+}
+
+int omds_scene_memory_reset(omds_ctx* ctx) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    ctx->cloud.memKey.grid.have = false;
+    return OMDS_OK;
+}
+
+int omds_get_scene_memory(omds_ctx* ctx, int32_t* age, uint32_t* grid, int32_t* n_cells_out) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    CloudState& s = ctx->cloud;
+    const bool have = s.memKey.grid.have;
+    if (n_cells_out) *n_cells_out = have ? s.memKey.n_cells : 0;
+    if (age && ctx->n_obs > 0) {
+        if (s.mem_age.size() == (size_t)ctx->n_obs) std::memcpy(age, s.mem_age.data(), (size_t)ctx->n_obs * 4);
+        else std::fill(age, age + ctx->n_obs, -1);
+    }
+    if (grid && have) {
+        CK(hipSetDevice(ctx->dev));
+        CK(hipMemcpyAsync(grid, s.mem.kept(), (size_t)s.memKey.n_cells * 4, hipMemcpyDeviceToHost, ctx->stream));
+        CK(hipStreamSynchronize(ctx->stream));
+    }
+    return OMDS_OK;
 }
 
 int omds_get_cloud_objects(omds_ctx* ctx, int32_t* label, int32_t* object, int32_t* n_objects_out) {

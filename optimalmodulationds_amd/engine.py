@@ -159,39 +159,60 @@ class Engine:
         tensors on the engine's device (``uint16``; ``int16``, reinterpreted; ``float32``), which are read in place -- rows need not
         be contiguous as long as the last dimension has stride 1 (the camera's ``pitch`` is then taken from the row stride).  ``cams``:
         ``OmdsDepthCamera`` s (``depth_camera`` builds one); shape and format must be the image's."""
-        if isinstance(cams, L.OmdsDepthCamera):
-            images, cams = [images], [cams]
-        images, cams = list(images), list(cams)
-        if len(images) != len(cams):
-            raise ValueError(f"set_obstacles_from_depth: {len(images)} images but {len(cams)} cameras")
-        n = len(cams)
-        table = (L.OmdsDepthCamera * max(n, 1))()
-        addrs = (C.c_void_p * max(n, 1))()
-        on_dev = [hasattr(im, "data_ptr") and im.is_cuda for im in images]
-        if n and any(on_dev) != all(on_dev):
-            raise ValueError("set_obstacles_from_depth: the images must all be on the host or all on the engine's device")
-        keep = []
-        for i, (im, cam) in enumerate(zip(images, cams)):
-            C.memmove(C.byref(table[i]), C.byref(cam), C.sizeof(L.OmdsDepthCamera))
-            if im is None:
-                continue                      # a null image: the library refuses the call
-            im, addr, pitch = _depth_image(im, cam, self.device)
-            keep.append(im)
-            addrs[i] = addr
-            if pitch is not None:
-                table[i].pitch = pitch
-        if n and all(on_dev):
-            import torch
-            torch.cuda.current_stream(self.device).synchronize()      # the library reads the images on its own stream
+        table, addrs, n, on_dev, keep = _depth_table("set_obstacles_from_depth", images, cams, self.device)
         qn = None if q is None else L.f32(q).reshape(self.n)
         n_sph, n_occ, n_match = np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32)
         n_objects, n_objects_matched = np.zeros(1, np.int32), np.zeros(1, np.int32)
         rc = self.lib.omds_set_obstacles_from_depth(self.h, C.byref(spec), None if track is None else C.byref(track),
-                                                    None if obj is None else C.byref(obj), table, addrs, n, 1 if n and all(on_dev) else 0,
+                                                    None if obj is None else C.byref(obj), table, addrs, n, on_dev,
                                                     L.fptr(qn), L.iptr(n_sph), L.iptr(n_occ), L.iptr(n_match), L.iptr(n_objects),
                                                     L.iptr(n_objects_matched))
         out = self._scene_call_done(rc, qn, obj, n_sph, n_occ, n_match, n_objects, n_objects_matched)
         return out[:2] if track is None else out
+
+    # ---- the scene memory of the depth route (omds.h: THE SCENE MEMORY OF THE DEPTH ROUTE) ---------------------------------------------
+    def set_obstacles_from_depth_memory(self, images, cams, spec, mem, q=None):
+        """``set_obstacles_from_depth`` (the plain route) with a memory of occupancy between calls: a cell that got no points this call
+        stays in the scene unless a camera looked through it (a return farther than the cell by ``mem.clear_margin``), it is older
+        than ``mem.max_age`` calls, or the self-filter at ``q`` drops it -> (n_spheres before padding, counts): ``counts`` the cells
+        (seen, remembered, cleared, expired, self-forgotten) as a tuple.  ``images``, ``cams``, ``spec``, ``q`` as there; ``mem``: an
+        ``OmdsSceneMemorySpec`` (``scene_memory_spec`` builds one).  Installs a static scene.  More seen and remembered cells than
+        ``spec.max_spheres`` raises with scene and memory unchanged; the error carries ``counts`` and ``n_occupied``."""
+        table, addrs, n, on_dev, keep = _depth_table("set_obstacles_from_depth_memory", images, cams, self.device)
+        qn = None if q is None else L.f32(q).reshape(self.n)
+        n_sph, counts = np.zeros(1, np.int32), np.zeros(5, np.int32)
+        rc = self.lib.omds_set_obstacles_from_depth_memory(self.h, C.byref(spec), C.byref(mem), table, addrs, n, on_dev, L.fptr(qn),
+                                                           L.iptr(n_sph), L.iptr(counts))
+        n_obs = np.zeros(1, np.int32)
+        self.lib.omds_get_obstacles(self.h, None, L.iptr(n_obs))      # also after a failure: the context may have dropped its scene
+        self.n_obs = int(n_obs[0])
+        self.max_obs = max(self.max_obs, self.n_obs, int(counts[0] + counts[1]) if (rc == 0 and qn is not None) else 0)
+        try:
+            self._ck(rc)
+        except L.OmdsError as e:
+            e.counts = tuple(int(v) for v in counts)
+            e.n_occupied = int(counts[0] + counts[1])
+            raise
+        return int(n_sph[0]), tuple(int(v) for v in counts)
+
+    def scene_memory_reset(self):
+        """Forget the stored scene memory: the next ``set_obstacles_from_depth_memory`` starts from an empty one."""
+        self._ck(self.lib.omds_scene_memory_reset(self.h))
+
+    def get_scene_memory(self, grid=False):
+        """age [n_obs] (int32) of the scene in force: calls since each sphere's cell was last counted (0: seen in the installing call),
+        -1 for a padding sphere and everywhere when another setter installed the scene.  ``grid=True``: (age, words) with the stored
+        memory words [cells] (uint32; 0 empty, k: last counted k - 1 calls ago), empty when no memory is stored."""
+        n_obs, n_cells = np.zeros(1, np.int32), np.zeros(1, np.int32)
+        self._ck(self.lib.omds_get_obstacles(self.h, None, L.iptr(n_obs)))
+        age = np.full(max(int(n_obs[0]), 1), -1, np.int32)
+        self._ck(self.lib.omds_get_scene_memory(self.h, L.iptr(age), None, L.iptr(n_cells)))
+        age = age[:int(n_obs[0])]
+        if not grid:
+            return age
+        words = np.zeros(max(int(n_cells[0]), 1), np.uint32)
+        self._ck(self.lib.omds_get_scene_memory(self.h, None, words.ctypes.data, None))
+        return age, words[:int(n_cells[0])]
 
     def cloud_track_reset(self):
         """Forget the previous tracked frame: the next ``set_obstacles_from_cloud_tracked`` stores its own and sets no velocities."""
@@ -809,6 +830,68 @@ def _depth_image(im, cam, device=None):
     if flat.size < (shape[0] - 1) * pitch + shape[1]:
         raise ValueError(f"depth image: {flat.size} elements, the camera needs {(shape[0] - 1) * pitch + shape[1]}")
     return flat, flat.ctypes.data, None
+
+
+def _depth_table(who, images, cams, device=None):
+    """(camera table, image addresses, n_cams, images_on_device, objects to keep alive) of a depth call; ``device`` None: host images
+    only.  A single image and camera may be passed bare; a strided image puts its row stride into the table's pitch."""
+    if isinstance(cams, L.OmdsDepthCamera):
+        images, cams = [images], [cams]
+    images, cams = list(images), list(cams)
+    if len(images) != len(cams):
+        raise ValueError(f"{who}: {len(images)} images but {len(cams)} cameras")
+    n = len(cams)
+    table = (L.OmdsDepthCamera * max(n, 1))()
+    addrs = (C.c_void_p * max(n, 1))()
+    on_dev = [hasattr(im, "data_ptr") and im.is_cuda for im in images]
+    if n and any(on_dev) != all(on_dev):
+        raise ValueError(f"{who}: the images must all be on the host or all on the engine's device")
+    if device is None and any(on_dev):
+        raise ValueError(f"{who}: host images only")
+    keep = []
+    for i, (im, cam) in enumerate(zip(images, cams)):
+        C.memmove(C.byref(table[i]), C.byref(cam), C.sizeof(L.OmdsDepthCamera))
+        if im is None:
+            continue                      # a null image: the library refuses the call
+        im, addr, pitch = _depth_image(im, cam, device)
+        keep.append(im)
+        addrs[i] = addr
+        if pitch is not None:
+            table[i].pitch = pitch
+    if n and all(on_dev):
+        import torch
+        torch.cuda.current_stream(device).synchronize()      # the library reads the images on its own stream
+    return table, addrs, n, (1 if n and all(on_dev) else 0), keep
+
+
+def scene_memory_spec(max_age, clear_margin=0.0, footprint=0):
+    """An ``OmdsSceneMemorySpec``: a cell unseen for more than ``max_age`` calls is dropped (< 1: never); a camera clears an unseen cell
+    when every pixel within ``footprint`` (0 .. 3) visited pixels of the cell centre's projection returns from more than
+    ``clear_margin`` metres behind it (<= 0: the grid's sphere radius)."""
+    m = L.OmdsSceneMemorySpec()
+    m.max_age, m.clear_margin, m.footprint = int(max_age), float(clear_margin), int(footprint)
+    return m
+
+
+def depth_scene_memory(images, cams, spec, mem, mem_in=None):
+    """The definition of the scene memory on the host (omds_depth_scene_memory, no GPU, no self-filter): the depth images of one call
+    and the stored words ``mem_in`` [cells] (uint32; None: all empty) -> (words [cells] uint32, (seen, remembered, cleared, expired))."""
+    lib = L.load()
+    table, addrs, n, _, keep = _depth_table("depth_scene_memory", images, cams)
+    cells = max(int(spec.dims[0]), 0) * max(int(spec.dims[1]), 0) * max(int(spec.dims[2]), 0)
+    if cells > 1 << 22:
+        cells = 0                         # more than the library takes: it refuses the call
+    src = None
+    if mem_in is not None:
+        src = np.ascontiguousarray(mem_in, np.uint32).reshape(-1)
+        if src.size != cells:
+            raise ValueError(f"depth_scene_memory: mem_in must hold {cells} words, got {src.size}")
+    out, counts = np.zeros(max(cells, 1), np.uint32), np.zeros(4, np.int32)
+    rc = lib.omds_depth_scene_memory(C.byref(spec), C.byref(mem), table, addrs, n, None if src is None else src.ctypes.data, out.ctypes.data,
+                                     L.iptr(counts))
+    if rc != 0:
+        raise L.OmdsError(f"omds_depth_scene_memory failed ({rc}): {lib.omds_last_error(None).decode()}")
+    return out[:cells], tuple(int(v) for v in counts)
 
 
 def depth_points(image, cam):

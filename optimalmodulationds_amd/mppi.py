@@ -95,6 +95,7 @@ class MPPI:
         self.Policy._owner = self
         self.Cost = Cost(self.qf, self.dh_params, owner=self)
         self.obs_focus = None         # focus_obstacles: the master index of every sphere of self.obs, else None
+        self.obs_age = None           # update_obstacles_from_depth(memory=): calls since every sphere's cell was last counted, else None
         self.cur_cost = None
         self._cache = {}
         self._generation = 0          # propagate() calls so far (LazyRollout tensors belong to one of them)
@@ -137,6 +138,7 @@ class MPPI:
         # so the handle -- network, samples, RCCL communicator, screening state -- survives
         self._engine.set_obstacles(self.obs.numpy())
         self.obs_focus = None                        # (and ended an obstacle focus)
+        self.obs_age = None
         self._max_obs = self._engine.max_obs
         if vel is not None:                          # (set_obstacles cleared the previous motion)
             self._engine.set_obstacle_motion(vel)
@@ -167,15 +169,35 @@ class MPPI:
             voxel, lo, hi, radius, self_margin, min_points, max_spheres, dt_frame, reach, still, moving_frame, objects, link, min_cells)
 
     def update_obstacles_from_depth(self, images, cameras, voxel, lo, hi, radius=None, self_margin=None, min_points=1, max_spheres=4096,
-                                    dt_frame=None, reach=2, still=0.0, moving_frame=False, objects=False, link=1, min_cells=4):
+                                    dt_frame=None, reach=2, still=0.0, moving_frame=False, objects=False, link=1, min_cells=4, **route):
         """``update_obstacles_from_cloud`` straight from depth images (new here): ``images`` [H, W] one per camera (numpy ``uint16`` /
         ``float32``, or torch tensors on the engine's device, read in place) and ``cameras`` their ``OmdsDepthCamera`` s
         (``engine.depth_camera``: intrinsics, range gate, pose in the frame of ``lo`` .. ``hi``).  The pixels are deprojected inside the
         counting pass on the device (Engine.set_obstacles_from_depth); everything else -- arguments, routes, return value and the
-        attributes set -- is ``update_obstacles_from_cloud`` on the points of the images, bit for bit."""
-        return self._update_obstacles_sensed("update_obstacles_from_depth", lambda e, spec, q, track, obj: (
-            e.set_obstacles_from_depth(images, cameras, spec, q, track, obj)),
-            voxel, lo, hi, radius, self_margin, min_points, max_spheres, dt_frame, reach, still, moving_frame, objects, link, min_cells)
+        attributes set -- is ``update_obstacles_from_cloud`` on the points of the images, bit for bit.
+        ``memory`` (an ``OmdsSceneMemorySpec``, or a dict of ``engine.scene_memory_spec``'s arguments): the route with a memory of
+        occupancy between calls (Engine.set_obstacles_from_depth_memory) -- a cell without points stays in the scene unless a camera
+        looked through it, it is older than ``max_age`` calls or the self-filter drops it.  Returns (spheres before padding, (seen,
+        remembered, cleared, expired, self-forgotten)); ``self.obs_age`` then holds, per sphere, the calls since its cell was last
+        counted (-1: padding), and is None after every other call.  A static scene: not together with ``dt_frame`` or ``objects``.
+        (``memory`` is the one keyword ``**route`` takes, default None: the named keywords stay those of
+        ``update_obstacles_from_cloud``, which has no cameras to ask.)"""
+        memory = route.pop("memory", None)
+        if route:
+            raise TypeError(f"update_obstacles_from_depth: unexpected keyword arguments {sorted(route)}")
+        if memory is None:
+            return self._update_obstacles_sensed("update_obstacles_from_depth", lambda e, spec, q, track, obj: (
+                e.set_obstacles_from_depth(images, cameras, spec, q, track, obj)),
+                voxel, lo, hi, radius, self_margin, min_points, max_spheres, dt_frame, reach, still, moving_frame, objects, link, min_cells)
+        if dt_frame is not None or objects:
+            raise ValueError("update_obstacles_from_depth: memory= installs a static scene; not together with dt_frame or objects")
+        from .engine import scene_memory_spec
+        mem = scene_memory_spec(**memory) if isinstance(memory, dict) else memory
+        out = self._update_obstacles_sensed("update_obstacles_from_depth", lambda e, spec, q, track, obj: (
+            e.set_obstacles_from_depth_memory(images, cameras, spec, mem, q)),
+            voxel, lo, hi, radius, self_margin, min_points, max_spheres, None, reach, still, moving_frame, False, link, min_cells)
+        self.obs_age = torch.as_tensor(self._engine.get_scene_memory())
+        return out
 
     def _update_obstacles_sensed(self, who, install, voxel, lo, hi, radius, self_margin, min_points, max_spheres, dt_frame, reach, still,
                                  moving_frame, objects, link, min_cells):
@@ -194,6 +216,7 @@ class MPPI:
         self.obs_velocities, self.cloud_matched = None, None
         self.cloud_objects, self.cloud_objects_matched = None, None
         self.obs_focus = None                        # a scene setter ends an obstacle focus
+        self.obs_age = None                          # ... and only the memory route says how old a sphere is
         if dt_frame is None:
             out = install(self._engine, spec, q, None, None)
         else:
@@ -239,6 +262,7 @@ class MPPI:
         self.obs_velocities = torch.as_tensor(vel) if have else None
         idx = self._engine.obstacle_focus()
         self.obs_focus = None if idx is None else torch.as_tensor(idx)
+        self.obs_age = None                          # the ages belong to the scene the memory call installed
 
     def set_screening(self, mode, eps=0.0, over_horizon=False):
         """The screened pass 1 (Engine.set_screening: mode -1 | 0 | 1 | 2, ``eps`` as there); ``over_horizon``: also while
