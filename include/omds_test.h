@@ -1,8 +1,8 @@
 /*
  * omds_test.h -- test hooks of the MI355X-native MPPI rollout path.  NOT part of the product ABI: libomds_hip.so does not export
- * them.  They exist in libomds_hip_test.so (`make test-lib`: the same objects except mlp_pack, screening, tail_kernel and train, which are compiled
- * with -DOMDS_TEST_HOOKS; the sin / cos hooks live beside k_encode in train.hip; the raw Philox hook is csrc/philox_test.hip and the top-k hook
- * csrc/select_test.hip, files that only the test library links), which tests/ load explicitly (optimalmodulationds_amd._lib.load_test_hooks()).  Neither
+ * them.  They exist in libomds_hip_test.so (`make test-lib`: the same objects except mlp_pack, screening, tail_kernel, propagate and train -- the
+ * trainer's host side; its kernels are train_kernels.hip -- which are compiled with -DOMDS_TEST_HOOKS; the sin / cos hooks are csrc/trig_test.hip,
+ * the raw Philox hook csrc/philox_test.hip and the top-k hook csrc/select_test.hip, files that only the test library links), which tests/ load explicitly (optimalmodulationds_amd._lib.load_test_hooks()).  Neither
  * library reads experiment environment variables.
  */
 #ifndef OMDS_TEST_H

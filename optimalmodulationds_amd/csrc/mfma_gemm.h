@@ -1,5 +1,5 @@
 // The fp32 MFMA GEMM cores of the distance-network kernels (32x32x2: gemm256, gemm_k32; 16x16x4: gemm16, gemm16_k32; 4-row groups: W4Ring, gemm4), their
-// C-layout helpers and the tile geometry (Geo).  Included by the pass-1 and pass-2 headers, and on its own by train.hip (gemm256) and tools/ubench/gemm_loop.hip.
+// C-layout helpers and the tile geometry (Geo).  Included by the pass-1 and pass-2 headers, and on its own by train_kernels.hip (f32x16, LDH) and tools/ubench/gemm_loop.hip.
 #pragma once
 #include "omds_internal.h"
 

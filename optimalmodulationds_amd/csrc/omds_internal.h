@@ -510,7 +510,8 @@ void omds_launch_blend(hipStream_t s, const float* gradx, const float* drow, int
 void omds_launch_approach_rate(hipStream_t s, const float* gradx, const float* drow, const int32_t* idx, const float* vel, int ldv,
                                int B, int k, int d, int n, float softmax_k, float max_speed, float* rate, float* qo);
 
-// ---- train.hip: the trainer's exact-fp32 MFMA GEMM, for callers outside the trainer (wide_kernels.hip) -------------------
+// ---- train_kernels.hip: the trainer's exact-fp32 MFMA GEMM, for callers outside the trainer (wide_kernels.hip); the trainer's own
+// launchers are train_kernels.h's ------------------------------------------------------------------------------------------
 // Out [B][out] = act(H [B][in] . W^T + b), W [out][in] row-major like torch; act: OMDS_ACT_* or -1 (none)
 void omds_launch_linear_forward(hipStream_t s, const float* H, int in, const float* W, const float* b, float* Out, int out, int B, int act);
 // Gi [B][in] = (G [B][out] . W) * act'(Hact [B][in]); Hact == nullptr: no derivative factor

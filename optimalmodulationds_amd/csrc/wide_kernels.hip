@@ -3,7 +3,7 @@
 // MLPRegression is width-agnostic (network_macros_mod.py:96-135); every network the reference ships is 256 (or 128) wide and runs on
 // the fused LDS-resident MFMA kernels of this library.  A network with a wider hidden layer (<= 4096) takes THIS path: the
 // reference's own unfused op sequence (MPPI.py:227-282, robot_sdf.py:153-158) on the exact-fp32 MFMA GEMM of the trainer
-// (train.hip: k_gemm, 128 x 128 tiles, operands through LDS), with the activations of a layer materialised in HBM -- 288 GB make
+// (train_kernels.hip: k_gemm, 128 x 128 tiles, operands through LDS), with the activations of a layer materialised in HBM -- 288 GB make
 // that affordable, and it is the honest shape for a layer that does not fit a CU's LDS tile:
 //   pass 1   chunks of <= 65536 (rollout, obstacle) pairs: [x, sin x, cos x] -> Linear + act ... -> Linear (GEMM per layer, bias +
 //            activation fused into the stores) -> min over the un-ignored links of y / out_div - radius -> Dmin

@@ -13,13 +13,9 @@ eps sqrt(n), the same order.  The yardstick is 2.4e-7 (its floor) to 9e-7 on the
 device has been seen at 2.1 x the yardstick at most (EXPERIMENTS.md R13).  One dropped row of 3001 is 3e-4, of 49 153 2e-5; the
 faults seeded in tests/test_train_grad_cpu.py exceed the bar 3 800-fold and more.
 
-Routes (forward() and omds_trainer_step() of train.hip), per layer in -> out:
-  forward          k_gemm_thin in <= 32 and 64 <= out <= 256; k_gemm_thin_out out <= 16 and 32 < in <= 256; k_gemm_tall in == 256
-                   and 128 < out <= 256; else k_gemm
-  weight gradient  k_wgrad_thin<4 | 12 | 16 | 32> (by the thin width T) when in <= 32 < out (first-layer form) or out <= 32 < in
-                   (last-layer form); else k_gemm split over the batch
-  input gradient   k_gemm_thin out <= 32 and 64 <= in <= 256; k_gemm_tall out == 256 and 128 < in <= 256; else k_gemm
-The cases below name what each reaches.  Every case is also run with every product on k_gemm (the test library's
+Routes: which kernel multiplies a layer's forward, weight gradient and input gradient, and how the batch is split, is stated in
+optimalmodulationds_amd/csrc/train_plan_def.h and nowhere else.  The cases below name what each reaches;
+tests/test_train_plan_cpu.py holds every case to the routes it names and pins the split numbers.  Every case is also run with every product on k_gemm (the test library's
 omds_debug_trainer_general_gemm) and must give the same bits: the bit-for-bit claim of tests/test_gpu_train.py at every shape here."""
 import functools
 
@@ -52,7 +48,7 @@ CASES = (
         # C5: a hidden bottleneck: thin forward 20 -> 256, thin input gradient 256 <- 20, k_wgrad_thin<32> (T = 20) in both forms
         ("C5", [30, 256, 20, 256, 9], "tanh", 193, "random"),
         # C6: 769 row tiles on 256 CUs: a persistent k_gemm_tall workgroup runs 3 to 4 tiles, both LDS buffers turn from parked
-        # output to next input; 256 splits of 208 rows, rsplit 192
+        # output to next input; 237 chunks of 208 rows (the last one 65), rsplit 192
         ("C6", SHIPPED, "relu", 3 * 64 * 256 + 1, "random"),
         # C7: in = 33 > THIN_KMAX and out = 17 > THINN_NMAX on k_gemm; k_wgrad_thin<32> with T = 17; thin input gradient K = 17, N = 200
         ("C7", [33, 130, 200, 17], "relu", 257, "random"),
