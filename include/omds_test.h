@@ -2,7 +2,7 @@
  * omds_test.h -- test hooks of the MI355X-native MPPI rollout path.  NOT part of the product ABI: libomds_hip.so does not export
  * them.  They exist in libomds_hip_test.so (`make test-lib`: the same objects except mlp_pack, screening, tail_kernel, propagate and train -- the
  * trainer's host side; its kernels are train_kernels.hip -- which are compiled with -DOMDS_TEST_HOOKS; the sin / cos hooks are csrc/trig_test.hip,
- * the raw Philox hook csrc/philox_test.hip and the top-k hook csrc/select_test.hip, files that only the test library links), which tests/ load explicitly (optimalmodulationds_amd._lib.load_test_hooks()).  Neither
+ * the raw Philox hook csrc/philox_test.hip, the top-k hook csrc/select_test.hip and the one-step modulation hook csrc/modulate_test.hip, files that only the test library links), which tests/ load explicitly (optimalmodulationds_amd._lib.load_test_hooks()).  Neither
  * library reads experiment environment variables.
  */
 #ifndef OMDS_TEST_H
@@ -51,6 +51,34 @@ OMDS_API int omds_test_philox(const uint32_t* ctr /*[n][4]*/, const uint32_t* ke
  * as it does on the pass-1 matrix, and idx_out[b][j] = the index of the j-th smallest entry of row b under the rule at the top of
  * topk_device.h.  1 <= k <= O.  (csrc/select_test.hip, a file that only the test library links.)                                */
 OMDS_API int omds_test_topk(const float* rows /*[B][O]*/, int B, int O, int k, int32_t* idx_out /*[B][k]*/);
+/* ONE horizon step `step` of the per-rollout modulation (csrc/step_device.h: modulate_core, everything of a step behind the distance
+ * network) on caller-supplied inputs, with no network and no context, for tests/test_gpu_step_edges.py.  nsub = 1: the production
+ * launcher omds_launch_modulate (k_modulate, n_dof = 1..7, the only caller with the SEDS branch); nsub = 16: a small kernel of
+ * csrc/modulate_test.hip (a file that only the test library links) that calls modulate_core with 16 lanes per rollout the way the
+ * fused step kernels do, n_dof = 2 or 7, no SEDS.  All arrays are host memory in the DEVICE's layouts (rollout index fastest).  Every
+ * output buffer of the device is pre-filled with the byte 0xFF, so what the step did not write reads back as the bits 0xFFFFFFFF:
+ * q_next is slab `step` of the rollouts (left alone at step == H), qdot is written at step 1 only.  maxact / phisum0 go in with
+ * their previous contents and come back as the step left them.  OMDS_ERR_INVALID_ARG, before anything is launched: a size < 1,
+ * n_dof > 7, nsub not 1 or 16, k > 32 (the fused tails' maximum), K > Kmax, d < n_dof or > 16, step outside 1..H, H > 64,
+ * N > 2^16, Kmax > 2^10, rbf_p <= 0, a null array that the step reads or writes, seds_G outside 0..64 (or with A), nsub = 16 with
+ * another n_dof or with SEDS, and with frame != 0: O outside 1..2^16, ldVel < d - n_dof or > 8, frame_max negative or NaN, a rowObs
+ * entry outside [0, O).                                                                                                          */
+typedef struct omds_test_modulate_args {
+    int32_t n_dof, nsub, N, K, Kmax, k, d, step, H;
+    int32_t frame, O, ldVel, seds_G;
+    float frame_max, seds_lin_thr, seds_thr;
+    omds_params prm;
+    const float* qf;                 /* [n]                                                                        */
+    const float* A;                  /* [n][n] matrix DS (velocity = (q - qf) @ A), NULL = linear                    */
+    const float *seds_mu_in, *seds_b, *seds_sigma_inv, *seds_A, *seds_prior, *seds_den;   /* as omds_set_ds_seds takes them; seds_G > 0 */
+    const float* vel;                /* [O][ldVel]; frame only                                                     */
+    const int32_t* rowObs;           /* [N][k] obstacle of every gradient row; frame only                          */
+    const float *q, *drow, *gradx;   /* [n][N], [N][k], [N][k][d]                                                  */
+    const float *mu, *sigma, *alpha; /* [K][n][N], [K][N], [K][n][N]; K > 0                                        */
+    float *maxact, *phisum0;         /* in / out: [Kmax][N], [Kmax]                                                */
+    float *q_next, *qdot, *dist, *dot, *act, *normal, *kval;   /* out: [n][N], [n][N], [N], [N], [N], [n][N], [Kmax][N] */
+} omds_test_modulate_args;
+OMDS_API int omds_test_modulate(const omds_test_modulate_args* args);
 
 #ifdef __cplusplus
 }

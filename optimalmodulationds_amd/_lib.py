@@ -94,6 +94,15 @@ class OmdsObstacleFocusSpec(C.Structure):
     _fields_ = [("margin", C.c_float), ("lookahead", C.c_float), ("max_keep", C.c_int32)]
 
 
+class OmdsTestModulateArgs(C.Structure):
+    """omds_test_modulate_args (include/omds_test.h): one horizon step of the modulation on caller-supplied inputs."""
+    _fields_ = ([(f, C.c_int32) for f in ("n_dof", "nsub", "N", "K", "Kmax", "k", "d", "step", "H", "frame", "O", "ldVel", "seds_G")]
+                + [(f, C.c_float) for f in ("frame_max", "seds_lin_thr", "seds_thr")] + [("prm", OmdsParams)]
+                + [(f, C.c_void_p) for f in ("qf", "A", "seds_mu_in", "seds_b", "seds_sigma_inv", "seds_A", "seds_prior", "seds_den", "vel",
+                                             "rowObs", "q", "drow", "gradx", "mu", "sigma", "alpha", "maxact", "phisum0", "q_next", "qdot",
+                                             "dist", "dot", "act", "normal", "kval")])
+
+
 class OmdsError(RuntimeError):
     pass
 
@@ -232,6 +241,7 @@ TEST_HOOK_SIGNATURES = {
     "omds_test_trig_sweep": (C.c_int, [C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64)]),
     "omds_test_philox": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "omds_test_topk": (C.c_int, [F32P, C.c_int, C.c_int, C.c_int, I32P]),
+    "omds_test_modulate": (C.c_int, [C.POINTER(OmdsTestModulateArgs)]),
 }
 # include/omds_test_tiles.h: the hooks of the block-ordered pass 1, in the test library likewise
 TILE_HOOK_SIGNATURES = {
@@ -301,7 +311,7 @@ def load_test_hooks():
     """libomds_hip_test.so: the product's objects plus the hooks of include/omds_test.h (damage the screening inputs, force a tile
     shape, the trainer's general GEMM, the host half of omds_set_mlp_ex, the encoding's sin / cos, the raw words of the device's
     Philox4x32-10: omds_test_philox(ctr [n, 4] uint32, key [n, 2] uint32, out [n, 4] uint32, n), the top-k selection on given rows:
-    ``select_topk`` below).  For tests only:
+    ``select_topk`` below, one step of the modulation on given inputs: ``modulate_step`` below).  For tests only:
     ``Engine(..., lib=load_test_hooks())``."""
     return load(TEST_LIB_PATH, dict(TEST_HOOK_SIGNATURES, **TILE_HOOK_SIGNATURES, **HORIZON_HOOK_SIGNATURES))
 
@@ -316,6 +326,63 @@ def select_topk(rows, k):
     if rc != 0:
         raise OmdsError(f"omds_test_topk failed ({rc})")
     return idx
+
+
+def modulate_step(*, nsub, step, H, prm, qf, q, drow, gradx, mu, sigma, alpha, Kmax, maxact=None, phisum0=None, A=None, seds=None,
+                  frame=False, frame_max=1.0, vel=None, row_obs=None, check=True):
+    """omds_test_modulate (include/omds_test.h): ONE horizon step of the per-rollout modulation on the device, in the reference's
+    layouts: q [N, n], drow [N, k], gradx [N, k, d], mu / alpha [N, K, n], sigma [N, K], the previous maxact [N, Kmax] and phisum0
+    [Kmax] (None: the bits 0xFFFFFFFF), prm an OmdsParams, seds the keyword arguments of Engine.set_ds_seds, vel [O, ldVel] and
+    row_obs [N, k] with ``frame``.  -> dict of float32 arrays q_next, qdot, normal [N, n], dist, dot, act [N], kval, maxact [N, Kmax],
+    phisum0 [Kmax]; what the step did not write holds the bits 0xFFFFFFFF.  ``check`` False: returns the status code instead of
+    raising.  Needs no context; loads the test library."""
+    f32 = lambda x: np.ascontiguousarray(x, dtype=np.float32)
+    q, drow, gradx, qf = f32(q), f32(drow), f32(gradx), f32(qf)
+    N, n = q.shape
+    k, d = gradx.shape[1], gradx.shape[2]
+    assert drow.shape == (N, k) and gradx.shape[0] == N and qf.shape == (n,)
+    mu, sigma, alpha = f32(mu), f32(sigma), f32(alpha)
+    K = sigma.shape[1]
+    assert mu.shape == (N, K, n) and alpha.shape == (N, K, n) and sigma.shape == (N, K)
+    sentinel = lambda *shape: np.full(shape, 0xFFFFFFFF, np.uint32).view(np.float32)
+    keep = [f32(mu.transpose(1, 2, 0)), f32(sigma.T), f32(alpha.transpose(1, 2, 0)), f32(q.T),
+            sentinel(Kmax, N) if maxact is None else f32(np.asarray(maxact, np.float32).T),
+            sentinel(Kmax) if phisum0 is None else f32(phisum0).copy()]
+    muT, sigmaT, alphaT, qT, maxactT, ph0 = keep
+    assert maxactT.shape == (Kmax, N) and ph0.shape == (Kmax,)
+    out = dict(q_next=np.zeros((n, N), np.float32), qdot=np.zeros((n, N), np.float32), dist=np.zeros(N, np.float32),
+               dot=np.zeros(N, np.float32), act=np.zeros(N, np.float32), normal=np.zeros((n, N), np.float32),
+               kval=np.zeros((Kmax, N), np.float32))
+    a = OmdsTestModulateArgs(n_dof=n, nsub=nsub, N=N, K=K, Kmax=Kmax, k=k, d=d, step=step, H=H, frame=int(bool(frame)), frame_max=frame_max,
+                             prm=prm, qf=qf.ctypes.data, q=qT.ctypes.data, drow=drow.ctypes.data, gradx=gradx.ctypes.data,
+                             mu=muT.ctypes.data if K else None, sigma=sigmaT.ctypes.data if K else None,
+                             alpha=alphaT.ctypes.data if K else None, maxact=maxactT.ctypes.data, phisum0=ph0.ctypes.data,
+                             **{name: arr.ctypes.data for name, arr in out.items()})
+    if A is not None:
+        A = f32(A)
+        assert A.shape == (n, n)
+        a.A = A.ctypes.data
+    if seds is not None:
+        sd = {name: f32(seds[name]) for name in ("mu_in", "b", "sigma_inv", "A", "prior", "den")}
+        G = sd["prior"].shape[0]
+        assert sd["mu_in"].shape == (G, n) and sd["b"].shape == (G, n) and sd["sigma_inv"].shape == (G, n, n) and sd["A"].shape == (G, n, n) \
+            and sd["den"].shape == (G,)
+        a.seds_G, a.seds_lin_thr, a.seds_thr = G, float(seds["lin_thr"]), float(seds["seds_thr"])
+        for name, arr in sd.items():
+            setattr(a, "seds_" + name, arr.ctypes.data)
+    if frame:
+        vel = f32(vel)
+        row_obs = np.ascontiguousarray(row_obs, dtype=np.int32)
+        assert vel.ndim == 2 and row_obs.shape == (N, k)
+        a.O, a.ldVel, a.vel, a.rowObs = vel.shape[0], vel.shape[1], vel.ctypes.data, row_obs.ctypes.data
+    rc = load_test_hooks().omds_test_modulate(C.byref(a))
+    if not check:
+        return rc
+    if rc != 0:
+        raise OmdsError(f"omds_test_modulate failed ({rc})")
+    res = {name: np.ascontiguousarray(arr.T) for name, arr in out.items()}
+    res["maxact"], res["phisum0"] = np.ascontiguousarray(maxactT.T), ph0
+    return res
 
 
 def f32(a, shape=None):

@@ -265,6 +265,23 @@ int install_obstacles(omds_ctx* ctx, const float* xyzr, int n_obs) {
     return OMDS_OK;
 }
 
+// The SEDS components as the step reads them (omds_internal.h: StepArgs::seds), one record of omds_seds_stride(n) floats each
+std::vector<float> omds_pack_seds(int n, int G, const float* mu_in, const float* b, const float* sigma_inv, const float* A,
+                                  const float* prior, const float* den) {
+    const int st = omds_seds_stride(n);
+    std::vector<float> pk((size_t)G * st);
+    for (int j = 0; j < G; ++j) {
+        float* p = &pk[(size_t)j * st];
+        std::memcpy(p, mu_in + (size_t)j * n, n * sizeof(float));
+        std::memcpy(p + n, b + (size_t)j * n, n * sizeof(float));
+        p[2 * n] = prior[j];
+        p[2 * n + 1] = den[j];
+        std::memcpy(p + 2 * n + 2, sigma_inv + (size_t)j * n * n, (size_t)n * n * sizeof(float));
+        std::memcpy(p + 2 * n + 2 + n * n, A + (size_t)j * n * n, (size_t)n * n * sizeof(float));
+    }
+    return pk;
+}
+
 extern "C" {
 
 int omds_set_obstacles(omds_ctx* ctx, const float* xyzr, int n_obs) {
@@ -312,17 +329,7 @@ int omds_set_ds_seds(omds_ctx* ctx, const float* q_goal, int G, const float* mu_
     if (rc || G == 0) return rc;
     REQUIRE(G >= 1 && G <= 64 && mu_in && b && sigma_inv && A && prior && den, OMDS_ERR_INVALID_ARG,
             "omds_set_ds_seds: need 1 <= n_gauss <= 64 and non-null component arrays");
-    const int n = ctx->cfg.n_dof, st = omds_seds_stride(n);
-    std::vector<float> pk((size_t)G * st);
-    for (int j = 0; j < G; ++j) {
-        float* p = &pk[(size_t)j * st];
-        std::memcpy(p, mu_in + (size_t)j * n, n * sizeof(float));
-        std::memcpy(p + n, b + (size_t)j * n, n * sizeof(float));
-        p[2 * n] = prior[j];
-        p[2 * n + 1] = den[j];
-        std::memcpy(p + 2 * n + 2, sigma_inv + (size_t)j * n * n, (size_t)n * n * sizeof(float));
-        std::memcpy(p + 2 * n + 2 + n * n, A + (size_t)j * n * n, (size_t)n * n * sizeof(float));
-    }
+    const std::vector<float> pk = omds_pack_seds(ctx->cfg.n_dof, G, mu_in, b, sigma_inv, A, prior, den);
     CK(hipSetDevice(ctx->dev));
     CK(hipStreamSynchronize(ctx->stream));
     CK(ctx->d_seds.alloc(pk.size()));

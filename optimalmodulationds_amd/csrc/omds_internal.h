@@ -162,6 +162,9 @@ struct ProfEvents {
 };
 
 __host__ __device__ inline int omds_seds_stride(int n) { return 2 * n + 2 + 2 * n * n; }
+// context.hip: G records of omds_seds_stride(n) floats in the layout of StepArgs::seds, from the arrays omds_set_ds_seds takes
+std::vector<float> omds_pack_seds(int n, int G, const float* mu_in, const float* b, const float* sigma_inv, const float* A,
+                                  const float* prior, const float* den);
 struct StepArgs {
     int N, H, n, K, Kmax, k, d, step;   // step = i in 1..H
     float* trajT; float* distT; float* dotT; float* actT; float* normalT; float* kvalT; float* qdotT;

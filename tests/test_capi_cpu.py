@@ -38,14 +38,14 @@ def test_header_symbols_exported_and_bound(lib):
 
 
 def test_test_hooks_with_trig_live_in_the_test_library_only(lib):
-    """include/omds_test.h: the eight hooks (damage the screening inputs, force a tile shape, the trainer's general GEMM, the host half
-    of omds_set_mlp_ex, the encoding's sin / cos in array and sweep mode, the raw words of the device's Philox, the top-k selection on given rows) are exported by
+    """include/omds_test.h: the nine hooks (damage the screening inputs, force a tile shape, the trainer's general GEMM, the host half
+    of omds_set_mlp_ex, the encoding's sin / cos in array and sweep mode, the raw words of the device's Philox, the top-k selection on given rows, one modulation step on given inputs) are exported by
     libomds_hip_test.so and NOT by the product library; and the product library reads no experiment environment variable (only
     OMDS_SCREEN, OMDS_ROCTX, OMDS_RCCL_LIB appear among its strings)."""
     from optimalmodulationds_amd import _lib
     hooks = _declared("omds_test.h")
-    assert hooks == sorted(_lib.TEST_HOOK_SIGNATURES) and len(hooks) == 8
-    assert {"omds_test_trig", "omds_test_trig_sweep", "omds_test_philox", "omds_test_topk"} <= set(hooks)
+    assert hooks == sorted(_lib.TEST_HOOK_SIGNATURES) and len(hooks) == 9
+    assert {"omds_test_trig", "omds_test_trig_sweep", "omds_test_philox", "omds_test_topk", "omds_test_modulate"} <= set(hooks)
     raw, raw_test = C.CDLL(_lib.LIB_PATH), C.CDLL(_lib.TEST_LIB_PATH)
     for nme in hooks:
         assert not hasattr(raw, nme), f"{nme} is a test hook and must not be exported by the product library"
