@@ -45,17 +45,8 @@ __global__ __launch_bounds__(256) void k_rollout_features(MlpDev m, const float*
     Fq[(size_t)t * OMDS_FROW + c] = q;
     Fq[(size_t)t * OMDS_FROW + d + c] = sq;
     Fq[(size_t)t * OMDS_FROW + 2 * d + c] = cq;
-    if (FqH) {   // the screening kernel's input row of this rollout (the other slots stay zero)
-        FqH[omds_screen_fidx(c, t, ldF)] = (_Float16)q;
-        FqH[omds_screen_fidx(d + c, t, ldF)] = (_Float16)sq;
-        FqH[omds_screen_fidx(2 * d + c, t, ldF)] = (_Float16)cq;
-        if (m.scrQ) {   // skip-connection networks: the same values at the slots of the concatenated columns
-            _Float16* S = reinterpret_cast<_Float16*>(m.scrQ);
-            S[omds_screen_sidx(c, 3 * d, t, ldF)] = (_Float16)q;
-            S[omds_screen_sidx(d + c, 3 * d, t, ldF)] = (_Float16)sq;
-            S[omds_screen_sidx(2 * d + c, 3 * d, t, ldF)] = (_Float16)cq;
-        }
-    }
+    // the screening kernel's input row of this rollout (the other slots stay zero)
+    if (FqH) omds_screen_store_row(FqH, reinterpret_cast<_Float16*>(m.scrQ), c, d, t, ldF, q, sq, cq);
 }
 
 __global__ __launch_bounds__(256) void k_obstacle_features(MlpDev m, const float* __restrict__ xyzr, int O,
@@ -70,17 +61,7 @@ __global__ __launch_bounds__(256) void k_obstacle_features(MlpDev m, const float
     Fp[(size_t)o * OMDS_FROW + n + c] = p;
     Fp[(size_t)o * OMDS_FROW + d + n + c] = sp;
     Fp[(size_t)o * OMDS_FROW + 2 * d + n + c] = cp;
-    if (FpH) {
-        FpH[omds_screen_fidx(n + c, o, ldF)] = (_Float16)p;
-        FpH[omds_screen_fidx(d + n + c, o, ldF)] = (_Float16)sp;
-        FpH[omds_screen_fidx(2 * d + n + c, o, ldF)] = (_Float16)cp;
-        if (m.scrP) {
-            _Float16* S = reinterpret_cast<_Float16*>(m.scrP);
-            S[omds_screen_sidx(n + c, 3 * d, o, ldF)] = (_Float16)p;
-            S[omds_screen_sidx(d + n + c, 3 * d, o, ldF)] = (_Float16)sp;
-            S[omds_screen_sidx(2 * d + n + c, 3 * d, o, ldF)] = (_Float16)cp;
-        }
-    }
+    if (FpH) omds_screen_store_row(FpH, reinterpret_cast<_Float16*>(m.scrP), n + c, d, o, ldF, p, sp, cp);
 }
 
 // The same tables for every slab of an obstacle horizon (omds.h: omds_set_obstacle_motion / omds_set_obstacle_horizon): row
@@ -115,18 +96,7 @@ __global__ __launch_bounds__(256) void k_obstacle_horizon_features(MlpDev m, con
     FpT[row * OMDS_FROW + n + c] = p;
     FpT[row * OMDS_FROW + d + n + c] = sp;
     FpT[row * OMDS_FROW + 2 * d + n + c] = cp;
-    if (FpHT) {
-        _Float16* F = FpHT + (size_t)h * 32 * ld;
-        F[omds_screen_fidx(n + c, o, ld)] = (_Float16)p;
-        F[omds_screen_fidx(d + n + c, o, ld)] = (_Float16)sp;
-        F[omds_screen_fidx(2 * d + n + c, o, ld)] = (_Float16)cp;
-        if (scrPT) {
-            _Float16* S = scrPT + (size_t)h * 32 * ld;
-            S[omds_screen_sidx(n + c, 3 * d, o, ld)] = (_Float16)p;
-            S[omds_screen_sidx(d + n + c, 3 * d, o, ld)] = (_Float16)sp;
-            S[omds_screen_sidx(2 * d + n + c, 3 * d, o, ld)] = (_Float16)cp;
-        }
-    }
+    if (FpHT) omds_screen_store_row(FpHT + (size_t)h * 32 * ld, scrPT ? scrPT + (size_t)h * 32 * ld : nullptr, n + c, d, o, ld, p, sp, cp);
 }
 
 template <int MT, int MR, int NR, int ACT>
@@ -505,7 +475,7 @@ void omds_launch_pass2(hipStream_t s, const MlpDev& m, const float* Fq, const fl
     }
     // same tile height as the fused tail would pick for this batch, so that the batch entry points (omds_dist_grad)
     // reproduce the step path bit for bit
-    const int rows = omds_tail_rows(B, k);
+    const int rows = omds_pass2_rows(B, k);
     const dim3 grid((total + rows - 1) / rows);
 #define OMDS_P2_LAUNCH(A, R) hipLaunchKernelGGL((k_pass2<A, R>), grid, dim3(P2_NT), lds, s, m, Fq, Fp, radius, xyzr, idx, total, k, qT, ldq, gradx, drow, yraw, minidx, dscr, seed_col)
     if (m.act == OMDS_ACT_RELU) { if (rows == 16) OMDS_P2_LAUNCH(OMDS_ACT_RELU, 16); else OMDS_P2_LAUNCH(OMDS_ACT_RELU, 32); }

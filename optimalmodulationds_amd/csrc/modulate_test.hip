@@ -1,7 +1,7 @@
 // Test hook (include/omds_test.h, libomds_hip_test.so only: the Makefile links this file into no other library): ONE horizon step of
 // modulate_core (step_device.h) on caller-supplied inputs, with no network and no context, for tests/test_gpu_step_edges.py.
 //   nsub = 1 : the production launcher omds_launch_modulate (k_modulate<ND, FRAME>, ND = 1..7, the SEDS branch included) as shipped
-//   nsub = 16: k_modulate16 below, which calls modulate_core<ND, 16, false, FRAME> the way the fused step kernels do (tail_kernel.hip:
+//   nsub = 16: k_modulate16 below, which calls modulate_core<ND, 16, false, FRAME> the way the fused step kernels do (step_advance, step_epilogue.h:
 //              16 consecutive lanes of a wave per rollout, sub = lane & 15, whole 16-lane groups on or off by t < N), gradients and
 //              distances in global memory; ND = 2 and 7, the two the fused kernels instantiate, and never with SEDS (no product kernel
 //              instantiates WITH_SEDS with NSUB = 16)

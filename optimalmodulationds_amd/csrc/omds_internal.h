@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "omds.h"
+#include "tail_plan_def.h"
 
 // The library reads OMDS_SCREEN (0 | 1 | 2: the screening mode of contexts left on the default, -1), OMDS_ROCTX and OMDS_RCCL_LIB from the
 // environment, nothing else (tests/test_capi_cpu.py).
@@ -102,6 +103,21 @@ __host__ __device__ inline size_t omds_screen_sidx(int kappa, int F, int t, int 
     const int v = 256 - F + kappa, f = v & 15;
     const int piece = 2 * ((v >> 4) - 14) + ((f >> 2) & 1), slot = 4 * (f >> 3) + (f & 3);
     return ((size_t)piece * stride + t) * 8 + slot;
+}
+
+// (x, sin x, cos x) of feature slot c (joint c of a rollout, n_dof + c of an obstacle point) of row t, rounded to fp16, into the input
+// table F of row capacity ld and, for skip-connection networks (S != nullptr), at the slots of the concatenated columns of S.  Every
+// writer of the screening tables stores through here: the screened step is the fp32 step's bits only while they agree on slot,
+// piece and rounding.
+__device__ __forceinline__ void omds_screen_store_row(_Float16* F, _Float16* S, int c, int d, int t, int ld, float x, float sx, float cx) {
+    F[omds_screen_fidx(c, t, ld)] = (_Float16)x;
+    F[omds_screen_fidx(d + c, t, ld)] = (_Float16)sx;
+    F[omds_screen_fidx(2 * d + c, t, ld)] = (_Float16)cx;
+    if (S) {
+        S[omds_screen_sidx(c, 3 * d, t, ld)] = (_Float16)x;
+        S[omds_screen_sidx(d + c, 3 * d, t, ld)] = (_Float16)sx;
+        S[omds_screen_sidx(2 * d + c, 3 * d, t, ld)] = (_Float16)cx;
+    }
 }
 
 // hipFuncSetAttribute applies to the current device only: true the first time a kernel is launched on each device.
@@ -581,26 +597,36 @@ void omds_launch_exact(hipStream_t s, const MlpDev& m, const float* Fq, const fl
 // ---- launchers implemented in rollout_kernels.hip ---------------------------------------------
 void omds_launch_modulate(hipStream_t s, const StepArgs& a);
 // fused per-step tail (tail_kernel.hip): top-k + pass 2 + blend + modulation + next-step layer-1 half
+// tail_plan_def.h: the tile heights, the instantiations and the LDS block; omds_tail_scratch_rows(N, k) = rows of the tanh-derivative
+// scratch the tail may touch (either tile height)
 bool omds_tail_supported(int n_dof, int k);
-int omds_tail_scratch_rows(int N, int k);   // rows of the tanh-derivative scratch the tail may touch (either tile height)
-int omds_tail_rows(int N, int k, bool g4_ok = false);   // pass-2 tile height (16 | 32; 4 = 4-row groups, only with g4_ok) for N rollouts with k closest obstacles
-// FqOut: where the next step's encoded joint inputs go (nullptr: in place).  guard_range / e_bound / viol: screened tanh step --
-// Dmin holds exact values on the candidates and screening values elsewhere; the tail counts the rollouts whose k-th smallest
-// value is not e_bound below k_select's tau (range[4 t + 2]) into *viol.  shared_row: Dmin is ONE row [O] that every rollout
-// selects from (the first step of a propagate that starts all rollouts at one state)
+// k_pass2's tile height (16 | 32) for N states with k closest obstacles on this device: omds_tail_rows without the 4-row groups, so that
+// the batch entry points reproduce the step bit for bit (reads the CU count and, in the test library, the forced shape)
+int omds_pass2_rows(int N, int k);
+// What only a SCREENED step hands the tails; the default value means "not screened".
+struct TailScreen {
+    uint16_t* FqH = nullptr;      // the next step's states as fp16 network inputs of the screening kernel ...
+    int ldF = 0;                  // ... and that table's row capacity
+    float* FqOut = nullptr;       // k_tail: where the next step's encoded joint inputs go (nullptr: in place, Fq)
+    const int* rowlist = nullptr; // k_tail_sel: the candidate list of k_select, pair t * O + o per entry (nullptr: EVERY pair is an entry, in pair order)
+    // [N][4] start and length of each rollout's entries, tau of k_select (float bits).  k_tail_sel selects from the entries; k_tail reads
+    // tau only -- the screened tanh step: Dmin holds exact values on the candidates and screening values elsewhere
+    const int* range = nullptr;
+    float e_bound = 0.f;          // the tails count the rollouts whose k-th smallest value is not e_bound below tau ...
+    unsigned* viol = nullptr;     // ... into *viol (the slack guard)
+};
+// shared_row: Dmin is ONE row [O] that every rollout selects from (the first step of a propagate that starts all rollouts at one state)
 void omds_launch_tail(hipStream_t s, const MlpDev& m, const float* Fp, const float* radius, const float* xyzr,
-                      const float* Dmin, float* Fq, float* dscr, int O, const StepArgs& st,
-                      uint16_t* FqH = nullptr, int ldF = 0, float* FqOut = nullptr, const int* guard_range = nullptr,
-                      float e_bound = 0.f, unsigned* viol = nullptr, bool shared_row = false);
-// screened step's tail: top-k over the candidates k_exact evaluated + pass-2 backward on its masks + the rest of k_tail
+                      const float* Dmin, float* Fq, float* dscr, int O, const StepArgs& st, const TailScreen& scr, bool shared_row);
+// screened step's tail: top-k over the candidates k_exact evaluated + pass-2 backward on its masks + the rest of k_tail.  The next
+// step's encoded joint inputs go to Fq.
 bool omds_tail_sel_supported(int n_dof, int k);
 int omds_cu_count();   // CUs of the current device (asked once per device)
 #ifdef OMDS_TEST_HOOKS
 void omds_force_tile_rows(int tail_sel_rows, int tail_rows);   // test hook (libomds_hip_test.so): 0 = the launcher's own choice
 #endif
 void omds_launch_tail_sel(hipStream_t s, const MlpDev& m, const float* Fp, const float* radius, const float* xyzr,
-                          float* Fq, int O, const StepArgs& st, const int* rowlist, const int* range, const ExactOut& ex,
-                          uint16_t* FqH, int ldF, float e_bound, unsigned* viol);
+                          float* Fq, int O, const StepArgs& st, const ExactOut& ex, const TailScreen& scr);
 // fused one-launch step for scenes with few obstacles (step_small.hip): rollouts per workgroup, 0 = scene does not qualify
 int omds_step_small_rollouts(const MlpDev& m, int n_dof, int O, int k);
 void omds_launch_step_small(hipStream_t s, const MlpDev& m, const float* Fp, const float* radius, const float* xyzr, float* Fq,

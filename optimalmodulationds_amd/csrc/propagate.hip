@@ -194,7 +194,7 @@ static int enqueue_dense(omds_ctx* ctx, StepArgs& a) {
         RoctxRange r2("TAG: evaluate NN_3-5 + Modulation-propagation");
         a.step = i;
         omds_launch_tail(ctx->stream, ctx->mlp, t.Fp, t.radius, t.obs, ctx->d_Dmin, ctx->d_Fq,
-                         ctx->d_dscr, ctx->n_obs, a, nullptr, 0, nullptr, nullptr, 0.f, nullptr, one_row);
+                         ctx->d_dscr, ctx->n_obs, a, TailScreen{}, one_row);
     }
     return OMDS_OK;
 }
@@ -217,8 +217,8 @@ static int enqueue_emit(omds_ctx* ctx, StepArgs& a) {
         }
         RoctxRange r2("TAG: evaluate NN_3-5 + Modulation-propagation");
         a.step = i;
-        omds_launch_tail_sel(ctx->stream, ctx->mlp, t.Fp, t.radius, t.obs, ctx->d_Fq, ctx->n_obs, a,
-                             nullptr, nullptr, ex_all, nullptr, 0, 0.f, nullptr);   // (no window, no slack to count: viol = NULL)
+        // every pair is an entry of ex_all: no list, no window, no slack to count
+        omds_launch_tail_sel(ctx->stream, ctx->mlp, t.Fp, t.radius, t.obs, ctx->d_Fq, ctx->n_obs, a, ex_all, TailScreen{});
     }
     return OMDS_OK;
 }
@@ -252,12 +252,16 @@ static int enqueue_screened(omds_ctx* ctx, StepArgs& a, bool list_tail) {
         enqueue_sweep_of_step(ctx, fq_i, N, i);
         RoctxRange r2("TAG: evaluate NN_3-5 + Modulation-propagation");
         a.step = i;
-        if (list_tail)
-            omds_launch_tail_sel(ctx->stream, ctx->mlp, t.Fp, t.radius, t.obs, fq_next, ctx->n_obs, a,
-                                 ctx->d_rowlist, ctx->d_range, p.ex, ctx->d_FqH, N, p.eps, ctx->d_scerr + 1);
-        else
-            omds_launch_tail(ctx->stream, ctx->mlp, t.Fp, t.radius, t.obs, ctx->d_Dmin, fq_i,
-                             ctx->d_dscr, ctx->n_obs, a, ctx->d_FqH, N, fq_next, ctx->d_range, p.eps, ctx->d_scerr + 1);
+        TailScreen scr;
+        scr.FqH = ctx->d_FqH; scr.ldF = N;
+        scr.range = ctx->d_range; scr.e_bound = p.eps; scr.viol = ctx->d_scerr + 1;
+        if (list_tail) {
+            scr.rowlist = ctx->d_rowlist;
+            omds_launch_tail_sel(ctx->stream, ctx->mlp, t.Fp, t.radius, t.obs, fq_next, ctx->n_obs, a, p.ex, scr);
+        } else {
+            scr.FqOut = fq_next;
+            omds_launch_tail(ctx->stream, ctx->mlp, t.Fp, t.radius, t.obs, ctx->d_Dmin, fq_i, ctx->d_dscr, ctx->n_obs, a, scr, false);
+        }
     }
     return screen_finish_propagate(ctx, p);
 }

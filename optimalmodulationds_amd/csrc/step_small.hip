@@ -25,7 +25,7 @@
 #include "pass1_tile.h"
 #include "pass2_device.h"
 #include "trig_device.h"
-#include "step_device.h"
+#include "step_epilogue.h"
 
 constexpr int SS_RK = 4;      // backward rows per workgroup (R * k)
 constexpr int SS_NT = 512;
@@ -216,33 +216,10 @@ __global__ __launch_bounds__(SS_NT, TR == 16 ? 4 : 2) void k_step_small(SmallArg
     }
 
     // ---- 4. modulation / policy / Euler step: 16 lanes per rollout (as k_tail) -----------------------------------------
-    {
-        const int rl = tid >> 4, sub = tid & 15;
-        const int t = t_base + rl;
-        if (rl < R && t < N) {
-            float q[ND], qn[ND];
-#pragma unroll
-            for (int j = 0; j < ND; ++j) q[j] = qT[(size_t)j * ldq + t];
-            modulate_core<ND, 16, false, FRAME>(a.st, a.st.step, t, sub, gx, dr, rl * k, q, qn, selO);
-            if (sub < ND) {
-                float v = qn[0];
-#pragma unroll
-                for (int j = 1; j < ND; ++j) v = (sub == j) ? qn[j] : v;
-                feat[rl * 3 * ND + sub] = v;
-                feat[rl * 3 * ND + ND + sub] = omds_sinf(v);
-                feat[rl * 3 * ND + 2 * ND + sub] = omds_cosf(v);
-            }
-        }
-    }
+    step_advance<ND, FRAME>(a.st, m, qT, ldq, N, t_base, R, k, gx, dr, selO, feat, nullptr, 0);   // (no fp16 table: this step is never screened)
     if (a.st.step >= a.st.H) return;   // last step: nothing is integrated, no next network evaluation
     __syncthreads();
-    {   // the encoded joint inputs of the next step (as k_rollout_features writes them)
-        const int d = m.d;
-        for (int e = tid; e < R * 3 * ND; e += SS_NT) {
-            const int rl = e / (3 * ND), cc = e - rl * (3 * ND), part = cc / ND, t = t_base + rl;
-            if (t < N) a.Fq[(size_t)t * OMDS_FROW + part * d + (cc - part * ND)] = feat[e];
-        }
-    }
+    step_write_next_rows<ND, SS_NT>(a.Fq, feat, m.d, N, t_base, R);
 }
 
 static size_t small_lds_bytes(int nhid, int TR) {

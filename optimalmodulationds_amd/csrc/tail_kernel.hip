@@ -8,14 +8,18 @@
 // The stand-alone kernels (k_topk, k_pass2, k_modulate, k_rollout_layer1) remain for the batch entry
 // points (omds_dist_grad, omds_mlp_forward_vjp) and for n_dof / k combinations not instantiated here.
 #include <algorithm>
-
 #include <atomic>
+#include <cstdio>
+#include <cstdlib>
 
 #include "pass2_device.h"
 #include "timeline_device.h"
 #include "topk_device.h"
 #include "trig_device.h"
-#include "step_device.h"
+#include "step_epilogue.h"
+#include "tail_plan_def.h"
+
+static_assert(TAIL_MT == P2_MT && TAIL_NT == P2_NT && TAIL_LDH == LDH, "tail_plan_def.h restates pass 2's tile");
 
 struct TailArgs {
     MlpDev m;
@@ -40,22 +44,36 @@ struct TailArgs {
     StepArgs st;
 };
 
+// The two tails' pointers into their dynamic LDS block.  Where the blocks lie and how large the launch is, is TailLdsPlan
+// (tail_plan_def.h); every pointer is formed from the block's start and its offset there (k_tail does not read sel).
+struct TailLds {
+    P2Smem sm;
+    float *gx, *dr, *feat;
+    int* sel;
+    __device__ __forceinline__ TailLds(float* smem, int nhid) {
+        const TailLdsPlan o(nhid, true);
+        sm.Hs = smem + o.Hs;
+        sm.gf = smem + o.gf;
+        sm.maskL = reinterpret_cast<uint16_t*>(smem + o.maskL);
+        sm.rowT = reinterpret_cast<int*>(smem + o.rowT);
+        sm.rowO = reinterpret_cast<int*>(smem + o.rowO);
+        sm.rowMin = reinterpret_cast<int*>(smem + o.rowMin);
+        gx = smem + o.gx;
+        dr = smem + o.dr;
+        feat = smem + o.feat;
+        sel = reinterpret_cast<int*>(smem + o.sel);
+    }
+};
+
 // FRAME: the modulation runs in the moving obstacle's frame (step_device.h); its own instantiation, so that the kernel of every
 // other propagate is the code it was
 template <int ND, int ACT, int ROWS, bool FRAME = false>
 __global__ __launch_bounds__(P2_NT) void k_tail(TailArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const MlpDev& m = a.m;
-    P2Smem sm;
-    sm.Hs = smem;
-    sm.gf = sm.Hs + P2_MT * LDH;
-    sm.maskL = reinterpret_cast<uint16_t*>(sm.gf + 32 * 33);
-    sm.rowT = reinterpret_cast<int*>(sm.maskL + ((m.nhh + 2) / 2 * 2) * P2_NT);
-    sm.rowO = sm.rowT + P2_MT;
-    sm.rowMin = sm.rowO + P2_MT;
-    float* gx = reinterpret_cast<float*>(sm.rowMin + P2_MT);   // [32][d]
-    float* dr = gx + 32 * 12;                                   // [32]
-    float* feat = dr + 32;                                      // [32][3*ND]: q_next, sin, cos
+    TailLds L(smem, m.nhh + 1);
+    P2Smem& sm = L.sm;
+    float *const gx = L.gx, *const dr = L.dr, *const feat = L.feat;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int N = a.st.N, k = a.st.k, O = a.O;
     // ROWS = 4: forward and backward on 4-row groups (pass2_body_g4): 4 G4_NG = 20 network rows per workgroup
@@ -97,55 +115,15 @@ __global__ __launch_bounds__(P2_NT) void k_tail(TailArgs a) {
     __syncthreads();
     OMDS_TL_STAMP(9);
 
-    // ---- modulation / policy / Euler step: 16 lanes per rollout -------------------------------------
-    {
-        const int rl = tid >> 4, sub = tid & 15;
-        const int t = t_base + rl;
-        if (rl < RW && t < N) {
-            float q[ND], qn[ND];
-#pragma unroll
-            for (int j = 0; j < ND; ++j) q[j] = qT[(size_t)j * N + t];
-            modulate_core<ND, 16, false, FRAME>(a.st, a.st.step, t, sub, gx, dr, rl * k, q, qn, sm.rowO);
-            if (sub < ND) {
-                float v = qn[0];
-#pragma unroll
-                for (int j = 1; j < ND; ++j) v = (sub == j) ? qn[j] : v;
-                feat[rl * 3 * ND + sub] = v;
-                feat[rl * 3 * ND + ND + sub] = omds_sinf(v);
-                feat[rl * 3 * ND + 2 * ND + sub] = omds_cosf(v);
-                if (a.FqH && a.st.step < a.st.H) {
-                    const int d = m.d;
-                    a.FqH[omds_screen_fidx(sub, t, a.ldF)] = (_Float16)v;
-                    a.FqH[omds_screen_fidx(d + sub, t, a.ldF)] = (_Float16)feat[rl * 3 * ND + ND + sub];
-                    a.FqH[omds_screen_fidx(2 * d + sub, t, a.ldF)] = (_Float16)feat[rl * 3 * ND + 2 * ND + sub];
-                    if (m.scrQ) {   // skip-connection networks: the concatenation operand of the screening kernel
-                        _Float16* S = reinterpret_cast<_Float16*>(m.scrQ);
-                        S[omds_screen_sidx(sub, 3 * d, t, a.ldF)] = (_Float16)v;
-                        S[omds_screen_sidx(d + sub, 3 * d, t, a.ldF)] = (_Float16)feat[rl * 3 * ND + ND + sub];
-                        S[omds_screen_sidx(2 * d + sub, 3 * d, t, a.ldF)] = (_Float16)feat[rl * 3 * ND + 2 * ND + sub];
-                    }
-                }
-            }
-        }
-    }
+    // ---- modulation / policy / Euler step: 16 lanes per rollout; then the encoded joint inputs of the next step -------------
+    step_advance<ND, FRAME>(a.st, m, qT, N, N, t_base, RW, k, gx, dr, sm.rowO, feat, a.FqH, a.ldF);
     OMDS_TL_STAMP(10);
     if (a.st.step >= a.st.H) return;   // last step: nothing is integrated, no next network evaluation
     __syncthreads();
-
-    // ---- the encoded joint inputs of the next step (as k_rollout_features writes them) --------
-    {
-        const int d = m.d;
-        for (int e = tid; e < RW * 3 * ND; e += P2_NT) {
-            const int rl = e / (3 * ND), cc = e - rl * (3 * ND), part = cc / ND, t = t_base + rl;
-            if (t < N) a.FqOut[(size_t)t * OMDS_FROW + part * d + (cc - part * ND)] = feat[e];
-        }
-    }
+    step_write_next_rows<ND, P2_NT>(a.FqOut, feat, m.d, N, t_base, RW);
     OMDS_TL_STAMP(11);
     OMDS_TL_STAMP(19);
 }
-
-
-static size_t tail_lds_bytes(int nhid);
 
 // ------------------------------------------------------------------------------------------------
 // Screened step: k_screen -> k_select -> k_exact -> k_tail_sel.  k_exact has evaluated every candidate row in fp32 with
@@ -162,17 +140,10 @@ __global__ __launch_bounds__(P2_NT) void k_tail_sel(TailArgs a) {
     static_assert(ACT == OMDS_ACT_RELU || ROWS != 4, "the 4-row-group backward works on ReLU masks");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const MlpDev& m = a.m;
-    P2Smem sm;
-    sm.Hs = smem;
-    sm.gf = sm.Hs + P2_MT * LDH;
-    sm.maskL = reinterpret_cast<uint16_t*>(sm.gf + 32 * 33);
-    sm.rowT = reinterpret_cast<int*>(sm.maskL + ((m.nhh + 2) / 2 * 2) * P2_NT);
-    sm.rowO = sm.rowT + P2_MT;
-    sm.rowMin = sm.rowO + P2_MT;
-    float* gx = reinterpret_cast<float*>(sm.rowMin + P2_MT);   // [32][d]
-    float* dr = gx + 32 * 12;                                   // [32]
-    float* feat = dr + 32;                                      // [32][3*ND]: q_next, sin, cos
-    int* sel = reinterpret_cast<int*>(feat + 32 * 3 * OMDS_MAX_DOF);   // [32] list entry of each backward row (-1: padding)
+    TailLds L(smem, m.nhh + 1);
+    P2Smem& sm = L.sm;
+    float *const gx = L.gx, *const dr = L.dr, *const feat = L.feat;
+    int* const sel = L.sel;
     uint32_t* maskRow = reinterpret_cast<uint32_t*>(sm.Hs);     // [32][nhid][8] gathered masks; the tile buffer is idle until the seed
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int N = a.st.N, k = a.st.k, O = a.O, nhid = m.nhh + 1;
@@ -307,49 +278,12 @@ __global__ __launch_bounds__(P2_NT) void k_tail_sel(TailArgs a) {
     __syncthreads();
     OMDS_TL_STAMP(9);
 
-    // ---- modulation / policy / Euler step: 16 lanes per rollout -------------------------------------
-    {
-        const int rl = tid >> 4, sub = tid & 15;
-        const int t = t_base + rl;
-        if (rl < RW && t < N) {
-            float q[ND], qn[ND];
-#pragma unroll
-            for (int j = 0; j < ND; ++j) q[j] = qT[(size_t)j * N + t];
-            modulate_core<ND, 16, false, FRAME>(a.st, a.st.step, t, sub, gx, dr, rl * k, q, qn, sm.rowO);
-            if (sub < ND) {
-                float v = qn[0];
-#pragma unroll
-                for (int j = 1; j < ND; ++j) v = (sub == j) ? qn[j] : v;
-                feat[rl * 3 * ND + sub] = v;
-                feat[rl * 3 * ND + ND + sub] = omds_sinf(v);
-                feat[rl * 3 * ND + 2 * ND + sub] = omds_cosf(v);
-                if (a.FqH && a.st.step < a.st.H) {
-                    const int d = m.d;
-                    a.FqH[omds_screen_fidx(sub, t, a.ldF)] = (_Float16)v;
-                    a.FqH[omds_screen_fidx(d + sub, t, a.ldF)] = (_Float16)feat[rl * 3 * ND + ND + sub];
-                    a.FqH[omds_screen_fidx(2 * d + sub, t, a.ldF)] = (_Float16)feat[rl * 3 * ND + 2 * ND + sub];
-                    if (m.scrQ) {   // skip-connection networks: the concatenation operand of the screening kernel
-                        _Float16* S = reinterpret_cast<_Float16*>(m.scrQ);
-                        S[omds_screen_sidx(sub, 3 * d, t, a.ldF)] = (_Float16)v;
-                        S[omds_screen_sidx(d + sub, 3 * d, t, a.ldF)] = (_Float16)feat[rl * 3 * ND + ND + sub];
-                        S[omds_screen_sidx(2 * d + sub, 3 * d, t, a.ldF)] = (_Float16)feat[rl * 3 * ND + 2 * ND + sub];
-                    }
-                }
-            }
-        }
-    }
+    // ---- modulation / policy / Euler step: 16 lanes per rollout; then the encoded joint inputs of the next step -------------
+    step_advance<ND, FRAME>(a.st, m, qT, N, N, t_base, RW, k, gx, dr, sm.rowO, feat, a.FqH, a.ldF);
     OMDS_TL_STAMP(10);
     if (a.st.step >= a.st.H) return;   // last step: nothing is integrated, no next network evaluation
     __syncthreads();
-
-    // ---- the encoded joint inputs of the next step (as k_rollout_features writes them) --------
-    {
-        const int d = m.d;
-        for (int e = tid; e < RW * 3 * ND; e += P2_NT) {
-            const int rl = e / (3 * ND), cc = e - rl * (3 * ND), part = cc / ND, t = t_base + rl;
-            if (t < N) a.FqOut[(size_t)t * OMDS_FROW + part * d + (cc - part * ND)] = feat[e];
-        }
-    }
+    step_write_next_rows<ND, P2_NT>(a.FqOut, feat, m.d, N, t_base, RW);
     OMDS_TL_STAMP(11);
     OMDS_TL_STAMP(19);
 }
@@ -373,29 +307,42 @@ static void tail_tl_dump(hipStream_t s, int step, int grid) {
 static void tail_tl_dump(hipStream_t, int, int) {}
 #endif
 
-template <int ND, int ROWS, int ACT = OMDS_ACT_RELU, bool FRAME = false>
-static void launch_tail_sel_t(hipStream_t s, const TailArgs& a) {
+// ---- launchers: the tile height, the key and the LDS size are tail_plan_def.h's ----------------------------------------------------
+// one launch of instantiation K on tiles of ROWS rows; SEL: k_tail_sel's LDS block
+template <void (*K)(TailArgs), int ROWS, bool SEL>
+static void launch_tail_k(hipStream_t s, const TailArgs& a) {
     static std::atomic<uint64_t> configured{0};
-    const size_t extra = 32 * 4;   // sel
     if (omds_first_use_on_device(configured)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tail_sel<ND, ROWS, ACT, FRAME>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)(tail_lds_bytes(OMDS_MAX_HIDDEN + 1) + extra));
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)TailLdsPlan::bytes(OMDS_MAX_HIDDEN + 1, SEL));
     }
-    const int RW = (ROWS == 4 ? 20 : ROWS) / a.st.k;
-    const int grid = (a.st.N + RW - 1) / RW;
-    hipLaunchKernelGGL((k_tail_sel<ND, ROWS, ACT, FRAME>), dim3(grid), dim3(P2_NT), tail_lds_bytes(a.m.nhh + 1) + extra, s, a);
+    const int grid = tail_workgroups(a.st.N, ROWS, a.st.k);
+    hipLaunchKernelGGL(K, dim3(grid), dim3(P2_NT), TailLdsPlan::bytes(a.m.nhh + 1, SEL), s, a);
     tail_tl_dump(s, a.st.step, grid);
 }
 
-// The step in the moving frame (StepArgs::frame) runs on 16- or 32-row tiles: every tile shape computes the same bits, so the 4-row
-// groups are a choice of speed that the frame's instantiations do without.
-static int frame_rows(int rows, int k) { return rows != 4 ? rows : (k <= 16 ? 16 : 32); }
+// entry i launches the kernel of TAIL_KEYS[i]: the key's four constants are the template arguments
+using TailLauncher = void (*)(hipStream_t, const TailArgs&);
+#define OMDS_TAIL_LAUNCHER(ND, ACT, ROWS, FRAME) launch_tail_k<k_tail<ND, ACT, ROWS, FRAME>, ROWS, false>,
+#define OMDS_TAIL_SEL_LAUNCHER(ND, ACT, ROWS, FRAME) launch_tail_k<k_tail_sel<ND, ROWS, ACT, FRAME>, ROWS, true>,
+static const TailLauncher TAIL_LAUNCHERS[TAIL_N_KEYS] = {OMDS_TAIL_KEYS(OMDS_TAIL_LAUNCHER)};
+static const TailLauncher TAIL_SEL_LAUNCHERS[TAIL_N_KEYS] = {OMDS_TAIL_KEYS(OMDS_TAIL_SEL_LAUNCHER)};
 
-// 16-row tiles (bit-identical to 32-row ones, mfma_gemm.h) while their workgroups still fit the CUs two at a time: twice as
-// many, half as long, and the second resident fills the first one's top-k / gather / modulation phases
-// Tile shapes (4 | 16 | 32 rows) forced by the test hook omds_debug_force_tile_rows (libomds_hip_test.so, include/omds_test.h):
-// every shape computes the same bits, and the tests say so by running them against each other.  The release library has no hook:
-// 0 = the launcher's own choice.
+static void launch_tail_key(const TailLauncher* launchers, const TailKey& key, hipStream_t s, const TailArgs& a) {
+    const int i = tail_key_index(key);
+    // A miss cannot happen: omds_tail_supported / omds_tail_sel_supported (the routes ask them, propagate.hip) admit n_dof 7 and 2 only,
+    // an activation is ReLU or tanh, the choosers return 4 only under g4_ok, which the plan keys grant to ReLU networks outside
+    // the moving frame alone (frame_rows turns a 4 into 16 or 32), and 16 and 32 exist for every (n_dof, activation, frame)
+    // (tests/test_tail_plan_cpu.py walks the grid).
+    if (i < 0) {   // (not an assert: whatever the build's flags, a miss neither launches nothing in silence nor indexes the table)
+        fprintf(stderr, "omds: no tail kernel is instantiated for n_dof %d, activation %d, %d rows, frame %d\n", key.n_dof, key.act, key.rows, (int)key.frame);
+        abort();
+    }
+    launchers[i](s, a);
+}
+
+// The `forced` argument of the row choosers: the tile shape of the test hook omds_debug_force_tile_rows (libomds_hip_test.so,
+// include/omds_test.h).  The release library has no hook: 0 = the launcher's own choice.
 #ifdef OMDS_TEST_HOOKS
 static std::atomic<int> g_force_sel_rows{0}, g_force_tail_rows{0};
 void omds_force_tile_rows(int tail_sel_rows, int tail_rows) {
@@ -406,143 +353,37 @@ void omds_force_tile_rows(int tail_sel_rows, int tail_rows) {
 #else
 #define OMDS_FORCED_ROWS(slot) 0
 #endif
-static int tail_sel_rows(int N, int k, bool g4_ok) {
-    const int forced = OMDS_FORCED_ROWS(g_force_sel_rows);
-    if (k > 16) return 32;
-    if (forced == 4 && g4_ok && k <= 20) return 4;
-    if (forced == 16 || forced == 32) return forced;
-    // 4-row groups (20 rows per workgroup) where the busiest CU multiplies less that way: matrix-pipe cycles per layer of the CU
-    // with the most workgroups, 5 groups x 2048 (x 1.1: one wave per SIMD issues a 4x4x1 every 9 cycles, not 8) against 8192 per
-    // 16-row tile.  N = 1024, k = 5: 256 workgroups, one per CU, against 342 tiles of 16 rows (40.5 -> 35 us); N = 4096: four
-    // per CU against six tiles (20.5 -> 20.1 ms per iteration); N = 1500: 375 workgroups would put two on 119 CUs where 500
-    // tiles of 16 rows are two per CU and cheaper.  A lone 16-row tile (no CU with two) is the shorter chain anyway.
-    const int RW16 = 16 / k;
-    if (forced == 0 && g4_ok && k <= 10) {
-        const int ncu = omds_cu_count(), RW4 = 20 / k;
-        const long long wg16 = (N + RW16 - 1) / RW16, wg4 = (N + RW4 - 1) / RW4;
-        const long long cost16 = ((wg16 + ncu - 1) / ncu) * 8192, cost4 = ((wg4 + ncu - 1) / ncu) * (5 * 2048 * 11 / 10);
-        if (wg16 > ncu && cost4 < cost16) return 4;
-    }
-    return (N + RW16 - 1) / RW16 <= 512 ? 16 : 32;
-}
 
 bool omds_tail_sel_supported(int n_dof, int k) { return (n_dof == 7 || n_dof == 2) && k >= 1 && k <= 32; }
 
 void omds_launch_tail_sel(hipStream_t s, const MlpDev& m, const float* Fp, const float* radius, const float* xyzr,
-                          float* Fq, int O, const StepArgs& st, const int* rowlist, const int* range, const ExactOut& ex,
-                          uint16_t* FqH, int ldF, float e_bound, unsigned* viol) {
+                          float* Fq, int O, const StepArgs& st, const ExactOut& ex, const TailScreen& scr) {
     TailArgs a;
-    a.e_bound = e_bound;
-    a.viol = viol;
-    a.FqH = reinterpret_cast<_Float16*>(FqH);
-    a.ldF = ldF;
+    a.e_bound = scr.e_bound;
+    a.viol = scr.viol;
+    a.FqH = reinterpret_cast<_Float16*>(scr.FqH);
+    a.ldF = scr.ldF;
     a.n_slots = 0;
     a.m = m; a.Fp = Fp; a.radius = radius; a.xyzr = xyzr; a.Dmin = nullptr; a.ldD = O; a.Fq = Fq; a.FqOut = Fq; a.dscr = nullptr; a.O = O; a.st = st;
-    a.rowlist = rowlist; a.range = range; a.ex = ex;
-    if (st.frame) {
-        const int rows = frame_rows(tail_sel_rows(st.N, st.k, false), st.k);
-        if (m.act == OMDS_ACT_TANH) {
-            if (st.n == 7) { if (rows == 16) launch_tail_sel_t<7, 16, OMDS_ACT_TANH, true>(s, a); else launch_tail_sel_t<7, 32, OMDS_ACT_TANH, true>(s, a); }
-            else { if (rows == 16) launch_tail_sel_t<2, 16, OMDS_ACT_TANH, true>(s, a); else launch_tail_sel_t<2, 32, OMDS_ACT_TANH, true>(s, a); }
-        } else {
-            if (st.n == 7) { if (rows == 16) launch_tail_sel_t<7, 16, OMDS_ACT_RELU, true>(s, a); else launch_tail_sel_t<7, 32, OMDS_ACT_RELU, true>(s, a); }
-            else { if (rows == 16) launch_tail_sel_t<2, 16, OMDS_ACT_RELU, true>(s, a); else launch_tail_sel_t<2, 32, OMDS_ACT_RELU, true>(s, a); }
-        }
-        return;
-    }
-    if (m.act == OMDS_ACT_TANH) {   // derivative rows instead of masks: 16- or 32-row tiles (the 4-row-group backward is a ReLU-mask form)
-        const int rows = tail_sel_rows(st.N, st.k, false);
-        if (st.n == 7) { if (rows == 16) launch_tail_sel_t<7, 16, OMDS_ACT_TANH>(s, a); else launch_tail_sel_t<7, 32, OMDS_ACT_TANH>(s, a); }
-        else { if (rows == 16) launch_tail_sel_t<2, 16, OMDS_ACT_TANH>(s, a); else launch_tail_sel_t<2, 32, OMDS_ACT_TANH>(s, a); }
-        return;
-    }
-    const int rows = tail_sel_rows(st.N, st.k, m.skip_mask == 0 && m.nhh >= 1);
-    if (st.n == 7) { if (rows == 4) launch_tail_sel_t<7, 4>(s, a); else if (rows == 16) launch_tail_sel_t<7, 16>(s, a); else launch_tail_sel_t<7, 32>(s, a); }
-    else { if (rows == 4) launch_tail_sel_t<2, 4>(s, a); else if (rows == 16) launch_tail_sel_t<2, 16>(s, a); else launch_tail_sel_t<2, 32>(s, a); }
-}
-
-static size_t tail_lds_bytes(int nhid) {
-    return ((size_t)P2_MT * LDH + 32 * 33) * 4 + (size_t)nhid * P2_NT * 4 + 3 * P2_MT * 4 +
-           (32 * 12 + 32 + 32 * 3 * OMDS_MAX_DOF) * 4;
-}
-
-template <int ND, int ACT, int ROWS, bool FRAME = false>
-static void launch_tail_a(hipStream_t s, const TailArgs& a) {
-    static std::atomic<uint64_t> configured{0};
-    if (omds_first_use_on_device(configured)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tail<ND, ACT, ROWS, FRAME>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)tail_lds_bytes(OMDS_MAX_HIDDEN + 1));
-    }
-    const int RW = (ROWS == 4 ? 20 : ROWS) / a.st.k;
-    const int grid = (a.st.N + RW - 1) / RW;
-    hipLaunchKernelGGL((k_tail<ND, ACT, ROWS, FRAME>), dim3(grid), dim3(P2_NT), tail_lds_bytes(a.m.nhh + 1), s, a);
-    tail_tl_dump(s, a.st.step, grid);
-}
-
-template <int ND, int ROWS>
-static void launch_tail_t(hipStream_t s, const TailArgs& a) {
-    if constexpr (ROWS != 4) {
-        if (a.st.frame) {
-            if (a.m.act == OMDS_ACT_RELU) launch_tail_a<ND, OMDS_ACT_RELU, ROWS, true>(s, a);
-            else launch_tail_a<ND, OMDS_ACT_TANH, ROWS, true>(s, a);
-            return;
-        }
-    }
-    if (a.m.act == OMDS_ACT_RELU) launch_tail_a<ND, OMDS_ACT_RELU, ROWS>(s, a);
-    else if constexpr (ROWS != 4) launch_tail_a<ND, OMDS_ACT_TANH, ROWS>(s, a);
+    a.rowlist = scr.rowlist; a.range = scr.range; a.ex = ex;
+    launch_tail_key(TAIL_SEL_LAUNCHERS, tail_sel_plan_key(st.n, m.act, m.skip_mask == 0 && m.nhh >= 1, st.frame != 0, st.N, st.k, omds_cu_count(),
+                                                          OMDS_FORCED_ROWS(g_force_sel_rows)), s, a);
 }
 
 bool omds_tail_supported(int n_dof, int k) { return (n_dof == 7 || n_dof == 2) && k >= 1 && k <= P2_MT; }
 
-// 16-row tiles when 32-row tiles would leave most CUs without a workgroup; g4_ok (ReLU network without skip concatenations): 4-row groups, 20 rows per workgroup (k_tail<ND, ACT, 4>), while its workgroups fit the CUs in ONE
-// round -- 5 groups x 2048 x 1.1 matrix-pipe cycles per hidden layer against 16 384 per 32-row tile.  N = 1024, k = 5: 256 workgroups,
-// one per CU, against 171 tiles of 32 rows (71.6 -> 58.4 us).  Beyond one round the 32-row tile wins: the 4-row-group kernel holds
-// the weight ring in 64 registers (134 in all: one workgroup per CU, nothing fills its top-k / modulation phases) and multiplies on
-// four of its eight waves -- N = 4096: 233 against 200 us, N = 8192: 460 against 358 (tools/tail_rows_ab.sh).
-int omds_tail_rows(int N, int k, bool g4_ok) {
-    const int forced = OMDS_FORCED_ROWS(g_force_tail_rows);
-    if (k > 16) return 32;
-    if (forced == 4 && g4_ok && k <= 20) return 4;
-    if (forced == 16 || forced == 32) return forced;
-    const int RW32 = 32 / k;
-    const long long wg32 = (N + RW32 - 1) / RW32;
-    if (wg32 <= 128) return 16;
-    if (forced == 0 && g4_ok && k <= 10) {
-        const int ncu = omds_cu_count(), RW4 = 20 / k;
-        const long long wg4 = (N + RW4 - 1) / RW4;
-        if (wg4 <= ncu) return 4;
-    }
-    return 32;
-}
-
-int omds_tail_scratch_rows(int N, int k) {
-    const int RW32 = P2_MT / k;
-    int rows = (N + RW32 - 1) / RW32 * 32;
-    if (k <= 16) { const int RW16 = 16 / k; rows = std::max(rows, (N + RW16 - 1) / RW16 * 16); }
-    return rows;
-}
+int omds_pass2_rows(int N, int k) { return omds_tail_rows(N, k, false, omds_cu_count(), OMDS_FORCED_ROWS(g_force_tail_rows)); }
 
 void omds_launch_tail(hipStream_t s, const MlpDev& m, const float* Fp, const float* radius, const float* xyzr,
-                      const float* Dmin, float* Fq, float* dscr, int O, const StepArgs& st, uint16_t* FqH, int ldF,
-                      float* FqOut, const int* guard_range, float e_bound, unsigned* viol, bool shared_row) {
+                      const float* Dmin, float* Fq, float* dscr, int O, const StepArgs& st, const TailScreen& scr, bool shared_row) {
     TailArgs a;
     a.ldD = shared_row ? 0 : O;
-    a.FqH = reinterpret_cast<_Float16*>(FqH);
-    a.ldF = ldF;
-    int rows = omds_tail_rows(st.N, st.k, m.act == OMDS_ACT_RELU && m.skip_mask == 0 && m.nhh >= 1);
-    if (st.frame) rows = frame_rows(rows, st.k);
-    const int RW = (rows == 4 ? 20 : rows) / st.k;
-    a.n_slots = (st.N + RW - 1) / RW;
-    a.rowlist = nullptr; a.range = guard_range; a.ex = ExactOut{}; a.e_bound = e_bound; a.viol = viol;
-    a.m = m; a.Fp = Fp; a.radius = radius; a.xyzr = xyzr; a.Dmin = Dmin; a.Fq = Fq; a.FqOut = FqOut ? FqOut : Fq; a.dscr = dscr; a.O = O; a.st = st;
-    if (rows == 4) {
-        if (st.n == 7) launch_tail_t<7, 4>(s, a);
-        else launch_tail_t<2, 4>(s, a);
-    } else if (rows == 16) {
-        if (st.n == 7) launch_tail_t<7, 16>(s, a);
-        else launch_tail_t<2, 16>(s, a);
-    } else {
-        if (st.n == 7) launch_tail_t<7, 32>(s, a);
-        else launch_tail_t<2, 32>(s, a);
-    }
+    a.FqH = reinterpret_cast<_Float16*>(scr.FqH);
+    a.ldF = scr.ldF;
+    const TailKey key = tail_plan_key(st.n, m.act, m.skip_mask == 0 && m.nhh >= 1, st.frame != 0, st.N, st.k, omds_cu_count(),
+                                      OMDS_FORCED_ROWS(g_force_tail_rows));
+    a.n_slots = tail_workgroups(st.N, key.rows, st.k);
+    a.rowlist = nullptr; a.range = scr.range; a.ex = ExactOut{}; a.e_bound = scr.e_bound; a.viol = scr.viol;
+    a.m = m; a.Fp = Fp; a.radius = radius; a.xyzr = xyzr; a.Dmin = Dmin; a.Fq = Fq; a.FqOut = scr.FqOut ? scr.FqOut : Fq; a.dscr = dscr; a.O = O; a.st = st;
+    launch_tail_key(TAIL_LAUNCHERS, key, s, a);
 }
