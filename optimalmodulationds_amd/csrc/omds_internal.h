@@ -9,6 +9,7 @@
 
 #include "omds.h"
 #include "tail_plan_def.h"
+#include "screen_plan_def.h"
 
 // The library reads OMDS_SCREEN (0 | 1 | 2: the screening mode of contexts left on the default, -1), OMDS_ROCTX and OMDS_RCCL_LIB from the
 // environment, nothing else (tests/test_capi_cpu.py).
@@ -126,6 +127,20 @@ inline bool omds_first_use_on_device(std::atomic<uint64_t>& mask) {
     (void)hipGetDevice(&dev);
     const uint64_t bit = 1ull << (dev & 63);
     return (mask.fetch_or(bit) & bit) == 0;
+}
+// CUs of the current device (asked once per device)
+inline int omds_cu_count() {
+    static std::atomic<int> ncu_of[64];
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    int ncu = ncu_of[dev & 63].load();
+    if (ncu == 0) {
+        ncu = 256;
+        (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+        if (ncu <= 0) ncu = 256;
+        ncu_of[dev & 63].store(ncu);
+    }
+    return ncu;
 }
 
 // A distance network with a hidden layer wider than OMDS_WIDTH (wide_kernels.hip): raw row-major weights, materialised activations
@@ -540,14 +555,13 @@ struct omds_ctx;
 int omds_wide_network(omds_ctx* ctx, const float* qT, int ldq, int B);
 int omds_wide_vjp(omds_ctx* ctx, const float* d_x, int rows, int seed_col = -1);
 
-// ---- launchers implemented in screen_kernel.hip -----------------------------------------------
+// ---- launchers implemented in screen_kernel.hip, screen_exact.hip and screen_stats.hip --------
 // sel != nullptr (a DEVICE pointer to the step's sink; needs omds_screen_can_select(O)): every workgroup owns whole rollouts
 // and its flush phase selects their candidates from LDS -- Dmin is not written and no k_select runs; otherwise the N x O
 // matrix goes to Dmin
 void omds_launch_screen(hipStream_t s, const ScreenDev& sd, const MlpDev& m, const uint16_t* FqH, int ldFq, const uint16_t* FpH,
                         int ldFp, const float* radius, int O, int B, uint32_t ignored, float* Dmin, const SelectSink* sel = nullptr);
-bool omds_screen_supported(const MlpDev& m);
-bool omds_screen_can_select(int O);
+bool omds_screen_supported(const MlpDev& m);   // (omds_screen_can_select: screen_plan_def.h)
 // What k_exact leaves behind for the screened step's tail (k_tail_sel), per entry of the candidate list: the pass-1 value,
 // and everything pass 2's forward would produce for that row -- its arithmetic is the same bit for bit -- so that the tail
 // only runs the backward: the pass-2 distance, the arg-min link, and the ReLU masks of every hidden layer.  mask layout per
@@ -621,7 +635,6 @@ void omds_launch_tail(hipStream_t s, const MlpDev& m, const float* Fp, const flo
 // screened step's tail: top-k over the candidates k_exact evaluated + pass-2 backward on its masks + the rest of k_tail.  The next
 // step's encoded joint inputs go to Fq.
 bool omds_tail_sel_supported(int n_dof, int k);
-int omds_cu_count();   // CUs of the current device (asked once per device)
 #ifdef OMDS_TEST_HOOKS
 void omds_force_tile_rows(int tail_sel_rows, int tail_rows);   // test hook (libomds_hip_test.so): 0 = the launcher's own choice
 #endif

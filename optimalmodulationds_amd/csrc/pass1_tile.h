@@ -1,5 +1,5 @@
 // The dense pass-1 tile: pass1_tile in all its forms (k_pass1, k_pass1e, k_exact, k_audit, k_step_small) and the divisor by
-// multiplication its row bookkeeping uses.  Included by mlp_kernels.hip, screen_kernel.hip, step_small.hip and pass1_tile_dyn.h.
+// multiplication its row bookkeeping uses.  Included by mlp_kernels.hip, screen_kernel.hip, screen_exact.hip, screen_stats.hip, step_small.hip and pass1_tile_dyn.h.
 #pragma once
 #include "mfma_gemm.h"
 #include "timeline_device.h"
@@ -27,7 +27,7 @@ struct OmdsDivisor {
 enum class TileMode {
     Dmin,       // The tile covers rows row0 .. row0+MT-1 of the virtual rollout-major pair space (row = t*O + o) and writes Dmin[row].  (k_pass1,
                 // k_pass1_mixed)
-    List,       // Screening, screen_kernel.hip: the tile covers entries row0 .. of `rowlist`, each naming a pair t*O + o; the exact value, what pass
+    List,       // Screening, screen_exact.hip: the tile covers entries row0 .. of `rowlist`, each naming a pair t*O + o; the exact value, what pass
                 // 2's forward would compute for the row (pass-2 distance, arg-min link) and the ReLU masks go to ex->... per list entry, and max
                 // |screening value - exact value| to *maxerr_bits.  (k_exact, ReLU)
     SmallScene, // Fused small-O step, step_small.hip: rows as in Dmin, outputs as in List but indexed by the row within the tile (ex-> pointers are
@@ -80,7 +80,7 @@ __device__ __forceinline__ void pass1_tile(const MlpDev& m, float* smem, const f
     constexpr bool LIST = tile_lists(MODE), EMIT = tile_emits_masks(MODE), DERIV = tile_emits_deriv(MODE), EMITY = tile_emits_y(MODE);
     static_assert(!DERIV || MT == 16, "the derivative hand-over is written for the 16-row tiles of k_exact");
     using G = Geo<MT, MR, NR>;
-    float* Hs = smem;                                           // [MT][LDH]
+    float* Hs = smem;                                           // [MT][LDH]   (the blocks' sizes for the launchers: screen_plan_def.h)
     float* rowRad = smem + MT * LDH;                            // [MT] obstacle radius of each row
     int* rowIdx = reinterpret_cast<int*>(rowRad + MT);          // [MT] LIST: pair index of each row
     uint32_t* maskS = reinterpret_cast<uint32_t*>(rowIdx + MT); // [MT][nhid][8] LIST: ReLU masks of the tile's rows

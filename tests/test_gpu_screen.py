@@ -271,7 +271,7 @@ def test_screened_tanh_and_skip_fixtures(name, kind):
 
 
 def test_rows_longer_than_a_workgroups_result_buffer_take_the_matrix_route():
-    """O = 6000 obstacles: a rollout's screening values no longer fit one workgroup's LDS (5120), so k_screen writes the
+    """O = 6000 obstacles: a rollout's screening values no longer fit one workgroup's LDS (SC_MAX_TILES * SC_ROWS, screen_plan_def.h), so k_screen writes the
     matrix and k_select -- its long-row form, values re-read instead of held in registers -- does the selection: same bits."""
     rng = np.random.RandomState(8)
     p = rng.uniform([-0.3, -0.8, 0.0], [1.0, 0.8, 1.2], (6000, 3))

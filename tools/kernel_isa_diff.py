@@ -5,8 +5,9 @@
 
 Every kernel translation unit of each side (a .hip file with a __global__) is compiled with the Makefile's CXXFLAGS plus
 --cuda-device-only -S into a scratch directory, the assembly is cut per kernel symbol, and each kernel is reported as
-"identical" or with instruction count and resource figures of both sides.  It diffs and counts; it looks for no instruction.
-Exit status 1 when a kernel differs or exists on one side only.
+"identical" or with instruction count, resource figures and spill counts of both sides.  Kernels are matched by name over all the
+translation units of a side, so one that moved to another file is compared with itself.  It diffs and counts; it looks for no
+instruction.  Exit status 1 when a kernel differs or exists on one side only.
 """
 import argparse
 import concurrent.futures
@@ -50,6 +51,9 @@ def kernels(asm):
         figs = {k: int(re.search(rf"^; {k}: (\d+)", chunk, re.M).group(1)) for k in FIGURES}
         code = body[:next(i for i, l in enumerate(body) if l.startswith("\t.section"))]
         figs["instructions"] = sum(1 for l in code if re.match(r"\t[a-z]", l))
+        meta = text[text.index(f".name:           {sym}\n"):]           # the kernel's entry of amdhsa.kernels: its spill counts
+        for k in ("sgpr_spill_count", "vgpr_spill_count"):
+            figs[k] = int(re.search(rf"\.{k}:\s+(\d+)", meta[:meta.index(".wavefront_size:")] if ".wavefront_size:" in meta else meta).group(1))
         found[demangle(sym)] = (body, figs)
     return found
 
@@ -76,26 +80,30 @@ def main():
         if a.scratch:
             tmp = a.scratch
             pathlib.Path(tmp).mkdir(parents=True, exist_ok=True)
-        jobs, stems = [], None
+        jobs = []
         for side, csrc in (("parent", a.parent), ("child", a.child)):
             units = sorted(p for p in csrc.glob("*.hip") if "__global__" in p.read_text() and (not a.files or p.stem in a.files))
-            stems = [p.stem for p in units] if stems is None else [s for s in stems if s in {p.stem for p in units}]
             jobs += [(p, pathlib.Path(tmp) / f"{side}_{p.stem}.s", cxxflags(csrc) + a.flags.split()) for p in units]
         with concurrent.futures.ThreadPoolExecutor(a.jobs) as pool:
             list(pool.map(compile_asm, jobs))
-        differing = 0
-        for stem in stems:
-            old, new = kernels(pathlib.Path(tmp) / f"parent_{stem}.s"), kernels(pathlib.Path(tmp) / f"child_{stem}.s")
-            same = [s for s in old if s in new and old[s][0] == new[s][0]]
-            print(f"== {stem}: {len(same)} of {len(old)} kernels identical")
-            for sym in sorted(set(old) | set(new)):
-                if sym in same:
-                    continue
-                differing += 1
-                print(f"  {sym}")
-                for side, table in (("parent", old), ("child", new)):
-                    print(f"    {side:6s} " + ("absent" if sym not in table else "  ".join(f"{k} {v}" for k, v in table[sym][1].items())))
-        return 1 if differing else 0
+        old, new, where = {}, {}, {}
+        for _, out, _ in jobs:
+            side, stem = out.stem.split("_", 1)
+            for sym, entry in kernels(out).items():
+                (old if side == "parent" else new)[sym] = entry
+                where.setdefault(sym, {})[side] = stem
+        same = [s for s in old if s in new and old[s][0] == new[s][0]]
+        print(f"== {len(same)} of {len(old)} kernels identical ({len(new)} on the child's side)")
+        for sym in sorted(set(old) | set(new)):
+            moved = len(set(where[sym].values())) > 1
+            if sym in same:
+                if moved:
+                    print(f"  {sym}: identical, {where[sym]['parent']} -> {where[sym]['child']}")
+                continue
+            print(f"  {sym}" + (f" ({where[sym]['parent']} -> {where[sym]['child']})" if moved else ""))
+            for side, table in (("parent", old), ("child", new)):
+                print(f"    {side:6s} " + ("absent" if sym not in table else "  ".join(f"{k} {v}" for k, v in table[sym][1].items())))
+        return 1 if len(same) < len(set(old) | set(new)) else 0
 
 
 if __name__ == "__main__":
