@@ -368,8 +368,9 @@ OMDS_API int omds_get_cloud_objects(omds_ctx* ctx, int32_t* label, int32_t* obje
  * grid; a depth camera delivers a uint16 (or float32) image, intrinsics and a pose, and a cell around an arm has two or three of them.
  * The depth call deprojects inside the counting pass, without ever writing a point: everything after that pass is integer sums and
  * ordered compactions, a function of the SET of points.  Additive: no other entry point changes its launches or its bits.
- * OUT OF SCOPE: lens distortion (the image is taken as rectified), range-type depth (z is depth along the optical axis), depth-noise
- * filtering, registration of the cameras against each other (the poses are taken as given), temporal smoothing.
+ * OUT OF SCOPE: lens distortion (the image is taken as rectified), range-type depth (z is depth along the optical axis),
+ * registration of the cameras against each other (the poses are taken as given), temporal smoothing.  (Flying pixels and speckle:
+ * THE DEPTH FILTER below.)
  *   omds_depth_points : host only (no context, no GPU), the DEFINITION.  All fp32, every operation named one rounding.  Once per
  *       camera: ifx = 1.0f / fx, ify = 1.0f / fy.  The visited pixels are columns u and rows v in 0, step, 2 step, ... (step < 1 is 1),
  *       in row-major order, ceil(H / step) * ceil(W / step) of them; the raw value is d = image[v * pitch + u] (pitch in ELEMENTS, 0 is
@@ -474,6 +475,51 @@ OMDS_API int omds_set_obstacles_from_depth_memory(omds_ctx* ctx, const omds_clou
 OMDS_API int omds_scene_memory_reset(omds_ctx* ctx);
 OMDS_API int omds_get_scene_memory(omds_ctx* ctx, int32_t* age /* [n_obs] or NULL */, uint32_t* grid /* [cells] or NULL */,
                                    int32_t* n_cells_out);
+/* THE DEPTH FILTER: FLYING PIXELS AND SPECKLE LEAVE INSIDE THE COUNTING PASS (new work).  At a depth discontinuity a camera returns
+ * mixed pixels with depths between foreground and background, and in low-texture regions isolated speckle; each becomes a sphere in
+ * free space that the planner bends around and the scene memory keeps.  The filter asks the neighbours of a pixel whether they see the
+ * same surface, inside the counting pass of the depth routes: still no point is ever written.  Additive: with no filter set every entry
+ * point keeps its launches and its bits.
+ * OUT OF SCOPE: bilateral or temporal smoothing of depth VALUES (a kept pixel keeps its depth), confidence images, tolerances that
+ * follow the z^2 noise model of stereo cameras (tol is affine in z).
+ *   THE RULE.  All fp32, every operation named one rounding.  A visited pixel (ju, jv) that omds_depth_points keeps (return, range
+ *       gate) at depth z is kept by the filter iff s >= min_support, where tol = fmaf(edge_rel, z, edge_abs) and s counts the window
+ *       positions (ju + a, jv + b) with |a|, |b| <= radius, (a, b) != (0, 0), inside [0, nu) x [0, nv), whose raw element at column
+ *       (ju + a) step, row (jv + b) step is a return (U16: d != 0, z_n = (float)d * depth_scale; F32: z_n = the element) with
+ *       fabsf(z_n - z) <= tol (NaN fails the comparison).  The window is one of VISITED pixels: with step > 1 the neighbours are step
+ *       elements apart.  Neighbours are deliberately NOT range-gated: a surface just beyond z_max still supports its neighbour, for the
+ *       same reason as the scene memory's z_pix.  Positions outside the image give no support: a corner pixel at radius 1 has 3
+ *       possible supporters, a border pixel 5.
+ *   omds_depth_points_filtered : host only, the DEFINITION.  The output of omds_depth_points with a rejected pixel written as three
+ *       NaNs; *n_valid_out = pixels kept by both, *n_rejected_out = pixels omds_depth_points keeps and the filter drops.  filt == NULL
+ *       is exactly omds_depth_points (*n_rejected_out = 0 when given).  OMDS_ERR_INVALID_ARG before anything is written: as
+ *       omds_depth_points, a spec outside the ranges of the struct, and with a filter a null n_rejected_out.
+ *   omds_depth_scene_memory_filtered : omds_depth_scene_memory with the counts n[c] of the filtered points (filt == NULL: the same
+ *       call).  Only the counts change: the verdicts of step 3 read the RAW images -- a flying pixel is still a return.
+ *   omds_set_depth_filter : the filter is CONTEXT STATE, off at creation; spec == NULL turns it off.  A refused spec leaves the stored
+ *       filter as it was.  omds_set_obstacles_from_depth (plain, tracked, objects) and omds_set_obstacles_from_depth_memory consult it.
+ *       THE CONTRACT with a filter set -- every effect of those calls is that of the cloud call on the concatenation of
+ *       omds_depth_points_filtered of each image, bit for bit; of the memory call, omds_depth_scene_memory_filtered iterated.  The filter
+ *       is not part of the scene memory's key.  On the device: k_depth_count_filt / k_depth_count_filt_rec in place of the counting
+ *       kernels -- a workgroup owns a tile of 32 x 32 visited pixels, stages it with a halo of radius as z_n into LDS (NaN: no return,
+ *       or outside the image; every raw element read once per tile), one barrier, the support test on LDS alone, and the surviving
+ *       pixels go on as before.  Integer counters, reduced per wave.
+ *   omds_get_depth_filter_stats : out[0] = pixels kept, out[1] = pixels rejected by the filter in the last depth call of the context
+ *       that got as far as its counting pass (the too-many-cells refusal included), summed over cameras; 0, 0 when no filter ran.    */
+typedef struct {
+    int32_t radius;       /* window = (2 radius + 1)^2 VISITED pixels around the pixel: 1 .. 3                             */
+    int32_t min_support;  /* kept when at least this many OTHER window pixels support it: 1 .. (2 radius + 1)^2 - 1        */
+    float   edge_abs;     /* metres; finite, >= 0                                                                          */
+    float   edge_rel;     /* per metre of the pixel's depth; finite, >= 0                                                  */
+} omds_depth_filter_spec;
+OMDS_API int omds_depth_points_filtered(const omds_depth_camera* cam, const omds_depth_filter_spec* filt /* NULL: off */, const void* image,
+                                        float* xyz_out, int64_t cap_points, int64_t* n_valid_out, int64_t* n_rejected_out);
+OMDS_API int omds_depth_scene_memory_filtered(const omds_cloud_spec* spec, const omds_scene_memory_spec* mem_spec,
+                                              const omds_depth_filter_spec* filt /* NULL: off */, const omds_depth_camera* cams,
+                                              const void* const* images, int32_t n_cams, const uint32_t* mem_in, uint32_t* mem_out,
+                                              int32_t counts_out[4]);
+OMDS_API int omds_set_depth_filter(omds_ctx* ctx, const omds_depth_filter_spec* spec /* NULL: off */);
+OMDS_API int omds_get_depth_filter_stats(omds_ctx* ctx, int64_t out[2] /* kept, rejected */);
 /* THE OBSTACLE FOCUS (new work).  A sensed scene has thousands of spheres; everything behind pass 1 uses the n_closest nearest per
  * (rollout, step).  A focus call evaluates the distance of every sphere of the scene at ONE joint state, selects the near ones and
  * installs them as the scene in force, on the device; the full scene (the MASTER) is kept, so that the next call selects from it again

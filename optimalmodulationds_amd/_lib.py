@@ -89,6 +89,11 @@ class OmdsSceneMemorySpec(C.Structure):
     _fields_ = [("max_age", C.c_int32), ("clear_margin", C.c_float), ("footprint", C.c_int32)]
 
 
+class OmdsDepthFilterSpec(C.Structure):
+    """omds_depth_filter_spec (include/omds.h): which depth pixels the depth routes drop as flying pixels or speckle."""
+    _fields_ = [("radius", C.c_int32), ("min_support", C.c_int32), ("edge_abs", C.c_float), ("edge_rel", C.c_float)]
+
+
 class OmdsObstacleFocusSpec(C.Structure):
     """omds_obstacle_focus_spec (include/omds.h): which spheres of a large scene an obstacle focus keeps."""
     _fields_ = [("margin", C.c_float), ("lookahead", C.c_float), ("max_keep", C.c_int32)]
@@ -152,6 +157,12 @@ SIGNATURES = {
                                                        C.POINTER(OmdsDepthCamera), C.POINTER(C.c_void_p), C.c_int32, C.c_int, F32P, I32P, I32P]),
     "omds_scene_memory_reset": (C.c_int, [C.c_void_p]),
     "omds_get_scene_memory": (C.c_int, [C.c_void_p, I32P, C.c_void_p, I32P]),
+    "omds_depth_points_filtered": (C.c_int, [C.POINTER(OmdsDepthCamera), C.POINTER(OmdsDepthFilterSpec), C.c_void_p, F32P, C.c_int64,
+                                             C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "omds_depth_scene_memory_filtered": (C.c_int, [C.POINTER(OmdsCloudSpec), C.POINTER(OmdsSceneMemorySpec), C.POINTER(OmdsDepthFilterSpec),
+                                                   C.POINTER(OmdsDepthCamera), C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.c_void_p, I32P]),
+    "omds_set_depth_filter": (C.c_int, [C.c_void_p, C.POINTER(OmdsDepthFilterSpec)]),
+    "omds_get_depth_filter_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "omds_obstacle_focus_select": (C.c_int, [C.POINTER(OmdsObstacleFocusSpec), F32P, F32P, C.c_int, C.c_int, I32P, C.c_int32, I32P, I32P]),
     "omds_focus_obstacles": (C.c_int, [C.c_void_p, C.POINTER(OmdsObstacleFocusSpec), F32P, I32P, I32P]),
     "omds_get_obstacle_focus": (C.c_int, [C.c_void_p, I32P, I32P, I32P]),
@@ -255,7 +266,7 @@ HORIZON_HOOK_SIGNATURES = {
 }
 TEST_LIB_PATH = os.path.join(_HERE, "csrc", "libomds_hip_test.so")
 
-ABI_VERSION = 510     # omds_version() of the library this binding was written against
+ABI_VERSION = 511     # omds_version() of the library this binding was written against
 _libs = {}             # path -> bound CDLL
 
 

@@ -22,8 +22,8 @@ inline size_t cloud_padded_cells(const CloudGrid& g) { return (size_t)cloud_comp
 struct DepthCamDev {
     DepthCam c;
     const void* image;     // device memory, element (0, 0)
-    int runs;              // items per visited row: ceil(nu / DEPTH_RUN)       (these two are the launcher's to fill)
-    long long items;       // runs * nv
+    int runs;              // items per visited row: ceil(nu / DEPTH_RUN)       (these two are the launcher's to fill; the filtered
+    long long items;       // runs * nv                                          pass: tiles per tile row, and the camera's tiles)
 };
 struct DepthTable {
     DepthCamDev cam[OMDS_DEPTH_MAX_CAMERAS];
@@ -35,6 +35,12 @@ void omds_launch_cloud_count(hipStream_t s, const float* xyz, long long P, const
 void omds_launch_cloud_count(hipStream_t s, const float* xyz, long long P, const CloudGrid& g, uint4* rec);
 void omds_launch_cloud_count(hipStream_t s, DepthTable tab, int n_cams, const CloudGrid& g, unsigned* count);
 void omds_launch_cloud_count(hipStream_t s, DepthTable tab, int n_cams, const CloudGrid& g, uint4* rec);
+// ... from the pixels of the images the depth filter f keeps (depth_filter_def.h); counters [2], cleared by the caller, takes the pixels
+// the filter kept and those it rejected
+void omds_launch_cloud_count_filtered(hipStream_t s, DepthTable tab, int n_cams, const CloudGrid& g, const DepthFilter& f, unsigned* count,
+                                      unsigned* counters);
+void omds_launch_cloud_count_filtered(hipStream_t s, DepthTable tab, int n_cams, const CloudGrid& g, const DepthFilter& f, uint4* rec,
+                                      unsigned* counters);
 
 // The ordered compactions, one per item space: the kept items to out (and what goes with them) in item order, at most cap of them
 // written; sums [blocks of the item space + 1] is scratch, and sums[cloud_compaction_blocks(n)] holds the number of kept items after.

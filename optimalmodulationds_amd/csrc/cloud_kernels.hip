@@ -13,6 +13,7 @@
 // The scene memory of the depth route (scene_memory_def.h) is one more pass over the cells behind that counting pass (k_scene_memory),
 // a fifth item space of the compaction (MemSrc) and two small launches over the candidates (k_scene_memory_forget, k_scene_memory_age).
 #include <algorithm>
+#include <type_traits>
 
 #include "cloud_kernels.h"
 
@@ -198,6 +199,16 @@ constexpr int DEPTH_RUN = 4;
 constexpr int DEPTH_ROUNDS = 8;       // wave rounds before the lanes that are left issue their own atomics
 constexpr unsigned DEPTH_MAX_BLOCKS = 2048;
 
+// the cell of pixel (u, v) at a depth z behind the range gate (-1: outside the grid) and, when REC, k[3] of cloud_cell_sub: the one
+// deprojection of every depth kernel here
+template <bool REC>
+__device__ inline int depth_pixel_cell(const DepthCam& c, const CloudGrid& g, int u, int v, float z, unsigned* k) {
+    float w[3];
+    depth_point(c, u, v, z, w);
+    if (REC) return cloud_cell_sub(g, w[0], w[1], w[2], k);
+    return cloud_cell(g, w[0], w[1], w[2]);
+}
+
 // the cells of item `item` of camera d: cell[t] (-1: no point) and, when REC, k[t][3] of cloud_cell_sub
 template <bool REC>
 __device__ inline void depth_item_cells(const DepthCamDev& d, const CloudGrid& g, long long item, int* cell, unsigned (*k)[3]) {
@@ -239,10 +250,7 @@ __device__ inline void depth_item_cells(const DepthCamDev& d, const CloudGrid& g
     for (int t = 0; t < DEPTH_RUN; ++t) {
         cell[t] = -1;
         if (!have[t] || !depth_gate(c, z[t])) continue;
-        float w[3];
-        depth_point(c, (j0 + t) * c.step, v, z[t], w);
-        if (REC) cell[t] = cloud_cell_sub(g, w[0], w[1], w[2], k[t]);
-        else cell[t] = cloud_cell(g, w[0], w[1], w[2]);
+        cell[t] = depth_pixel_cell<REC>(c, g, (j0 + t) * c.step, v, z[t], k[t]);
     }
 }
 
@@ -274,6 +282,10 @@ template <> struct DepthAcc<true> {
 // image in which every lane holds other cells does not serialise 64 rounds.  Integer sums: no order can change a bit.  No atomic
 // returns a value and nothing waits for one.  (The plain form, one atomic per kept pixel, was 0.02-0.06 ms slower per tracked call
 // at 640 x 480: EXPERIMENTS R20.)
+// THE MERGE STANDS TWICE: here, inside depth_count's loop, and as depth_add_cells below it for the filtered pass (why: there).  A
+// change to the rounds, to DepthAcc or to the field bound is a change to both; the contention extremes of tests/test_gpu_depth.py (every
+// pixel in one cell, two cells, more cells in a wave than rounds) go through this one there and through the other in
+// tests/test_gpu_depth_filter.py.
 template <bool REC>
 __device__ inline void depth_count(const DepthTable& tab, const CloudGrid& g, void* buf) {
     typedef DepthAcc<REC> Acc;
@@ -311,6 +323,172 @@ __device__ inline void depth_count(const DepthTable& tab, const CloudGrid& g, vo
         for (int t = 0; t < DEPTH_RUN; ++t)
             if (cell[t] >= 0) Acc::add(buf, cell[t], acc[t]);
     }
+}
+
+// ... and the merge of depth_count as a function, for the filtered pass below: reached by every lane of a wave (the cross-lane steps
+// need it whole), uses cell[] up.  depth_count keeps its own text: calling this from there changes the instructions of k_depth_count
+// and k_depth_count_rec (the compiler unrolls the rounds), and those two stay the kernels they were
+template <bool REC>
+__device__ inline void depth_add_cells(int* cell, const unsigned (*k)[3], void* buf) {
+    typedef DepthAcc<REC> Acc;
+    typedef typename Acc::T T;
+    const int lane = threadIdx.x & 63;
+    T acc[DEPTH_RUN];
+    for (int t = 0; t < DEPTH_RUN; ++t) acc[t] = Acc::one(k[t]);
+    for (int t = 1; t < DEPTH_RUN; ++t)
+        for (int s = 0; s < t; ++s)
+            if (cell[t] >= 0 && cell[t] == cell[s]) {
+                acc[s] += acc[t];
+                cell[t] = -1;
+            }
+    for (int round = 0; round < DEPTH_ROUNDS; ++round) {
+        const int mine = cell[0] >= 0 ? cell[0] : cell[1] >= 0 ? cell[1] : cell[2] >= 0 ? cell[2] : cell[3];
+        const unsigned long long pending = __ballot(mine >= 0);
+        if (!pending) break;   // the same for every lane of the wave
+        const int namer = __ffsll((long long)pending) - 1;
+        const int named = __shfl(mine, namer, 64);
+        T part = 0;
+        for (int t = 0; t < DEPTH_RUN; ++t)
+            if (cell[t] == named) {
+                part = acc[t];
+                cell[t] = -1;
+            }
+        const T sum = wave_sum(part);
+        if (lane == namer) Acc::add(buf, named, sum);
+    }
+    for (int t = 0; t < DEPTH_RUN; ++t)
+        if (cell[t] >= 0) Acc::add(buf, cell[t], acc[t]);
+}
+
+// ---- the counting pass behind the depth filter (depth_filter_def.h) ----------------------------------------------------------------
+// The same launch shape -- one launch, the table by value, blockIdx.y the camera, a lane a run of DEPTH_RUN visited pixels of a row --
+// but a workgroup owns a TILE of FILT_TW x FILT_TH visited pixels: FILT_TW / DEPTH_RUN = 8 runs across, 32 rows down.  It stages the
+// tile with a halo of R as z_n into LDS, one float per visited pixel, NaN for "no return" and for "outside the image" alike (which
+// makes the support test the definition's one comparison for either format); every raw element is read from global memory once per
+// tile.  One barrier per tile: the tiles alternate between two LDS images, and a lane that stages image i has passed the barrier of
+// tile i - 1, behind which no lane reads image i - 2 = i any more.  The tile loop's bound is the same for every lane of the workgroup.
+//   TILE SHAPE: the halo reads (TW + 2R)(TH + 2R) / (TW TH) of the tile: 32 x 32: 1.13 (R = 1), 1.41 (R = 3); 64 x 16: 1.16, 1.50;
+//   128 x 8: 1.27, 1.83.  32 x 32 is the smallest overhead and also the shape whose run reads have no bank conflict:
+//   ROW STRIDE: the support test is ds_read_b32 / ds_read2_b32 traffic, banked (address / 4) mod 32 over each 32-lane half of a wave.  A half holds 4
+//   rows of 8 runs; at window offset (a, b) its lanes read the dwords row * S + 4 run + const.  4 run covers the banks = 0 (mod 4), so
+//   the four rows must differ mod 4: S = 1 (mod 4), the smallest such S >= TW + 2R -- 37, 37, 41 -- puts the 32 lanes on 32 banks.
+//   (With 16 runs to a row, a 64-wide tile, lanes run and run + 8 of ONE row are 32 dwords apart: 2-way whatever the stride.)
+constexpr int FILT_TW = 32, FILT_TH = 32, FILT_RUNS = FILT_TW / DEPTH_RUN;
+static_assert(FILT_RUNS * FILT_TH == CLOUD_NT, "one lane per run of the tile");
+constexpr int filt_stride(int R) { return (FILT_TW + 2 * R + 2) / 4 * 4 + 1; }
+static_assert(filt_stride(1) == 37 && filt_stride(2) == 37 && filt_stride(3) == 41, "the smallest stride = 1 (mod 4) that holds a staged row");
+
+// one aligned load of a group: 4 bytes = 2 U16 elements, 16 bytes = 4 F32 elements
+__device__ inline void filt_load_group(const uint16_t* p, uint16_t* raw) {
+    const unsigned w = *reinterpret_cast<const unsigned*>(p);
+    raw[0] = (uint16_t)(w & 0xffffu);
+    raw[1] = (uint16_t)(w >> 16);
+}
+__device__ inline void filt_load_group(const float* p, float* raw) {
+    const float4 w = *reinterpret_cast<const float4*>(p);
+    raw[0] = w.x; raw[1] = w.y; raw[2] = w.z; raw[3] = w.w;
+}
+
+// step == 1 (nu = width, nv = height): the rows of the staged region by the aligned loads of depth_item_cells -- a GROUP is G elements
+// whose first address is a multiple of G elements (4 bytes of a U16 row, 16 of an F32 row), whatever the base, the pitch and the tile's
+// first column; a lane takes one group of one row.  A group that lies whole inside its image row is one load; the groups on the row's
+// ends load their inside elements one by one (the next row, or the end of the buffer, lies behind them).  Elements of a group outside
+// the region are not stored; region positions outside the image hold NaN
+template <int R, class E, int G, class Z>
+__device__ inline void filt_stage_rows(const DepthCam& c, const E* image, int x0, int y0, float* tile, const Z& z_of) {
+    constexpr int RW = FILT_TW + 2 * R, RH = FILT_TH + 2 * R, S = filt_stride(R), NG = (RW + 2 * G - 2) / G;   // groups that touch a region row
+    const float nan = __builtin_nanf("");
+    const long long e0 = (long long)(reinterpret_cast<uintptr_t>(image) / sizeof(E));   // the image's address in elements
+    for (int i = threadIdx.x; i < NG * RH; i += CLOUD_NT) {
+        const int ry = i / NG, gi = i - ry * NG, y = y0 + ry;
+        const bool row_in = y >= 0 && y < c.nv;
+        const long long row = (long long)y * c.pitch;
+        const int lead = (int)((e0 + row + x0) & (long long)(G - 1));   // elements between the group boundary and the region's first column
+        const int xg = x0 - lead + gi * G;                              // column of the group's first element
+        float z[G];
+        for (int e = 0; e < G; ++e) z[e] = nan;
+        if (row_in && xg >= 0 && xg + G <= c.width) {
+            E raw[G];
+            filt_load_group(image + row + xg, raw);
+            for (int e = 0; e < G; ++e) z[e] = z_of(raw[e]);
+        } else if (row_in) {
+            for (int e = 0; e < G; ++e)
+                if (xg + e >= 0 && xg + e < c.width) z[e] = z_of(image[row + xg + e]);
+        }
+        for (int e = 0; e < G; ++e) {
+            const int rx = xg + e - x0;
+            if (rx >= 0 && rx < RW) tile[ry * S + rx] = z[e];
+        }
+    }
+}
+
+// the region of visited pixels [tu0 - R, tu0 + FILT_TW + R) x [tv0 - R, tv0 + FILT_TH + R) as z_n into tile [FILT_TH + 2R][stride]
+template <int R>
+__device__ inline void filt_stage(const DepthCam& c, const void* image, int tu0, int tv0, float* tile) {
+    constexpr int RW = FILT_TW + 2 * R, RH = FILT_TH + 2 * R, S = filt_stride(R);
+    const int x0 = tu0 - R, y0 = tv0 - R;
+    if (c.step == 1) {
+        if (c.format == OMDS_DEPTH_U16)
+            filt_stage_rows<R, uint16_t, 2>(c, static_cast<const uint16_t*>(image), x0, y0, tile, [&](uint16_t d) { return depth_filter_z_u16(c, d); });
+        else
+            filt_stage_rows<R, float, 4>(c, static_cast<const float*>(image), x0, y0, tile, [](float z) { return z; });
+        return;
+    }
+    for (int i = threadIdx.x; i < RW * RH; i += CLOUD_NT) {
+        const int ry = i / RW, rx = i - ry * RW, x = x0 + rx, y = y0 + ry;
+        float z = __builtin_nanf("");
+        if (x >= 0 && x < c.nu && y >= 0 && y < c.nv) z = depth_filter_z(c, image, (long long)y * c.step * c.pitch + (long long)x * c.step);
+        tile[ry * S + rx] = z;
+    }
+}
+
+// counters[0] += pixels the filter keeps, counters[1] += pixels it rejects: integers, reduced per wave, one atomic each
+template <bool REC, int R>
+__device__ inline void depth_count_filt(const DepthTable& tab, const CloudGrid& g, const DepthFilter& f, void* buf, unsigned* counters) {
+    constexpr int S = filt_stride(R), RH = FILT_TH + 2 * R;
+    __shared__ float tile[2][RH * S];
+    const DepthCamDev& d = tab.cam[blockIdx.y];
+    const DepthCam& c = d.c;
+    const int ly = threadIdx.x / FILT_RUNS, lx = threadIdx.x % FILT_RUNS * DEPTH_RUN;   // this lane's row and first column in the tile
+    unsigned kept = 0, rejected = 0;
+    int flip = 0;
+    for (long long t = blockIdx.x; t < d.items; t += gridDim.x, flip ^= 1) {   // items: the camera's tiles, runs of them to a tile row
+        const int tv0 = (int)(t / d.runs) * FILT_TH, tu0 = (int)(t % d.runs) * FILT_TW;
+        filt_stage<R>(c, d.image, tu0, tv0, tile[flip]);
+        __syncthreads();
+        const float* own = tile[flip] + (ly + R) * S + lx + R;
+        int cell[DEPTH_RUN] = {-1, -1, -1, -1};
+        unsigned k[DEPTH_RUN][3] = {};
+        for (int j = 0; j < DEPTH_RUN; ++j) {
+            const float z = own[j];                // NaN: no return, or a column / row past the image
+            if (!depth_gate(c, z)) continue;
+            const float* at = own + j;
+            if (!depth_filter_keep(f, R, z, [&](int a, int b) { return at[b * S + a]; })) {
+                ++rejected;
+                continue;
+            }
+            ++kept;
+            cell[j] = depth_pixel_cell<REC>(c, g, (tu0 + lx + j) * c.step, (tv0 + ly) * c.step, z, k[j]);
+        }
+        depth_add_cells<REC>(cell, k, buf);
+    }
+    kept = wave_sum(kept);
+    rejected = wave_sum(rejected);
+    if ((threadIdx.x & 63) == 0) {
+        if (kept) atomicAdd(counters, kept);
+        if (rejected) atomicAdd(counters + 1, rejected);
+    }
+}
+
+template <int R>
+__global__ __launch_bounds__(CLOUD_NT) void k_depth_count_filt(DepthTable tab, CloudGrid g, DepthFilter f, unsigned* __restrict__ count,
+                                                               unsigned* __restrict__ counters) {
+    depth_count_filt<false, R>(tab, g, f, count, counters);
+}
+template <int R>
+__global__ __launch_bounds__(CLOUD_NT) void k_depth_count_filt_rec(DepthTable tab, CloudGrid g, DepthFilter f, uint4* __restrict__ rec,
+                                                                   unsigned* __restrict__ counters) {
+    depth_count_filt<true, R>(tab, g, f, rec, counters);
 }
 
 __global__ __launch_bounds__(CLOUD_NT) void k_depth_count(DepthTable tab, CloudGrid g, unsigned* __restrict__ count) {
@@ -684,7 +862,43 @@ dim3 depth_blocks(DepthTable& tab, int n_cams) {
     return dim3((unsigned)std::min<long long>((most + CLOUD_NT - 1) / CLOUD_NT, per_camera), (unsigned)n_cams);
 }
 
+// ... of the filtered pass: an item is a tile, `runs` of them to a tile row
+dim3 depth_filt_blocks(DepthTable& tab, int n_cams) {
+    long long most = 1;
+    for (int i = 0; i < n_cams; ++i) {
+        DepthCamDev& d = tab.cam[i];
+        d.runs = (d.c.nu + FILT_TW - 1) / FILT_TW;
+        d.items = (long long)d.runs * ((d.c.nv + FILT_TH - 1) / FILT_TH);
+        most = std::max(most, d.items);
+    }
+    const unsigned per_camera = std::max(DEPTH_MAX_BLOCKS / (unsigned)n_cams, 1u);
+    return dim3((unsigned)std::min<long long>(most, per_camera), (unsigned)n_cams);
+}
+
+// the radius as a constant of the kernel (the window loops unroll): f(std::integral_constant<int, radius>)
+template <class F>
+void with_radius(int radius, const F& f) {
+    if (radius == 1) f(std::integral_constant<int, 1>{});
+    else if (radius == 2) f(std::integral_constant<int, 2>{});
+    else f(std::integral_constant<int, 3>{});
+}
+
 }  // namespace
+
+void omds_launch_cloud_count_filtered(hipStream_t s, DepthTable tab, int n_cams, const CloudGrid& g, const DepthFilter& f, unsigned* count,
+                                      unsigned* counters) {
+    const dim3 grid = depth_filt_blocks(tab, n_cams);
+    with_radius(f.radius, [&](auto R) {
+        hipLaunchKernelGGL((k_depth_count_filt<decltype(R)::value>), grid, dim3(CLOUD_NT), 0, s, tab, g, f, count, counters);
+    });
+}
+void omds_launch_cloud_count_filtered(hipStream_t s, DepthTable tab, int n_cams, const CloudGrid& g, const DepthFilter& f, uint4* rec,
+                                      unsigned* counters) {
+    const dim3 grid = depth_filt_blocks(tab, n_cams);
+    with_radius(f.radius, [&](auto R) {
+        hipLaunchKernelGGL((k_depth_count_filt_rec<decltype(R)::value>), grid, dim3(CLOUD_NT), 0, s, tab, g, f, rec, counters);
+    });
+}
 
 void omds_launch_cloud_count(hipStream_t s, const float* xyz, long long P, const CloudGrid& g, unsigned* count) {
     if (P > 0) hipLaunchKernelGGL(k_cloud_count, point_blocks(P), dim3(CLOUD_NT), 0, s, xyz, P, g, count);

@@ -114,6 +114,11 @@ struct CloudState {
     DevBuf<int> age;                  // [max_spheres] m' - 1 of every final sphere's cell
     DevBuf<unsigned> memCounts;       // [SCENE_MEM_COUNTS] seen, remembered, cleared, expired, self-forgotten of the call under way
     std::vector<int32_t> mem_age;     // [n_obs] of the scene in force when the memory call installed it (padding: -1), else empty
+    // ... the depth filter (omds_set_depth_filter): context state that every depth call consults; no key of anything stored
+    bool filter_on = false;
+    DepthFilter filter = {};          // behind its checks, while filter_on
+    DevBuf<unsigned> filtCounts;      // [2] pixels the filter kept and rejected in the call under way
+    int64_t filter_stats[2] = {0, 0}; // ... of the last depth call that reached its counting pass; 0, 0 when no filter ran
 
     void forget_tracking() { frame.have = false; tab.have = false; }          // omds_cloud_track_reset
     void forget_labels() { obj_label.clear(); obj_flag.clear(); mem_age.clear(); }   // another setter installed the scene in force

@@ -1,5 +1,5 @@
 // The scene from a depth point cloud or from depth images (omds.h: omds_set_obstacles_from_cloud[_tracked|_objects],
-// omds_set_obstacles_from_depth[_memory]), as host stages over the launchers of cloud_kernels.h; the state between calls is omds_ctx::cloud
+// omds_set_obstacles_from_depth[_memory], omds_set_depth_filter), as host stages over the launchers of cloud_kernels.h; the state between calls is omds_ctx::cloud
 // (cloud_state.h).  One body, scene_from_cloud, for every route.  A route is a choice of three things (CloudCall): tracked or not,
 // objects or not (objects need tracked), and where the points come from.
 //   plain   : count per cell -> ordered compaction of the occupied cells -> the robot self-filter as ONE fp32 pass-1 launch over one
@@ -12,6 +12,8 @@
 //   depth   : any of the three with the images of up to eight cameras as the point source: no point is ever written
 //   memory  : the plain depth route with one word per cell kept between calls (scene_from_depth_memory, a stage sequence of its own
 //             over the same stages): occluded cells stay, cells a camera looked through leave
+//   filter  : while the context has a depth filter, the counting pass of every depth call above is the filtered one
+//             (depth_filter_def.h): another kernel in the same place, and two counters fetched behind it
 #include "capi_internal.h"
 #include "cloud_kernels.h"
 
@@ -23,6 +25,7 @@ struct DepthSource {
     const void* const* images;
     int n_cams;
     int on_device;
+    const DepthFilter* filt;                // the context's depth filter while it is on, else nullptr
 };
 struct PointSource {
     const float* xyz;
@@ -59,6 +62,7 @@ struct CloudWork {
     int n_list = 0, n_final = 0;    // spheres of d_list; of the installed scene (filled up to n_closest)
     bool have_prev = false, have_table = false;   // there is a stored frame on this grid; and a stored table under this object spec
     int n_comp = 0, matched = 0;
+    unsigned filt_counts[2] = {0u, 0u};           // pixels the depth filter kept and rejected, fetched behind the counting pass
     std::vector<float> vel4, obj_vel;             // [n_list][4] of cloud.vel, [n_comp][4] of cloud.objVel
     std::vector<int32_t> label, object;           // [n_final]
 };
@@ -87,6 +91,7 @@ int reserve_base(omds_ctx* ctx, const CloudCall& c) {
     CK(s.sums.reserve((size_t)CLOUD_MAX_BLOCKS + 1));
     CK(s.cand.reserve(m));
     CK(s.kept.reserve(m));
+    if (c.src.depth && c.src.depth->filt) CK(s.filtCounts.reserve(2));
     return OMDS_OK;
 }
 int reserve_tracked(omds_ctx* ctx, const CloudCall& c) {
@@ -171,12 +176,32 @@ int compaction_total(omds_ctx* ctx, int n, int* total_out) {
 // ---- count and compact the cells: the candidates in cell order, their cell indices when tracked, and w.occupied
 template <class T>   // unsigned: counts, uint4: records
 void enqueue_count(omds_ctx* ctx, const CloudCall& c, const CloudWork& w, T* into) {
-    if (c.src.depth) omds_launch_cloud_count(ctx->stream, w.depth, c.src.depth->n_cams, c.g, into);
-    else omds_launch_cloud_count(ctx->stream, w.d_xyz, (long long)c.src.n_points, c.g, into);
+    if (!c.src.depth) omds_launch_cloud_count(ctx->stream, w.d_xyz, (long long)c.src.n_points, c.g, into);
+    else if (!c.src.depth->filt) omds_launch_cloud_count(ctx->stream, w.depth, c.src.depth->n_cams, c.g, into);
+    else omds_launch_cloud_count_filtered(ctx->stream, w.depth, c.src.depth->n_cams, c.g, *c.src.depth->filt, into, ctx->cloud.filtCounts);
+}
+// The depth filter's counters around the counting pass of a depth call: cleared in front of it; fetched behind it into w, to be read
+// after the next synchronisation by filter_stats_done.  Without a filter the call leaves the stats at 0, 0
+int filter_stats_begin(omds_ctx* ctx, const CloudCall& c) {
+    CloudState& s = ctx->cloud;
+    if (!c.src.depth) return OMDS_OK;
+    s.filter_stats[0] = s.filter_stats[1] = 0;
+    if (c.src.depth->filt) CK(hipMemsetAsync(s.filtCounts, 0, 2 * 4, ctx->stream));
+    return OMDS_OK;
+}
+int filter_stats_fetch(omds_ctx* ctx, const CloudCall& c, CloudWork& w) {
+    if (c.src.depth && c.src.depth->filt) CK(hipMemcpyAsync(w.filt_counts, ctx->cloud.filtCounts, 2 * 4, hipMemcpyDeviceToHost, ctx->stream));
+    return OMDS_OK;
+}
+void filter_stats_done(omds_ctx* ctx, const CloudCall& c, const CloudWork& w) {
+    if (!c.src.depth || !c.src.depth->filt) return;
+    ctx->cloud.filter_stats[0] = (int64_t)w.filt_counts[0];
+    ctx->cloud.filter_stats[1] = (int64_t)w.filt_counts[1];
 }
 int count_cells(omds_ctx* ctx, const CloudCall& c, CloudWork& w) {
     CloudState& s = ctx->cloud;
     const size_t cells = cloud_padded_cells(c.g);
+    if (int rc = filter_stats_begin(ctx, c)) return rc;
     if (c.tracked) {
         uint4* rec = s.rec.next();
         CK(hipMemsetAsync(rec, 0, cells * 16, ctx->stream));
@@ -189,7 +214,10 @@ int count_cells(omds_ctx* ctx, const CloudCall& c, CloudWork& w) {
         omds_launch_cloud_compact_cells(ctx->stream, s.count, c.g, s.cand, s.sums);
     }
     w.d_list = s.cand;
-    return compaction_total(ctx, c.g.n_cells, &w.occupied);
+    if (int rc = filter_stats_fetch(ctx, c, w)) return rc;
+    if (int rc = compaction_total(ctx, c.g.n_cells, &w.occupied)) return rc;
+    filter_stats_done(ctx, c, w);
+    return OMDS_OK;
 }
 
 // ---- self-filter: the candidates become the obstacle rows of one state.  From here on the tables of the old scene are overwritten:
@@ -383,7 +411,9 @@ int scene_from_depth_memory(omds_ctx* ctx, const CloudCall& c, const SceneMem& s
     unsigned* next = s.mem.next();
     CK(hipMemsetAsync(s.count, 0, cloud_padded_cells(c.g) * 4, ctx->stream));
     CK(hipMemsetAsync(s.memCounts, 0, SCENE_MEM_COUNTS * 4, ctx->stream));
+    if ((rc = filter_stats_begin(ctx, c))) return rc;
     enqueue_count(ctx, c, w, s.count.get());
+    if ((rc = filter_stats_fetch(ctx, c, w))) return rc;
     if ((rc = prof_begin(ctx))) return rc;   // omds_prof_enable: this route's dominant kernel is k_scene_memory
     omds_launch_scene_memory(ctx->stream, w.depth, ks, c.src.depth->n_cams, c.g, sm, s.count, have ? s.mem.kept().get() : nullptr, next, s.memCounts);
     if ((rc = prof_end(ctx, c.g.n_cells, 0.0, "k_scene_memory"))) return rc;
@@ -393,6 +423,7 @@ int scene_from_depth_memory(omds_ctx* ctx, const CloudCall& c, const SceneMem& s
     w.d_list = s.cand;
     w.d_cell = s.candCell;
     if ((rc = compaction_total(ctx, c.g.n_cells, &w.occupied))) return rc;   // = seen + remembered
+    filter_stats_done(ctx, c, w);
     if (counts_out)
         for (int k = 0; k < SCENE_MEM_COUNTS; ++k) counts_out[k] = (int32_t)counts[k];
     REQUIRE(w.occupied <= c.g.max_spheres, OMDS_ERR_INVALID_ARG,
@@ -446,6 +477,33 @@ int omds_depth_points(const omds_depth_camera* cam, const void* image, float* xy
     return depth_points_host(cam, image, xyz_out, cap_points, n_valid_out, &g_create_err);
 }
 
+int omds_depth_points_filtered(const omds_depth_camera* cam, const omds_depth_filter_spec* filt, const void* image, float* xyz_out,
+                               int64_t cap_points, int64_t* n_valid_out, int64_t* n_rejected_out) {
+    return depth_points_filtered_host(cam, filt, image, xyz_out, cap_points, n_valid_out, n_rejected_out, &g_create_err);
+}
+
+int omds_set_depth_filter(omds_ctx* ctx, const omds_depth_filter_spec* spec) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    CloudState& s = ctx->cloud;
+    if (!spec) {
+        s.filter_on = false;
+        return OMDS_OK;
+    }
+    DepthFilter f;
+    if (int rc = depth_filter_resolve(spec, &f, &ctx->err)) return rc;   // the stored filter stays as it was
+    s.filter = f;
+    s.filter_on = true;
+    return OMDS_OK;
+}
+
+int omds_get_depth_filter_stats(omds_ctx* ctx, int64_t out[2]) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    REQUIRE(out, OMDS_ERR_INVALID_ARG, "omds_get_depth_filter_stats: null out");
+    out[0] = ctx->cloud.filter_stats[0];
+    out[1] = ctx->cloud.filter_stats[1];
+    return OMDS_OK;
+}
+
 int omds_set_obstacles_from_cloud(omds_ctx* ctx, const omds_cloud_spec* spec, const float* xyz, int64_t n_points, int xyz_on_device,
                                   const float* q_now, int32_t* n_spheres_out, int32_t* n_occupied_out) {
     if (!ctx) return OMDS_ERR_INVALID_ARG;
@@ -486,6 +544,7 @@ int omds_set_obstacles_from_depth(omds_ctx* ctx, const omds_cloud_spec* spec, co
     depth.images = images;
     depth.n_cams = n_cams;
     depth.on_device = images_on_device;
+    depth.filt = ctx->cloud.filter_on ? &ctx->cloud.filter : nullptr;
     if (int rc = resolve_depth_source(ctx, me, cams, depth)) return rc;
     c.src = PointSource{nullptr, 0, 0, &depth};
     c.q_now = q_now;
@@ -496,6 +555,12 @@ int omds_set_obstacles_from_depth(omds_ctx* ctx, const omds_cloud_spec* spec, co
 int omds_depth_scene_memory(const omds_cloud_spec* spec, const omds_scene_memory_spec* mem_spec, const omds_depth_camera* cams,
                             const void* const* images, int32_t n_cams, const uint32_t* mem_in, uint32_t* mem_out, int32_t counts_out[4]) {
     return scene_memory_host(spec, mem_spec, cams, images, n_cams, mem_in, mem_out, counts_out, &g_create_err);
+}
+
+int omds_depth_scene_memory_filtered(const omds_cloud_spec* spec, const omds_scene_memory_spec* mem_spec, const omds_depth_filter_spec* filt,
+                                     const omds_depth_camera* cams, const void* const* images, int32_t n_cams, const uint32_t* mem_in,
+                                     uint32_t* mem_out, int32_t counts_out[4]) {
+    return scene_memory_host(spec, mem_spec, filt, cams, images, n_cams, mem_in, mem_out, counts_out, &g_create_err);
 }
 
 int omds_set_obstacles_from_depth_memory(omds_ctx* ctx, const omds_cloud_spec* spec, const omds_scene_memory_spec* mem_spec,
@@ -511,6 +576,7 @@ int omds_set_obstacles_from_depth_memory(omds_ctx* ctx, const omds_cloud_spec* s
     depth.images = images;
     depth.n_cams = n_cams;
     depth.on_device = images_on_device;
+    depth.filt = ctx->cloud.filter_on ? &ctx->cloud.filter : nullptr;
     if (int rc = resolve_depth_source(ctx, me, cams, depth)) return rc;
     SceneMemCams ks;
     std::memset(static_cast<void*>(&ks), 0, sizeof(ks));

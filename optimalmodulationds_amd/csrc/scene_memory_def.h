@@ -5,7 +5,7 @@
 // 1.0f / zc is the IEEE-rounded one on both sides: no fast division, no reciprocal intrinsic.
 //   m[c] == 0: cell c is empty;  m[c] == k >= 1: occupied, last counted k - 1 calls ago.
 #pragma once
-#include "depth_def.h"
+#include "depth_filter_def.h"
 
 // an omds_scene_memory_spec behind its checks: what the kernels take by value
 struct SceneMem {
@@ -113,16 +113,20 @@ OMDS_CLOUD_FN unsigned scene_memory_cell(const CloudGrid& g, const SceneMem& sm,
     return next;
 }
 
-// omds_depth_scene_memory without its argument messages: the counting pass of the depth route (omds_depth_points + cloud_cell), then
-// steps 1 - 5 per cell.  No self-filter
-inline int scene_memory_host(const omds_cloud_spec* spec, const omds_scene_memory_spec* mem_spec, const omds_depth_camera* cams,
-                             const void* const* images, int32_t n_cams, const uint32_t* mem_in, uint32_t* mem_out, int32_t* counts_out,
-                             std::string* err) {
+// omds_depth_scene_memory[_filtered] without its argument messages, the one body of both: the counting pass of the depth route
+// (omds_depth_points[_filtered] + cloud_cell), then steps 1 - 5 per cell.  filt == nullptr: no depth filter.  The filter changes the
+// counts alone: the verdicts of step 3 read the raw images (a flying pixel is still a return).  No self-filter
+inline int scene_memory_host(const omds_cloud_spec* spec, const omds_scene_memory_spec* mem_spec, const omds_depth_filter_spec* filt,
+                             const omds_depth_camera* cams, const void* const* images, int32_t n_cams, const uint32_t* mem_in,
+                             uint32_t* mem_out, int32_t* counts_out, std::string* err) {
     auto fail = [&](const char* m) { if (err) *err = m; return (int)OMDS_ERR_INVALID_ARG; };
     CloudGrid g;
     SceneMem sm;
+    DepthFilter f;
     if (int rc = cloud_resolve_spec(spec, &g, err)) return rc;
     if (int rc = scene_memory_resolve(mem_spec, g, &sm, err)) return rc;
+    if (filt)
+        if (int rc = depth_filter_resolve(filt, &f, err)) return rc;
     if (n_cams < 1 || n_cams > OMDS_DEPTH_MAX_CAMERAS || !cams || !images) return fail("omds_depth_scene_memory: need 1 <= n_cams <= 8 and non-null cams, images [n_cams]");
     if (!mem_out) return fail("omds_depth_scene_memory: null mem_out");
     DepthCam cam[OMDS_DEPTH_MAX_CAMERAS];
@@ -138,19 +142,13 @@ inline int scene_memory_host(const omds_cloud_spec* spec, const omds_scene_memor
     std::vector<uint32_t> count((size_t)g.n_cells, 0u);
     for (int i = 0; i < n_cams; ++i) {
         const DepthCam& c = cam[i];
-        for (int iv = 0; iv < c.nv; ++iv) {
-            const int v = iv * c.step;
-            const int64_t row = (int64_t)v * c.pitch;
+        for (int iv = 0; iv < c.nv; ++iv)
             for (int iu = 0; iu < c.nu; ++iu) {
-                const int u = iu * c.step;
                 float w[3];
-                const bool kept = c.format == OMDS_DEPTH_U16 ? depth_pixel_u16(c, u, v, static_cast<const uint16_t*>(images[i])[row + u], w)
-                                                             : depth_pixel_f32(c, u, v, static_cast<const float*>(images[i])[row + u], w);
-                if (!kept) continue;
+                if (depth_filtered_pixel(c, filt ? &f : nullptr, images[i], iu, iv, w) != 1) continue;
                 const int cell = cloud_cell(g, w[0], w[1], w[2]);
                 if (cell >= 0) count[(size_t)cell]++;
             }
-        }
     }
     struct HostCams {
         const DepthCam* c;
@@ -167,4 +165,9 @@ inline int scene_memory_host(const omds_cloud_spec* spec, const omds_scene_memor
     if (counts_out)
         for (int k = 0; k < 4; ++k) counts_out[k] = counts[k];
     return OMDS_OK;
+}
+inline int scene_memory_host(const omds_cloud_spec* spec, const omds_scene_memory_spec* mem_spec, const omds_depth_camera* cams,
+                             const void* const* images, int32_t n_cams, const uint32_t* mem_in, uint32_t* mem_out, int32_t* counts_out,
+                             std::string* err) {
+    return scene_memory_host(spec, mem_spec, nullptr, cams, images, n_cams, mem_in, mem_out, counts_out, err);
 }

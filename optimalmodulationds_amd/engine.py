@@ -24,6 +24,7 @@ class Engine:
         self.params = L.default_params()
         self.K = 0
         self.n_obs = 0
+        self.depth_filter = None      # the depth filter in force (set_depth_filter), None: off
         self.C = 0
         self.config_version = 0      # bumped by every call that changes params / nominal DS / cost on the context (MPPI._push re-syncs on it)
 
@@ -194,6 +195,24 @@ class Engine:
             e.n_occupied = int(counts[0] + counts[1])
             raise
         return int(n_sph[0]), tuple(int(v) for v in counts)
+
+    # ---- the depth filter (omds.h: THE DEPTH FILTER) --------------------------------------------------------------------------------
+    def set_depth_filter(self, spec):
+        """The context's depth filter: an ``OmdsDepthFilterSpec`` (``depth_filter_spec`` builds one; a dict of its arguments is taken
+        too), or None to turn it off; ``self.depth_filter`` holds the spec in force (None: off).  While set,
+        ``set_obstacles_from_depth`` (every route) and ``set_obstacles_from_depth_memory`` drop flying pixels and speckle inside their
+        counting pass: every effect is that of the cloud call on ``depth_points(image, cam, filter=spec)``.  A refused spec raises and
+        leaves the stored filter as it was."""
+        spec = _filter_of(spec)
+        self._ck(self.lib.omds_set_depth_filter(self.h, None if spec is None else C.byref(spec)))
+        self.depth_filter = spec      # behind the check: a refused spec leaves the stored one, here as in the library
+
+    def depth_filter_stats(self):
+        """(kept, rejected): the pixels the depth filter kept and rejected in the last depth call, summed over cameras; (0, 0) when
+        no filter ran."""
+        out = (C.c_int64 * 2)()
+        self._ck(self.lib.omds_get_depth_filter_stats(self.h, out))
+        return int(out[0]), int(out[1])
 
     def scene_memory_reset(self):
         """Forget the stored scene memory: the next ``set_obstacles_from_depth_memory`` starts from an empty one."""
@@ -873,9 +892,24 @@ def scene_memory_spec(max_age, clear_margin=0.0, footprint=0):
     return m
 
 
-def depth_scene_memory(images, cams, spec, mem, mem_in=None):
-    """The definition of the scene memory on the host (omds_depth_scene_memory, no GPU, no self-filter): the depth images of one call
-    and the stored words ``mem_in`` [cells] (uint32; None: all empty) -> (words [cells] uint32, (seen, remembered, cleared, expired))."""
+def depth_filter_spec(radius=1, min_support=4, edge_abs=0.01, edge_rel=0.01):
+    """An ``OmdsDepthFilterSpec``: a depth pixel at depth z stays when at least ``min_support`` of the other pixels of its window of
+    (2 ``radius`` + 1)^2 visited pixels (``radius`` 1 .. 3) return a depth within ``edge_abs`` + ``edge_rel`` z metres of z."""
+    f = L.OmdsDepthFilterSpec()
+    f.radius, f.min_support, f.edge_abs, f.edge_rel = int(radius), int(min_support), float(edge_abs), float(edge_rel)
+    return f
+
+
+def _filter_of(filter):
+    """None, an ``OmdsDepthFilterSpec`` or a dict of ``depth_filter_spec``'s arguments -> None or the spec"""
+    return depth_filter_spec(**filter) if isinstance(filter, dict) else filter
+
+
+def depth_scene_memory(images, cams, spec, mem, mem_in=None, filter=None):
+    """The definition of the scene memory on the host (omds_depth_scene_memory[_filtered], no GPU, no self-filter): the depth images of
+    one call and the stored words ``mem_in`` [cells] (uint32; None: all empty) -> (words [cells] uint32, (seen, remembered, cleared,
+    expired)).  ``filter`` (an ``OmdsDepthFilterSpec`` or a dict of ``depth_filter_spec``'s arguments): the counts are those of the
+    filtered points."""
     lib = L.load()
     table, addrs, n, _, keep = _depth_table("depth_scene_memory", images, cams)
     cells = max(int(spec.dims[0]), 0) * max(int(spec.dims[1]), 0) * max(int(spec.dims[2]), 0)
@@ -887,17 +921,23 @@ def depth_scene_memory(images, cams, spec, mem, mem_in=None):
         if src.size != cells:
             raise ValueError(f"depth_scene_memory: mem_in must hold {cells} words, got {src.size}")
     out, counts = np.zeros(max(cells, 1), np.uint32), np.zeros(4, np.int32)
-    rc = lib.omds_depth_scene_memory(C.byref(spec), C.byref(mem), table, addrs, n, None if src is None else src.ctypes.data, out.ctypes.data,
-                                     L.iptr(counts))
+    filt = _filter_of(filter)
+    if filt is None:
+        rc = lib.omds_depth_scene_memory(C.byref(spec), C.byref(mem), table, addrs, n, None if src is None else src.ctypes.data, out.ctypes.data,
+                                         L.iptr(counts))
+    else:
+        rc = lib.omds_depth_scene_memory_filtered(C.byref(spec), C.byref(mem), C.byref(filt), table, addrs, n,
+                                                  None if src is None else src.ctypes.data, out.ctypes.data, L.iptr(counts))
     if rc != 0:
         raise L.OmdsError(f"omds_depth_scene_memory failed ({rc}): {lib.omds_last_error(None).decode()}")
     return out[:cells], tuple(int(v) for v in counts)
 
 
-def depth_points(image, cam):
+def depth_points(image, cam, filter=None):
     """The definition on the host (omds_depth_points, no GPU): one depth image (numpy ``uint16`` / ``float32``) -> (xyz [visited, 3],
     n_valid): the visited pixels in row-major order as points in the frame of the voxel grid, a dropped pixel as three NaNs (which
-    the cloud calls drop), and how many were kept."""
+    the cloud calls drop), and how many were kept.  ``filter`` (an ``OmdsDepthFilterSpec`` or a dict of ``depth_filter_spec``'s
+    arguments; omds_depth_points_filtered): a pixel the depth filter rejects is three NaNs too -> (xyz, n_valid, n_rejected)."""
     lib = L.load()
     c = L.OmdsDepthCamera()
     C.memmove(C.byref(c), C.byref(cam), C.sizeof(L.OmdsDepthCamera))
@@ -907,6 +947,13 @@ def depth_points(image, cam):
     step = max(int(c.step), 1)
     visited = max(-(-int(c.height) // step), 0) * max(-(-int(c.width) // step), 0)
     out, n_valid = np.zeros((max(visited, 1), 3), np.float32), C.c_int64(0)
+    filt = _filter_of(filter)
+    if filt is not None:
+        n_rejected = C.c_int64(0)
+        rc = lib.omds_depth_points_filtered(C.byref(c), C.byref(filt), addr, L.fptr(out), visited, C.byref(n_valid), C.byref(n_rejected))
+        if rc != 0:
+            raise L.OmdsError(f"omds_depth_points_filtered failed ({rc}): {lib.omds_last_error(None).decode()}")
+        return out[:visited], int(n_valid.value), int(n_rejected.value)
     rc = lib.omds_depth_points(C.byref(c), addr, L.fptr(out), visited, C.byref(n_valid))
     if rc != 0:
         raise L.OmdsError(f"omds_depth_points failed ({rc}): {lib.omds_last_error(None).decode()}")

@@ -96,6 +96,7 @@ class MPPI:
         self.Cost = Cost(self.qf, self.dh_params, owner=self)
         self.obs_focus = None         # focus_obstacles: the master index of every sphere of self.obs, else None
         self.obs_age = None           # update_obstacles_from_depth(memory=): calls since every sphere's cell was last counted, else None
+        self.depth_filter_stats = None   # update_obstacles_from_depth(filter=): (pixels kept, pixels rejected) of the last such call
         self.cur_cost = None
         self._cache = {}
         self._generation = 0          # propagate() calls so far (LazyRollout tensors belong to one of them)
@@ -180,11 +181,32 @@ class MPPI:
         looked through it, it is older than ``max_age`` calls or the self-filter drops it.  Returns (spheres before padding, (seen,
         remembered, cleared, expired, self-forgotten)); ``self.obs_age`` then holds, per sphere, the calls since its cell was last
         counted (-1: padding), and is None after every other call.  A static scene: not together with ``dt_frame`` or ``objects``.
-        (``memory`` is the one keyword ``**route`` takes, default None: the named keywords stay those of
+        ``filter`` (an ``OmdsDepthFilterSpec``, or a dict of ``engine.depth_filter_spec``'s arguments): sets the engine's depth filter
+        for this call (Engine.set_depth_filter) -- flying pixels at depth edges and isolated speckle leave inside the counting pass, and
+        everything is the cloud call on ``engine.depth_points(image, camera, filter=...)``; ``self.depth_filter_stats`` then holds
+        (pixels kept, pixels rejected), and the engine's filter is what it was before the call (off, or what
+        ``Engine.set_depth_filter`` had installed).  None (the default) leaves the call, and whatever filter the engine has, as it is.  Works
+        together with ``dt_frame``, ``objects`` and ``memory``.
+        (``memory`` and ``filter`` are the keywords ``**route`` takes, default None: the named keywords stay those of
         ``update_obstacles_from_cloud``, which has no cameras to ask.)"""
-        memory = route.pop("memory", None)
+        memory, filt = route.pop("memory", None), route.pop("filter", None)
         if route:
             raise TypeError(f"update_obstacles_from_depth: unexpected keyword arguments {sorted(route)}")
+        if filt is None:
+            return self._update_obstacles_from_depth(images, cameras, voxel, lo, hi, radius, self_margin, min_points, max_spheres, dt_frame, reach,
+                                                     still, moving_frame, objects, link, min_cells, memory)
+        before = self._engine.depth_filter
+        self._engine.set_depth_filter(filt)
+        try:
+            return self._update_obstacles_from_depth(images, cameras, voxel, lo, hi, radius, self_margin, min_points, max_spheres, dt_frame, reach,
+                                                     still, moving_frame, objects, link, min_cells, memory)
+        finally:
+            self.depth_filter_stats = self._engine.depth_filter_stats()
+            self._engine.set_depth_filter(before)
+
+    def _update_obstacles_from_depth(self, images, cameras, voxel, lo, hi, radius, self_margin, min_points, max_spheres, dt_frame, reach, still,
+                                     moving_frame, objects, link, min_cells, memory):
+        """``update_obstacles_from_depth`` behind its route keywords"""
         if memory is None:
             return self._update_obstacles_sensed("update_obstacles_from_depth", lambda e, spec, q, track, obj: (
                 e.set_obstacles_from_depth(images, cameras, spec, q, track, obj)),
