@@ -564,6 +564,26 @@ OMDS_API int omds_get_depth_filter_stats(omds_ctx* ctx, int64_t out[2] /* kept, 
  *       exactly as they were; a HIP failure later in the call leaves the context without a scene.
  *       SCREENING: a focus that changes the sphere count discards a measured calibration, as any setter does (a calibration every
  *       planner iteration costs more than the focus saves): a caller who screens sets a fixed eps > 0 (omds_set_screening).
+ *   A FOCUS ALONG A PATH.  One state makes margin cover everything a rollout travels in (H - 1) dt; the planner knows where its
+ *   rollouts went last iteration.  A focus over B states keeps what EACH state needs, and margin covers only the deviation from them.
+ *   omds_obstacle_focus_select_path : host only, the DEFINITION over d [n_states][n_obs] (state-major), ahead [n_states] seconds or
+ *       NULL, vel [n_obs][3] or NULL.  All fp32, every operation named one rounding.  SPEED: s_o = sqrtf(s2) as above.  TIME:
+ *       L_b = lookahead + ahead_b (NULL: lookahead).  REACH: r_bo = d_bo without vel, else fmaf(-s_o, L_b, d_bo): a lower bound on the
+ *       distance the sphere can have when state b is reached; NaN as -inf, -0 as +0.  THRESHOLD per state: t_b = the reach of the
+ *       n_closest-th sphere of row b ordered by (r_bo, o); bar_b = t_b + margin.  PASSING: sphere o passes when r_bo <= bar_b for SOME
+ *       b; margin == +inf: every sphere; P of them (>= n_closest).  NEAREST: m_o = min_b r_bo.  KEPT: M = min(P, max_keep), or P; the
+ *       first M PASSING spheres of the order (m_o, o), listed in ascending index.  Minimum and OR over the states: their order does not
+ *       matter, nor does a state given twice; n_states == 1 with ahead NULL or {0} is omds_obstacle_focus_select.  Refusals as there,
+ *       and: n_states < 1, an ahead_b that is negative, NaN or infinite (checked without vel too).
+ *   omds_focus_obstacles_path : omds_focus_obstacles over q_path [n_states][n_dof] (host), 1 <= n_states <= 65536, ahead as above:
+ *       the same master, refusals, install, static rule, label gather, screening note, state rules and CONTRACT; omds_get_obstacle_focus
+ *       and omds_clear_obstacle_focus serve both.  d_bo is pass 1's value at (q_b, master sphere o), bit for bit row b of the mindist
+ *       matrix of omds_dist_grad(q_path, n_states) on the master.  The states go through the fp32 pass 1 in chunks of at most
+ *       min(n_traj, 4096) states (what the context's buffers hold; every size class of pass 1 computes the same bits): per chunk the
+ *       keys in place over pass 1's rows, one workgroup per row for its bar (the same k-th-smallest), and a merge of "passes in some
+ *       row" and "nearest key" into two words per sphere by integer atomic OR and minimum, which nothing reads back; after the last
+ *       chunk the selection above on (passing ? nearest key : 0xffffffff, above every key) and the same compaction.  The result
+ *       depends neither on the chunk size nor on scheduling.  omds_focus_obstacles itself keeps its launches and its bits.
  *   omds_get_obstacle_focus : the master index of every sphere in force into idx [n_obs] (NULL: no copy; untouched without a focus);
  *       *n_master_out = the master's size, 0 when no focus is in force; *n_kept_out = n_obs.  Host state, no GPU work.
  *   omds_clear_obstacle_focus : puts the master and its motion (and labels) back; a no-op without a focus.                            */
@@ -577,6 +597,13 @@ OMDS_API int omds_obstacle_focus_select(const omds_obstacle_focus_spec* spec, co
                                         int32_t* passed_out);
 OMDS_API int omds_focus_obstacles(omds_ctx* ctx, const omds_obstacle_focus_spec* spec, const float* q /* [n_dof] */, int32_t* kept_out,
                                   int32_t* passed_out);
+OMDS_API int omds_obstacle_focus_select_path(const omds_obstacle_focus_spec* spec, const float* d /* [n_states][O] */,
+                                             const float* ahead /* [n_states] or NULL */, const float* vel /* [O,3] or NULL */,
+                                             int n_states, int n_obs, int n_closest, int32_t* idx_out /* [cap] */, int32_t cap,
+                                             int32_t* kept_out, int32_t* passed_out);
+OMDS_API int omds_focus_obstacles_path(omds_ctx* ctx, const omds_obstacle_focus_spec* spec, const float* q_path /* [n_states][n_dof] */,
+                                       const float* ahead /* [n_states] or NULL */, int n_states, int32_t* kept_out,
+                                       int32_t* passed_out);
 OMDS_API int omds_get_obstacle_focus(omds_ctx* ctx, int32_t* idx /* [n_obs] or NULL */, int32_t* n_master_out, int32_t* n_kept_out);
 OMDS_API int omds_clear_obstacle_focus(omds_ctx* ctx);
 /* LinDS(q_goal) / MPPI.reset_DS / switch_DS_idx (LinDS.py:7-10, MPPI.py:76-84). */

@@ -165,6 +165,9 @@ SIGNATURES = {
     "omds_get_depth_filter_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "omds_obstacle_focus_select": (C.c_int, [C.POINTER(OmdsObstacleFocusSpec), F32P, F32P, C.c_int, C.c_int, I32P, C.c_int32, I32P, I32P]),
     "omds_focus_obstacles": (C.c_int, [C.c_void_p, C.POINTER(OmdsObstacleFocusSpec), F32P, I32P, I32P]),
+    "omds_obstacle_focus_select_path": (C.c_int, [C.POINTER(OmdsObstacleFocusSpec), F32P, F32P, F32P, C.c_int, C.c_int, C.c_int, I32P, C.c_int32, I32P,
+                                                  I32P]),
+    "omds_focus_obstacles_path": (C.c_int, [C.c_void_p, C.POINTER(OmdsObstacleFocusSpec), F32P, F32P, C.c_int, I32P, I32P]),
     "omds_get_obstacle_focus": (C.c_int, [C.c_void_p, I32P, I32P, I32P]),
     "omds_clear_obstacle_focus": (C.c_int, [C.c_void_p]),
     "omds_set_ds": (C.c_int, [C.c_void_p, F32P]),
@@ -266,7 +269,7 @@ HORIZON_HOOK_SIGNATURES = {
 }
 TEST_LIB_PATH = os.path.join(_HERE, "csrc", "libomds_hip_test.so")
 
-ABI_VERSION = 511     # omds_version() of the library this binding was written against
+ABI_VERSION = 512     # omds_version() of the library this binding was written against
 _libs = {}             # path -> bound CDLL
 
 

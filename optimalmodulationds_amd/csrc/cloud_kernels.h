@@ -65,6 +65,15 @@ void omds_launch_focus_compact(hipStream_t s, const unsigned* keys, const unsign
 void omds_launch_focus_keys(hipStream_t s, const float* d, const float* vel, int dims, float lookahead, int n, unsigned* keys);
 // res [4]: kept, passing, the key of the last kept sphere of the order, the index up to which a sphere with that key is kept.  One workgroup
 void omds_launch_focus_select(hipStream_t s, const unsigned* keys, int n, int n_closest, float margin, bool all_pass, int max_keep, unsigned* res);
+// ... along a path, one chunk of C states: rows [C][n], pass 1's distances, become the keys of their reaches in place (time [C]:
+// lookahead + ahead per state, read with vel); bars [C] is scratch; best [n] and pass [n], set to ~0 and 0 before the first chunk,
+// take the nearest key of every sphere and whether it passed in some row
+void omds_launch_focus_path_chunk(hipStream_t s, float* rows, const float* vel, int dims, const float* time, int C, int n, int n_closest, float margin,
+                                  bool all_pass, unsigned* bars, unsigned* best, unsigned* pass);
+// ... after the last chunk: sel [n] = the nearest key of a passing sphere, ~0 for the others, and res [4] as omds_launch_focus_select
+// leaves it, for omds_launch_focus_compact on sel
+void omds_launch_focus_path_select(hipStream_t s, const unsigned* best, const unsigned* pass, int n, int n_closest, int max_keep, unsigned* sel,
+                                   unsigned* res);
 
 // The scene memory (scene_memory_def.h).  mem_out [cloud_padded_cells]: the words of this call from the counts count and the stored
 // words mem_in (both padded with zeros; mem_in == nullptr: all empty); counters [SCENE_MEM_COUNTS], cleared by the caller, takes the

@@ -79,6 +79,9 @@ struct FocusState {
     DevBuf<float4> kept;                         // [n_master] the emission: spheres,
     DevBuf<int> keptIdx;                         // ... their master indices
     DevBuf<float> keptVel;                       // ... and [n_master][3] their velocities
+    // ... a focus along a path (omds_focus_obstacles_path), allocated at the first such call
+    DevBuf<unsigned> best, pass, bars;           // [n_master] nearest key, [n_master] passed in some state, [chunk] the bar of every row
+    DevBuf<float> time;                          // [n_states] lookahead + ahead of every state
 };
 
 struct CloudState {

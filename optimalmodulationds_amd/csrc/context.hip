@@ -8,7 +8,7 @@ thread_local std::string g_create_err;
 
 extern "C" {
 
-int omds_version(void) { return 511; }
+int omds_version(void) { return 512; }
 
 int omds_device_count(int32_t* count) {
     if (!count) return OMDS_ERR_INVALID_ARG;

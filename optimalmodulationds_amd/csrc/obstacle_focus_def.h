@@ -52,9 +52,12 @@ OMDS_FOCUS_FN float focus_float(uint32_t b) {
 }
 
 // the reach of a sphere at distance d that moves at (vx, vy, vz): the distance it can have after lookahead seconds of approaching
-OMDS_FOCUS_FN float focus_reach(float d, float vx, float vy, float vz, float lookahead) {
+OMDS_FOCUS_FN float focus_speed(float vx, float vy, float vz) {
     const float s2 = fmaf(vz, vz, fmaf(vy, vy, vx * vx));
-    const float speed = sqrtf(s2);
+    return sqrtf(s2);
+}
+OMDS_FOCUS_FN float focus_reach(float d, float vx, float vy, float vz, float lookahead) {
+    const float speed = focus_speed(vx, vy, vz);
     return fmaf(-speed, lookahead, d);
 }
 
@@ -96,6 +99,63 @@ inline int focus_select_host(const omds_obstacle_focus_spec* spec, const float* 
     *kept_out = (int32_t)kept;
     *passed_out = (int32_t)passed;
     if (cap < kept) return fail("omds_obstacle_focus_select: cap is smaller than the kept set (kept_out holds its size); idx_out is untouched");
+    for (int64_t i = 0; i < kept; ++i) idx_out[i] = order[(size_t)i].second;
+    std::sort(idx_out, idx_out + kept);
+    return OMDS_OK;
+}
+
+// The time a sphere has to approach until state b of a path is reached: lookahead + ahead_b, one rounding
+OMDS_FOCUS_FN float focus_path_time(float lookahead, float ahead) { return lookahead + ahead; }
+inline bool focus_ahead_ok(float a) { return a >= 0.f && std::isfinite(a); }
+// the word the final selection of a path orders by: the nearest key of a passing sphere, and for the others a word above every key
+// (no key exceeds 0xff800000, that of +inf)
+constexpr uint32_t FOCUS_NOT_PASSING = 0xffffffffu;
+
+// omds_obstacle_focus_select_path without its argument messages: d [n_states][n_obs], ahead [n_states] or null.  Per state the keys
+// of its row, the bar of its own n_closest-th key, and into per-sphere words an OR of "passes here" and a minimum of the keys: integer
+// work whose result no order of the states changes
+inline int focus_select_path_host(const omds_obstacle_focus_spec* spec, const float* d, const float* ahead, const float* vel, int n_states, int n_obs,
+                                  int n_closest, int32_t* idx_out, int32_t cap, int32_t* kept_out, int32_t* passed_out, std::string* err) {
+    auto fail = [&](const char* m) { if (err) *err = m; return (int)OMDS_ERR_INVALID_ARG; };
+    FocusRule r;
+    if (n_closest < 1) return fail("omds_obstacle_focus_select_path: need n_closest >= 1");
+    if (int rc = focus_resolve_spec(spec, n_closest, &r, err)) return rc;
+    if (n_obs < n_closest) return fail("omds_obstacle_focus_select_path: fewer spheres than n_closest");
+    if (n_states < 1) return fail("omds_obstacle_focus_select_path: need n_states >= 1");
+    if (!d || !idx_out || !kept_out || !passed_out || cap < 0)
+        return fail("omds_obstacle_focus_select_path: need non-null d [n_states][O], idx_out [cap], kept_out, passed_out and cap >= 0");
+    if (ahead)
+        for (int b = 0; b < n_states; ++b)
+            if (!focus_ahead_ok(ahead[b])) return fail("omds_obstacle_focus_select_path: every ahead must be finite and >= 0");
+    const size_t O = (size_t)n_obs;
+    std::vector<float> speed(vel ? O : 0);
+    for (size_t o = 0; o < speed.size(); ++o) speed[o] = focus_speed(vel[3 * o], vel[3 * o + 1], vel[3 * o + 2]);
+    std::vector<uint32_t> best(O, FOCUS_NOT_PASSING), row(O), sorted(O);
+    std::vector<unsigned char> pass(O, r.all_pass ? 1 : 0);
+    for (int b = 0; b < n_states; ++b) {
+        const float* db = d + (size_t)b * O;
+        const float time = ahead ? focus_path_time(r.lookahead, ahead[b]) : r.lookahead;
+        for (size_t o = 0; o < O; ++o) row[o] = focus_key(vel ? fmaf(-speed[o], time, db[o]) : db[o]);
+        uint32_t bar = FOCUS_NOT_PASSING;
+        if (!r.all_pass) {
+            sorted = row;
+            std::nth_element(sorted.begin(), sorted.begin() + (n_closest - 1), sorted.end());
+            bar = focus_bar_key(sorted[(size_t)n_closest - 1], r.margin);
+        }
+        for (size_t o = 0; o < O; ++o) {
+            pass[o] |= row[o] <= bar;
+            best[o] = std::min(best[o], row[o]);
+        }
+    }
+    std::vector<std::pair<uint32_t, int32_t>> order;   // (nearest key, index) of the passing spheres
+    for (size_t o = 0; o < O; ++o)
+        if (pass[o]) order.push_back({best[o], (int32_t)o});
+    std::sort(order.begin(), order.end());
+    const int64_t passed = (int64_t)order.size();
+    const int64_t kept = r.max_keep ? std::min<int64_t>(passed, r.max_keep) : passed;
+    *kept_out = (int32_t)kept;
+    *passed_out = (int32_t)passed;
+    if (cap < kept) return fail("omds_obstacle_focus_select_path: cap is smaller than the kept set (kept_out holds its size); idx_out is untouched");
     for (int64_t i = 0; i < kept; ++i) idx_out[i] = order[(size_t)i].second;
     std::sort(idx_out, idx_out + kept);
     return OMDS_OK;

@@ -268,6 +268,20 @@ class Engine:
         self.n_obs = int(kept[0])
         return int(kept[0]), int(passed[0])
 
+    def focus_obstacles_path(self, q_path, margin, max_keep=0, lookahead=0.0, ahead=None):
+        """``focus_obstacles`` along joint states ``q_path`` [B, n] (1 <= B <= 65 536) -> (kept, passed): a sphere passes when it is
+        within ``margin`` of the ``n_closest``-th nearest at SOME state, and the cap keeps those nearest to any state.  ``ahead`` [B]:
+        the seconds until each state is reached, added to ``lookahead`` for a moving sphere (None: zeros)."""
+        qn = L.f32(q_path).reshape(-1, self.n)
+        a = None if ahead is None else L.f32(ahead).reshape(-1)
+        if a is not None and a.shape[0] != qn.shape[0]:
+            raise ValueError(f"focus_obstacles_path: ahead must be [{qn.shape[0]}], got {a.shape}")
+        spec = obstacle_focus_spec(margin, max_keep, lookahead)
+        kept, passed = np.zeros(1, np.int32), np.zeros(1, np.int32)
+        self._ck(self.lib.omds_focus_obstacles_path(self.h, C.byref(spec), L.fptr(qn), L.fptr(a), qn.shape[0], L.iptr(kept), L.iptr(passed)))
+        self.n_obs = int(kept[0])
+        return int(kept[0]), int(passed[0])
+
     def obstacle_focus(self):
         """The master index of every sphere in force (ascending, int32 [n_obs]), or None when no focus is in force."""
         n_master, n_kept = np.zeros(1, np.int32), np.zeros(1, np.int32)
@@ -801,6 +815,30 @@ def obstacle_focus_select(d, n_closest, margin, max_keep=0, lookahead=0.0, vel=N
                                         L.iptr(passed))
     if rc != 0:
         raise L.OmdsError(f"omds_obstacle_focus_select failed ({rc}): {lib.omds_last_error(None).decode()}")
+    return idx[:int(kept[0])].copy(), int(passed[0])
+
+
+def obstacle_focus_select_path(d, n_closest, margin, max_keep=0, lookahead=0.0, ahead=None, vel=None, cap=None):
+    """The definition of the obstacle focus along a path on the host (omds_obstacle_focus_select_path; no context, no GPU): distances
+    ``d`` [B, O], one row per state, optional ``ahead`` [B] seconds and velocities ``vel`` [O, 3] -> (idx, passed)."""
+    lib = L.load()
+    d = L.f32(d)
+    if d.ndim != 2:
+        raise ValueError(f"obstacle_focus_select_path: distances must be [B, O], got {d.shape}")
+    B, O = d.shape
+    a = None if ahead is None else L.f32(ahead).reshape(-1)
+    v = None if vel is None else L.f32(vel).reshape(-1, 3)
+    if a is not None and a.shape[0] != B:
+        raise ValueError(f"obstacle_focus_select_path: ahead must be [{B}], got {a.shape}")
+    if v is not None and v.shape[0] != O:
+        raise ValueError(f"obstacle_focus_select_path: velocities must be [{O}, 3], got {v.shape}")
+    cap = O if cap is None else int(cap)
+    spec = obstacle_focus_spec(margin, max_keep, lookahead)
+    idx, kept, passed = np.zeros(max(cap, 1), np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32)
+    rc = lib.omds_obstacle_focus_select_path(C.byref(spec), L.fptr(d), L.fptr(a), L.fptr(v), B, O, int(n_closest), L.iptr(idx), cap, L.iptr(kept),
+                                             L.iptr(passed))
+    if rc != 0:
+        raise L.OmdsError(f"omds_obstacle_focus_select_path failed ({rc}): {lib.omds_last_error(None).decode()}")
     return idx[:int(kept[0])].copy(), int(passed[0])
 
 

@@ -258,17 +258,40 @@ class MPPI:
         self._engine.set_obstacle_frame(bool(moving_frame))       # as update_obstacles leaves it
         return out
 
-    def focus_obstacles(self, margin, max_keep=0, q=None):
+    def focus_obstacles(self, margin, max_keep=0, q=None, along=None, stride=1):
         """Narrow a large scene to the spheres near the robot, on the device (new here; Engine.focus_obstacles): of the MASTER -- the
         scene the last ``update_obstacles*`` call installed, kept for the next call -- the ``n_closest_obs`` spheres nearest to ``q``
         (None: ``self.q_cur``) and every sphere within ``margin`` metres of the farthest of those stay in force, at most ``max_keep``
         (0: no cap); a moving sphere is given the horizon, (dt_H - 1) dt seconds, to approach.  Meant for every planner iteration,
         before ``propagate``.  ``self.obs``, ``self.n_obs`` and ``self.obs_velocities`` then describe the scene in force and
         ``self.obs_focus`` holds the master index of each of its spheres.  Returns (kept, passed).  Whether the propagate equals the one
-        on the full scene is the caller's bet on ``margin`` (omds.h: THE OBSTACLE FOCUS)."""
+        on the full scene is the caller's bet on ``margin`` (omds.h: THE OBSTACLE FOCUS).
+        ``along`` focuses along a path of states instead (Engine.focus_obstacles_path): a sphere stays when it is near at SOME state, and
+        ``margin`` covers only the deviation from them.  An array or tensor [B, n]: ``q`` and those states, a moving sphere given the
+        whole horizon at each.  A sequence of rollout indices: ``q`` and the states ``all_traj[r, ::stride]`` of the last propagate
+        (fetched per rollout when ``lazy_rollouts``), a moving sphere given step * dt seconds to reach a state and (stride - 1) dt more."""
         self._push()                                 # the distances take their minimum over the links not in self.ignored_links
         q = _np(self.q_cur if q is None else q).reshape(-1)
-        out = self._engine.focus_obstacles(q, margin, max_keep, (self.dt_H - 1) * float(self.dt))
+        dt = float(self.dt)
+        if along is None:
+            out = self._engine.focus_obstacles(q, margin, max_keep, (self.dt_H - 1) * dt)
+        else:
+            a = _np(along)
+            if a.ndim == 2:
+                path = np.concatenate([q[None], a.astype(np.float32)])
+                out = self._engine.focus_obstacles_path(path, margin, max_keep, (self.dt_H - 1) * dt)
+            else:
+                rows, stride = np.atleast_1d(a).astype(np.int64).reshape(-1), int(stride)
+                if stride < 1 or rows.size == 0 or rows.min() < 0 or rows.max() >= self.N_traj:
+                    raise ValueError("focus_obstacles: along needs rollout indices in [0, N_traj) and stride >= 1")
+                if self.lazy_rollouts:
+                    traj = self._engine.get_rollout_rows(rows, want=("all_traj",))["all_traj"]
+                else:
+                    traj = _np(self.all_traj)[rows]
+                steps = np.arange(0, self.dt_H, stride)
+                path = np.concatenate([q[None], traj[:, steps].reshape(-1, self.n_dof).astype(np.float32)])
+                ahead = np.concatenate([[0.0], np.tile(steps * dt, rows.size)]).astype(np.float32)
+                out = self._engine.focus_obstacles_path(path, margin, max_keep, (stride - 1) * dt, ahead)
         self._focus_refresh()
         return out
 
