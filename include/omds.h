@@ -420,9 +420,10 @@ OMDS_API int omds_set_obstacles_from_depth(omds_ctx* ctx, const omds_cloud_spec*
  * about occupancy: a cell that got no points this frame is gone, whether a camera looked through it or the arm, a dropout (raw 0) or
  * the edge of a frustum kept every camera from telling.  This route keeps one word per cell between calls and asks the cameras.
  * Additive: no other entry point changes its launches or its bits.
- * OUT OF SCOPE: memory on the tracked / objects routes (velocities of remembered cells: remembered spheres stand still, this route
- * installs a static scene), the plain cloud route (no cameras, so no visibility), per-cell occupancy probabilities or log-odds,
- * sub-voxel footprints that follow the cell's projected size, motion compensation of the memory when the grid frame moves.
+ * OUT OF SCOPE: velocities on THIS route (it installs a static scene; memory together with the tracked / objects routes is
+ * omds_set_obstacles_from_depth_memory_tracked, below), the plain cloud route (no cameras, so no visibility), per-cell occupancy
+ * probabilities or log-odds, sub-voxel footprints that follow the cell's projected size, motion compensation of the memory when the
+ * grid frame moves.
  *   THE WORD: m[c] (uint32) per grid cell; 0 = empty, k >= 1 = occupied and last counted k - 1 calls ago.
  *   omds_depth_scene_memory : host only (no context, no GPU), the DEFINITION.  All fp32, every operation named one rounding.  n[c] are
  *       the counts of the depth route's counting pass (omds_depth_points of every image, cloud_cell), unchanged.  mem_in [cells] (NULL =
@@ -520,6 +521,65 @@ OMDS_API int omds_depth_scene_memory_filtered(const omds_cloud_spec* spec, const
                                               int32_t counts_out[4]);
 OMDS_API int omds_set_depth_filter(omds_ctx* ctx, const omds_depth_filter_spec* spec /* NULL: off */);
 OMDS_API int omds_get_depth_filter_stats(omds_ctx* ctx, int64_t out[2] /* kept, rejected */);
+/* MEMORY AND VELOCITIES IN ONE DEPTH CALL (new work).  The memory route keeps the shelf the arm reaches across and freezes the person
+ * walking by; the tracked / objects routes predict the person and lose the shelf the moment it is occluded; each installs its own scene,
+ * so calling both does not help.  This route does both in one call, on the stored memory, the stored record frame and the stored
+ * component table that the other routes already keep.  And the two have something to tell each other: a wall cell uncovered after a few
+ * occluded frames has no record in the previous frame, so the tracked route matches it with its neighbours and reports a sideways
+ * velocity it does not have -- the memory knows the cell was occupied all along.  Additive: no other entry point changes its launches
+ * or its bits.
+ * OUT OF SCOPE: velocities for remembered cells (dead reckoning behind an occluder: a remembered sphere stands still), objects formed
+ * over remembered cells, the centroid shift of an uncovered surface on the objects route, memory on the plain cloud route (no cameras),
+ * temporal smoothing.
+ *   omds_depth_scene_memory_flow : host only (no context, no GPU), the DEFINITION, a composition of the definitions above.  The
+ *       previous frame is given as its cameras and images (cams_prev == NULL: none); it stands for the stored record frame AND, with obj,
+ *       the stored component table (the components of its kept occupied cells).  filt (NULL: off) filters both frames.
+ *       1. RECORDS: those of the depth route's counting pass (omds_depth_points[_filtered] of every image, cloud_cell_sub); n[c] their count.
+ *       2. WORDS: m' = omds_depth_scene_memory[_filtered] on the same images and mem_in.  The candidates are the cells with m' != 0 in
+ *       cell order; keep_now [candidates] (NULL: keep all) stands for the self-filter, and a dropped candidate sets m'[cell] = 0 (counts
+ *       [4]).  seen + remembered > max_spheres (or cap): OMDS_ERR_INVALID_ARG with counts_out and *count_out filled, nothing else written.
+ *       3. THE SEEN SUBLIST T: the final spheres with n[c] >= min_points, in cell order.  On T the velocities and matched flags, and with
+ *       obj the labels, object flags, n_objects and n_objects_matched, are those of omds_point_cloud_flow / omds_point_cloud_object_flow
+ *       on the points of the two frames with keep_prev [occupied cells of the previous frame] and T as the kept cells of this one: T is
+ *       that call's final list; the memory adds spheres around it and changes nothing inside it.
+ *       4. PER FINAL SPHERE, LAST (it wins over an accepted object's velocity): a sphere not in T: velocity +0, not matched, label -1,
+ *       object 0.  A sphere of T whose STORED word mem_in[c] >= 2 (occupied and unseen at the previous memory call): velocity +0, not
+ *       matched, object 0; its label stays.  Every other sphere of T keeps step 3's values.
+ *       5. xyzr_out, vel_out, age_out (m' - 1), label_out (-1 without obj), object_out [count]; *n_matched_out = final spheres whose
+ *       matched flag survives step 4, -1 without a previous frame; *n_objects_matched_out = -1 without one.
+ *       OMDS_ERR_INVALID_ARG before anything is written: as omds_depth_scene_memory, omds_point_cloud_flow and, with obj,
+ *       omds_point_cloud_object_flow; a bad filter spec; null mem_out or count_out; cap < 0 or cap > 0 with a null output array.
+ *   omds_set_obstacles_from_depth_memory_tracked : THE CONTRACT -- stored words, counts_out [5], the installed spheres and their ages
+ *       are bit for bit those of omds_set_obstacles_from_depth_memory on the same stored memory (self-filter, self-forgetting and the
+ *       refusal included); on T, velocities, matched flags, labels, object flags, the component table that gets stored, *n_objects_out
+ *       and *n_objects_matched_out are bit for bit those of omds_set_obstacles_from_depth(track[, obj]) on the same images, q_now,
+ *       stored frame and stored table; step 4 then overrides.  *n_matched_out as in step 5 (-1 without a stored frame on this grid).
+ *       If every velocity is exactly 0 the horizon stays cleared (the static propagate follows); else horizon mode 1 through
+ *       omds_set_obstacle_motion.  Padding spheres: velocity 0, age -1, label -1.  obj == NULL: per-cell flow only, and the stored table
+ *       is invalidated as by a plain tracked call.  STATE: the route shares the one stored memory (and its key) with the memory route and
+ *       the one stored record frame and component table with the tracked / objects routes; a successful call commits all of them, a
+ *       refusal leaves scene, memory, frame and table exactly as they were.  Frames may alternate with every other route: the result is
+ *       a function of the stored state, and dt_frame is the caller's claim about the stored frame's age.  omds_get_scene_memory reports
+ *       this scene's ages, with obj omds_get_cloud_objects its labels and flags.  The context's depth filter is consulted.  On the
+ *       device: ONE counting pass (into the record buffer that is not the stored frame) and ONE staging copy; k_scene_memory<uint4>,
+ *       the memory kernel as a template, reads the .x of four consecutive records per lane; compaction, self-filter, forget and ages as on the memory route; one more ordered
+ *       compaction of the final list to T (cell and list index); the tracked / objects launchers on T, unchanged; one launch, one lane
+ *       per final sphere, carries T's results back under step 4's rule (the matched flag stays in .w: the host counts).  Synchronous.  */
+OMDS_API int omds_depth_scene_memory_flow(const omds_cloud_spec* spec, const omds_scene_memory_spec* mem_spec, const omds_cloud_track_spec* track,
+                                          const omds_cloud_object_spec* obj /* NULL: per-cell flow only */,
+                                          const omds_depth_filter_spec* filt /* NULL: off */, const omds_depth_camera* cams_prev /* NULL: none */,
+                                          const void* const* images_prev, int32_t n_cams_prev, const uint8_t* keep_prev,
+                                          const omds_depth_camera* cams, const void* const* images, int32_t n_cams, const uint8_t* keep_now,
+                                          const uint32_t* mem_in /* [cells] or NULL = empty */, uint32_t* mem_out /* [cells] */,
+                                          int32_t counts_out[5], float* xyzr_out /* [cap,4] */, float* vel_out /* [cap,3] */,
+                                          int32_t* age_out, int32_t* label_out, int32_t* object_out /* [cap] each */, int32_t cap,
+                                          int32_t* count_out, int32_t* n_matched_out, int32_t* n_objects_out, int32_t* n_objects_matched_out);
+OMDS_API int omds_set_obstacles_from_depth_memory_tracked(omds_ctx* ctx, const omds_cloud_spec* spec, const omds_scene_memory_spec* mem_spec,
+                                                          const omds_cloud_track_spec* track, const omds_cloud_object_spec* obj /* NULL: per-cell flow only */,
+                                                          const omds_depth_camera* cams, const void* const* images, int32_t n_cams,
+                                                          int images_on_device, const float* q_now, int32_t* n_spheres_out,
+                                                          int32_t counts_out[5], int32_t* n_matched_out, int32_t* n_objects_out,
+                                                          int32_t* n_objects_matched_out);
 /* THE OBSTACLE FOCUS (new work).  A sensed scene has thousands of spheres; everything behind pass 1 uses the n_closest nearest per
  * (rollout, step).  A focus call evaluates the distance of every sphere of the scene at ONE joint state, selects the near ones and
  * installs them as the scene in force, on the device; the full scene (the MASTER) is kept, so that the next call selects from it again

@@ -163,6 +163,15 @@ SIGNATURES = {
                                                    C.POINTER(OmdsDepthCamera), C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.c_void_p, I32P]),
     "omds_set_depth_filter": (C.c_int, [C.c_void_p, C.POINTER(OmdsDepthFilterSpec)]),
     "omds_get_depth_filter_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "omds_depth_scene_memory_flow": (C.c_int, [C.POINTER(OmdsCloudSpec), C.POINTER(OmdsSceneMemorySpec), C.POINTER(OmdsCloudTrackSpec),
+                                               C.POINTER(OmdsCloudObjectSpec), C.POINTER(OmdsDepthFilterSpec), C.POINTER(OmdsDepthCamera),
+                                               C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.POINTER(OmdsDepthCamera), C.POINTER(C.c_void_p),
+                                               C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, I32P, F32P, F32P, I32P, I32P, I32P, C.c_int32,
+                                               I32P, I32P, I32P, I32P]),
+    "omds_set_obstacles_from_depth_memory_tracked": (C.c_int, [C.c_void_p, C.POINTER(OmdsCloudSpec), C.POINTER(OmdsSceneMemorySpec),
+                                                               C.POINTER(OmdsCloudTrackSpec), C.POINTER(OmdsCloudObjectSpec),
+                                                               C.POINTER(OmdsDepthCamera), C.POINTER(C.c_void_p), C.c_int32, C.c_int, F32P, I32P,
+                                                               I32P, I32P, I32P, I32P]),
     "omds_obstacle_focus_select": (C.c_int, [C.POINTER(OmdsObstacleFocusSpec), F32P, F32P, C.c_int, C.c_int, I32P, C.c_int32, I32P, I32P]),
     "omds_focus_obstacles": (C.c_int, [C.c_void_p, C.POINTER(OmdsObstacleFocusSpec), F32P, I32P, I32P]),
     "omds_obstacle_focus_select_path": (C.c_int, [C.POINTER(OmdsObstacleFocusSpec), F32P, F32P, F32P, C.c_int, C.c_int, C.c_int, I32P, C.c_int32, I32P,

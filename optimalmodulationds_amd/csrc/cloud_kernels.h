@@ -7,6 +7,7 @@
 #include "depth_def.h"
 #include "point_cloud_objects_def.h"
 #include "scene_memory_def.h"
+#include "scene_memory_flow_def.h"
 
 constexpr int CLOUD_NT = 256;                          // lanes of every workgroup here
 constexpr int CLOUD_ITEMS = 4;                         // consecutive items per lane of a compaction block
@@ -80,6 +81,20 @@ void omds_launch_focus_path_select(hipStream_t s, const unsigned* best, const un
 // seen, remembered, cleared and expired cells
 void omds_launch_scene_memory(hipStream_t s, DepthTable tab, const SceneMemCams& ks, int n_cams, const CloudGrid& g, const SceneMem& sm,
                               const unsigned* count, const unsigned* mem_in, unsigned* mem_out, unsigned* counters);
+// ... the same pass with the counts read out of the records rec (the .x of each; padded with zeros like count)
+void omds_launch_scene_memory(hipStream_t s, DepthTable tab, const SceneMemCams& ks, int n_cams, const CloudGrid& g, const SceneMem& sm,
+                              const uint4* rec, const unsigned* mem_in, unsigned* mem_out, unsigned* counters);
+// Memory and velocities in one call (scene_memory_flow_def.h).  One more ordered compaction: of the n spheres of the final list (their
+// cells in cells) those whose cell has min_points points and more in the records now, in list order: the cell to cell, the index in
+// the final list to idx; sums as above
+void omds_launch_cloud_compact_seen(hipStream_t s, const uint4* now, const CloudGrid& g, const int* cells, int n, int* cell, int* idx,
+                                    unsigned* sums);
+// ... and the results of those n_seen spheres (velT as omds_launch_cloud_flow / omds_launch_cloud_apply left it, labelT, objectT; each
+// may be nullptr: zeros, -1, 0) to their places in vel, label, object [n] under scene_memory_flow_still, which reads the STORED words
+// mem_in (nullptr: all empty); the spheres outside them get velocity 0, label -1, object 0
+void omds_launch_scene_memory_flow(hipStream_t s, const uint4* now, const CloudGrid& g, const unsigned* mem_in, const int* cells, int n,
+                                   const int* idx, int n_seen, const float4* velT, const int* labelT, const int* objectT, float4* vel, int* label,
+                                   int* object);
 // ... mem[cell[i]] = 0 for every candidate i of n the self-filter drops at its pass-1 distance d[i]; counters[SCENE_MEM_FORGOTTEN] += them
 void omds_launch_scene_memory_forget(hipStream_t s, const float* d, const int* cell, int n, float margin, unsigned* mem, unsigned* counters);
 // ... age[i] = mem[cell[i]] - 1 for the n final spheres

@@ -117,6 +117,11 @@ struct CloudState {
     DevBuf<int> age;                  // [max_spheres] m' - 1 of every final sphere's cell
     DevBuf<unsigned> memCounts;       // [SCENE_MEM_COUNTS] seen, remembered, cleared, expired, self-forgotten of the call under way
     std::vector<int32_t> mem_age;     // [n_obs] of the scene in force when the memory call installed it (padding: -1), else empty
+    // ... memory and velocities in one call (omds_set_obstacles_from_depth_memory_tracked): the seen sublist T of the final list, on
+    // which the tracked / objects stages run, and their results carried back to the whole list
+    DevBuf<int> seenCell, seenIdx;    // [max_spheres] cell of every sphere of T; its index in the final list
+    DevBuf<float4> velAll;            // [max_spheres] velocity of every final sphere behind scene_memory_flow_still; .w as vel's
+    DevBuf<int> labelAll, objectAll;  // [max_spheres] ... its label (-1 outside T) and whether it moves with an accepted object
     // ... the depth filter (omds_set_depth_filter): context state that every depth call consults; no key of anything stored
     bool filter_on = false;
     DepthFilter filter = {};          // behind its checks, while filter_on

@@ -1,5 +1,5 @@
 // The scene from a depth point cloud or from depth images (omds.h: omds_set_obstacles_from_cloud[_tracked|_objects],
-// omds_set_obstacles_from_depth[_memory], omds_set_depth_filter), as host stages over the launchers of cloud_kernels.h; the state between calls is omds_ctx::cloud
+// omds_set_obstacles_from_depth[_memory[_tracked]], omds_set_depth_filter), as host stages over the launchers of cloud_kernels.h; the state between calls is omds_ctx::cloud
 // (cloud_state.h).  One body, scene_from_cloud, for every route.  A route is a choice of three things (CloudCall): tracked or not,
 // objects or not (objects need tracked), and where the points come from.
 //   plain   : count per cell -> ordered compaction of the occupied cells -> the robot self-filter as ONE fp32 pass-1 launch over one
@@ -12,6 +12,8 @@
 //   depth   : any of the three with the images of up to eight cameras as the point source: no point is ever written
 //   memory  : the plain depth route with one word per cell kept between calls (scene_from_depth_memory, a stage sequence of its own
 //             over the same stages): occluded cells stay, cells a camera looked through leave
+//   memory + tracked / objects : both in one call (scene_from_depth_memory_tracked, a third stage sequence): one counting pass into
+//             records, the memory's words out of their counts, and the tracked / objects stages on the spheres that were counted now
 //   filter  : while the context has a depth filter, the counting pass of every depth call above is the filtered one
 //             (depth_filter_def.h): another kernel in the same place, and two counters fetched behind it
 #include "capi_internal.h"
@@ -59,6 +61,7 @@ struct CloudWork {
     int occupied = 0;               // cells with min_points points and more
     const float4* d_list = nullptr; // the final list so far: the candidates, behind the self-filter those it keeps
     const int* d_cell = nullptr;    // tracked: the cell of every sphere of d_list, else nullptr
+    const float4* d_vel = nullptr;  // where install_scene fetches the velocities of d_list from; nullptr: cloud.vel
     int n_list = 0, n_final = 0;    // spheres of d_list; of the installed scene (filled up to n_closest)
     bool have_prev = false, have_table = false;   // there is a stored frame on this grid; and a stored table under this object spec
     int n_comp = 0, matched = 0;
@@ -280,7 +283,8 @@ int object_velocities(omds_ctx* ctx, const CloudCall& c, CloudWork& w) {
 // follows is the static one
 int install_scene(omds_ctx* ctx, const CloudCall& c, CloudWork& w) {
     const int n_list = w.n_list, n_final = w.n_final;
-    if (!w.vel4.empty()) CK(hipMemcpyAsync(w.vel4.data(), ctx->cloud.vel, (size_t)n_list * 16, hipMemcpyDeviceToHost, ctx->stream));
+    if (!w.vel4.empty())
+        CK(hipMemcpyAsync(w.vel4.data(), w.d_vel ? w.d_vel : ctx->cloud.vel.get(), (size_t)n_list * 16, hipMemcpyDeviceToHost, ctx->stream));
     std::vector<float> list((size_t)n_final * 4);
     if (n_list > 0) CK(hipMemcpyAsync(list.data(), w.d_list, (size_t)n_list * 16, hipMemcpyDeviceToHost, ctx->stream));
     CK(hipStreamSynchronize(ctx->stream));
@@ -450,6 +454,119 @@ int scene_from_depth_memory(omds_ctx* ctx, const CloudCall& c, const SceneMem& s
     return OMDS_OK;
 }
 
+// ---- memory and velocities in one call (omds_set_obstacles_from_depth_memory_tracked; the definition: scene_memory_flow_def.h): a
+// third stage sequence over the same stages.  ONE counting pass, into the record buffer that is not the stored frame, and ONE staging
+// copy serve both halves: k_scene_memory reads its counts out of the records -> compaction of the words that are not 0 -> the refusal
+// check -> self-filter, forget, ages as on the memory route -> the ordered compaction of the final list to T, the spheres whose cell
+// was counted now -> the tracked / objects stages on T, unchanged -> one launch carries T's results back to the whole list under
+// scene_memory_flow_still -> install -> commit of the memory, the frame and the table, behind everything that can fail
+int reserve_memory_flow(omds_ctx* ctx, const CloudCall& c) {
+    CloudState& s = ctx->cloud;
+    const size_t m = (size_t)c.g.max_spheres;
+    if (s.seenCell.count() < m || s.seenIdx.count() < m || s.velAll.count() < m || s.labelAll.count() < m || s.objectAll.count() < m)
+        CK(hipStreamSynchronize(ctx->stream));
+    CK(s.seenCell.reserve(m));
+    CK(s.seenIdx.reserve(m));
+    CK(s.velAll.reserve(m));
+    CK(s.labelAll.reserve(m));
+    CK(s.objectAll.reserve(m));
+    return OMDS_OK;
+}
+
+int scene_from_depth_memory_tracked(omds_ctx* ctx, const CloudCall& c, const SceneMem& sm, const SceneMemCams& ks, int32_t* counts_out) {
+    const std::string me(c.who);
+    CloudState& s = ctx->cloud;
+    int rc;
+    if (c.q_now) {
+        REQUIRE(ctx->have_mlp, OMDS_ERR_NOT_INITIALISED, me + ": the self-filter needs the distance network (omds_set_mlp)");
+        REQUIRE(!ctx->wide.on, OMDS_ERR_UNSUPPORTED, me + ": no self-filter on networks wider than 256 (no obstacle tables)");
+    }
+    CK(hipSetDevice(ctx->dev));
+    CloudWork w;
+    if ((rc = reserve_base(ctx, c))) return rc;
+    if ((rc = reserve_tracked(ctx, c))) return rc;
+    if (c.objects && (rc = reserve_objects(ctx, c))) return rc;
+    if ((rc = reserve_memory(ctx, c))) return rc;
+    if ((rc = reserve_memory_flow(ctx, c))) return rc;
+    if ((rc = stage_points(ctx, c, w))) return rc;
+    const bool have = s.memKey.same(c.g, sm);   // else: from empty memory, whatever is stored stays until the commit
+    const unsigned* stored = have ? s.mem.kept().get() : nullptr;
+    unsigned* next = s.mem.next();
+    uint4* rec = s.rec.next();
+    CK(hipMemsetAsync(rec, 0, cloud_padded_cells(c.g) * 16, ctx->stream));
+    CK(hipMemsetAsync(s.memCounts, 0, SCENE_MEM_COUNTS * 4, ctx->stream));
+    if ((rc = filter_stats_begin(ctx, c))) return rc;
+    enqueue_count(ctx, c, w, rec);
+    if ((rc = filter_stats_fetch(ctx, c, w))) return rc;
+    if ((rc = prof_begin(ctx))) return rc;
+    omds_launch_scene_memory(ctx->stream, w.depth, ks, c.src.depth->n_cams, c.g, sm, rec, stored, next, s.memCounts);
+    if ((rc = prof_end(ctx, c.g.n_cells, 0.0, "k_scene_memory"))) return rc;
+    omds_launch_cloud_compact_cells(ctx->stream, next, c.g, s.cand, s.candCell, s.sums);
+    unsigned counts[SCENE_MEM_COUNTS] = {0u, 0u, 0u, 0u, 0u};
+    CK(hipMemcpyAsync(counts, s.memCounts, 4 * 4, hipMemcpyDeviceToHost, ctx->stream));
+    w.d_list = s.cand;
+    w.d_cell = s.candCell;
+    if ((rc = compaction_total(ctx, c.g.n_cells, &w.occupied))) return rc;   // = seen + remembered
+    filter_stats_done(ctx, c, w);
+    if (counts_out)
+        for (int k = 0; k < SCENE_MEM_COUNTS; ++k) counts_out[k] = (int32_t)counts[k];
+    REQUIRE(w.occupied <= c.g.max_spheres, OMDS_ERR_INVALID_ARG,
+            me + ": more seen and remembered cells than max_spheres (counts_out holds their numbers); the scene, the memory, the record frame and "
+                 "the component table are unchanged");
+    w.n_list = w.occupied;
+    if (c.q_now && w.occupied > 0) {
+        if ((rc = self_filter(ctx, c, w))) return rc;
+        omds_launch_scene_memory_forget(ctx->stream, ctx->d_Dmin, s.candCell, w.occupied, c.spec->self_margin, next, s.memCounts);
+        CK(hipGetLastError());
+        CK(hipMemcpyAsync(counts + SCENE_MEM_FORGOTTEN, s.memCounts + SCENE_MEM_FORGOTTEN, 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    w.n_final = std::max(w.n_list, ctx->cfg.n_closest);
+    std::vector<int32_t> age((size_t)w.n_final, -1);   // padding spheres: -1
+    w.label.assign((size_t)w.n_final, -1);             // ... label -1, no object
+    w.object.assign((size_t)w.n_final, 0);
+    w.have_prev = s.frame.same(c.g);
+    CloudWork t;                                       // the stages of the tracked / objects routes see T as their final list
+    if (w.n_list > 0) {
+        omds_launch_scene_memory_age(ctx->stream, next, w.d_cell, w.n_list, s.age);
+        CK(hipGetLastError());
+        CK(hipMemcpyAsync(age.data(), s.age, (size_t)w.n_list * 4, hipMemcpyDeviceToHost, ctx->stream));
+        omds_launch_cloud_compact_seen(ctx->stream, rec, c.g, w.d_cell, w.n_list, s.seenCell, s.seenIdx, s.sums);
+        if ((rc = compaction_total(ctx, w.n_list, &t.n_list))) return rc;
+        t.d_cell = s.seenCell;
+        t.n_final = t.n_list;
+        if ((rc = sphere_velocities(ctx, c, t))) return rc;
+        if (c.objects && (rc = object_velocities(ctx, c, t))) return rc;
+        const bool flowed = t.have_prev && t.n_list > 0, labelled = c.objects && t.n_list > 0;
+        omds_launch_scene_memory_flow(ctx->stream, rec, c.g, stored, w.d_cell, w.n_list, s.seenIdx, t.n_list, flowed ? s.vel.get() : nullptr,
+                                      labelled ? s.label.get() : nullptr, labelled && t.have_table ? s.object.get() : nullptr, s.velAll,
+                                      s.labelAll, s.objectAll);
+        CK(hipGetLastError());
+        if (c.objects) {
+            CK(hipMemcpyAsync(w.label.data(), s.labelAll, (size_t)w.n_list * 4, hipMemcpyDeviceToHost, ctx->stream));
+            CK(hipMemcpyAsync(w.object.data(), s.objectAll, (size_t)w.n_list * 4, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        if (w.have_prev) {
+            w.vel4.resize((size_t)w.n_list * 4);
+            w.d_vel = s.velAll;
+        }
+    } else if (c.objects) {
+        t.have_table = w.have_prev && s.tab.same(c.ob);
+    }
+    if ((rc = install_scene(ctx, c, w))) return rc;   // synchronises
+    if (counts_out) counts_out[SCENE_MEM_FORGOTTEN] = (int32_t)counts[SCENE_MEM_FORGOTTEN];
+    s.mem_age = std::move(age);
+    s.mem.commit();
+    s.memKey.set(c.g, sm);
+    commit_frame(ctx, c, w);
+    if (c.objects) {
+        w.have_table = t.have_table;
+        w.n_comp = t.n_comp;
+        w.obj_vel = std::move(t.obj_vel);
+        commit_objects(ctx, c, w);
+    }
+    return OMDS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -585,6 +702,44 @@ int omds_set_obstacles_from_depth_memory(omds_ctx* ctx, const omds_cloud_spec* s
     c.q_now = q_now;
     c.out = CloudOuts{n_spheres_out, nullptr, nullptr, nullptr, nullptr};
     return scene_from_depth_memory(ctx, c, sm, ks, counts_out);
+}
+
+int omds_depth_scene_memory_flow(const omds_cloud_spec* spec, const omds_scene_memory_spec* mem_spec, const omds_cloud_track_spec* track,
+                                 const omds_cloud_object_spec* obj, const omds_depth_filter_spec* filt, const omds_depth_camera* cams_prev,
+                                 const void* const* images_prev, int32_t n_cams_prev, const uint8_t* keep_prev, const omds_depth_camera* cams,
+                                 const void* const* images, int32_t n_cams, const uint8_t* keep_now, const uint32_t* mem_in, uint32_t* mem_out,
+                                 int32_t counts_out[5], float* xyzr_out, float* vel_out, int32_t* age_out, int32_t* label_out,
+                                 int32_t* object_out, int32_t cap, int32_t* count_out, int32_t* n_matched_out, int32_t* n_objects_out,
+                                 int32_t* n_objects_matched_out) {
+    return scene_memory_flow_host(spec, mem_spec, track, obj, filt, cams_prev, images_prev, n_cams_prev, keep_prev, cams, images, n_cams, keep_now,
+                                  mem_in, mem_out, counts_out, xyzr_out, vel_out, age_out, label_out, object_out, cap, count_out, n_matched_out,
+                                  n_objects_out, n_objects_matched_out, &g_create_err);
+}
+
+int omds_set_obstacles_from_depth_memory_tracked(omds_ctx* ctx, const omds_cloud_spec* spec, const omds_scene_memory_spec* mem_spec,
+                                                 const omds_cloud_track_spec* track, const omds_cloud_object_spec* obj,
+                                                 const omds_depth_camera* cams, const void* const* images, int32_t n_cams, int images_on_device,
+                                                 const float* q_now, int32_t* n_spheres_out, int32_t counts_out[5], int32_t* n_matched_out,
+                                                 int32_t* n_objects_out, int32_t* n_objects_matched_out) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    const char* me = "omds_set_obstacles_from_depth_memory_tracked";
+    CloudCall c;
+    SceneMem sm;
+    if (int rc = resolve_call(ctx, me, spec, true, track, obj != nullptr, obj, &c)) return rc;
+    if (int rc = scene_memory_resolve(mem_spec, c.g, &sm, &ctx->err)) return rc;
+    DepthSource depth;
+    depth.images = images;
+    depth.n_cams = n_cams;
+    depth.on_device = images_on_device;
+    depth.filt = ctx->cloud.filter_on ? &ctx->cloud.filter : nullptr;
+    if (int rc = resolve_depth_source(ctx, me, cams, depth)) return rc;
+    SceneMemCams ks;
+    std::memset(static_cast<void*>(&ks), 0, sizeof(ks));
+    for (int i = 0; i < n_cams; ++i) ks.k[i] = scene_memory_camera(cams[i], depth.cam[i]);
+    c.src = PointSource{nullptr, 0, 0, &depth};
+    c.q_now = q_now;
+    c.out = CloudOuts{n_spheres_out, nullptr, n_matched_out, n_objects_out, n_objects_matched_out};
+    return scene_from_depth_memory_tracked(ctx, c, sm, ks, counts_out);
 }
 
 int omds_scene_memory_reset(omds_ctx* ctx) {

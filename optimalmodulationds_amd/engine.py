@@ -196,6 +196,35 @@ class Engine:
             raise
         return int(n_sph[0]), tuple(int(v) for v in counts)
 
+    def set_obstacles_from_depth_memory_tracked(self, images, cams, spec, mem, track, objects=None, q=None):
+        """``set_obstacles_from_depth_memory`` and ``set_obstacles_from_depth(track=[, obj=])`` in one call (omds.h: MEMORY AND
+        VELOCITIES IN ONE DEPTH CALL), on the stored memory, record frame and component table those routes keep: the scene, the stored
+        words, ``counts`` and the ages are the memory call's; the spheres whose cell was counted now carry the tracked (``objects``
+        None) or objects (an ``OmdsCloudObjectSpec``) call's velocities, labels and flags; a remembered sphere, and a seen one that
+        was occupied and unseen at the previous memory call, stands still -> (n_spheres, counts, n_matched, n_objects,
+        n_objects_matched); n_matched is -1 without a stored frame on this grid, n_objects_matched -1 without a stored table, and
+        n_objects 0 without ``objects``.  Raises like ``set_obstacles_from_depth_memory``, with scene, memory, frame and table
+        unchanged."""
+        table, addrs, n, on_dev, keep = _depth_table("set_obstacles_from_depth_memory_tracked", images, cams, self.device)
+        qn = None if q is None else L.f32(q).reshape(self.n)
+        n_sph, counts, n_match = np.zeros(1, np.int32), np.zeros(5, np.int32), np.zeros(1, np.int32)
+        n_objects, n_objects_matched = np.zeros(1, np.int32), np.full(1, -1, np.int32)
+        rc = self.lib.omds_set_obstacles_from_depth_memory_tracked(self.h, C.byref(spec), C.byref(mem), C.byref(track),
+                                                                   None if objects is None else C.byref(objects), table, addrs, n, on_dev,
+                                                                   L.fptr(qn), L.iptr(n_sph), L.iptr(counts), L.iptr(n_match), L.iptr(n_objects),
+                                                                   L.iptr(n_objects_matched))
+        n_obs = np.zeros(1, np.int32)
+        self.lib.omds_get_obstacles(self.h, None, L.iptr(n_obs))      # also after a failure: the context may have dropped its scene
+        self.n_obs = int(n_obs[0])
+        self.max_obs = max(self.max_obs, self.n_obs, int(counts[0] + counts[1]) if (rc == 0 and qn is not None) else 0)
+        try:
+            self._ck(rc)
+        except L.OmdsError as e:
+            e.counts = tuple(int(v) for v in counts)
+            e.n_occupied = int(counts[0] + counts[1])
+            raise
+        return int(n_sph[0]), tuple(int(v) for v in counts), int(n_match[0]), int(n_objects[0]), int(n_objects_matched[0])
+
     # ---- the depth filter (omds.h: THE DEPTH FILTER) --------------------------------------------------------------------------------
     def set_depth_filter(self, spec):
         """The context's depth filter: an ``OmdsDepthFilterSpec`` (``depth_filter_spec`` builds one; a dict of its arguments is taken
@@ -969,6 +998,54 @@ def depth_scene_memory(images, cams, spec, mem, mem_in=None, filter=None):
     if rc != 0:
         raise L.OmdsError(f"omds_depth_scene_memory failed ({rc}): {lib.omds_last_error(None).decode()}")
     return out[:cells], tuple(int(v) for v in counts)
+
+
+def depth_scene_memory_flow(images, cams, spec, mem, track, objects=None, prev=None, mem_in=None, keep_prev=None, keep_now=None, filter=None,
+                            cap=None):
+    """The definition of ``Engine.set_obstacles_from_depth_memory_tracked`` on the host (omds_depth_scene_memory_flow, no GPU): the depth
+    images of one call, the previous frame ``prev`` = (images, cams) standing for the stored record frame and component table (None: no
+    previous frame) and the stored words ``mem_in`` (None: all empty) -> dict(words [cells] uint32, counts (seen, remembered, cleared,
+    expired, self-forgotten), spheres [n, 4], vel [n, 3], age [n], label [n], object [n], n_matched, n_objects, n_objects_matched).
+    ``keep_prev`` one flag per occupied cell of the previous frame, ``keep_now`` one per candidate cell (the cells with a word that is
+    not 0, in cell order) stand for the self-filter; None: keep all.  More candidates than ``spec.max_spheres`` or ``cap`` raises; the
+    error carries ``counts`` and ``n_occupied``."""
+    lib = L.load()
+    table, addrs, n, _, keep = _depth_table("depth_scene_memory_flow", images, cams)
+    if prev is None:
+        ptable, paddrs, pn, pkeep = None, None, 0, None
+    else:
+        ptable, paddrs, pn, _, pkeep = _depth_table("depth_scene_memory_flow", prev[0], prev[1])
+    cells = max(int(spec.dims[0]), 0) * max(int(spec.dims[1]), 0) * max(int(spec.dims[2]), 0)
+    if cells > 1 << 22:
+        cells = 0                         # more than the library takes: it refuses the call
+    src = None
+    if mem_in is not None:
+        src = np.ascontiguousarray(mem_in, np.uint32).reshape(-1)
+        if src.size != cells:
+            raise ValueError(f"depth_scene_memory_flow: mem_in must hold {cells} words, got {src.size}")
+    kp = None if keep_prev is None else np.ascontiguousarray(np.asarray(keep_prev) != 0, np.uint8)
+    kn = None if keep_now is None else np.ascontiguousarray(np.asarray(keep_now) != 0, np.uint8)
+    cap = int(cap) if cap is not None else (spec.max_spheres if spec.max_spheres >= 1 else 4096)
+    words, counts = np.zeros(max(cells, 1), np.uint32), np.zeros(5, np.int32)
+    out, vel = np.zeros((max(cap, 1), 4), np.float32), np.zeros((max(cap, 1), 3), np.float32)
+    age, label, flag = (np.zeros(max(cap, 1), np.int32) for _ in range(3))
+    cnt, matched, n_obj, n_acc = (np.zeros(1, np.int32) for _ in range(4))
+    filt = _filter_of(filter)
+    rc = lib.omds_depth_scene_memory_flow(C.byref(spec), C.byref(mem), C.byref(track), None if objects is None else C.byref(objects),
+                                          None if filt is None else C.byref(filt), ptable, paddrs, pn,
+                                          None if kp is None or not kp.size else kp.ctypes.data, table, addrs, n,
+                                          None if kn is None or not kn.size else kn.ctypes.data, None if src is None else src.ctypes.data,
+                                          words.ctypes.data, L.iptr(counts), L.fptr(out), L.fptr(vel), L.iptr(age), L.iptr(label), L.iptr(flag),
+                                          cap, L.iptr(cnt), L.iptr(matched), L.iptr(n_obj), L.iptr(n_acc))
+    if rc != 0:
+        e = L.OmdsError(f"omds_depth_scene_memory_flow failed ({rc}): {lib.omds_last_error(None).decode()}")
+        e.counts = tuple(int(v) for v in counts)
+        e.n_occupied = int(cnt[0])
+        raise e
+    k = int(cnt[0])
+    return dict(words=words[:cells], counts=tuple(int(v) for v in counts), spheres=out[:k].copy(), vel=vel[:k].copy(), age=age[:k].copy(),
+                label=label[:k].copy(), object=flag[:k].copy(), n_matched=int(matched[0]), n_objects=int(n_obj[0]),
+                n_objects_matched=int(n_acc[0]))
 
 
 def depth_points(image, cam, filter=None):

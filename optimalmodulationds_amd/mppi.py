@@ -187,33 +187,54 @@ class MPPI:
         (pixels kept, pixels rejected), and the engine's filter is what it was before the call (off, or what
         ``Engine.set_depth_filter`` had installed).  None (the default) leaves the call, and whatever filter the engine has, as it is.  Works
         together with ``dt_frame``, ``objects`` and ``memory``.
-        (``memory`` and ``filter`` are the keywords ``**route`` takes, default None: the named keywords stay those of
-        ``update_obstacles_from_cloud``, which has no cameras to ask.)"""
-        memory, filt = route.pop("memory", None), route.pop("filter", None)
+        ``memory_motion=True`` (with ``memory`` and ``dt_frame``, optionally ``objects``): memory and velocities in one call
+        (Engine.set_obstacles_from_depth_memory_tracked) -- the scene, the counts returned and ``self.obs_age`` are the memory route's,
+        the spheres counted in this frame carry the tracked / objects route's velocities (``self.obs_velocities``,
+        ``self.cloud_matched``, ``self.cloud_objects[_matched]`` as there, ``moving_frame`` honoured), remembered spheres and seen
+        ones that were occluded at the previous memory call stand still.  Without it, ``memory`` together with ``dt_frame`` /
+        ``objects`` is the error it was.
+        (``memory``, ``filter`` and ``memory_motion`` are the keywords ``**route`` takes, default None / None / False: the named keywords
+        stay those of ``update_obstacles_from_cloud``, which has no cameras to ask.)"""
+        memory, filt, motion = route.pop("memory", None), route.pop("filter", None), bool(route.pop("memory_motion", False))
         if route:
             raise TypeError(f"update_obstacles_from_depth: unexpected keyword arguments {sorted(route)}")
+        if motion and (memory is None or dt_frame is None):
+            raise ValueError("update_obstacles_from_depth: memory_motion=True needs both memory= and dt_frame=")
         if filt is None:
             return self._update_obstacles_from_depth(images, cameras, voxel, lo, hi, radius, self_margin, min_points, max_spheres, dt_frame, reach,
-                                                     still, moving_frame, objects, link, min_cells, memory)
+                                                     still, moving_frame, objects, link, min_cells, memory, motion)
         before = self._engine.depth_filter
         self._engine.set_depth_filter(filt)
         try:
             return self._update_obstacles_from_depth(images, cameras, voxel, lo, hi, radius, self_margin, min_points, max_spheres, dt_frame, reach,
-                                                     still, moving_frame, objects, link, min_cells, memory)
+                                                     still, moving_frame, objects, link, min_cells, memory, motion)
         finally:
             self.depth_filter_stats = self._engine.depth_filter_stats()
             self._engine.set_depth_filter(before)
 
     def _update_obstacles_from_depth(self, images, cameras, voxel, lo, hi, radius, self_margin, min_points, max_spheres, dt_frame, reach, still,
-                                     moving_frame, objects, link, min_cells, memory):
+                                     moving_frame, objects, link, min_cells, memory, motion=False):
         """``update_obstacles_from_depth`` behind its route keywords"""
         if memory is None:
             return self._update_obstacles_sensed("update_obstacles_from_depth", lambda e, spec, q, track, obj: (
                 e.set_obstacles_from_depth(images, cameras, spec, q, track, obj)),
                 voxel, lo, hi, radius, self_margin, min_points, max_spheres, dt_frame, reach, still, moving_frame, objects, link, min_cells)
-        if dt_frame is not None or objects:
-            raise ValueError("update_obstacles_from_depth: memory= installs a static scene; not together with dt_frame or objects")
         from .engine import scene_memory_spec
+        if motion:
+            mem = scene_memory_spec(**memory) if isinstance(memory, dict) else memory
+            counts = []
+
+            def install(e, spec, q, track, obj):
+                n, c, matched, n_objects, n_objects_matched = e.set_obstacles_from_depth_memory_tracked(images, cameras, spec, mem, track, obj, q)
+                counts.append(c)
+                return (n, matched) if obj is None else (n, matched, n_objects, n_objects_matched)
+            (n,) = self._update_obstacles_sensed("update_obstacles_from_depth", install, voxel, lo, hi, radius, self_margin, min_points, max_spheres,
+                                                 dt_frame, reach, still, moving_frame, objects, link, min_cells)
+            self.obs_age = torch.as_tensor(self._engine.get_scene_memory())
+            return n, counts[0]
+        if dt_frame is not None or objects:
+            raise ValueError("update_obstacles_from_depth: memory= installs a static scene; not together with dt_frame or objects "
+                             "(memory_motion=True asks for the route that does both)")
         mem = scene_memory_spec(**memory) if isinstance(memory, dict) else memory
         out = self._update_obstacles_sensed("update_obstacles_from_depth", lambda e, spec, q, track, obj: (
             e.set_obstacles_from_depth_memory(images, cameras, spec, mem, q)),
