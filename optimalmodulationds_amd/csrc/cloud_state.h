@@ -1,6 +1,7 @@
 // What a context keeps for the scene from a point cloud or from depth images (scene_cloud.hip): omds_ctx::cloud, and for the obstacle
 // focus (obstacle_focus.hip): omds_ctx::focus.  Included by
-// omds_internal.h behind DevBuf.  Every buffer is allocated at the first call of the route that needs it and grown with the spec.
+// omds_internal.h behind DevBuf.  Every buffer is allocated at the first call of the route that needs it and grown with the spec: a
+// route is a choice of flags over scene_from_cloud's one list of stages, and each flag reserves its own group of buffers.
 #pragma once
 #include <cstring>
 
@@ -110,15 +111,16 @@ struct CloudState {
     DevBuf<float4> objVel;            // [max_spheres] per component: the object's velocity; .w: 0 no object, 1 object, 2 accepted
     std::vector<int32_t> obj_label, obj_flag;   // [n_obs] of the scene in force when the objects call installed it, else empty
     int obj_count = 0;                // its objects
-    // ... scene memory (omds_set_obstacles_from_depth_memory): per cell the word of scene_memory_def.h.  One of the two buffers holds
-    // the stored memory, the other is written; a successful memory call makes its own the stored one
+    // ... scene memory (omds_set_obstacles_from_depth_memory[_tracked]: the memory flag of scene_from_cloud): per cell the word of
+    // scene_memory_def.h.  One of the two buffers holds the stored memory, the other is written; a successful memory call makes its
+    // own the stored one
     Flip<unsigned> mem;               // [cells rounded up to whole compaction blocks] each, allocated when first written
     SceneMemKey memKey;
     DevBuf<int> age;                  // [max_spheres] m' - 1 of every final sphere's cell
     DevBuf<unsigned> memCounts;       // [SCENE_MEM_COUNTS] seen, remembered, cleared, expired, self-forgotten of the call under way
     std::vector<int32_t> mem_age;     // [n_obs] of the scene in force when the memory call installed it (padding: -1), else empty
-    // ... memory and velocities in one call (omds_set_obstacles_from_depth_memory_tracked): the seen sublist T of the final list, on
-    // which the tracked / objects stages run, and their results carried back to the whole list
+    // ... memory and tracked in one call (omds_set_obstacles_from_depth_memory_tracked; memory_velocities): the seen sublist T of the
+    // final list, on which the tracked / objects stages run, and their results carried back to the whole list
     DevBuf<int> seenCell, seenIdx;    // [max_spheres] cell of every sphere of T; its index in the final list
     DevBuf<float4> velAll;            // [max_spheres] velocity of every final sphere behind scene_memory_flow_still; .w as vel's
     DevBuf<int> labelAll, objectAll;  // [max_spheres] ... its label (-1 outside T) and whether it moves with an accepted object

@@ -1,7 +1,8 @@
 // The scene from a depth point cloud or from depth images (omds.h: omds_set_obstacles_from_cloud[_tracked|_objects],
 // omds_set_obstacles_from_depth[_memory[_tracked]], omds_set_depth_filter), as host stages over the launchers of cloud_kernels.h; the state between calls is omds_ctx::cloud
-// (cloud_state.h).  One body, scene_from_cloud, for every route.  A route is a choice of three things (CloudCall): tracked or not,
-// objects or not (objects need tracked), and where the points come from.
+// (cloud_state.h).  One body, scene_from_cloud, for every route: it alone says which stage follows which, one flag per line.  A route is
+// a choice of four things (CloudCall): tracked or not, objects or not (objects need tracked), the scene memory or not (memory needs
+// the images), and where the points come from.
 //   plain   : count per cell -> ordered compaction of the occupied cells -> the robot self-filter as ONE fp32 pass-1 launch over one
 //             state with the candidates as its obstacle rows, and a second compaction of those it keeps -> the final list to the host
 //             (a few thousand x 16 bytes) and in through install_obstacles, the body of omds_set_obstacles (context.hip)
@@ -10,10 +11,12 @@
 //   objects : the tracked one with the components of the final list, into the table that is NOT the stored one, their match against
 //             the stored table and the object velocities over the spheres', between the velocities and the install
 //   depth   : any of the three with the images of up to eight cameras as the point source: no point is ever written
-//   memory  : the plain depth route with one word per cell kept between calls (scene_from_depth_memory, a stage sequence of its own
-//             over the same stages): occluded cells stay, cells a camera looked through leave
-//   memory + tracked / objects : both in one call (scene_from_depth_memory_tracked, a third stage sequence): one counting pass into
-//             records, the memory's words out of their counts, and the tracked / objects stages on the spheres that were counted now
+//   memory  : the plain depth route with one word per cell kept between calls: occluded cells stay, cells a camera looked through
+//             leave.  k_scene_memory, into the buffer that is NOT the stored memory, stands between the counting pass and the
+//             compaction, which is then of the words that are not 0; the cells the self-filter drops leave the memory; the ages
+//   memory + tracked / objects : both in one call (the definition: scene_memory_flow_def.h).  ONE counting pass, into records, and
+//             ONE staging copy serve both halves: the memory's words out of the records' counts, and the tracked / objects stages
+//             on T, the spheres of the final list whose cell was counted now, carried back to the whole list by one launch
 //   filter  : while the context has a depth filter, the counting pass of every depth call above is the filtered one
 //             (depth_filter_def.h): another kernel in the same place, and two counters fetched behind it
 #include "capi_internal.h"
@@ -33,12 +36,12 @@ struct PointSource {
     const float* xyz;
     int64_t n_points;
     int xyz_on_device;
-    const DepthSource* depth;   // != nullptr: the images, and the three fields above are unused
 };
 
-// the five counts a call may return; a route leaves those of the routes above it alone
+// every pointer of the caller's that a call may write: five counts, and counts [5], the cells of a memory call in place of
+// n_occupied.  A route leaves those of the routes above it alone
 struct CloudOuts {
-    int32_t *n_spheres, *n_occupied, *n_matched, *n_objects, *n_objects_matched;
+    int32_t *n_spheres, *n_occupied, *n_matched, *n_objects, *n_objects_matched, *counts;
 };
 
 // One call behind the checks of its specs: the route and the caller's pointers
@@ -46,12 +49,16 @@ struct CloudCall {
     const char* who;
     const omds_cloud_spec* spec;
     CloudGrid g;
-    bool tracked, objects;
+    bool tracked, objects, memory, images;   // images: the points are those of depth, not of src
     CloudTrack tr;      // while tracked
     CloudObjects ob;    // while objects
+    SceneMem sm;        // while memory,
+    SceneMemCams ks;    // ... and what its verdicts need of depth's cameras
     PointSource src;
+    DepthSource depth;
     const float* q_now;
     CloudOuts out;
+    const DepthFilter* filter() const { return images ? depth.filt : nullptr; }
 };
 
 // What the stages of one call hand on
@@ -60,7 +67,7 @@ struct CloudWork {
     DepthTable depth;               // ... the camera table of a depth call
     int occupied = 0;               // cells with min_points points and more
     const float4* d_list = nullptr; // the final list so far: the candidates, behind the self-filter those it keeps
-    const int* d_cell = nullptr;    // tracked: the cell of every sphere of d_list, else nullptr
+    const int* d_cell = nullptr;    // tracked or memory: the cell of every sphere of d_list, else nullptr
     const float4* d_vel = nullptr;  // where install_scene fetches the velocities of d_list from; nullptr: cloud.vel
     int n_list = 0, n_final = 0;    // spheres of d_list; of the installed scene (filled up to n_closest)
     bool have_prev = false, have_table = false;   // there is a stored frame on this grid; and a stored table under this object spec
@@ -68,6 +75,10 @@ struct CloudWork {
     unsigned filt_counts[2] = {0u, 0u};           // pixels the depth filter kept and rejected, fetched behind the counting pass
     std::vector<float> vel4, obj_vel;             // [n_list][4] of cloud.vel, [n_comp][4] of cloud.objVel
     std::vector<int32_t> label, object;           // [n_final]
+    const unsigned* mem_stored = nullptr;         // memory: the stored words while they are of this grid and memory spec, else nullptr:
+                                                  // from empty memory, and whatever is stored stays until the commit
+    unsigned counts[SCENE_MEM_COUNTS] = {0u, 0u, 0u, 0u, 0u};   // ... the cells of this call, the last fetched behind the self-filter
+    std::vector<int32_t> age;                     // ... [n_final], padding spheres: -1
 };
 
 // spec, then track when the route is tracked, then obj when it has objects: each behind its checks, in that order
@@ -94,7 +105,7 @@ int reserve_base(omds_ctx* ctx, const CloudCall& c) {
     CK(s.sums.reserve((size_t)CLOUD_MAX_BLOCKS + 1));
     CK(s.cand.reserve(m));
     CK(s.kept.reserve(m));
-    if (c.src.depth && c.src.depth->filt) CK(s.filtCounts.reserve(2));
+    if (c.filter()) CK(s.filtCounts.reserve(2));
     return OMDS_OK;
 }
 int reserve_tracked(omds_ctx* ctx, const CloudCall& c) {
@@ -124,12 +135,36 @@ int reserve_objects(omds_ctx* ctx, const CloudCall& c) {
     CK(s.table.next().reserve(m));     // written; the stored table is the other one
     return OMDS_OK;
 }
+int reserve_memory(omds_ctx* ctx, const CloudCall& c) {
+    CloudState& s = ctx->cloud;
+    const size_t cells = cloud_padded_cells(c.g), m = (size_t)c.g.max_spheres;
+    if (s.mem.next().count() < cells || s.candCell.count() < m || s.keptCell.count() < m || s.age.count() < m || s.memCounts.count() < SCENE_MEM_COUNTS)
+        CK(hipStreamSynchronize(ctx->stream));
+    CK(s.mem.next().reserve(cells));   // written; the stored memory is the other one
+    CK(s.candCell.reserve(m));
+    CK(s.keptCell.reserve(m));
+    CK(s.age.reserve(m));
+    CK(s.memCounts.reserve(SCENE_MEM_COUNTS));
+    return OMDS_OK;
+}
+int reserve_memory_flow(omds_ctx* ctx, const CloudCall& c) {
+    CloudState& s = ctx->cloud;
+    const size_t m = (size_t)c.g.max_spheres;
+    if (s.seenCell.count() < m || s.seenIdx.count() < m || s.velAll.count() < m || s.labelAll.count() < m || s.objectAll.count() < m)
+        CK(hipStreamSynchronize(ctx->stream));
+    CK(s.seenCell.reserve(m));
+    CK(s.seenIdx.reserve(m));
+    CK(s.velAll.reserve(m));
+    CK(s.labelAll.reserve(m));
+    CK(s.objectAll.reserve(m));
+    return OMDS_OK;
+}
 
 // ---- stage the points: the caller's device memory as it is, host memory through a staging buffer of the context (a host array by
 // one asynchronous copy, host images by one each)
 int stage_points(omds_ctx* ctx, const CloudCall& c, CloudWork& w) {
     CloudState& s = ctx->cloud;
-    if (!c.src.depth) {
+    if (!c.images) {
         const size_t n = (size_t)c.src.n_points;
         w.d_xyz = c.src.xyz;
         if (c.src.xyz_on_device || n == 0) return OMDS_OK;
@@ -141,7 +176,7 @@ int stage_points(omds_ctx* ctx, const CloudCall& c, CloudWork& w) {
         w.d_xyz = s.xyz;
         return OMDS_OK;
     }
-    const DepthSource& src = *c.src.depth;
+    const DepthSource& src = c.depth;
     size_t offset[OMDS_DEPTH_MAX_CAMERAS], bytes[OMDS_DEPTH_MAX_CAMERAS], total = 0;
     for (int i = 0; i < src.n_cams; ++i) {
         bytes[i] = (size_t)depth_extent(src.cam[i]) * (src.cam[i].format == OMDS_DEPTH_U16 ? 2 : 4);
@@ -176,49 +211,56 @@ int compaction_total(omds_ctx* ctx, int n, int* total_out) {
     return OMDS_OK;
 }
 
-// ---- count and compact the cells: the candidates in cell order, their cell indices when tracked, and w.occupied
-template <class T>   // unsigned: counts, uint4: records
-void enqueue_count(omds_ctx* ctx, const CloudCall& c, const CloudWork& w, T* into) {
-    if (!c.src.depth) omds_launch_cloud_count(ctx->stream, w.d_xyz, (long long)c.src.n_points, c.g, into);
-    else if (!c.src.depth->filt) omds_launch_cloud_count(ctx->stream, w.depth, c.src.depth->n_cams, c.g, into);
-    else omds_launch_cloud_count_filtered(ctx->stream, w.depth, c.src.depth->n_cams, c.g, *c.src.depth->filt, into, ctx->cloud.filtCounts);
+// ---- count and compact the cells: the candidates in cell order, their cell indices when tracked or memory, and w.occupied (with
+// memory: seen + remembered).  The depth filter's counters go round the counting pass of a depth call: cleared in front of it, fetched
+// behind the compaction, read after the synchronisation; without a filter the call leaves the stats at 0, 0
+void compact_counted(omds_ctx* ctx, const CloudCall& c, const unsigned* count) {
+    omds_launch_cloud_compact_cells(ctx->stream, count, c.g, ctx->cloud.cand, ctx->cloud.sums);
 }
-// The depth filter's counters around the counting pass of a depth call: cleared in front of it; fetched behind it into w, to be read
-// after the next synchronisation by filter_stats_done.  Without a filter the call leaves the stats at 0, 0
-int filter_stats_begin(omds_ctx* ctx, const CloudCall& c) {
+void compact_counted(omds_ctx* ctx, const CloudCall& c, const uint4* rec) {
+    omds_launch_cloud_compact_cells(ctx->stream, rec, c.g, ctx->cloud.cand, ctx->cloud.candCell, ctx->cloud.sums);
+}
+template <class T>   // unsigned: counts, uint4: records
+int count_into(omds_ctx* ctx, const CloudCall& c, CloudWork& w, T* into) {
     CloudState& s = ctx->cloud;
-    if (!c.src.depth) return OMDS_OK;
-    s.filter_stats[0] = s.filter_stats[1] = 0;
-    if (c.src.depth->filt) CK(hipMemsetAsync(s.filtCounts, 0, 2 * 4, ctx->stream));
+    int rc;
+    CK(hipMemsetAsync(into, 0, cloud_padded_cells(c.g) * sizeof(T), ctx->stream));
+    if (c.memory) CK(hipMemsetAsync(s.memCounts, 0, SCENE_MEM_COUNTS * 4, ctx->stream));
+    if (!c.images) omds_launch_cloud_count(ctx->stream, w.d_xyz, (long long)c.src.n_points, c.g, into);
+    else if (!c.filter()) omds_launch_cloud_count(ctx->stream, w.depth, c.depth.n_cams, c.g, into);
+    else omds_launch_cloud_count_filtered(ctx->stream, w.depth, c.depth.n_cams, c.g, *c.filter(), into, s.filtCounts);
+    if (!c.memory) {
+        compact_counted(ctx, c, into);
+        return OMDS_OK;
+    }
+    w.mem_stored = s.memKey.same(c.g, c.sm) ? s.mem.kept().get() : nullptr;
+    if ((rc = prof_begin(ctx))) return rc;   // omds_prof_enable: a memory route's dominant kernel is k_scene_memory
+    omds_launch_scene_memory(ctx->stream, w.depth, c.ks, c.depth.n_cams, c.g, c.sm, into, w.mem_stored, s.mem.next(), s.memCounts);
+    if ((rc = prof_end(ctx, c.g.n_cells, 0.0, "k_scene_memory"))) return rc;
+    omds_launch_cloud_compact_cells(ctx->stream, s.mem.next().get(), c.g, s.cand, s.candCell, s.sums);
     return OMDS_OK;
 }
-int filter_stats_fetch(omds_ctx* ctx, const CloudCall& c, CloudWork& w) {
-    if (c.src.depth && c.src.depth->filt) CK(hipMemcpyAsync(w.filt_counts, ctx->cloud.filtCounts, 2 * 4, hipMemcpyDeviceToHost, ctx->stream));
+int filter_stats_begin(omds_ctx* ctx, const CloudCall& c) {
+    CloudState& s = ctx->cloud;
+    if (c.images) s.filter_stats[0] = s.filter_stats[1] = 0;
+    if (c.filter()) CK(hipMemsetAsync(s.filtCounts, 0, 2 * 4, ctx->stream));
     return OMDS_OK;
 }
 void filter_stats_done(omds_ctx* ctx, const CloudCall& c, const CloudWork& w) {
-    if (!c.src.depth || !c.src.depth->filt) return;
+    if (!c.filter()) return;
     ctx->cloud.filter_stats[0] = (int64_t)w.filt_counts[0];
     ctx->cloud.filter_stats[1] = (int64_t)w.filt_counts[1];
 }
 int count_cells(omds_ctx* ctx, const CloudCall& c, CloudWork& w) {
     CloudState& s = ctx->cloud;
-    const size_t cells = cloud_padded_cells(c.g);
-    if (int rc = filter_stats_begin(ctx, c)) return rc;
-    if (c.tracked) {
-        uint4* rec = s.rec.next();
-        CK(hipMemsetAsync(rec, 0, cells * 16, ctx->stream));
-        enqueue_count(ctx, c, w, rec);
-        omds_launch_cloud_compact_cells(ctx->stream, rec, c.g, s.cand, s.candCell, s.sums);
-        w.d_cell = s.candCell;
-    } else {
-        CK(hipMemsetAsync(s.count, 0, cells * 4, ctx->stream));
-        enqueue_count(ctx, c, w, s.count.get());
-        omds_launch_cloud_compact_cells(ctx->stream, s.count, c.g, s.cand, s.sums);
-    }
+    int rc;
+    if ((rc = filter_stats_begin(ctx, c))) return rc;
+    if ((rc = c.tracked ? count_into(ctx, c, w, s.rec.next().get()) : count_into(ctx, c, w, s.count.get()))) return rc;
     w.d_list = s.cand;
-    if (int rc = filter_stats_fetch(ctx, c, w)) return rc;
-    if (int rc = compaction_total(ctx, c.g.n_cells, &w.occupied)) return rc;
+    if (c.tracked || c.memory) w.d_cell = s.candCell;
+    if (c.filter()) CK(hipMemcpyAsync(w.filt_counts, s.filtCounts, 2 * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (c.memory) CK(hipMemcpyAsync(w.counts, s.memCounts, 4 * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = compaction_total(ctx, c.g.n_cells, &w.occupied))) return rc;
     filter_stats_done(ctx, c, w);
     return OMDS_OK;
 }
@@ -240,7 +282,13 @@ int self_filter(omds_ctx* ctx, const CloudCall& c, CloudWork& w) {
                                    s.sums);
     w.d_list = s.kept;
     if (w.d_cell) w.d_cell = s.keptCell;
-    return compaction_total(ctx, occupied, &w.n_list);
+    if (int rc = compaction_total(ctx, occupied, &w.n_list)) return rc;
+    if (!c.memory) return OMDS_OK;
+    // ... and the cells of the candidates it drops leave the memory; their number is on the host after the next synchronisation
+    omds_launch_scene_memory_forget(ctx->stream, ctx->d_Dmin, s.candCell, occupied, c.spec->self_margin, s.mem.next(), s.memCounts);
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(w.counts + SCENE_MEM_FORGOTTEN, s.memCounts + SCENE_MEM_FORGOTTEN, 4, hipMemcpyDeviceToHost, ctx->stream));
+    return OMDS_OK;
 }
 
 // ---- sphere velocities: the final list against the stored frame, if there is one on this grid
@@ -275,6 +323,55 @@ int object_velocities(omds_ctx* ctx, const CloudCall& c, CloudWork& w) {
     w.obj_vel.resize((size_t)w.n_comp * 4);
     CK(hipMemcpyAsync(w.obj_vel.data(), s.objVel, (size_t)w.n_comp * 16, hipMemcpyDeviceToHost, ctx->stream));
     CK(hipMemcpyAsync(w.label.data(), s.label, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    return OMDS_OK;
+}
+
+// ---- memory: the calls since the cell of every final sphere was last counted
+int memory_ages(omds_ctx* ctx, const CloudCall&, CloudWork& w) {
+    CloudState& s = ctx->cloud;
+    w.age.assign((size_t)w.n_final, -1);
+    if (w.n_list == 0) return OMDS_OK;
+    omds_launch_scene_memory_age(ctx->stream, s.mem.next(), w.d_cell, w.n_list, s.age);
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(w.age.data(), s.age, (size_t)w.n_list * 4, hipMemcpyDeviceToHost, ctx->stream));
+    return OMDS_OK;
+}
+
+// ---- memory and tracked: the ordered compaction of the final list to T, the spheres whose cell was counted now -> the two stages
+// above on T as their final list, unchanged -> one launch carries T's results back to the whole list under scene_memory_flow_still,
+// which reads the STORED words.  t is the caller's: copies to its vectors are under way until install_scene synchronises
+int memory_velocities(omds_ctx* ctx, const CloudCall& c, CloudWork& w, CloudWork& t) {
+    CloudState& s = ctx->cloud;
+    int rc;
+    w.label.assign((size_t)w.n_final, -1);   // padding spheres: label -1, no object
+    w.object.assign((size_t)w.n_final, 0);
+    w.have_prev = s.frame.same(c.g);
+    if (w.n_list == 0) {
+        w.have_table = c.objects && w.have_prev && s.tab.same(c.ob);
+        return OMDS_OK;
+    }
+    omds_launch_cloud_compact_seen(ctx->stream, s.rec.next(), c.g, w.d_cell, w.n_list, s.seenCell, s.seenIdx, s.sums);
+    if ((rc = compaction_total(ctx, w.n_list, &t.n_list))) return rc;
+    t.d_cell = s.seenCell;
+    t.n_final = t.n_list;
+    if ((rc = sphere_velocities(ctx, c, t))) return rc;
+    if (c.objects && (rc = object_velocities(ctx, c, t))) return rc;
+    const bool flowed = t.have_prev && t.n_list > 0, labelled = c.objects && t.n_list > 0;
+    omds_launch_scene_memory_flow(ctx->stream, s.rec.next(), c.g, w.mem_stored, w.d_cell, w.n_list, s.seenIdx, t.n_list,
+                                  flowed ? s.vel.get() : nullptr, labelled ? s.label.get() : nullptr,
+                                  labelled && t.have_table ? s.object.get() : nullptr, s.velAll, s.labelAll, s.objectAll);
+    CK(hipGetLastError());
+    if (c.objects) {
+        CK(hipMemcpyAsync(w.label.data(), s.labelAll, (size_t)w.n_list * 4, hipMemcpyDeviceToHost, ctx->stream));
+        CK(hipMemcpyAsync(w.object.data(), s.objectAll, (size_t)w.n_list * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (w.have_prev) {
+        w.vel4.resize((size_t)w.n_list * 4);
+        w.d_vel = s.velAll;
+    }
+    w.have_table = t.have_table;   // what commit_objects takes of T: the table is of its components
+    w.n_comp = t.n_comp;
+    w.obj_vel = std::move(t.obj_vel);
     return OMDS_OK;
 }
 
@@ -329,31 +426,53 @@ void commit_objects(omds_ctx* ctx, const CloudCall& c, CloudWork& w) {
     if (c.out.n_objects_matched) *c.out.n_objects_matched = w.have_table ? n_accepted : -1;
 }
 
+// ... and, first of the three, what was written the stored memory, with the ages of the scene in force
+void commit_memory(omds_ctx* ctx, const CloudCall& c, CloudWork& w) {
+    CloudState& s = ctx->cloud;
+    if (c.out.counts) c.out.counts[SCENE_MEM_FORGOTTEN] = (int32_t)w.counts[SCENE_MEM_FORGOTTEN];
+    s.mem_age = std::move(w.age);
+    s.mem.commit();
+    s.memKey.set(c.g, c.sm);
+}
+
+// THE sequence of every route.  A refusal and every failure in front of the commits leave what is stored as it was: each Flip was
+// written in the buffer that is not the stored one.  Without `tracked` no line touches the records, the frame key or the table key
 int scene_from_cloud(omds_ctx* ctx, const CloudCall& c) {
     const std::string me(c.who);
     int rc;
-    REQUIRE(c.src.depth || (c.src.n_points >= 0 && c.src.n_points <= OMDS_CLOUD_MAX_POINTS && (c.src.n_points == 0 || c.src.xyz)),
+    REQUIRE(c.images || (c.src.n_points >= 0 && c.src.n_points <= OMDS_CLOUD_MAX_POINTS && (c.src.n_points == 0 || c.src.xyz)),
             OMDS_ERR_INVALID_ARG, me + ": need 0 <= n_points <= 16 777 216 and a non-null xyz [P,3]");
     if (c.q_now) {
         REQUIRE(ctx->have_mlp, OMDS_ERR_NOT_INITIALISED, me + ": the self-filter needs the distance network (omds_set_mlp)");
         REQUIRE(!ctx->wide.on, OMDS_ERR_UNSUPPORTED, me + ": no self-filter on networks wider than 256 (no obstacle tables)");
     }
     CK(hipSetDevice(ctx->dev));
-    CloudWork w;
+    CloudWork w, t;   // t: with memory and tracked, the seen sublist as the final list of the velocity stages
     if ((rc = reserve_base(ctx, c))) return rc;
     if (c.tracked && (rc = reserve_tracked(ctx, c))) return rc;
     if (c.objects && (rc = reserve_objects(ctx, c))) return rc;
+    if (c.memory && (rc = reserve_memory(ctx, c))) return rc;
+    if (c.memory && c.tracked && (rc = reserve_memory_flow(ctx, c))) return rc;
     if ((rc = stage_points(ctx, c, w))) return rc;
     if ((rc = count_cells(ctx, c, w))) return rc;
     if (c.out.n_occupied) *c.out.n_occupied = w.occupied;
+    if (c.out.counts)
+        for (int k = 0; k < SCENE_MEM_COUNTS; ++k) c.out.counts[k] = (int32_t)w.counts[k];
     REQUIRE(w.occupied <= c.g.max_spheres, OMDS_ERR_INVALID_ARG,
-            me + ": more occupied cells than max_spheres (n_occupied_out holds their number); the scene is unchanged");
+            me + (!c.memory   ? ": more occupied cells than max_spheres (n_occupied_out holds their number); the scene is unchanged"
+                  : !c.tracked ? ": more seen and remembered cells than max_spheres (counts_out holds their numbers); the scene and the memory are "
+                                 "unchanged"
+                               : ": more seen and remembered cells than max_spheres (counts_out holds their numbers); the scene, the memory, the "
+                                 "record frame and the component table are unchanged"));
     w.n_list = w.occupied;
     if (c.q_now && w.occupied > 0 && (rc = self_filter(ctx, c, w))) return rc;
     w.n_final = std::max(w.n_list, ctx->cfg.n_closest);
-    if (c.tracked && (rc = sphere_velocities(ctx, c, w))) return rc;
-    if (c.objects && (rc = object_velocities(ctx, c, w))) return rc;
+    if (c.memory && (rc = memory_ages(ctx, c, w))) return rc;
+    if (c.tracked && !c.memory && (rc = sphere_velocities(ctx, c, w))) return rc;
+    if (c.objects && !c.memory && (rc = object_velocities(ctx, c, w))) return rc;
+    if (c.tracked && c.memory && (rc = memory_velocities(ctx, c, w, t))) return rc;
     if ((rc = install_scene(ctx, c, w))) return rc;
+    if (c.memory) commit_memory(ctx, c, w);
     if (c.tracked) commit_frame(ctx, c, w);
     if (c.objects) commit_objects(ctx, c, w);
     return OMDS_OK;
@@ -361,7 +480,7 @@ int scene_from_cloud(omds_ctx* ctx, const CloudCall& c) {
 
 // a cloud entry point behind resolve_call: the caller's array as the point source
 int scene_from_points(omds_ctx* ctx, CloudCall& c, const float* xyz, int64_t n_points, int xyz_on_device, const float* q_now, const CloudOuts& out) {
-    c.src = PointSource{xyz, n_points, xyz_on_device, nullptr};
+    c.src = PointSource{xyz, n_points, xyz_on_device};
     c.q_now = q_now;
     c.out = out;
     return scene_from_cloud(ctx, c);
@@ -381,190 +500,23 @@ int resolve_depth_source(omds_ctx* ctx, const char* me, const omds_depth_camera*
     return OMDS_OK;
 }
 
-// ---- the depth route with the scene memory (omds_set_obstacles_from_depth_memory): a stage sequence of its own beside
-// scene_from_cloud, over the same stages -- count -> k_scene_memory into the buffer that is NOT the stored memory -> compaction of the
-// words that are not 0, with their cells -> the refusal check -> self-filter, and the cells it drops leave the memory -> ages ->
-// install -> commit, behind everything that can fail
-int reserve_memory(omds_ctx* ctx, const CloudCall& c) {
-    CloudState& s = ctx->cloud;
-    const size_t cells = cloud_padded_cells(c.g), m = (size_t)c.g.max_spheres;
-    if (s.mem.next().count() < cells || s.candCell.count() < m || s.keptCell.count() < m || s.age.count() < m || s.memCounts.count() < SCENE_MEM_COUNTS)
-        CK(hipStreamSynchronize(ctx->stream));
-    CK(s.mem.next().reserve(cells));   // written; the stored memory is the other one
-    CK(s.candCell.reserve(m));
-    CK(s.keptCell.reserve(m));
-    CK(s.age.reserve(m));
-    CK(s.memCounts.reserve(SCENE_MEM_COUNTS));
-    return OMDS_OK;
-}
-
-int scene_from_depth_memory(omds_ctx* ctx, const CloudCall& c, const SceneMem& sm, const SceneMemCams& ks, int32_t* counts_out) {
-    const std::string me(c.who);
-    CloudState& s = ctx->cloud;
-    int rc;
-    if (c.q_now) {
-        REQUIRE(ctx->have_mlp, OMDS_ERR_NOT_INITIALISED, me + ": the self-filter needs the distance network (omds_set_mlp)");
-        REQUIRE(!ctx->wide.on, OMDS_ERR_UNSUPPORTED, me + ": no self-filter on networks wider than 256 (no obstacle tables)");
-    }
-    CK(hipSetDevice(ctx->dev));
-    CloudWork w;
-    if ((rc = reserve_base(ctx, c))) return rc;
-    if ((rc = reserve_memory(ctx, c))) return rc;
-    if ((rc = stage_points(ctx, c, w))) return rc;
-    const bool have = s.memKey.same(c.g, sm);   // else: from empty memory, whatever is stored stays until the commit
-    unsigned* next = s.mem.next();
-    CK(hipMemsetAsync(s.count, 0, cloud_padded_cells(c.g) * 4, ctx->stream));
-    CK(hipMemsetAsync(s.memCounts, 0, SCENE_MEM_COUNTS * 4, ctx->stream));
-    if ((rc = filter_stats_begin(ctx, c))) return rc;
-    enqueue_count(ctx, c, w, s.count.get());
-    if ((rc = filter_stats_fetch(ctx, c, w))) return rc;
-    if ((rc = prof_begin(ctx))) return rc;   // omds_prof_enable: this route's dominant kernel is k_scene_memory
-    omds_launch_scene_memory(ctx->stream, w.depth, ks, c.src.depth->n_cams, c.g, sm, s.count, have ? s.mem.kept().get() : nullptr, next, s.memCounts);
-    if ((rc = prof_end(ctx, c.g.n_cells, 0.0, "k_scene_memory"))) return rc;
-    omds_launch_cloud_compact_cells(ctx->stream, next, c.g, s.cand, s.candCell, s.sums);
-    unsigned counts[SCENE_MEM_COUNTS] = {0u, 0u, 0u, 0u, 0u};
-    CK(hipMemcpyAsync(counts, s.memCounts, 4 * 4, hipMemcpyDeviceToHost, ctx->stream));
-    w.d_list = s.cand;
-    w.d_cell = s.candCell;
-    if ((rc = compaction_total(ctx, c.g.n_cells, &w.occupied))) return rc;   // = seen + remembered
-    filter_stats_done(ctx, c, w);
-    if (counts_out)
-        for (int k = 0; k < SCENE_MEM_COUNTS; ++k) counts_out[k] = (int32_t)counts[k];
-    REQUIRE(w.occupied <= c.g.max_spheres, OMDS_ERR_INVALID_ARG,
-            me + ": more seen and remembered cells than max_spheres (counts_out holds their numbers); the scene and the memory are unchanged");
-    w.n_list = w.occupied;
-    if (c.q_now && w.occupied > 0) {
-        if ((rc = self_filter(ctx, c, w))) return rc;
-        omds_launch_scene_memory_forget(ctx->stream, ctx->d_Dmin, s.candCell, w.occupied, c.spec->self_margin, next, s.memCounts);
-        CK(hipGetLastError());
-        CK(hipMemcpyAsync(counts + SCENE_MEM_FORGOTTEN, s.memCounts + SCENE_MEM_FORGOTTEN, 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    w.n_final = std::max(w.n_list, ctx->cfg.n_closest);
-    std::vector<int32_t> age((size_t)w.n_final, -1);   // padding spheres: -1
-    if (w.n_list > 0) {
-        omds_launch_scene_memory_age(ctx->stream, next, w.d_cell, w.n_list, s.age);
-        CK(hipGetLastError());
-        CK(hipMemcpyAsync(age.data(), s.age, (size_t)w.n_list * 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    if ((rc = install_scene(ctx, c, w))) return rc;   // synchronises
-    if (counts_out) counts_out[SCENE_MEM_FORGOTTEN] = (int32_t)counts[SCENE_MEM_FORGOTTEN];
-    s.mem_age = std::move(age);
-    s.mem.commit();
-    s.memKey.set(c.g, sm);
-    return OMDS_OK;
-}
-
-// ---- memory and velocities in one call (omds_set_obstacles_from_depth_memory_tracked; the definition: scene_memory_flow_def.h): a
-// third stage sequence over the same stages.  ONE counting pass, into the record buffer that is not the stored frame, and ONE staging
-// copy serve both halves: k_scene_memory reads its counts out of the records -> compaction of the words that are not 0 -> the refusal
-// check -> self-filter, forget, ages as on the memory route -> the ordered compaction of the final list to T, the spheres whose cell
-// was counted now -> the tracked / objects stages on T, unchanged -> one launch carries T's results back to the whole list under
-// scene_memory_flow_still -> install -> commit of the memory, the frame and the table, behind everything that can fail
-int reserve_memory_flow(omds_ctx* ctx, const CloudCall& c) {
-    CloudState& s = ctx->cloud;
-    const size_t m = (size_t)c.g.max_spheres;
-    if (s.seenCell.count() < m || s.seenIdx.count() < m || s.velAll.count() < m || s.labelAll.count() < m || s.objectAll.count() < m)
-        CK(hipStreamSynchronize(ctx->stream));
-    CK(s.seenCell.reserve(m));
-    CK(s.seenIdx.reserve(m));
-    CK(s.velAll.reserve(m));
-    CK(s.labelAll.reserve(m));
-    CK(s.objectAll.reserve(m));
-    return OMDS_OK;
-}
-
-int scene_from_depth_memory_tracked(omds_ctx* ctx, const CloudCall& c, const SceneMem& sm, const SceneMemCams& ks, int32_t* counts_out) {
-    const std::string me(c.who);
-    CloudState& s = ctx->cloud;
-    int rc;
-    if (c.q_now) {
-        REQUIRE(ctx->have_mlp, OMDS_ERR_NOT_INITIALISED, me + ": the self-filter needs the distance network (omds_set_mlp)");
-        REQUIRE(!ctx->wide.on, OMDS_ERR_UNSUPPORTED, me + ": no self-filter on networks wider than 256 (no obstacle tables)");
-    }
-    CK(hipSetDevice(ctx->dev));
-    CloudWork w;
-    if ((rc = reserve_base(ctx, c))) return rc;
-    if ((rc = reserve_tracked(ctx, c))) return rc;
-    if (c.objects && (rc = reserve_objects(ctx, c))) return rc;
-    if ((rc = reserve_memory(ctx, c))) return rc;
-    if ((rc = reserve_memory_flow(ctx, c))) return rc;
-    if ((rc = stage_points(ctx, c, w))) return rc;
-    const bool have = s.memKey.same(c.g, sm);   // else: from empty memory, whatever is stored stays until the commit
-    const unsigned* stored = have ? s.mem.kept().get() : nullptr;
-    unsigned* next = s.mem.next();
-    uint4* rec = s.rec.next();
-    CK(hipMemsetAsync(rec, 0, cloud_padded_cells(c.g) * 16, ctx->stream));
-    CK(hipMemsetAsync(s.memCounts, 0, SCENE_MEM_COUNTS * 4, ctx->stream));
-    if ((rc = filter_stats_begin(ctx, c))) return rc;
-    enqueue_count(ctx, c, w, rec);
-    if ((rc = filter_stats_fetch(ctx, c, w))) return rc;
-    if ((rc = prof_begin(ctx))) return rc;
-    omds_launch_scene_memory(ctx->stream, w.depth, ks, c.src.depth->n_cams, c.g, sm, rec, stored, next, s.memCounts);
-    if ((rc = prof_end(ctx, c.g.n_cells, 0.0, "k_scene_memory"))) return rc;
-    omds_launch_cloud_compact_cells(ctx->stream, next, c.g, s.cand, s.candCell, s.sums);
-    unsigned counts[SCENE_MEM_COUNTS] = {0u, 0u, 0u, 0u, 0u};
-    CK(hipMemcpyAsync(counts, s.memCounts, 4 * 4, hipMemcpyDeviceToHost, ctx->stream));
-    w.d_list = s.cand;
-    w.d_cell = s.candCell;
-    if ((rc = compaction_total(ctx, c.g.n_cells, &w.occupied))) return rc;   // = seen + remembered
-    filter_stats_done(ctx, c, w);
-    if (counts_out)
-        for (int k = 0; k < SCENE_MEM_COUNTS; ++k) counts_out[k] = (int32_t)counts[k];
-    REQUIRE(w.occupied <= c.g.max_spheres, OMDS_ERR_INVALID_ARG,
-            me + ": more seen and remembered cells than max_spheres (counts_out holds their numbers); the scene, the memory, the record frame and "
-                 "the component table are unchanged");
-    w.n_list = w.occupied;
-    if (c.q_now && w.occupied > 0) {
-        if ((rc = self_filter(ctx, c, w))) return rc;
-        omds_launch_scene_memory_forget(ctx->stream, ctx->d_Dmin, s.candCell, w.occupied, c.spec->self_margin, next, s.memCounts);
-        CK(hipGetLastError());
-        CK(hipMemcpyAsync(counts + SCENE_MEM_FORGOTTEN, s.memCounts + SCENE_MEM_FORGOTTEN, 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    w.n_final = std::max(w.n_list, ctx->cfg.n_closest);
-    std::vector<int32_t> age((size_t)w.n_final, -1);   // padding spheres: -1
-    w.label.assign((size_t)w.n_final, -1);             // ... label -1, no object
-    w.object.assign((size_t)w.n_final, 0);
-    w.have_prev = s.frame.same(c.g);
-    CloudWork t;                                       // the stages of the tracked / objects routes see T as their final list
-    if (w.n_list > 0) {
-        omds_launch_scene_memory_age(ctx->stream, next, w.d_cell, w.n_list, s.age);
-        CK(hipGetLastError());
-        CK(hipMemcpyAsync(age.data(), s.age, (size_t)w.n_list * 4, hipMemcpyDeviceToHost, ctx->stream));
-        omds_launch_cloud_compact_seen(ctx->stream, rec, c.g, w.d_cell, w.n_list, s.seenCell, s.seenIdx, s.sums);
-        if ((rc = compaction_total(ctx, w.n_list, &t.n_list))) return rc;
-        t.d_cell = s.seenCell;
-        t.n_final = t.n_list;
-        if ((rc = sphere_velocities(ctx, c, t))) return rc;
-        if (c.objects && (rc = object_velocities(ctx, c, t))) return rc;
-        const bool flowed = t.have_prev && t.n_list > 0, labelled = c.objects && t.n_list > 0;
-        omds_launch_scene_memory_flow(ctx->stream, rec, c.g, stored, w.d_cell, w.n_list, s.seenIdx, t.n_list, flowed ? s.vel.get() : nullptr,
-                                      labelled ? s.label.get() : nullptr, labelled && t.have_table ? s.object.get() : nullptr, s.velAll,
-                                      s.labelAll, s.objectAll);
-        CK(hipGetLastError());
-        if (c.objects) {
-            CK(hipMemcpyAsync(w.label.data(), s.labelAll, (size_t)w.n_list * 4, hipMemcpyDeviceToHost, ctx->stream));
-            CK(hipMemcpyAsync(w.object.data(), s.objectAll, (size_t)w.n_list * 4, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        if (w.have_prev) {
-            w.vel4.resize((size_t)w.n_list * 4);
-            w.d_vel = s.velAll;
-        }
-    } else if (c.objects) {
-        t.have_table = w.have_prev && s.tab.same(c.ob);
-    }
-    if ((rc = install_scene(ctx, c, w))) return rc;   // synchronises
-    if (counts_out) counts_out[SCENE_MEM_FORGOTTEN] = (int32_t)counts[SCENE_MEM_FORGOTTEN];
-    s.mem_age = std::move(age);
-    s.mem.commit();
-    s.memKey.set(c.g, sm);
-    commit_frame(ctx, c, w);
-    if (c.objects) {
-        w.have_table = t.have_table;
-        w.n_comp = t.n_comp;
-        w.obj_vel = std::move(t.obj_vel);
-        commit_objects(ctx, c, w);
-    }
-    return OMDS_OK;
+// a depth entry point behind resolve_call: the images, with the context's filter, as the point source; with `memory` the route with
+// the scene memory, mem_spec behind its checks in front of the cameras'
+int scene_from_images(omds_ctx* ctx, CloudCall& c, bool memory, const omds_scene_memory_spec* mem_spec, const omds_depth_camera* cams,
+                      const void* const* images, int32_t n_cams, int images_on_device, const float* q_now, const CloudOuts& out) {
+    if (memory)
+        if (int rc = scene_memory_resolve(mem_spec, c.g, &c.sm, &ctx->err)) return rc;
+    c.images = true;
+    c.memory = memory;
+    c.depth.images = images;
+    c.depth.n_cams = n_cams;
+    c.depth.on_device = images_on_device;
+    c.depth.filt = ctx->cloud.filter_on ? &ctx->cloud.filter : nullptr;
+    if (int rc = resolve_depth_source(ctx, c.who, cams, c.depth)) return rc;
+    for (int i = 0; memory && i < n_cams; ++i) c.ks.k[i] = scene_memory_camera(cams[i], c.depth.cam[i]);
+    c.q_now = q_now;
+    c.out = out;
+    return scene_from_cloud(ctx, c);
 }
 
 }  // namespace
@@ -654,19 +606,10 @@ int omds_set_obstacles_from_depth(omds_ctx* ctx, const omds_cloud_spec* spec, co
                                   int images_on_device, const float* q_now, int32_t* n_spheres_out, int32_t* n_occupied_out,
                                   int32_t* n_matched_out, int32_t* n_objects_out, int32_t* n_objects_matched_out) {
     if (!ctx) return OMDS_ERR_INVALID_ARG;
-    const char* me = "omds_set_obstacles_from_depth";
     CloudCall c;
-    if (int rc = resolve_call(ctx, me, spec, track != nullptr, track, obj != nullptr, obj, &c)) return rc;
-    DepthSource depth;
-    depth.images = images;
-    depth.n_cams = n_cams;
-    depth.on_device = images_on_device;
-    depth.filt = ctx->cloud.filter_on ? &ctx->cloud.filter : nullptr;
-    if (int rc = resolve_depth_source(ctx, me, cams, depth)) return rc;
-    c.src = PointSource{nullptr, 0, 0, &depth};
-    c.q_now = q_now;
-    c.out = CloudOuts{n_spheres_out, n_occupied_out, n_matched_out, n_objects_out, n_objects_matched_out};
-    return scene_from_cloud(ctx, c);
+    if (int rc = resolve_call(ctx, "omds_set_obstacles_from_depth", spec, track != nullptr, track, obj != nullptr, obj, &c)) return rc;
+    return scene_from_images(ctx, c, false, nullptr, cams, images, n_cams, images_on_device, q_now,
+                             {n_spheres_out, n_occupied_out, n_matched_out, n_objects_out, n_objects_matched_out, nullptr});
 }
 
 int omds_depth_scene_memory(const omds_cloud_spec* spec, const omds_scene_memory_spec* mem_spec, const omds_depth_camera* cams,
@@ -684,24 +627,10 @@ int omds_set_obstacles_from_depth_memory(omds_ctx* ctx, const omds_cloud_spec* s
                                          const omds_depth_camera* cams, const void* const* images, int32_t n_cams, int images_on_device,
                                          const float* q_now, int32_t* n_spheres_out, int32_t counts_out[5]) {
     if (!ctx) return OMDS_ERR_INVALID_ARG;
-    const char* me = "omds_set_obstacles_from_depth_memory";
     CloudCall c;
-    SceneMem sm;
-    if (int rc = resolve_call(ctx, me, spec, false, nullptr, false, nullptr, &c)) return rc;
-    if (int rc = scene_memory_resolve(mem_spec, c.g, &sm, &ctx->err)) return rc;
-    DepthSource depth;
-    depth.images = images;
-    depth.n_cams = n_cams;
-    depth.on_device = images_on_device;
-    depth.filt = ctx->cloud.filter_on ? &ctx->cloud.filter : nullptr;
-    if (int rc = resolve_depth_source(ctx, me, cams, depth)) return rc;
-    SceneMemCams ks;
-    std::memset(static_cast<void*>(&ks), 0, sizeof(ks));
-    for (int i = 0; i < n_cams; ++i) ks.k[i] = scene_memory_camera(cams[i], depth.cam[i]);
-    c.src = PointSource{nullptr, 0, 0, &depth};
-    c.q_now = q_now;
-    c.out = CloudOuts{n_spheres_out, nullptr, nullptr, nullptr, nullptr};
-    return scene_from_depth_memory(ctx, c, sm, ks, counts_out);
+    if (int rc = resolve_call(ctx, "omds_set_obstacles_from_depth_memory", spec, false, nullptr, false, nullptr, &c)) return rc;
+    return scene_from_images(ctx, c, true, mem_spec, cams, images, n_cams, images_on_device, q_now,
+                             {n_spheres_out, nullptr, nullptr, nullptr, nullptr, counts_out});
 }
 
 int omds_depth_scene_memory_flow(const omds_cloud_spec* spec, const omds_scene_memory_spec* mem_spec, const omds_cloud_track_spec* track,
@@ -722,24 +651,10 @@ int omds_set_obstacles_from_depth_memory_tracked(omds_ctx* ctx, const omds_cloud
                                                  const float* q_now, int32_t* n_spheres_out, int32_t counts_out[5], int32_t* n_matched_out,
                                                  int32_t* n_objects_out, int32_t* n_objects_matched_out) {
     if (!ctx) return OMDS_ERR_INVALID_ARG;
-    const char* me = "omds_set_obstacles_from_depth_memory_tracked";
     CloudCall c;
-    SceneMem sm;
-    if (int rc = resolve_call(ctx, me, spec, true, track, obj != nullptr, obj, &c)) return rc;
-    if (int rc = scene_memory_resolve(mem_spec, c.g, &sm, &ctx->err)) return rc;
-    DepthSource depth;
-    depth.images = images;
-    depth.n_cams = n_cams;
-    depth.on_device = images_on_device;
-    depth.filt = ctx->cloud.filter_on ? &ctx->cloud.filter : nullptr;
-    if (int rc = resolve_depth_source(ctx, me, cams, depth)) return rc;
-    SceneMemCams ks;
-    std::memset(static_cast<void*>(&ks), 0, sizeof(ks));
-    for (int i = 0; i < n_cams; ++i) ks.k[i] = scene_memory_camera(cams[i], depth.cam[i]);
-    c.src = PointSource{nullptr, 0, 0, &depth};
-    c.q_now = q_now;
-    c.out = CloudOuts{n_spheres_out, nullptr, n_matched_out, n_objects_out, n_objects_matched_out};
-    return scene_from_depth_memory_tracked(ctx, c, sm, ks, counts_out);
+    if (int rc = resolve_call(ctx, "omds_set_obstacles_from_depth_memory_tracked", spec, true, track, obj != nullptr, obj, &c)) return rc;
+    return scene_from_images(ctx, c, true, mem_spec, cams, images, n_cams, images_on_device, q_now,
+                             {n_spheres_out, nullptr, n_matched_out, n_objects_out, n_objects_matched_out, counts_out});
 }
 
 int omds_scene_memory_reset(omds_ctx* ctx) {

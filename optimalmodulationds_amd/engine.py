@@ -124,33 +124,41 @@ class Engine:
             keep = L.f32(points).reshape(-1, 3)
             addr, P, on_dev = L.fptr(keep) if keep.shape[0] else None, keep.shape[0], 0
         qn = None if q is None else L.f32(q).reshape(self.n)
-        n_sph, n_occ, n_match = np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32)
-        n_objects, n_objects_matched = np.zeros(1, np.int32), np.zeros(1, np.int32)
+        o, p = _scene_outs()
         if obj is not None:
             rc = self.lib.omds_set_obstacles_from_cloud_objects(self.h, C.byref(spec), C.byref(track), C.byref(obj), addr, P, on_dev, L.fptr(qn),
-                                                                L.iptr(n_sph), L.iptr(n_occ), L.iptr(n_match), L.iptr(n_objects),
-                                                                L.iptr(n_objects_matched))
+                                                                *p[:5])
         elif track is None:
-            rc = self.lib.omds_set_obstacles_from_cloud(self.h, C.byref(spec), addr, P, on_dev, L.fptr(qn), L.iptr(n_sph), L.iptr(n_occ))
+            rc = self.lib.omds_set_obstacles_from_cloud(self.h, C.byref(spec), addr, P, on_dev, L.fptr(qn), *p[:2])
         else:
-            rc = self.lib.omds_set_obstacles_from_cloud_tracked(self.h, C.byref(spec), C.byref(track), addr, P, on_dev, L.fptr(qn),
-                                                                L.iptr(n_sph), L.iptr(n_occ), L.iptr(n_match))
-        return self._scene_call_done(rc, qn, obj, n_sph, n_occ, n_match, n_objects, n_objects_matched)
+            rc = self.lib.omds_set_obstacles_from_cloud_tracked(self.h, C.byref(spec), C.byref(track), addr, P, on_dev, L.fptr(qn), *p[:3])
+        return self._scene_call_done(rc, qn, o, False, 5 if obj is not None else 3)
 
-    def _scene_call_done(self, rc, qn, obj, n_sph, n_occ, n_match, n_objects, n_objects_matched):
-        """what follows every cloud / depth scene call: the wrapper's view of the scene, the error with its count, the counts"""
+    def _scene_call_done(self, rc, qn, o, memory, n_out):
+        """what follows every cloud / depth scene call (``o``: its counts, ``_scene_outs``): the wrapper's view of the scene, the error with
+        its counts, and the first ``n_out`` of (n_spheres, n_occupied -- ``memory``: the five counts --, n_matched, n_objects,
+        n_objects_matched)"""
+        counts = tuple(int(v) for v in o[5:])
+        candidates = counts[0] + counts[1] if memory else int(o[1])
         n_obs = np.zeros(1, np.int32)
         self.lib.omds_get_obstacles(self.h, None, L.iptr(n_obs))      # also after a failure: the context may have dropped its scene
         self.n_obs = int(n_obs[0])
-        self.max_obs = max(self.max_obs, self.n_obs, int(n_occ[0]) if (rc == 0 and qn is not None) else 0)      # the candidates were obstacle rows
+        self.max_obs = max(self.max_obs, self.n_obs, candidates if (rc == 0 and qn is not None) else 0)      # the candidates were obstacle rows
         try:
             self._ck(rc)
         except L.OmdsError as e:
-            e.n_occupied = int(n_occ[0])
+            e.n_occupied = candidates
+            if memory:
+                e.counts = counts
             raise
-        if obj is not None:
-            return int(n_sph[0]), int(n_occ[0]), int(n_match[0]), int(n_objects[0]), int(n_objects_matched[0])
-        return int(n_sph[0]), int(n_occ[0]), int(n_match[0])
+        return (int(o[0]), counts if memory else int(o[1]), int(o[2]), int(o[3]), int(o[4]))[:n_out]
+
+    def _depth_call(self, who, images, cams, q):
+        """what opens every depth scene call -> (the arguments from the camera table to q, q as the library takes it, the counts and their
+        addresses as ``_scene_outs`` makes them, what has to stay alive over the call)"""
+        table, addrs, n, on_dev, keep = _depth_table(who, images, cams, self.device)
+        qn = None if q is None else L.f32(q).reshape(self.n)
+        return (table, addrs, n, on_dev, L.fptr(qn)), qn, *_scene_outs(), keep
 
     def set_obstacles_from_depth(self, images, cams, spec, q=None, track=None, obj=None):
         """The scene straight from depth images (omds.h: THE SCENE STRAIGHT FROM DEPTH IMAGES): every effect is that of
@@ -160,16 +168,10 @@ class Engine:
         tensors on the engine's device (``uint16``; ``int16``, reinterpreted; ``float32``), which are read in place -- rows need not
         be contiguous as long as the last dimension has stride 1 (the camera's ``pitch`` is then taken from the row stride).  ``cams``:
         ``OmdsDepthCamera`` s (``depth_camera`` builds one); shape and format must be the image's."""
-        table, addrs, n, on_dev, keep = _depth_table("set_obstacles_from_depth", images, cams, self.device)
-        qn = None if q is None else L.f32(q).reshape(self.n)
-        n_sph, n_occ, n_match = np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32)
-        n_objects, n_objects_matched = np.zeros(1, np.int32), np.zeros(1, np.int32)
+        args, qn, o, p, keep = self._depth_call("set_obstacles_from_depth", images, cams, q)
         rc = self.lib.omds_set_obstacles_from_depth(self.h, C.byref(spec), None if track is None else C.byref(track),
-                                                    None if obj is None else C.byref(obj), table, addrs, n, on_dev,
-                                                    L.fptr(qn), L.iptr(n_sph), L.iptr(n_occ), L.iptr(n_match), L.iptr(n_objects),
-                                                    L.iptr(n_objects_matched))
-        out = self._scene_call_done(rc, qn, obj, n_sph, n_occ, n_match, n_objects, n_objects_matched)
-        return out[:2] if track is None else out
+                                                    None if obj is None else C.byref(obj), *args, *p[:5])
+        return self._scene_call_done(rc, qn, o, False, 2 if track is None else 5 if obj is not None else 3)
 
     # ---- the scene memory of the depth route (omds.h: THE SCENE MEMORY OF THE DEPTH ROUTE) ---------------------------------------------
     def set_obstacles_from_depth_memory(self, images, cams, spec, mem, q=None):
@@ -179,22 +181,9 @@ class Engine:
         (seen, remembered, cleared, expired, self-forgotten) as a tuple.  ``images``, ``cams``, ``spec``, ``q`` as there; ``mem``: an
         ``OmdsSceneMemorySpec`` (``scene_memory_spec`` builds one).  Installs a static scene.  More seen and remembered cells than
         ``spec.max_spheres`` raises with scene and memory unchanged; the error carries ``counts`` and ``n_occupied``."""
-        table, addrs, n, on_dev, keep = _depth_table("set_obstacles_from_depth_memory", images, cams, self.device)
-        qn = None if q is None else L.f32(q).reshape(self.n)
-        n_sph, counts = np.zeros(1, np.int32), np.zeros(5, np.int32)
-        rc = self.lib.omds_set_obstacles_from_depth_memory(self.h, C.byref(spec), C.byref(mem), table, addrs, n, on_dev, L.fptr(qn),
-                                                           L.iptr(n_sph), L.iptr(counts))
-        n_obs = np.zeros(1, np.int32)
-        self.lib.omds_get_obstacles(self.h, None, L.iptr(n_obs))      # also after a failure: the context may have dropped its scene
-        self.n_obs = int(n_obs[0])
-        self.max_obs = max(self.max_obs, self.n_obs, int(counts[0] + counts[1]) if (rc == 0 and qn is not None) else 0)
-        try:
-            self._ck(rc)
-        except L.OmdsError as e:
-            e.counts = tuple(int(v) for v in counts)
-            e.n_occupied = int(counts[0] + counts[1])
-            raise
-        return int(n_sph[0]), tuple(int(v) for v in counts)
+        args, qn, o, p, keep = self._depth_call("set_obstacles_from_depth_memory", images, cams, q)
+        rc = self.lib.omds_set_obstacles_from_depth_memory(self.h, C.byref(spec), C.byref(mem), *args, p[0], p[5])
+        return self._scene_call_done(rc, qn, o, True, 2)
 
     def set_obstacles_from_depth_memory_tracked(self, images, cams, spec, mem, track, objects=None, q=None):
         """``set_obstacles_from_depth_memory`` and ``set_obstacles_from_depth(track=[, obj=])`` in one call (omds.h: MEMORY AND
@@ -205,25 +194,10 @@ class Engine:
         n_objects_matched); n_matched is -1 without a stored frame on this grid, n_objects_matched -1 without a stored table, and
         n_objects 0 without ``objects``.  Raises like ``set_obstacles_from_depth_memory``, with scene, memory, frame and table
         unchanged."""
-        table, addrs, n, on_dev, keep = _depth_table("set_obstacles_from_depth_memory_tracked", images, cams, self.device)
-        qn = None if q is None else L.f32(q).reshape(self.n)
-        n_sph, counts, n_match = np.zeros(1, np.int32), np.zeros(5, np.int32), np.zeros(1, np.int32)
-        n_objects, n_objects_matched = np.zeros(1, np.int32), np.full(1, -1, np.int32)
+        args, qn, o, p, keep = self._depth_call("set_obstacles_from_depth_memory_tracked", images, cams, q)
         rc = self.lib.omds_set_obstacles_from_depth_memory_tracked(self.h, C.byref(spec), C.byref(mem), C.byref(track),
-                                                                   None if objects is None else C.byref(objects), table, addrs, n, on_dev,
-                                                                   L.fptr(qn), L.iptr(n_sph), L.iptr(counts), L.iptr(n_match), L.iptr(n_objects),
-                                                                   L.iptr(n_objects_matched))
-        n_obs = np.zeros(1, np.int32)
-        self.lib.omds_get_obstacles(self.h, None, L.iptr(n_obs))      # also after a failure: the context may have dropped its scene
-        self.n_obs = int(n_obs[0])
-        self.max_obs = max(self.max_obs, self.n_obs, int(counts[0] + counts[1]) if (rc == 0 and qn is not None) else 0)
-        try:
-            self._ck(rc)
-        except L.OmdsError as e:
-            e.counts = tuple(int(v) for v in counts)
-            e.n_occupied = int(counts[0] + counts[1])
-            raise
-        return int(n_sph[0]), tuple(int(v) for v in counts), int(n_match[0]), int(n_objects[0]), int(n_objects_matched[0])
+                                                                   None if objects is None else C.byref(objects), *args, p[0], p[5], *p[2:5])
+        return self._scene_call_done(rc, qn, o, True, 5)
 
     # ---- the depth filter (omds.h: THE DEPTH FILTER) --------------------------------------------------------------------------------
     def set_depth_filter(self, spec):
@@ -888,6 +862,14 @@ def depth_camera(width, height, fx, fy, cx, cy, pose=None, format=L.DEPTH_U16, d
 
 
 _DEPTH_NUMPY = {L.DEPTH_U16: (np.uint16,), L.DEPTH_F32: (np.float32,)}
+
+
+def _scene_outs():
+    """the counts a cloud / depth scene call writes, zeroed, and the address of each: n_spheres, n_occupied, n_matched, n_objects,
+    n_objects_matched (-1 until written) and the five counts of the memory routes"""
+    o = np.zeros(10, np.int32)
+    o[4] = -1
+    return o, [o.ctypes.data + 4 * i for i in range(6)]
 
 
 def _depth_image(im, cam, device=None):

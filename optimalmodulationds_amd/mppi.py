@@ -220,27 +220,23 @@ class MPPI:
                 e.set_obstacles_from_depth(images, cameras, spec, q, track, obj)),
                 voxel, lo, hi, radius, self_margin, min_points, max_spheres, dt_frame, reach, still, moving_frame, objects, link, min_cells)
         from .engine import scene_memory_spec
-        if motion:
-            mem = scene_memory_spec(**memory) if isinstance(memory, dict) else memory
-            counts = []
-
-            def install(e, spec, q, track, obj):
-                n, c, matched, n_objects, n_objects_matched = e.set_obstacles_from_depth_memory_tracked(images, cameras, spec, mem, track, obj, q)
-                counts.append(c)
-                return (n, matched) if obj is None else (n, matched, n_objects, n_objects_matched)
-            (n,) = self._update_obstacles_sensed("update_obstacles_from_depth", install, voxel, lo, hi, radius, self_margin, min_points, max_spheres,
-                                                 dt_frame, reach, still, moving_frame, objects, link, min_cells)
-            self.obs_age = torch.as_tensor(self._engine.get_scene_memory())
-            return n, counts[0]
-        if dt_frame is not None or objects:
+        if not motion and (dt_frame is not None or objects):
             raise ValueError("update_obstacles_from_depth: memory= installs a static scene; not together with dt_frame or objects "
                              "(memory_motion=True asks for the route that does both)")
         mem = scene_memory_spec(**memory) if isinstance(memory, dict) else memory
-        out = self._update_obstacles_sensed("update_obstacles_from_depth", lambda e, spec, q, track, obj: (
-            e.set_obstacles_from_depth_memory(images, cameras, spec, mem, q)),
-            voxel, lo, hi, radius, self_margin, min_points, max_spheres, None, reach, still, moving_frame, False, link, min_cells)
+        counts = []
+
+        def install(e, spec, q, track, obj):      # the counts go round the tracked route's unpacking: (n, [matched, [objects, objects matched]])
+            if motion:
+                n, c, *rest = e.set_obstacles_from_depth_memory_tracked(images, cameras, spec, mem, track, obj, q)
+            else:
+                n, c, *rest = e.set_obstacles_from_depth_memory(images, cameras, spec, mem, q)
+            counts.append(c)
+            return (n, *rest) if obj is not None else (n, *rest[:1])
+        (n,) = self._update_obstacles_sensed("update_obstacles_from_depth", install, voxel, lo, hi, radius, self_margin, min_points, max_spheres,
+                                             dt_frame, reach, still, moving_frame, objects, link, min_cells)
         self.obs_age = torch.as_tensor(self._engine.get_scene_memory())
-        return out
+        return n, counts[0]
 
     def _update_obstacles_sensed(self, who, install, voxel, lo, hi, radius, self_margin, min_points, max_spheres, dt_frame, reach, still,
                                  moving_frame, objects, link, min_cells):
