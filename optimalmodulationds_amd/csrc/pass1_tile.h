@@ -80,11 +80,12 @@ __device__ __forceinline__ void pass1_tile(const MlpDev& m, float* smem, const f
     constexpr bool LIST = tile_lists(MODE), EMIT = tile_emits_masks(MODE), DERIV = tile_emits_deriv(MODE), EMITY = tile_emits_y(MODE);
     static_assert(!DERIV || MT == 16, "the derivative hand-over is written for the 16-row tiles of k_exact");
     using G = Geo<MT, MR, NR>;
-    float* Hs = smem;                                           // [MT][LDH]   (the blocks' sizes for the launchers: screen_plan_def.h)
-    float* rowRad = smem + MT * LDH;                            // [MT] obstacle radius of each row
-    int* rowIdx = reinterpret_cast<int*>(rowRad + MT);          // [MT] LIST: pair index of each row
-    uint32_t* maskS = reinterpret_cast<uint32_t*>(rowIdx + MT); // [MT][nhid][8] LIST: ReLU masks of the tile's rows
     const int nhid = m.nhh + 1;
+    constexpr Pass1Lds lds(MT, 0);                              // the blocks and what each launch reserves of them: pass1_plan_def.h (nhid moves the end only)
+    float* Hs = smem + lds.Hs;                                  // [MT][LDH]
+    float* rowRad = smem + lds.rowRad;                          // [MT] obstacle radius of each row
+    int* rowIdx = reinterpret_cast<int*>(smem + lds.rowIdx);    // [MT] LIST: pair index of each row
+    uint32_t* maskS = reinterpret_cast<uint32_t*>(smem + lds.maskS);   // [MT][nhid][8] EMIT: ReLU masks of the tile's rows
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / G::WN, wn = wave % G::WN;
     // ListDeriv: the activation derivatives of the tile's rows at `level`, row-wise (a wave per row, one float4 per lane: 1 KB

@@ -147,10 +147,11 @@ __device__ __forceinline__ void pass1_tile_dyn(const MlpDev& m, float* smem, con
                                                const TileBlock blk = TileBlock{}) {
     using G = Geo<MT, MR, 1>;
     static_assert(G::NW == 8 && G::WM == 1, "eight waves, wave w owns the units 32 w .. 32 w + 31 of every level");
-    float* Hs = smem;                                              // [MT][LDH]
-    float* rowRad = smem + MT * LDH;                               // [MT]
-    uint32_t* aliveS = reinterpret_cast<uint32_t*>(rowRad + MT);   // [8] which of a wave's 32 units fired in this tile at the current level
-    uint32_t* idsS = aliveS + 8;                                   // [OMDS_IDS] position -> unit * 1024 of the current level
+    constexpr Pass1DynLds lds(MT);                                 // pass1_plan_def.h
+    float* Hs = smem + lds.Hs;                                     // [MT][LDH]
+    float* rowRad = smem + lds.rowRad;                             // [MT]
+    uint32_t* aliveS = reinterpret_cast<uint32_t*>(smem + lds.aliveS);   // [8] which of a wave's 32 units fired in this tile at the current level
+    uint32_t* idsS = reinterpret_cast<uint32_t*>(smem + lds.idsS);       // [OMDS_IDS] position -> unit * 1024 of the current level
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wv = __builtin_amdgcn_readfirstlane(wave);
     const int col = wv * 32 + (lane & 31);                         // the unit this thread's accumulators hold, at every level
@@ -184,8 +185,8 @@ __device__ __forceinline__ void pass1_tile_dyn(const MlpDev& m, float* smem, con
         for (int it = 0; it < IT; it += 2) frow[it * G::NW * LDH] = fv[it / 2];
         // what the last layer needs of the block: rowRad[0 .. 3] the obstacles' radii, behind them the rollout of every slot and the
         // obstacle of every slot (-1: padding, not stored)
-        int* slotT = reinterpret_cast<int*>(rowRad + 4);
-        int* slotO = slotT + MT / 4;
+        int* slotT = reinterpret_cast<int*>(smem + lds.slotT);
+        int* slotO = reinterpret_cast<int*>(smem + lds.slotO);
         if (tid < 4) {
             const int o = blk.op[tid];
             rowRad[tid] = radius[o];
@@ -372,10 +373,9 @@ __device__ __forceinline__ void pass1_tile_dyn(const MlpDev& m, float* smem, con
         for (int reg = 0; reg < 4; ++reg) y[reg] = link_row_distance(acc[reg], bj, pad, ign, m.out_div, rad[reg]);
         if constexpr (BLK) {
             if (j == 0) {
-                const int* slotT = reinterpret_cast<const int*>(rowRad + 4);
-                const int t = slotT[r4 >> 2];
+                const int t = reinterpret_cast<const int*>(smem + lds.slotT)[r4 >> 2];
                 if (t >= 0) {
-                    const int4 oo = *reinterpret_cast<const int4*>(slotT + MT / 4);
+                    const int4 oo = *reinterpret_cast<const int4*>(smem + lds.slotO);
                     float* drow = Dmin + (size_t)t * O;
                     if (oo.x >= 0) drow[oo.x] = y[0];
                     if (oo.y >= 0) drow[oo.y] = y[1];

@@ -75,7 +75,7 @@ static bool acquire_deriv_buffer(omds_ctx* ctx) {
 // EVERY pair, what pass 2's forward would compute for it (pass-2 distance, arg-min link, ReLU masks: the two forwards are
 // bit-identical), and k_tail_sel selects from the row of Dmin and runs the backward alone.  The chain of a step loses three
 // dependent GEMMs: integrator tick (N = 1) 0.66 -> 0.56 ms per 10-step propagate, planner defaults (N = 40) 1.02 -> 0.95.
-// Up to 24 576 pairs only: the masks cost the pass-1 epilogue 32 ballots + 64 single-lane LDS stores per wave and layer, which
+// Up to 24 576 pairs only (PASS1_EMIT_MAX_PAIRS, pass1_plan_def.h; pass1_emit_ok): the masks cost the pass-1 epilogue 32 ballots + 64 single-lane LDS stores per wave and layer, which
 // a throughput-bound launch cannot hide (k_pass1 +18 % at 1024 x 294, the step 29.5 -> 33.3 ms: EXPERIMENTS.md B.5).
 bool fused_step_available(const omds_ctx* ctx) {
     return !(ctx->cfg.flags & OMDS_FLAG_UNFUSED_STEP) && omds_tail_supported(ctx->cfg.n_dof, ctx->cfg.n_closest) && ctx->seds_G == 0 && !ctx->wide.on;
@@ -88,7 +88,7 @@ StepRoute choose_route(omds_ctx* ctx, bool screen_requested) {
     if (screen_requested) return (relu || acquire_deriv_buffer(ctx)) ? StepRoute::ScreenList : StepRoute::ScreenMatrix;
     if (small_step_wanted(ctx)) return StepRoute::SmallScene;
     if (relu && !(ctx->cfg.flags & OMDS_FLAG_TAIL_FORWARD) && ctx->mlp.skip_mask == 0 && ctx->mlp.nhh >= 1 && omds_tail_sel_supported(n, k) &&
-        (long long)ctx->cfg.n_traj * ctx->n_obs <= 24576 && acquire_emit_buffers(ctx))
+        pass1_emit_ok((long long)ctx->cfg.n_traj * ctx->n_obs) && acquire_emit_buffers(ctx))
         return StepRoute::Emit;
     return StepRoute::Dense;
 }

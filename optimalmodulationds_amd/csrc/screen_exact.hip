@@ -1,11 +1,11 @@
 // The fp32 re-evaluation of the screened step (gfx950): the pass-1 tile code (pass1_tile, bit-identical arithmetic per row) on listed
 // rows -- k_exact on the candidates of every horizon step, the audit kernels on the audit sample of a whole propagate.  Grids, rounds
-// and LDS sizes are screen_plan_def.h's.
+// are screen_plan_def.h's, the LDS sizes pass1_plan_def.h's.
 #include <algorithm>
 
 #include "pass1_tile.h"
 
-static_assert(SC_LDH == LDH && SC_WIDTH == OMDS_WIDTH, "screen_plan_def.h sizes the tiles of pass1_tile");
+static_assert(P1_LDH == LDH && SC_WIDTH == OMDS_WIDTH, "pass1_plan_def.h sizes the tiles of pass1_tile, screen_plan_def.h the bias table");
 
 // k_exact: fp32 pass-1 tiles over the listed rows, 16 rows per tile (v_mfma_f32_16x16x4 fed in the k order of the 32-row
 // kernels: the same bits per row, mfma_gemm.h), up to three workgroups resident per CU (78 registers).  A tile is a chain of

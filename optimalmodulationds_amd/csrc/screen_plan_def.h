@@ -1,5 +1,5 @@
 // The screened step's LAUNCH PLAN, stated once: the geometry of k_screen, which pairs each of its workgroups owns, how many result
-// tiles and how much LDS a launch gets, the rounds of the audit kernels, and the LDS blocks of the k_exact / k_audit launches.
+// tiles and how much LDS a launch gets, and the rounds of the audit kernels (the LDS of the k_exact / k_audit launches: pass1_plan_def.h).
 // screen_kernel.hip and screen_exact.hip launch by it and their kernels call the same rules; the stand-alone host build of
 // tests/screen_plan_host.cpp prints it for tests/test_screen_plan_cpu.py.  Plain C++, integer arithmetic only, no HIP header (a
 // constexpr function is host-and-device under hipcc).
@@ -7,7 +7,9 @@
 #include <algorithm>
 #include <cstddef>
 
-constexpr int SC_WIDTH = 256, SC_LDH = 260;   // OMDS_WIDTH, LDH (omds_internal.h, mfma_gemm.h): asserted by the files that launch by this
+#include "pass1_plan_def.h"
+
+constexpr int SC_WIDTH = 256;   // OMDS_WIDTH (omds_internal.h): asserted by the files that launch by this
 
 // ---- k_screen's geometry ----------------------------------------------------------------------------------------------------------
 // SC_WAVES waves per workgroup, each owning one block of 32 pairs; every A fragment (1 KiB of weights) a wave reads from the ring
@@ -106,12 +108,4 @@ constexpr AuditRounds audit_rounds(int n, int G) {
 }
 
 // ---- the LDS of the k_exact and k_audit launches ----------------------------------------------------------------------------------
-// The blocks pass1_tile carves for a tile of MT rows (pass1_tile.h), in bytes: the activation tile Hs [MT][LDH], rowRad [MT], rowIdx
-// [MT] and -- the modes that keep the ReLU masks -- maskS [MT][nhid][8].
-constexpr size_t pass1_lds_Hs(int MT) { return (size_t)MT * SC_LDH * 4; }
-constexpr size_t pass1_lds_rowRad(int MT) { return (size_t)MT * 4; }
-constexpr size_t pass1_lds_rowIdx(int MT) { return (size_t)MT * 4; }
-constexpr size_t pass1_lds_maskS(int MT, int nhid) { return (size_t)MT * nhid * 8 * 4; }
-// k_exact: 16-row tiles, every mode sized for the masks; k_audit: its 64-row tiles (the 32-row ones fit inside), no masks
-constexpr size_t exact_lds_bytes(int nhh) { return pass1_lds_Hs(16) + pass1_lds_rowRad(16) + pass1_lds_rowIdx(16) + pass1_lds_maskS(16, nhh + 1); }
-constexpr size_t audit_lds_bytes() { return pass1_lds_Hs(64) + pass1_lds_rowRad(64) + pass1_lds_rowIdx(64); }
+// exact_lds_bytes(nhh) and audit_lds_bytes() are sums of the blocks pass1_tile carves: pass1_plan_def.h, beside the carve.

@@ -27,8 +27,8 @@
 #include "trig_device.h"
 #include "step_epilogue.h"
 
-constexpr int SS_RK = 4;      // backward rows per workgroup (R * k)
-constexpr int SS_NT = 512;
+static_assert(P1_LDH == LDH, "pass1_plan_def.h sizes pass1_tile's block");
+constexpr int SS_NT = 512;    // (SS_RK, the backward rows per workgroup: pass1_plan_def.h)
 
 struct SmallArgs {
     MlpDev m;
@@ -64,10 +64,11 @@ __global__ __launch_bounds__(SS_NT, TR == 16 ? 4 : 2) void k_step_small(SmallArg
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const MlpDev& m = a.m;
     const int nhid = m.nhh + 1;
-    // pass1_tile's block: Hs [TR][LDH], rowRad [TR], rowIdx [TR], maskS [TR][nhid][8]
-    float* Hs = smem;
-    uint32_t* maskS = reinterpret_cast<uint32_t*>(smem + TR * LDH + 2 * TR);
-    float* D1 = reinterpret_cast<float*>(maskS + TR * nhid * 8);     // [32] pass-1 value of each tile row
+    // pass1_tile's block (Hs, rowRad, rowIdx and the masks it leaves in maskS), this kernel's arrays behind it (small_lds_bytes, pass1_plan_def.h)
+    const Pass1Lds lds(TR, nhid);
+    float* Hs = smem + lds.Hs;
+    uint32_t* maskS = reinterpret_cast<uint32_t*>(smem + lds.maskS);
+    float* D1 = smem + lds.end;                                      // [32] pass-1 value of each tile row
     float* Dr = D1 + 32;                                             // [32] pass-2 distance
     int* Amin = reinterpret_cast<int*>(Dr + 32);                     // [32] arg-min link
     int* selRow = Amin + 32;                                         // [SS_RK] tile row of each backward row (-1: none)
@@ -222,29 +223,9 @@ __global__ __launch_bounds__(SS_NT, TR == 16 ? 4 : 2) void k_step_small(SmallArg
     step_write_next_rows<ND, SS_NT>(a.Fq, feat, m.d, N, t_base, R);
 }
 
-static size_t small_lds_bytes(int nhid, int TR) {
-    // the last term: gemm4's A-operand reads span 32 tile rows (lanes 16-31 are never selected, but they read): a 16-row tile
-    // buffer is followed by at least another 16 rows' worth of allocation
-    return ((size_t)TR * LDH + 2 * TR + (size_t)TR * nhid * 8) * 4 + (32 * 3 + SS_RK * 3) * 4 +
-           (SS_RK + SS_RK * 12 + 16 * 33 + SS_RK * 3 * OMDS_MAX_DOF + 4) * 4 + 16 + (TR == 16 ? (size_t)16 * LDH * 4 : 0);
-}
-
-// rollouts per workgroup for (O, k) on a tile of `rows` rows, 0 = the scene does not qualify
-static int small_rollouts(const MlpDev& m, int n_dof, int O, int k, int rows) {
-    if (m.act != OMDS_ACT_RELU || m.skip_mask || (n_dof != 7 && n_dof != 2)) return 0;
-    if (O < 1 || O > rows || k < 1 || k > SS_RK || k > O) return 0;
-    return std::max(1, std::min(rows / O, SS_RK / k));
-}
-int omds_step_small_rollouts(const MlpDev& m, int n_dof, int O, int k) { return small_rollouts(m, n_dof, O, k, 32); }
-// Tile height: 16 rows when that costs no rollouts per workgroup (the cap of four backward rows binds, not the tile: half the
-// forward's MFMA chain for the same work); else 32.  Halving the rollouts per workgroup to get two 16-row workgroups resident
-// per CU (one's backward and modulation under the other's forward) was measured on planar 7-DoF 1024 x 32: 17.0 M against
-// 18.9 M rollout-steps/s -- twice the workgroups stream the backward's weights twice.
-static int small_tile_rows(const MlpDev& m, int n_dof, int O, int k) {
-    const int r16 = small_rollouts(m, n_dof, O, k, 16), r32 = small_rollouts(m, n_dof, O, k, 32);
-    if (r16 <= 0) return 32;
-    return r16 == r32 ? 16 : 32;
-}
+// The LDS size, the rollouts per workgroup and the tile height: small_lds_bytes, small_rollouts, small_tile_rows (pass1_plan_def.h)
+static bool small_plain_relu(const MlpDev& m) { return m.act == OMDS_ACT_RELU && !m.skip_mask; }
+int omds_step_small_rollouts(const MlpDev& m, int n_dof, int O, int k) { return small_rollouts(small_plain_relu(m), n_dof, O, k, 32); }
 
 template <int ND, int TR, bool FRAME = false>
 static void launch_small_r(hipStream_t s, const SmallArgs& a) {
@@ -256,8 +237,8 @@ static void launch_small_r(hipStream_t s, const SmallArgs& a) {
 }
 template <int ND>
 static void launch_small_t(hipStream_t s, SmallArgs& a, int k) {
-    const int TR = small_tile_rows(a.m, ND, a.O, k);
-    a.R = small_rollouts(a.m, ND, a.O, k, TR);
+    const int TR = small_tile_rows(small_plain_relu(a.m), ND, a.O, k);
+    a.R = small_rollouts(small_plain_relu(a.m), ND, a.O, k, TR);
     if (a.R <= 0) return;
     if (a.o_gradx == nullptr && a.st.frame) {   // the step form in the moving frame
         if (TR == 16) launch_small_r<ND, 16, true>(s, a);

@@ -133,7 +133,8 @@ struct TailLdsPlan {
     // per thread and layer for the masks, the size pass 2's own launch reserves (omds_launch_pass2), where the carve steps over 2
     // (layers rounded up to even): 2048 nhid - 1024 (nhid + nhid % 2) >= 0 bytes more for every nhid >= 1.  The size of a launch is
     // part of how many workgroups a CU holds, so it stays the number it was.
-    static constexpr size_t bytes(int nhid, bool with_sel) {
-        return (size_t)TailLdsPlan(nhid, with_sel).end * 4 + ((size_t)nhid * TAIL_NT * 4 - (size_t)((nhid + 1) / 2 * 2) * TAIL_NT * 2);
-    }
+    static constexpr size_t mask_overcount(int nhid) { return (size_t)nhid * TAIL_NT * 4 - (size_t)((nhid + 1) / 2 * 2) * TAIL_NT * 2; }
+    static constexpr size_t bytes(int nhid, bool with_sel) { return (size_t)TailLdsPlan(nhid, with_sel).end * 4 + mask_overcount(nhid); }
+    // pass 2's own launch (k_pass2, mlp_kernels.hip): the first six blocks, with the same over-count
+    static constexpr size_t pass2_bytes(int nhid) { return (size_t)TailLdsPlan(nhid, false).gx * 4 + mask_overcount(nhid); }
 };
