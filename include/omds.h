@@ -262,8 +262,9 @@ OMDS_API int omds_get_obstacles(omds_ctx* ctx, float* xyzr, int32_t* n_obs_out);
  * WHAT IT MEASURES: the NORMAL flow of a surface -- the centroid of a cell now minus the pooled centroid of the nearest previously
  * occupied cell(s).  Motion along a surface's own tangent is invisible to it (a sliding plane occupies the same cells); an object
  * thicker than its displacement along the motion is under-estimated (its interior cells find themselves at d2 = 0).  The normal
- * component is the part omds_approach_rate and the moving frame consume, because the distance gradient points along it.  No temporal
- * smoothing, no segmentation or clustering, no tangential flow: out of scope.
+ * component is the part omds_approach_rate and the moving frame consume, because the distance gradient points along it.  No
+ * segmentation or clustering, no tangential flow, no motion model beyond constant velocity, no smoothing of positions: out of scope
+ * (smoothing of the velocities over frames: THE VELOCITY FILTER below).
  *   omds_point_cloud_flow : host only (no context, no GPU), the DEFINITION.  All fp32, every operation named one rounding, every
  *       conversion to float round-to-nearest; all sums are integers, so the result is a function of the two SETS of points.
  *       Per frame, for every point omds_point_cloud_spheres keeps: u_c = (p_c - origin_c) * inv, f_c = floorf(u_c), r_c = u_c - f_c
@@ -314,7 +315,8 @@ OMDS_API int omds_get_obstacle_motion(omds_ctx* ctx, float* vel, int32_t* have_o
  * Additive: no other entry point changes its launches or its bits.
  * WHAT IT MEASURES: the rigid TRANSLATION of an object, from the displacement of the centroid of its visible points.  Rotation shows up
  * as the centroid's motion alone; two objects that touch (within link cells) are one object; an object entering the view, or being
- * uncovered, shifts its visible centroid and so reports a velocity it does not have; no temporal smoothing.
+ * uncovered, shifts its visible centroid and so reports a velocity it does not have (THE VELOCITY FILTER below damps it); no motion
+ * model beyond constant velocity, no smoothing of positions.
  *   omds_point_cloud_object_flow : host only (no context, no GPU), the DEFINITION.  Records, occupancy and spheres are those of
  *       omds_point_cloud_flow.  keep_prev / keep_now: one uint8 per OCCUPIED cell of that frame in ascending cell order, NULL = keep all;
  *       they stand for the self-filter.  The output lists the occupied NOW cells with keep_now != 0 in cell order; *count_out = occupied
@@ -369,8 +371,8 @@ OMDS_API int omds_get_cloud_objects(omds_ctx* ctx, int32_t* label, int32_t* obje
  * The depth call deprojects inside the counting pass, without ever writing a point: everything after that pass is integer sums and
  * ordered compactions, a function of the SET of points.  Additive: no other entry point changes its launches or its bits.
  * OUT OF SCOPE: lens distortion (the image is taken as rectified), range-type depth (z is depth along the optical axis),
- * registration of the cameras against each other (the poses are taken as given), temporal smoothing.  (Flying pixels and speckle:
- * THE DEPTH FILTER below.)
+ * registration of the cameras against each other (the poses are taken as given), a motion model beyond constant velocity; smoothing
+ * of positions.  (Flying pixels and speckle: THE DEPTH FILTER below; velocities smoothed over frames: THE VELOCITY FILTER below.)
  *   omds_depth_points : host only (no context, no GPU), the DEFINITION.  All fp32, every operation named one rounding.  Once per
  *       camera: ifx = 1.0f / fx, ify = 1.0f / fy.  The visited pixels are columns u and rows v in 0, step, 2 step, ... (step < 1 is 1),
  *       in row-major order, ceil(H / step) * ceil(W / step) of them; the raw value is d = image[v * pitch + u] (pitch in ELEMENTS, 0 is
@@ -530,7 +532,7 @@ OMDS_API int omds_get_depth_filter_stats(omds_ctx* ctx, int64_t out[2] /* kept, 
  * or its bits.
  * OUT OF SCOPE: velocities for remembered cells (dead reckoning behind an occluder: a remembered sphere stands still), objects formed
  * over remembered cells, the centroid shift of an uncovered surface on the objects route, memory on the plain cloud route (no cameras),
- * temporal smoothing.
+ * a motion model beyond constant velocity; smoothing of positions.
  *   omds_depth_scene_memory_flow : host only (no context, no GPU), the DEFINITION, a composition of the definitions above.  The
  *       previous frame is given as its cameras and images (cams_prev == NULL: none); it stands for the stored record frame AND, with obj,
  *       the stored component table (the components of its kept occupied cells).  filt (NULL: off) filters both frames.
@@ -580,6 +582,73 @@ OMDS_API int omds_set_obstacles_from_depth_memory_tracked(omds_ctx* ctx, const o
                                                           int images_on_device, const float* q_now, int32_t* n_spheres_out,
                                                           int32_t counts_out[5], int32_t* n_matched_out, int32_t* n_objects_out,
                                                           int32_t* n_objects_matched_out);
+/* THE VELOCITY FILTER: SENSED SPHERE VELOCITIES SMOOTHED OVER FRAMES (new work).  Every velocity route above estimates from two frames
+ * only, and omds_set_obstacle_motion extrapolates that one estimate over the whole horizon: at H = 32 a one-frame error is multiplied
+ * by the horizon before pass 1 sees the predicted spheres.  The filter keeps one smoothed velocity per grid cell between calls and
+ * blends every new estimate against its predecessor, on the device.  Additive: with no filter set every entry point keeps its launches
+ * and its bits.
+ * OUT OF SCOPE: a motion model beyond constant velocity; smoothing of positions (the spheres stay the cell centres of this frame);
+ * compensation of the state when the grid frame moves.
+ *   THE STATE: per grid cell four int32 (q_x, q_y, q_z, hits).  hits == 0: no history.  hits >= 1: q is the smoothed velocity in units
+ *       of 2^-16 m/s and hits the frames behind it, saturating at 255.
+ *   omds_velocity_filter_step : host only (no context, no GPU), the DEFINITION.  All fp32, every operation named one rounding, every
+ *       conversion to float round-to-nearest; all sums are integers.  INPUTS: cell [n] the cells of the final list, ascending, without
+ *       padding; raw [n,3] its velocities as the route computes them (the still rule applied); live [n] (NULL: all 1): 1 where the
+ *       route's matched flag is set (a non-empty window, or the sphere moves with an accepted object, and the memory route did not force
+ *       it still); group [n] (NULL: none): the sphere's label where it moves with an accepted object, else -1.  state_in [cells,4] (NULL:
+ *       all empty) -> state_out [cells,4] (may be the same array).
+ *       1. PREDECESSOR of sphere i: over the cells j = cell_i + k, |k_c| <= reach (the track spec's) on all axes, inside the grid, whose
+ *       state_in has hits >= 1: d2 = k . k, m = min d2, T = {j : d2 = m};  S_c = sum_T q_jc (int64), t = |T|, h = min_T hits_j.  An empty
+ *       window: h = 0.   2. GROUPS: per group, over its live spheres with h_i > 0:  G_c = sum S_ic,  Gt = sum t_i (int64),  Gh = min h_i
+ *       (0 when there are none).  A grouped sphere uses (G, Gt, Gh) in place of its own (S, t, h): every sphere of an object blends
+ *       against one predecessor and, the raw velocity of an object being one, receives one velocity -- the objects route stays rigid.
+ *       3. BLEND, for a live sphere.  h == 0: v = raw, hits' = 1.  Else  p_c = ((float)S_c / (float)t) * 1.52587890625e-5f;
+ *       a = fmaxf(alpha, 1.0f / (float)(h + 1)) with alpha_object for a grouped sphere;  d_c = raw_c - p_c;  j2 = fmaf(d_z, d_z,
+ *       fmaf(d_y, d_y, d_x * d_x)).  max_jump > 0 && j2 > max_jump * max_jump: v = raw, hits' = 1, a RESTART.  Else a >= 1.0f: v = raw;
+ *       else v_c = fmaf(a, d_c, p_c); in both hits' = min(h + 1, 255).  The 1 / (h + 1) term makes the first frames a running mean, so
+ *       that the filter converges at the rate of the data and not of alpha.   4. state_out[cell_i] = ((int)rintf(fminf(fmaxf(v_c,
+ *       -1024.f), 1024.f) * 65536.0f), hits'); vel_out [n,3] is v behind the still rule of omds_point_cloud_flow (the stored q is not
+ *       zeroed by it).  A sphere with live == 0 outputs +0 and stores nothing; every cell not written is hits = 0 in state_out.
+ *       stats_out [3] (NULL = skip): the live spheres that had a predecessor (h > 0, restarts included), the restarts, the groups with
+ *       history.  OMDS_ERR_INVALID_ARG before anything is written: a bad cloud, track or filter spec, n < 0, cell not strictly ascending
+ *       or outside the grid, a group outside -1 .. cells - 1, a null state_out, null cell, raw or vel_out with n > 0.
+ *   omds_set_velocity_filter : the filter is CONTEXT STATE, off at creation; spec == NULL turns it off and empties the history.  A
+ *       refused spec leaves the stored filter as it was.  omds_set_obstacles_from_cloud_tracked / _objects, omds_set_obstacles_from_depth
+ *       with track (and obj) and omds_set_obstacles_from_depth_memory_tracked consult it.  THE CONTRACT with a filter set -- a filtered
+ *       call is the unfiltered call, bit for bit, in everything except the velocities it installs: the scene and its padding, labels and
+ *       flags, the stored records, table and memory, every out value (*n_matched_out keeps its meaning).  The installed velocities and
+ *       the stored state are omds_velocity_filter_step on the stored state and on that call's final list (cells, raw velocities, matched
+ *       flags, and label where the object flag is set).  Padding spheres stay at 0.  A scene whose OUTPUT velocities are all exactly 0
+ *       keeps the cleared horizon and the static propagate.  The state is keyed like the stored record frame (origin, voxel, dims
+ *       bitwise, resolved min_points) plus the resolved filter spec, bitwise; it is shared by all those routes, which may alternate.
+ *       THE HISTORY IS EMPTY after a call on another key, after a call without a previous frame (*n_matched_out == -1), after
+ *       omds_cloud_track_reset and after clearing the filter.  The state is written in the buffer that is not the stored one and
+ *       committed with the frame, behind everything that can fail: a refused call leaves it as it was.  On the device, between the
+ *       velocity launches (which run unchanged) and the install: k_vel_pred, one wave per sphere -- the own cell first (d2 = 0 is the
+ *       unique minimum), else the lanes stride the clipped window, a wave minimum and shuffle-added integer sums; k_vel_group (only with
+ *       an object spec), one lane per sphere, equal groups combined inside the wave and the workgroup before the 64-bit integer atomics at the list index
+ *       of the label's cell; k_vel_blend, one lane per sphere: the fp32 lines, the velocity with the matched flag kept, one 16-byte
+ *       state store.  In front of them one launch empties the cells the written buffer last held.
+ *   omds_get_velocity_filter : *spec_out = the spec in force as it was given, *on_out = 1 while one is set (either may be NULL).
+ *   omds_get_velocity_filter_frame : raw [n_obs,3] and live [n_obs] of the scene in force: the unfiltered velocities and matched flags of
+ *       the call that installed it (padding: 0), stats [3] its counts as stats_out above (each may be NULL); host state, no GPU work.
+ *       OMDS_ERR_NOT_INITIALISED unless a filtered call installed the scene in force.
+ *   omds_get_velocity_filter_state : grid [cells,4] = the stored state (NULL: no copy; untouched without one); *n_cells_out = its cells,
+ *       0 while the history is empty for want of a key.                                                                              */
+typedef struct {
+    float alpha;         /* weight of the new estimate once the running mean has passed it: finite, in (0, 1]     */
+    float alpha_object;  /* ... for a sphere that moves with an accepted object; <= 0: alpha; else in (0, 1]      */
+    float max_jump;      /* m/s; a new estimate farther than this from its predecessor restarts; <= 0: off; not NaN */
+} omds_velocity_filter_spec;
+OMDS_API int omds_velocity_filter_step(const omds_cloud_spec* spec, const omds_cloud_track_spec* track, const omds_velocity_filter_spec* filt,
+                                       const int32_t* state_in /* [cells,4] or NULL = empty */, const int32_t* cell /* [n] */,
+                                       const float* raw /* [n,3] */, const int32_t* live /* [n] or NULL: all */,
+                                       const int32_t* group /* [n] or NULL: none */, int32_t n, float* vel_out /* [n,3] */,
+                                       int32_t* state_out /* [cells,4] */, int32_t stats_out[3] /* with history, restarts, groups */);
+OMDS_API int omds_set_velocity_filter(omds_ctx* ctx, const omds_velocity_filter_spec* spec /* NULL: off */);
+OMDS_API int omds_get_velocity_filter(omds_ctx* ctx, omds_velocity_filter_spec* spec_out, int32_t* on_out);
+OMDS_API int omds_get_velocity_filter_frame(omds_ctx* ctx, float* raw /* [n_obs,3] */, int32_t* live /* [n_obs] */, int32_t stats[3]);
+OMDS_API int omds_get_velocity_filter_state(omds_ctx* ctx, int32_t* grid /* [cells,4] or NULL */, int32_t* n_cells_out);
 /* THE OBSTACLE FOCUS (new work).  A sensed scene has thousands of spheres; everything behind pass 1 uses the n_closest nearest per
  * (rollout, step).  A focus call evaluates the distance of every sphere of the scene at ONE joint state, selects the near ones and
  * installs them as the scene in force, on the device; the full scene (the MASTER) is kept, so that the next call selects from it again

@@ -94,6 +94,11 @@ class OmdsDepthFilterSpec(C.Structure):
     _fields_ = [("radius", C.c_int32), ("min_support", C.c_int32), ("edge_abs", C.c_float), ("edge_rel", C.c_float)]
 
 
+class OmdsVelocityFilterSpec(C.Structure):
+    """omds_velocity_filter_spec (include/omds.h): how the velocity routes blend a new sphere velocity against its predecessor."""
+    _fields_ = [("alpha", C.c_float), ("alpha_object", C.c_float), ("max_jump", C.c_float)]
+
+
 class OmdsObstacleFocusSpec(C.Structure):
     """omds_obstacle_focus_spec (include/omds.h): which spheres of a large scene an obstacle focus keeps."""
     _fields_ = [("margin", C.c_float), ("lookahead", C.c_float), ("max_keep", C.c_int32)]
@@ -172,6 +177,12 @@ SIGNATURES = {
                                                                C.POINTER(OmdsCloudTrackSpec), C.POINTER(OmdsCloudObjectSpec),
                                                                C.POINTER(OmdsDepthCamera), C.POINTER(C.c_void_p), C.c_int32, C.c_int, F32P, I32P,
                                                                I32P, I32P, I32P, I32P]),
+    "omds_velocity_filter_step": (C.c_int, [C.POINTER(OmdsCloudSpec), C.POINTER(OmdsCloudTrackSpec), C.POINTER(OmdsVelocityFilterSpec), I32P, I32P,
+                                            F32P, I32P, I32P, C.c_int32, F32P, I32P, I32P]),
+    "omds_set_velocity_filter": (C.c_int, [C.c_void_p, C.POINTER(OmdsVelocityFilterSpec)]),
+    "omds_get_velocity_filter": (C.c_int, [C.c_void_p, C.POINTER(OmdsVelocityFilterSpec), I32P]),
+    "omds_get_velocity_filter_frame": (C.c_int, [C.c_void_p, F32P, I32P, I32P]),
+    "omds_get_velocity_filter_state": (C.c_int, [C.c_void_p, I32P, I32P]),
     "omds_obstacle_focus_select": (C.c_int, [C.POINTER(OmdsObstacleFocusSpec), F32P, F32P, C.c_int, C.c_int, I32P, C.c_int32, I32P, I32P]),
     "omds_focus_obstacles": (C.c_int, [C.c_void_p, C.POINTER(OmdsObstacleFocusSpec), F32P, I32P, I32P]),
     "omds_obstacle_focus_select_path": (C.c_int, [C.POINTER(OmdsObstacleFocusSpec), F32P, F32P, F32P, C.c_int, C.c_int, C.c_int, I32P, C.c_int32, I32P,

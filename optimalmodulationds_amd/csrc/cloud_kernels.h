@@ -8,6 +8,7 @@
 #include "point_cloud_objects_def.h"
 #include "scene_memory_def.h"
 #include "scene_memory_flow_def.h"
+#include "velocity_filter_def.h"
 
 constexpr int CLOUD_NT = 256;                          // lanes of every workgroup here
 constexpr int CLOUD_ITEMS = 4;                         // consecutive items per lane of a compaction block
@@ -112,3 +113,15 @@ void omds_launch_cloud_match(hipStream_t s, const CloudGrid& g, const CloudTrack
                              const CloudComp* prev, int n_prev, float4* objVel);
 // the velocities of the accepted objects over vel [n], object [n] = 1 on their spheres
 void omds_launch_cloud_apply(hipStream_t s, const int* root, const int* compOf, const float4* objVel, int n, float4* vel, int* object);
+
+// The velocity filter (velocity_filter_def.h).  state[cells[i]] = no history for the n cells the buffer last held (n = 0: no launch)
+void omds_launch_vel_clear(hipStream_t s, const int* cells, int n, int4* state);
+// ... the stage on the n > 0 final spheres (their cells in cells, ascending): vel [n] as the velocity stages left it (.w: the matched
+// flag) against the stored state state_in [cells] (nullptr: an empty history) -> out [n] the filtered velocities, .w kept, and
+// state_out [cells] (all zero before the call) the records of the live spheres; held [n] = cells, for the next omds_launch_vel_clear
+// of that buffer.  label, object [n]: the spheres with object = 1 blend as the group of their label (object == nullptr: no groups,
+// and no group launch); pred [n], group [n][VEL_GROUP_ACC] and groupH [n] are scratch.  counters [3], cleared by the caller, takes the
+// live spheres with history, the restarts and the groups with history
+void omds_launch_vel_filter(hipStream_t s, const CloudGrid& g, const CloudTrack& tr, const VelFilter& f, const int4* state_in, const int* cells,
+                            int n, const float4* vel, const int* label, const int* object, VelPred* pred, unsigned long long* group, int* groupH,
+                            int4* state_out, int* held, float4* out, unsigned* counters);

@@ -7,6 +7,7 @@
 
 #include "point_cloud_objects_def.h"
 #include "scene_memory_def.h"
+#include "velocity_filter_def.h"
 
 // Two buffers, one of which holds what the last successful call stored while the other is written; commit() swaps them
 template <class T>
@@ -61,6 +62,15 @@ struct SceneMemKey {
         max_age = sm.max_age; footprint = sm.footprint; clear_margin = sm.clear_margin;
         n_cells = g.n_cells;
     }
+};
+
+// the grid and the filter spec the stored velocity-filter state was built under (omds_set_velocity_filter); floats bitwise
+struct VelFilterKey {
+    CloudFrameKey grid;           // grid.have: a state is stored (a filtered call with a previous frame succeeded; nothing emptied it since)
+    VelFilter f = {};
+    int n_cells = 0;
+    bool same(const CloudGrid& g, const VelFilter& o) const { return grid.same(g) && std::memcmp(&f, &o, sizeof(f)) == 0; }
+    void set(const CloudGrid& g, const VelFilter& o) { grid.set(g); f = o; n_cells = g.n_cells; }
 };
 
 // What a context keeps for the obstacle focus (obstacle_focus.hip): omds_ctx::focus.  While `on`, the scene in force is a subset of the
@@ -129,7 +139,28 @@ struct CloudState {
     DepthFilter filter = {};          // behind its checks, while filter_on
     DevBuf<unsigned> filtCounts;      // [2] pixels the filter kept and rejected in the call under way
     int64_t filter_stats[2] = {0, 0}; // ... of the last depth call that reached its counting pass; 0, 0 when no filter ran
+    // ... the velocity filter (omds_set_velocity_filter): context state that every velocity route consults, and per cell the record
+    // (q_x, q_y, q_z, hits) of velocity_filter_def.h.  One of the two buffers holds the stored state, the other is written; a
+    // successful filtered call with a previous frame makes its own the stored one.  A buffer is all zero outside the cells it last
+    // held: those are listed beside it, and one launch empties them in front of the next write
+    bool vfilter_on = false;
+    VelFilter vfilter = {};           // behind its checks, while vfilter_on
+    omds_velocity_filter_spec vfilter_spec = {};   // ... as it was given (omds_get_velocity_filter)
+    Flip<int4> vstate;                // [cells] each, allocated (and cleared) when first written
+    DevBuf<int> vcells[2];            // [max_spheres] the cells vstate.buf[side] last held,
+    int vn[2] = {0, 0};               // ... and their number
+    VelFilterKey vkey;
+    DevBuf<VelPred> vpred;            // [max_spheres] the predecessor of every final sphere (k_vel_pred)
+    DevBuf<unsigned long long> vgroup;   // [max_spheres][VEL_GROUP_ACC] at the list index of a label's cell: G_x, G_y, G_z, Gt of the group
+    DevBuf<int> vgroupH;              // [max_spheres] ... and Gh, VEL_NO_HISTORY while no member has added
+    DevBuf<float4> velOut;            // [max_spheres] the filtered velocity of every final sphere; .w as vel's
+    DevBuf<unsigned> vcounts;         // [3] live spheres with history, restarts, groups with history of the call under way
+    bool vf_have = false;             // the scene in force was installed by a filtered call:
+    std::vector<float> vf_raw;        // ... [n_obs][3] its unfiltered velocities (padding: 0),
+    std::vector<int32_t> vf_live;     // ... [n_obs] its matched flags
+    int32_t vf_stats[3] = {0, 0, 0};  // ... and its counts
 
-    void forget_tracking() { frame.have = false; tab.have = false; }          // omds_cloud_track_reset
-    void forget_labels() { obj_label.clear(); obj_flag.clear(); mem_age.clear(); }   // another setter installed the scene in force
+    void forget_tracking() { frame.have = false; tab.have = false; vkey.grid.have = false; }   // omds_cloud_track_reset
+    // another setter installed the scene in force
+    void forget_labels() { obj_label.clear(); obj_flag.clear(); mem_age.clear(); vf_have = false; }
 };

@@ -19,6 +19,8 @@
 //             on T, the spheres of the final list whose cell was counted now, carried back to the whole list by one launch
 //   filter  : while the context has a depth filter, the counting pass of every depth call above is the filtered one
 //             (depth_filter_def.h): another kernel in the same place, and two counters fetched behind it
+//   smoothed: while the context has a velocity filter, every tracked route above blends its velocities against the state kept per
+//             cell (velocity_filter_def.h): one stage between the velocity stages and the install, which run unchanged
 #include "capi_internal.h"
 #include "cloud_kernels.h"
 
@@ -58,6 +60,7 @@ struct CloudCall {
     DepthSource depth;
     const float* q_now;
     CloudOuts out;
+    const VelFilter* vfilt = nullptr;   // while tracked: the context's velocity filter while it is on
     const DepthFilter* filter() const { return images ? depth.filt : nullptr; }
 };
 
@@ -79,6 +82,8 @@ struct CloudWork {
                                                   // from empty memory, and whatever is stored stays until the commit
     unsigned counts[SCENE_MEM_COUNTS] = {0u, 0u, 0u, 0u, 0u};   // ... the cells of this call, the last fetched behind the self-filter
     std::vector<int32_t> age;                     // ... [n_final], padding spheres: -1
+    std::vector<float> raw4;                      // velocity filter: [n_list][4] the velocities in front of it (vel4 holds the filtered ones)
+    unsigned vcounts[3] = {0u, 0u, 0u};           // ... spheres with history, restarts, groups with history, fetched with the velocities
 };
 
 // spec, then track when the route is tracked, then obj when it has objects: each behind its checks, in that order
@@ -91,6 +96,7 @@ int resolve_call(omds_ctx* ctx, const char* who, const omds_cloud_spec* spec, bo
         if (int rc = cloud_resolve_track(track, &c->tr, &ctx->err)) return rc;
     if (objects)
         if (int rc = cloud_resolve_objects(obj, &c->ob, &ctx->err)) return rc;
+    if (tracked && ctx->cloud.vfilter_on) c->vfilt = &ctx->cloud.vfilter;
     return OMDS_OK;
 }
 
@@ -157,6 +163,28 @@ int reserve_memory_flow(omds_ctx* ctx, const CloudCall& c) {
     CK(s.velAll.reserve(m));
     CK(s.labelAll.reserve(m));
     CK(s.objectAll.reserve(m));
+    return OMDS_OK;
+}
+// the velocity filter: the state buffer that is not the stored one, the list of the cells it holds, and the scratch of the stage.  A
+// state buffer is all zero outside its listed cells: a new allocation of either starts cleared, with an empty list
+int reserve_vfilter(omds_ctx* ctx, const CloudCall& c) {
+    CloudState& s = ctx->cloud;
+    const size_t cells = (size_t)c.g.n_cells, m = (size_t)c.g.max_spheres;
+    const int side = 1 - s.vstate.stored;
+    const bool fresh = s.vstate.next().count() < cells || s.vcells[side].count() < m;
+    if (fresh || s.vpred.count() < m || s.vgroup.count() < m * VEL_GROUP_ACC || s.vgroupH.count() < m || s.velOut.count() < m)
+        CK(hipStreamSynchronize(ctx->stream));
+    CK(s.vstate.next().reserve(cells));   // written; the stored state is the other one
+    CK(s.vcells[side].reserve(m));
+    CK(s.vpred.reserve(m));
+    CK(s.vgroup.reserve(m * VEL_GROUP_ACC));
+    CK(s.vgroupH.reserve(m));
+    CK(s.velOut.reserve(m));
+    CK(s.vcounts.reserve(3));
+    if (fresh) {
+        CK(hipMemsetAsync(s.vstate.next(), 0, s.vstate.next().bytes(), ctx->stream));
+        s.vn[side] = 0;
+    }
     return OMDS_OK;
 }
 
@@ -375,6 +403,34 @@ int memory_velocities(omds_ctx* ctx, const CloudCall& c, CloudWork& w, CloudWork
     return OMDS_OK;
 }
 
+// ---- the velocity filter: the velocities of the final list, wherever the stages above left them, against the stored state while it is
+// of this grid and filter spec, into velOut, which install_scene then fetches; the records into the state buffer that is not the
+// stored one, emptied first of the cells it last held.  Without a previous frame there are no velocities: commit_vfilter empties the
+// history.  The labels and object flags are the route's: of the whole list behind k_scene_memory_flow, else of object_velocities
+int filter_velocities(omds_ctx* ctx, const CloudCall& c, CloudWork& w) {
+    CloudState& s = ctx->cloud;
+    if (!w.have_prev) return OMDS_OK;
+    const int n = w.n_list, side = 1 - s.vstate.stored;
+    omds_launch_vel_clear(ctx->stream, s.vcells[side], s.vn[side], s.vstate.next());
+    s.vn[side] = 0;
+    CK(hipGetLastError());
+    if (n == 0) return OMDS_OK;
+    const float4* raw = w.d_vel ? w.d_vel : s.vel.get();
+    const bool grouped = c.objects && w.have_table;
+    const int* label = !grouped ? nullptr : c.memory ? s.labelAll.get() : s.label.get();
+    const int* object = !grouped ? nullptr : c.memory ? s.objectAll.get() : s.object.get();
+    w.raw4.resize((size_t)n * 4);
+    CK(hipMemcpyAsync(w.raw4.data(), raw, (size_t)n * 16, hipMemcpyDeviceToHost, ctx->stream));
+    CK(hipMemsetAsync(s.vcounts, 0, 3 * 4, ctx->stream));
+    omds_launch_vel_filter(ctx->stream, c.g, c.tr, *c.vfilt, s.vkey.same(c.g, *c.vfilt) ? s.vstate.kept().get() : nullptr, w.d_cell, n, raw, label,
+                           object, s.vpred, s.vgroup, s.vgroupH, s.vstate.next(), s.vcells[side], s.velOut, s.vcounts);
+    CK(hipGetLastError());
+    s.vn[side] = n;   // what k_vel_blend lists
+    CK(hipMemcpyAsync(w.vcounts, s.vcounts, 3 * 4, hipMemcpyDeviceToHost, ctx->stream));
+    w.d_vel = s.velOut;
+    return OMDS_OK;
+}
+
 // ---- install: the list to the host, filled up to n_closest with the spec's pad sphere, and in as omds_set_obstacles puts a list in;
 // then the velocities, if any sphere moves: a scene whose every sphere stands still keeps the cleared horizon, and the propagate that
 // follows is the static one
@@ -426,6 +482,25 @@ void commit_objects(omds_ctx* ctx, const CloudCall& c, CloudWork& w) {
     if (c.out.n_objects_matched) *c.out.n_objects_matched = w.have_table ? n_accepted : -1;
 }
 
+// ... and what the velocity filter wrote the stored state, with the unfiltered velocities and flags of the scene in force.  A call
+// without a previous frame leaves an empty history
+void commit_vfilter(omds_ctx* ctx, const CloudCall& c, const CloudWork& w) {
+    CloudState& s = ctx->cloud;
+    s.vkey.grid.have = false;
+    if (w.have_prev) {
+        s.vstate.commit();
+        s.vkey.set(c.g, *c.vfilt);
+    }
+    s.vf_have = true;
+    s.vf_raw.assign((size_t)w.n_final * 3, 0.f);   // padding spheres stand still
+    s.vf_live.assign((size_t)w.n_final, 0);
+    for (size_t i = 0; i * 4 < w.raw4.size(); ++i) {
+        for (int k = 0; k < 3; ++k) s.vf_raw[i * 3 + k] = w.raw4[i * 4 + k];
+        s.vf_live[i] = w.raw4[i * 4 + 3] != 0.f;
+    }
+    for (int k = 0; k < 3; ++k) s.vf_stats[k] = (int32_t)w.vcounts[k];
+}
+
 // ... and, first of the three, what was written the stored memory, with the ages of the scene in force
 void commit_memory(omds_ctx* ctx, const CloudCall& c, CloudWork& w) {
     CloudState& s = ctx->cloud;
@@ -453,6 +528,7 @@ int scene_from_cloud(omds_ctx* ctx, const CloudCall& c) {
     if (c.objects && (rc = reserve_objects(ctx, c))) return rc;
     if (c.memory && (rc = reserve_memory(ctx, c))) return rc;
     if (c.memory && c.tracked && (rc = reserve_memory_flow(ctx, c))) return rc;
+    if (c.vfilt && (rc = reserve_vfilter(ctx, c))) return rc;
     if ((rc = stage_points(ctx, c, w))) return rc;
     if ((rc = count_cells(ctx, c, w))) return rc;
     if (c.out.n_occupied) *c.out.n_occupied = w.occupied;
@@ -471,9 +547,11 @@ int scene_from_cloud(omds_ctx* ctx, const CloudCall& c) {
     if (c.tracked && !c.memory && (rc = sphere_velocities(ctx, c, w))) return rc;
     if (c.objects && !c.memory && (rc = object_velocities(ctx, c, w))) return rc;
     if (c.tracked && c.memory && (rc = memory_velocities(ctx, c, w, t))) return rc;
+    if (c.vfilt && (rc = filter_velocities(ctx, c, w))) return rc;
     if ((rc = install_scene(ctx, c, w))) return rc;
     if (c.memory) commit_memory(ctx, c, w);
     if (c.tracked) commit_frame(ctx, c, w);
+    if (c.vfilt) commit_vfilter(ctx, c, w);
     if (c.objects) commit_objects(ctx, c, w);
     return OMDS_OK;
 }
@@ -688,6 +766,60 @@ int omds_get_cloud_objects(omds_ctx* ctx, int32_t* label, int32_t* object, int32
     if (label) std::memcpy(label, s.obj_label.data(), (size_t)ctx->n_obs * 4);
     if (object) std::memcpy(object, s.obj_flag.data(), (size_t)ctx->n_obs * 4);
     if (n_objects_out) *n_objects_out = s.obj_count;
+    return OMDS_OK;
+}
+
+int omds_velocity_filter_step(const omds_cloud_spec* spec, const omds_cloud_track_spec* track, const omds_velocity_filter_spec* filt,
+                              const int32_t* state_in, const int32_t* cell, const float* raw, const int32_t* live, const int32_t* group, int32_t n,
+                              float* vel_out, int32_t* state_out, int32_t stats_out[3]) {
+    return velocity_filter_step_host(spec, track, filt, state_in, cell, raw, live, group, n, vel_out, state_out, stats_out, &g_create_err);
+}
+
+int omds_set_velocity_filter(omds_ctx* ctx, const omds_velocity_filter_spec* spec) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    CloudState& s = ctx->cloud;
+    if (!spec) {
+        s.vfilter_on = false;
+        s.vkey.grid.have = false;   // the history goes with the filter
+        return OMDS_OK;
+    }
+    VelFilter f;
+    if (int rc = velocity_filter_resolve(spec, &f, &ctx->err)) return rc;   // the stored filter stays as it was
+    s.vfilter = f;
+    s.vfilter_spec = *spec;
+    s.vfilter_on = true;
+    return OMDS_OK;
+}
+
+int omds_get_velocity_filter(omds_ctx* ctx, omds_velocity_filter_spec* spec_out, int32_t* on_out) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    const CloudState& s = ctx->cloud;
+    if (spec_out) *spec_out = s.vfilter_on ? s.vfilter_spec : omds_velocity_filter_spec{0.f, 0.f, 0.f};
+    if (on_out) *on_out = s.vfilter_on ? 1 : 0;
+    return OMDS_OK;
+}
+
+int omds_get_velocity_filter_frame(omds_ctx* ctx, float* raw, int32_t* live, int32_t stats[3]) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    const CloudState& s = ctx->cloud;
+    REQUIRE(ctx->n_obs > 0 && s.vf_have && s.vf_live.size() == (size_t)ctx->n_obs, OMDS_ERR_NOT_INITIALISED,
+            "omds_get_velocity_filter_frame: the scene in force was not installed by a call under a velocity filter");
+    if (raw) std::memcpy(raw, s.vf_raw.data(), (size_t)ctx->n_obs * 12);
+    if (live) std::memcpy(live, s.vf_live.data(), (size_t)ctx->n_obs * 4);
+    for (int k = 0; stats && k < 3; ++k) stats[k] = s.vf_stats[k];
+    return OMDS_OK;
+}
+
+int omds_get_velocity_filter_state(omds_ctx* ctx, int32_t* grid, int32_t* n_cells_out) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    CloudState& s = ctx->cloud;
+    const bool have = s.vkey.grid.have;
+    if (n_cells_out) *n_cells_out = have ? s.vkey.n_cells : 0;
+    if (grid && have) {
+        CK(hipSetDevice(ctx->dev));
+        CK(hipMemcpyAsync(grid, s.vstate.kept(), (size_t)s.vkey.n_cells * 16, hipMemcpyDeviceToHost, ctx->stream));
+        CK(hipStreamSynchronize(ctx->stream));
+    }
     return OMDS_OK;
 }
 

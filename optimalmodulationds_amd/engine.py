@@ -25,6 +25,7 @@ class Engine:
         self.K = 0
         self.n_obs = 0
         self.depth_filter = None      # the depth filter in force (set_depth_filter), None: off
+        self.velocity_filter = None   # the velocity filter in force (set_velocity_filter), None: off
         self.C = 0
         self.config_version = 0      # bumped by every call that changes params / nominal DS / cost on the context (MPPI._push re-syncs on it)
 
@@ -216,6 +217,41 @@ class Engine:
         out = (C.c_int64 * 2)()
         self._ck(self.lib.omds_get_depth_filter_stats(self.h, out))
         return int(out[0]), int(out[1])
+
+    # ---- the velocity filter (omds.h: THE VELOCITY FILTER) ------------------------------------------------------------------------------
+    def set_velocity_filter(self, spec):
+        """The context's velocity filter: an ``OmdsVelocityFilterSpec`` (``velocity_filter_spec`` builds one; a dict of its arguments is
+        taken too), or None to turn it off, which also empties its history; ``self.velocity_filter`` holds the spec in force (None:
+        off).  While set, every call that estimates velocities (``set_obstacles_from_cloud_tracked`` / ``_objects``,
+        ``set_obstacles_from_depth`` with ``track``, ``set_obstacles_from_depth_memory_tracked``) blends them against the smoothed
+        velocity the context keeps per grid cell: everything but the installed velocities is the unfiltered call, bit for bit, and the
+        velocities are ``velocity_filter_step`` on the stored state.  A refused spec raises and leaves the stored filter as it was."""
+        spec = _vfilter_of(spec)
+        self._ck(self.lib.omds_set_velocity_filter(self.h, None if spec is None else C.byref(spec)))
+        self.velocity_filter = spec
+
+    def velocity_filter_frame(self):
+        """(raw [n_obs, 3], live [n_obs], stats) of the scene in force: the unfiltered velocities and matched flags of the filtered call
+        that installed it (padding: 0), and (live spheres with history, restarts, groups with history) of that call
+        (omds_get_velocity_filter_frame; host state, no GPU work).  Raises unless a filtered call installed the scene."""
+        n_obs = np.zeros(1, np.int32)
+        self._ck(self.lib.omds_get_obstacles(self.h, None, L.iptr(n_obs)))
+        n = int(n_obs[0])
+        raw, live, stats = np.zeros((max(n, 1), 3), np.float32), np.zeros(max(n, 1), np.int32), np.zeros(3, np.int32)
+        self._ck(self.lib.omds_get_velocity_filter_frame(self.h, L.fptr(raw), L.iptr(live), L.iptr(stats)))
+        return raw[:n], live[:n], tuple(int(v) for v in stats)
+
+    def velocity_filter_state(self):
+        """The stored state of the velocity filter, [cells, 4] int32 (q_x, q_y, q_z in 2^-16 m/s, hits), or None while the history
+        is empty for want of a stored state (no filtered call yet, the filter cleared, ``cloud_track_reset``, a call without a
+        previous frame)."""
+        n_cells = np.zeros(1, np.int32)
+        self._ck(self.lib.omds_get_velocity_filter_state(self.h, None, L.iptr(n_cells)))
+        if int(n_cells[0]) == 0:
+            return None
+        grid = np.zeros((int(n_cells[0]), 4), np.int32)
+        self._ck(self.lib.omds_get_velocity_filter_state(self.h, L.iptr(grid), None))
+        return grid
 
     def scene_memory_reset(self):
         """Forget the stored scene memory: the next ``set_obstacles_from_depth_memory`` starts from an empty one."""
@@ -947,6 +983,49 @@ def depth_filter_spec(radius=1, min_support=4, edge_abs=0.01, edge_rel=0.01):
     f = L.OmdsDepthFilterSpec()
     f.radius, f.min_support, f.edge_abs, f.edge_rel = int(radius), int(min_support), float(edge_abs), float(edge_rel)
     return f
+
+
+def velocity_filter_spec(alpha=0.3, alpha_object=0.0, max_jump=0.0):
+    """An ``OmdsVelocityFilterSpec``: a new sphere velocity enters the smoothed one with weight max(``alpha``, 1 / frames so far) (a
+    running mean first, then an exponential one; ``alpha`` in (0, 1], 1: no smoothing); ``alpha_object`` (<= 0: ``alpha``) is the
+    weight for the spheres of a matched object; a new velocity more than ``max_jump`` m/s (<= 0: off) from the smoothed one restarts."""
+    f = L.OmdsVelocityFilterSpec()
+    f.alpha, f.alpha_object, f.max_jump = float(alpha), float(alpha_object), float(max_jump)
+    return f
+
+
+def _vfilter_of(spec):
+    """None, an ``OmdsVelocityFilterSpec`` or a dict of ``velocity_filter_spec``'s arguments -> None or the spec"""
+    return velocity_filter_spec(**spec) if isinstance(spec, dict) else spec
+
+
+def velocity_filter_step(spec, track, filt, state_in, cell, raw, live=None, group=None):
+    """The definition of the velocity filter on the host (omds_velocity_filter_step, no GPU): the stored state ``state_in`` [cells, 4]
+    (int32; None: empty), the cells ``cell`` [n] of a final list (ascending), its velocities ``raw`` [n, 3], matched flags ``live``
+    [n] (None: all) and groups ``group`` [n] (the label of a sphere that moves with a matched object, else -1; None: none) ->
+    (vel [n, 3], state_out [cells, 4], (live spheres with history, restarts, groups with history)).  ``spec``: the grid's
+    ``OmdsCloudSpec``; ``track``: the ``OmdsCloudTrackSpec`` (its reach and still); ``filt``: an ``OmdsVelocityFilterSpec`` or a dict."""
+    lib = L.load()
+    filt = _vfilter_of(filt)
+    cells = max(int(spec.dims[0]), 0) * max(int(spec.dims[1]), 0) * max(int(spec.dims[2]), 0)
+    if cells > 1 << 22:
+        cells = 0                         # more than the library takes: it refuses the call
+    src = None
+    if state_in is not None:
+        src = np.ascontiguousarray(state_in, np.int32).reshape(-1, 4)
+        if src.shape[0] != cells:
+            raise ValueError(f"velocity_filter_step: state_in must hold {cells} records, got {src.shape[0]}")
+    cell = np.ascontiguousarray(cell, np.int32).reshape(-1)
+    n = cell.size
+    raw = L.f32(raw).reshape(n, 3)
+    live = None if live is None else np.ascontiguousarray(live, np.int32).reshape(n)
+    group = None if group is None else np.ascontiguousarray(group, np.int32).reshape(n)
+    vel, out, stats = np.zeros((max(n, 1), 3), np.float32), np.zeros((max(cells, 1), 4), np.int32), np.zeros(3, np.int32)
+    rc = lib.omds_velocity_filter_step(C.byref(spec), C.byref(track), None if filt is None else C.byref(filt), L.iptr(src), L.iptr(cell),
+                                       L.fptr(raw), L.iptr(live), L.iptr(group), n, L.fptr(vel), L.iptr(out), L.iptr(stats))
+    if rc != 0:
+        raise L.OmdsError(f"omds_velocity_filter_step failed ({rc}): {lib.omds_last_error(None).decode()}")
+    return vel[:n], out[:cells], tuple(int(v) for v in stats)
 
 
 def _filter_of(filter):

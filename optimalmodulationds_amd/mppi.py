@@ -97,6 +97,7 @@ class MPPI:
         self.obs_focus = None         # focus_obstacles: the master index of every sphere of self.obs, else None
         self.obs_age = None           # update_obstacles_from_depth(memory=): calls since every sphere's cell was last counted, else None
         self.depth_filter_stats = None   # update_obstacles_from_depth(filter=): (pixels kept, pixels rejected) of the last such call
+        self.vel_filter_stats = None  # update_obstacles_from_*(smooth=): (spheres with history, restarts, groups with history), else None
         self.cur_cost = None
         self._cache = {}
         self._generation = 0          # propagate() calls so far (LazyRollout tensors belong to one of them)
@@ -147,7 +148,7 @@ class MPPI:
         return 0
 
     def update_obstacles_from_cloud(self, points, voxel, lo, hi, radius=None, self_margin=None, min_points=1, max_spheres=4096,
-                                    dt_frame=None, reach=2, still=0.0, moving_frame=False, objects=False, link=1, min_cells=4):
+                                    dt_frame=None, reach=2, still=0.0, moving_frame=False, objects=False, link=1, min_cells=4, **route):
         """The scene from a depth point cloud ``points`` [P, 3] (new here; numpy, or a torch tensor on the engine's device): cropped
         to the box ``lo`` .. ``hi``, down-sampled to one sphere per occupied ``voxel`` cell (``radius`` None: the cell's circumsphere)
         and, when ``self_margin`` is given, without the spheres the distance network places within that margin of the robot at
@@ -162,12 +163,34 @@ class MPPI:
         connected components (cells at most ``link`` apart), a component of at least ``min_cells`` cells that is matched with one of
         the previous such call moves as a rigid body with its centroid, the other spheres keep the tracked velocities.
         ``self.cloud_objects`` then holds the objects of the scene and ``self.cloud_objects_matched`` those that were matched (-1: no
-        previous component table); both are None on the other routes."""
+        previous component table); both are None on the other routes.
+        ``smooth`` (needs ``dt_frame``; an ``OmdsVelocityFilterSpec``, or a dict of ``engine.velocity_filter_spec``'s arguments, as in
+        ``smooth=dict(alpha=0.3)``): sets the engine's velocity filter (Engine.set_velocity_filter), which STAYS set -- its history
+        lives in the context between calls, and turning it off empties it: the velocities of this and the following tracked / objects
+        calls are blended against the smoothed velocity kept per grid cell, and ``self.vel_filter_stats`` holds (spheres with
+        history, restarts, groups with history) of the call.  False turns the filter off; None (the default) leaves whatever filter
+        the engine has as it is.  (``smooth`` is the one keyword ``**route`` takes here: the named keywords stay what they were.)"""
+        smooth = route.pop("smooth", None)
+        if route:
+            raise TypeError(f"update_obstacles_from_cloud: unexpected keyword arguments {sorted(route)}")
+        self._set_smooth("update_obstacles_from_cloud", smooth, dt_frame)
         return self._update_obstacles_sensed("update_obstacles_from_cloud", lambda e, spec, q, track, obj: (
             e.set_obstacles_from_cloud(points, spec, q) if track is None else
             e.set_obstacles_from_cloud_tracked(points, spec, track, q) if obj is None else
             e.set_obstacles_from_cloud_objects(points, spec, track, obj, q)),
             voxel, lo, hi, radius, self_margin, min_points, max_spheres, dt_frame, reach, still, moving_frame, objects, link, min_cells)
+
+    def _set_smooth(self, who, smooth, dt_frame):
+        """the ``smooth`` keyword of the sensed-scene calls: None leaves the engine's velocity filter, False turns it off, a spec sets it"""
+        self.vel_filter_stats = None
+        if smooth is None:
+            return
+        if smooth is False:
+            self._engine.set_velocity_filter(None)
+            return
+        if dt_frame is None:
+            raise ValueError(f"{who}: smooth= needs dt_frame (only the tracked routes estimate velocities)")
+        self._engine.set_velocity_filter(smooth)
 
     def update_obstacles_from_depth(self, images, cameras, voxel, lo, hi, radius=None, self_margin=None, min_points=1, max_spheres=4096,
                                     dt_frame=None, reach=2, still=0.0, moving_frame=False, objects=False, link=1, min_cells=4, **route):
@@ -193,11 +216,14 @@ class MPPI:
         ``self.cloud_matched``, ``self.cloud_objects[_matched]`` as there, ``moving_frame`` honoured), remembered spheres and seen
         ones that were occluded at the previous memory call stand still.  Without it, ``memory`` together with ``dt_frame`` /
         ``objects`` is the error it was.
-        (``memory``, ``filter`` and ``memory_motion`` are the keywords ``**route`` takes, default None / None / False: the named keywords
-        stay those of ``update_obstacles_from_cloud``, which has no cameras to ask.)"""
+        ``smooth``: as in ``update_obstacles_from_cloud``; the cloud and depth calls share the one filter and its history.
+        (``memory``, ``filter``, ``memory_motion`` and ``smooth`` are the keywords ``**route`` takes, default None / None / False / None:
+        the named keywords stay those of ``update_obstacles_from_cloud``.)"""
         memory, filt, motion = route.pop("memory", None), route.pop("filter", None), bool(route.pop("memory_motion", False))
+        smooth = route.pop("smooth", None)
         if route:
             raise TypeError(f"update_obstacles_from_depth: unexpected keyword arguments {sorted(route)}")
+        self._set_smooth("update_obstacles_from_depth", smooth, dt_frame)
         if motion and (memory is None or dt_frame is None):
             raise ValueError("update_obstacles_from_depth: memory_motion=True needs both memory= and dt_frame=")
         if filt is None:
@@ -269,6 +295,8 @@ class MPPI:
             vel, have = self._engine.get_obstacle_motion()
             if have:
                 self.obs_velocities = torch.as_tensor(vel)
+            if self._engine.velocity_filter is not None:
+                self.vel_filter_stats = self._engine.velocity_filter_frame()[2]
         self.obs = torch.as_tensor(self._engine.get_obstacles())
         self.n_obs = self.obs.shape[0]
         self._max_obs = self._engine.max_obs
