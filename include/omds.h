@@ -370,7 +370,7 @@ OMDS_API int omds_get_cloud_objects(omds_ctx* ctx, int32_t* label, int32_t* obje
  * grid; a depth camera delivers a uint16 (or float32) image, intrinsics and a pose, and a cell around an arm has two or three of them.
  * The depth call deprojects inside the counting pass, without ever writing a point: everything after that pass is integer sums and
  * ordered compactions, a function of the SET of points.  Additive: no other entry point changes its launches or its bits.
- * OUT OF SCOPE: lens distortion (the image is taken as rectified), range-type depth (z is depth along the optical axis),
+ * OUT OF SCOPE: range-type depth (z is depth along the optical axis; an unrectified image: THE LENS OF A DEPTH CAMERA below),
  * registration of the cameras against each other (the poses are taken as given), a motion model beyond constant velocity; smoothing
  * of positions.  (Flying pixels and speckle: THE DEPTH FILTER below; velocities smoothed over frames: THE VELOCITY FILTER below.)
  *   omds_depth_points : host only (no context, no GPU), the DEFINITION.  All fp32, every operation named one rounding.  Once per
@@ -582,6 +582,78 @@ OMDS_API int omds_set_obstacles_from_depth_memory_tracked(omds_ctx* ctx, const o
                                                           int images_on_device, const float* q_now, int32_t* n_spheres_out,
                                                           int32_t counts_out[5], int32_t* n_matched_out, int32_t* n_objects_out,
                                                           int32_t* n_objects_matched_out);
+/* THE LENS OF A DEPTH CAMERA: UNRECTIFIED IMAGES INSIDE THE DEPTH ROUTES (new work).  Stereo cameras deliver rectified depth;
+ * time-of-flight cameras and every simulated camera with a lens model deliver the raw image and Brown-Conrady coefficients.  The ray of
+ * a pixel is a property of the camera, not of the frame: a per-camera table of rays that the counting pass reads in place of
+ * ((float)u - cx) * ifx, and the closed-form forward model where the scene memory projects a cell centre.  Additive: with no lens set
+ * every entry point keeps its launches and its bits, and omds_depth_camera keeps its layout.
+ * OUT OF SCOPE: range-type depth, fisheye (Kannala-Brandt), thin-prism and tilt terms, caller-supplied ray tables, models that fold
+ * back inside the image, resampling an image to a rectified one, registration of the cameras against each other.
+ *   THE MODEL (csrc/depth_lens_def.h).  All fp32, every operation named one rounding, IEEE division.  OpenCV's rational model,
+ *       k = k1 k2 p1 p2 k3 k4 k5 k6 (plumb-bob: k4 = k5 = k6 = 0).  With r2 = fmaf(a, a, b * b), num = 1 + k1 r2 + k2 r2^2 + k3 r2^3 and
+ *       den = 1 + k4 r2 + k5 r2^2 + k6 r2^3 in Horner form (fmaf), dx = fmaf(2 p1, a b, p2 fmaf(2, a a, r2)) and
+ *       dy = fmaf(2 p2, a b, p1 fmaf(2, b b, r2)):
+ *       FORWARD (a, b) -> (ad, bd): s = num / den; ad = fmaf(a, s, dx); bd = fmaf(b, s, dy); the pixel is (fx ad + cx, fy bd + cy).
+ *       INVERSE, the ray of visited pixel (u, v): x0 = ((float)u - cx) * ifx, y0 likewise; (x, y) = (x0, y0); exactly `iters` rounds of
+ *       ic = den / num; x = (x0 - dx) * ic; y = (y0 - dy) * ic (num, den, dx, dy at the current (x, y)); then FORWARD at (x, y): the ray is
+ *       (x, y) iff s > 0 && fabsf((ad - x0) * fx) <= max_residual && fabsf((bd - y0) * fy) <= max_residual (NaN fails), else the pixel
+ *       has NO RAY, stored as (NaN, NaN).  With all eight coefficients zero the ray is (x0, y0) exactly.  Plumb-bob (-0.3, 0.1, 1e-3,
+ *       -5e-4) at 640 x 480, fx 600 is within 1.1e-4 px after 10 rounds; a Kinect-NFOV-like rational set within 2.4e-4 px after 20.
+ *   omds_depth_lens_rays : host only, the table of the visited pixels, row-major: ab_out [nv * nu][2]; *r2_max_out = the largest
+ *       fmaf(a, a, b * b) over the valid entries (0 when there is none), *n_invalid_out = the pixels without a ray (either may be
+ *       NULL).  lens == NULL or model 0: the pinhole rays.
+ *   omds_depth_points_lens : host only, the DEFINITION: omds_depth_points_filtered with xc = a * z, yc = b * z from the pixel's ray,
+ *       then the same three pose fmafs.  A pixel that passes the gate and the filter but has no ray is three NaNs, counted neither as
+ *       valid nor as rejected; it is still a return for the filter's support test and for the memory's verdicts, which read raw depths
+ *       and never rays.  lens == NULL or model 0: exactly omds_depth_points_filtered.
+ *   omds_depth_scene_memory_lens : omds_depth_scene_memory_filtered with lenses [n_cams] (NULL: none).  The counts come from the lens
+ *       points.  In a verdict of a camera with a lens, after iz: a = xc * iz; b = yc * iz; !(fmaf(a, a, b * b) <= r2_max) is SILENT
+ *       (beyond the table's field of view the polynomial may fold back; SILENT never clears a cell); otherwise
+ *       uf = fmaf(ad, fx, cx), vf = fmaf(bd, fy, cy) from FORWARD, and from rintf on everything is as without a lens.
+ *   omds_depth_scene_memory_flow_lens : omds_depth_scene_memory_flow composed from the two above; lenses_prev [n_cams_prev], lenses
+ *       [n_cams], either may be NULL.
+ *   omds_set_depth_lenses : CONTEXT STATE like the depth filter, off at creation: lens i belongs to camera i of every later depth call
+ *       (plain, tracked, objects, memory, memory-tracked, with or without the depth filter); a camera index >= n, or an entry of model
+ *       0, is pinhole.  0 <= n <= OMDS_DEPTH_MAX_CAMERAS; lenses == NULL or n == 0 turns lenses off.  A refused array leaves the stored
+ *       lenses as they were.  THE CONTRACT with lenses set -- every effect of a depth call is that of the cloud call on the concatenated
+ *       omds_depth_points_lens of each image, bit for bit; of the memory calls, omds_depth_scene_memory[_flow]_lens iterated;
+ *       omds_get_depth_filter_stats counts a pixel without a ray neither as kept nor as rejected.  The lenses are not part of the scene
+ *       memory's key or the velocity filter's.  On the device: the table of a slot lives in the context under the bitwise key (width,
+ *       height, step, fx, fy, cx, cy, lens); k_depth_rays builds it on the context's stream in the first depth call that needs it (one
+ *       lane per visited pixel, one 8-byte store, r2_max as an integer maximum on the float's bits) and only a changed key rebuilds it:
+ *       a camera whose pose changes every frame never does.  The counting kernels and k_scene_memory have lens forms, launched only when
+ *       some camera of the call has a lens; without one every call enqueues the launches it always did.  A call refused for too many
+ *       cells may keep a freshly built table: a cache, not scene state.
+ *   omds_get_depth_lens_table : the device table of slot i as the last depth call that needed one left it: ab_out [n_entries][2] (NULL:
+ *       not fetched), its r2_max, its pixels without a ray, and *n_entries_out = nv * nu, 0 when the slot holds no table.          */
+typedef struct {
+    int32_t model;         /* 0: none (pinhole arithmetic, no table); 1: rational Brown-Conrady                              */
+    float   k[8];          /* k1 k2 p1 p2 k3 k4 k5 k6 (OpenCV's order); finite                                               */
+    int32_t iters;         /* rounds of the fixed-point inverse, <= 64; < 1: the default, 20                                 */
+    float   max_residual;  /* pixels: a ray whose forward image misses its pixel by more has no ray; finite; <= 0: 0.01      */
+} omds_depth_lens;
+OMDS_API int omds_depth_lens_rays(const omds_depth_camera* cam, const omds_depth_lens* lens, float* ab_out /* [nv*nu,2] */, float* r2_max_out,
+                                  int64_t* n_invalid_out);
+OMDS_API int omds_depth_points_lens(const omds_depth_camera* cam, const omds_depth_lens* lens /* NULL: none */,
+                                    const omds_depth_filter_spec* filt /* NULL: off */, const void* image, float* xyz_out, int64_t cap_points,
+                                    int64_t* n_valid_out, int64_t* n_rejected_out);
+OMDS_API int omds_depth_scene_memory_lens(const omds_cloud_spec* spec, const omds_scene_memory_spec* mem_spec,
+                                          const omds_depth_filter_spec* filt /* NULL: off */, const omds_depth_lens* lenses /* [n_cams] or NULL */,
+                                          const omds_depth_camera* cams, const void* const* images, int32_t n_cams,
+                                          const uint32_t* mem_in /* [cells] or NULL = empty */, uint32_t* mem_out /* [cells] */,
+                                          int32_t counts_out[4]);
+OMDS_API int omds_depth_scene_memory_flow_lens(const omds_cloud_spec* spec, const omds_scene_memory_spec* mem_spec,
+                                               const omds_cloud_track_spec* track, const omds_cloud_object_spec* obj,
+                                               const omds_depth_filter_spec* filt, const omds_depth_lens* lenses_prev,
+                                               const omds_depth_camera* cams_prev, const void* const* images_prev, int32_t n_cams_prev,
+                                               const uint8_t* keep_prev, const omds_depth_lens* lenses, const omds_depth_camera* cams,
+                                               const void* const* images, int32_t n_cams, const uint8_t* keep_now, const uint32_t* mem_in,
+                                               uint32_t* mem_out, int32_t counts_out[5], float* xyzr_out, float* vel_out, int32_t* age_out,
+                                               int32_t* label_out, int32_t* object_out, int32_t cap, int32_t* count_out,
+                                               int32_t* n_matched_out, int32_t* n_objects_out, int32_t* n_objects_matched_out);
+OMDS_API int omds_set_depth_lenses(omds_ctx* ctx, const omds_depth_lens* lenses /* [n] or NULL: off */, int32_t n);
+OMDS_API int omds_get_depth_lens_table(omds_ctx* ctx, int32_t i, float* ab_out /* [n_entries,2] or NULL */, float* r2_max_out,
+                                       int64_t* n_invalid_out, int64_t* n_entries_out);
 /* THE VELOCITY FILTER: SENSED SPHERE VELOCITIES SMOOTHED OVER FRAMES (new work).  Every velocity route above estimates from two frames
  * only, and omds_set_obstacle_motion extrapolates that one estimate over the whole horizon: at H = 32 a one-frame error is multiplied
  * by the horizon before pass 1 sees the predicted spheres.  The filter keeps one smoothed velocity per grid cell between calls and

@@ -94,6 +94,11 @@ class OmdsDepthFilterSpec(C.Structure):
     _fields_ = [("radius", C.c_int32), ("min_support", C.c_int32), ("edge_abs", C.c_float), ("edge_rel", C.c_float)]
 
 
+class OmdsDepthLens(C.Structure):
+    """omds_depth_lens (include/omds.h): the lens of a depth camera, OpenCV's rational Brown-Conrady model."""
+    _fields_ = [("model", C.c_int32), ("k", C.c_float * 8), ("iters", C.c_int32), ("max_residual", C.c_float)]
+
+
 class OmdsVelocityFilterSpec(C.Structure):
     """omds_velocity_filter_spec (include/omds.h): how the velocity routes blend a new sphere velocity against its predecessor."""
     _fields_ = [("alpha", C.c_float), ("alpha_object", C.c_float), ("max_jump", C.c_float)]
@@ -177,6 +182,20 @@ SIGNATURES = {
                                                                C.POINTER(OmdsCloudTrackSpec), C.POINTER(OmdsCloudObjectSpec),
                                                                C.POINTER(OmdsDepthCamera), C.POINTER(C.c_void_p), C.c_int32, C.c_int, F32P, I32P,
                                                                I32P, I32P, I32P, I32P]),
+    "omds_depth_lens_rays": (C.c_int, [C.POINTER(OmdsDepthCamera), C.POINTER(OmdsDepthLens), F32P, F32P, C.POINTER(C.c_int64)]),
+    "omds_depth_points_lens": (C.c_int, [C.POINTER(OmdsDepthCamera), C.POINTER(OmdsDepthLens), C.POINTER(OmdsDepthFilterSpec), C.c_void_p, F32P,
+                                         C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "omds_depth_scene_memory_lens": (C.c_int, [C.POINTER(OmdsCloudSpec), C.POINTER(OmdsSceneMemorySpec), C.POINTER(OmdsDepthFilterSpec),
+                                               C.POINTER(OmdsDepthLens), C.POINTER(OmdsDepthCamera), C.POINTER(C.c_void_p), C.c_int32, C.c_void_p,
+                                               C.c_void_p, I32P]),
+    "omds_depth_scene_memory_flow_lens": (C.c_int, [C.POINTER(OmdsCloudSpec), C.POINTER(OmdsSceneMemorySpec), C.POINTER(OmdsCloudTrackSpec),
+                                                    C.POINTER(OmdsCloudObjectSpec), C.POINTER(OmdsDepthFilterSpec), C.POINTER(OmdsDepthLens),
+                                                    C.POINTER(OmdsDepthCamera), C.POINTER(C.c_void_p), C.c_int32, C.c_void_p,
+                                                    C.POINTER(OmdsDepthLens), C.POINTER(OmdsDepthCamera), C.POINTER(C.c_void_p), C.c_int32,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, I32P, F32P, F32P, I32P, I32P, I32P, C.c_int32, I32P, I32P,
+                                                    I32P, I32P]),
+    "omds_set_depth_lenses": (C.c_int, [C.c_void_p, C.POINTER(OmdsDepthLens), C.c_int32]),
+    "omds_get_depth_lens_table": (C.c_int, [C.c_void_p, C.c_int32, F32P, F32P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "omds_velocity_filter_step": (C.c_int, [C.POINTER(OmdsCloudSpec), C.POINTER(OmdsCloudTrackSpec), C.POINTER(OmdsVelocityFilterSpec), I32P, I32P,
                                             F32P, I32P, I32P, C.c_int32, F32P, I32P, I32P]),
     "omds_set_velocity_filter": (C.c_int, [C.c_void_p, C.POINTER(OmdsVelocityFilterSpec)]),

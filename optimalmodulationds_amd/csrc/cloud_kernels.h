@@ -44,6 +44,18 @@ void omds_launch_cloud_count_filtered(hipStream_t s, DepthTable tab, int n_cams,
 void omds_launch_cloud_count_filtered(hipStream_t s, DepthTable tab, int n_cams, const CloudGrid& g, const DepthFilter& f, uint4* rec,
                                       unsigned* counters);
 
+// ... and the lens forms of the four (depth_lens_def.h), for a call in which some camera has a lens: lt.cam[i] beside tab.cam[i], its ab
+// the camera's ray table on the device or nullptr (pinhole arithmetic)
+void omds_launch_cloud_count(hipStream_t s, DepthTable tab, const DepthLensTable& lt, int n_cams, const CloudGrid& g, unsigned* count);
+void omds_launch_cloud_count(hipStream_t s, DepthTable tab, const DepthLensTable& lt, int n_cams, const CloudGrid& g, uint4* rec);
+void omds_launch_cloud_count_filtered(hipStream_t s, DepthTable tab, const DepthLensTable& lt, int n_cams, const CloudGrid& g, const DepthFilter& f,
+                                      unsigned* count, unsigned* counters);
+void omds_launch_cloud_count_filtered(hipStream_t s, DepthTable tab, const DepthLensTable& lt, int n_cams, const CloudGrid& g, const DepthFilter& f,
+                                      uint4* rec, unsigned* counters);
+// The ray table of camera c (fx, fy: the camera's) under lens l: ab [nv * nu][2]; red [2], cleared by the caller, takes the bits of the
+// largest r2 of a valid ray and the pixels without a ray
+void omds_launch_depth_rays(hipStream_t s, const DepthCam& c, float fx, float fy, const DepthLens& l, float* ab, unsigned* red);
+
 // The ordered compactions, one per item space: the kept items to out (and what goes with them) in item order, at most cap of them
 // written; sums [blocks of the item space + 1] is scratch, and sums[cloud_compaction_blocks(n)] holds the number of kept items after.
 // ... the cells of g with min_points points and more (count / rec padded with zeros to cloud_padded_cells): their spheres, cap = g.max_spheres
@@ -85,6 +97,11 @@ void omds_launch_scene_memory(hipStream_t s, DepthTable tab, const SceneMemCams&
 // ... the same pass with the counts read out of the records rec (the .x of each; padded with zeros like count)
 void omds_launch_scene_memory(hipStream_t s, DepthTable tab, const SceneMemCams& ks, int n_cams, const CloudGrid& g, const SceneMem& sm,
                               const uint4* rec, const unsigned* mem_in, unsigned* mem_out, unsigned* counters);
+// ... and both with the lens table of the call: the verdicts of a camera with a lens go through its forward model
+void omds_launch_scene_memory(hipStream_t s, DepthTable tab, const DepthLensTable& lt, const SceneMemCams& ks, int n_cams, const CloudGrid& g,
+                              const SceneMem& sm, const unsigned* count, const unsigned* mem_in, unsigned* mem_out, unsigned* counters);
+void omds_launch_scene_memory(hipStream_t s, DepthTable tab, const DepthLensTable& lt, const SceneMemCams& ks, int n_cams, const CloudGrid& g,
+                              const SceneMem& sm, const uint4* rec, const unsigned* mem_in, unsigned* mem_out, unsigned* counters);
 // Memory and velocities in one call (scene_memory_flow_def.h).  One more ordered compaction: of the n spheres of the final list (their
 // cells in cells) those whose cell has min_points points and more in the records now, in list order: the cell to cell, the index in
 // the final list to idx; sums as above

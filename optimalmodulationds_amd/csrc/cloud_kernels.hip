@@ -211,9 +211,22 @@ __device__ inline int depth_pixel_cell(const DepthCam& c, const CloudGrid& g, in
     return cloud_cell(g, w[0], w[1], w[2]);
 }
 
-// the cells of item `item` of camera d: cell[t] (-1: no point) and, when REC, k[t][3] of cloud_cell_sub
+// ... and of a pixel with the ray (a, b) of its camera's lens (depth_lens_def.h), which the caller has found valid
 template <bool REC>
-__device__ inline void depth_item_cells(const DepthCamDev& d, const CloudGrid& g, long long item, int* cell, unsigned (*k)[3]) {
+__device__ inline int depth_ray_cell(const DepthCam& c, const CloudGrid& g, float a, float b, float z, unsigned* k) {
+    float w[3];
+    depth_point_ray(c, a, b, z, w);
+    if (REC) return cloud_cell_sub(g, w[0], w[1], w[2], k);
+    return cloud_cell(g, w[0], w[1], w[2]);
+}
+
+// the cells of item `item` of camera d: cell[t] (-1: no point) and, when REC, k[t][3] of cloud_cell_sub.  LENS: lc is the camera's
+// entry of the lens table; with lc->ab the run's four rays come from it -- entry iv * nu + j0 + t, 8 bytes each: two 16-byte loads
+// where a pair starts at an even entry and lies whole inside the row, else 8-byte loads of the entries inside the row (the last run of
+// the last row ends the table) -- and a pixel without a ray gives no point
+template <bool REC, bool LENS = false>
+__device__ inline void depth_item_cells(const DepthCamDev& d, const CloudGrid& g, long long item, int* cell, unsigned (*k)[3],
+                                        const DepthLensCam* lc = nullptr) {
     const DepthCam& c = d.c;
     const int iv = (int)(item / d.runs), j0 = (int)(item % d.runs) * DEPTH_RUN;
     const int v = iv * c.step;
@@ -248,6 +261,28 @@ __device__ inline void depth_item_cells(const DepthCamDev& d, const CloudGrid& g
                 z[t] = have[t] ? p[(long long)t * c.step] : 0.f;
             }
         }
+    }
+    if (LENS && lc->ab) {
+        const long long e0 = (long long)iv * c.nu + j0;
+        const float2* rp = reinterpret_cast<const float2*>(lc->ab) + e0;
+        float2 ray[DEPTH_RUN];
+        for (int t = 0; t < DEPTH_RUN; t += 2) {
+            ray[t] = ray[t + 1] = make_float2(0.f, 0.f);
+            if (j0 + t + 1 < c.nu && ((e0 + t) & 1) == 0) {
+                const float4 w = *reinterpret_cast<const float4*>(rp + t);
+                ray[t] = make_float2(w.x, w.y);
+                ray[t + 1] = make_float2(w.z, w.w);
+            } else {
+                if (j0 + t < c.nu) ray[t] = rp[t];
+                if (j0 + t + 1 < c.nu) ray[t + 1] = rp[t + 1];
+            }
+        }
+        for (int t = 0; t < DEPTH_RUN; ++t) {
+            cell[t] = -1;
+            if (!have[t] || !depth_gate(c, z[t]) || ray[t].x != ray[t].x) continue;
+            cell[t] = depth_ray_cell<REC>(c, g, ray[t].x, ray[t].y, z[t], k[t]);
+        }
+        return;
     }
     for (int t = 0; t < DEPTH_RUN; ++t) {
         cell[t] = -1;
@@ -288,8 +323,8 @@ template <> struct DepthAcc<true> {
 // change to the rounds, to DepthAcc or to the field bound is a change to both; the contention extremes of tests/test_gpu_depth.py (every
 // pixel in one cell, two cells, more cells in a wave than rounds) go through this one there and through the other in
 // tests/test_gpu_depth_filter.py.
-template <bool REC>
-__device__ inline void depth_count(const DepthTable& tab, const CloudGrid& g, void* buf) {
+template <bool REC, bool LENS = false>   // LENS: lt is the lens table of the call, beside tab
+__device__ inline void depth_count(const DepthTable& tab, const CloudGrid& g, void* buf, const DepthLensTable* lt = nullptr) {
     typedef DepthAcc<REC> Acc;
     typedef typename Acc::T T;
     const DepthCamDev& d = tab.cam[blockIdx.y];
@@ -298,7 +333,7 @@ __device__ inline void depth_count(const DepthTable& tab, const CloudGrid& g, vo
         const long long item = base + threadIdx.x;
         int cell[DEPTH_RUN] = {-1, -1, -1, -1};
         unsigned k[DEPTH_RUN][3] = {};
-        if (item < d.items) depth_item_cells<REC>(d, g, item, cell, k);
+        if (item < d.items) depth_item_cells<REC, LENS>(d, g, item, cell, k, LENS ? &lt->cam[blockIdx.y] : nullptr);
         T acc[DEPTH_RUN];
         for (int t = 0; t < DEPTH_RUN; ++t) acc[t] = Acc::one(k[t]);
         for (int t = 1; t < DEPTH_RUN; ++t)
@@ -445,8 +480,11 @@ __device__ inline void filt_stage(const DepthCam& c, const void* image, int tu0,
 }
 
 // counters[0] += pixels the filter keeps, counters[1] += pixels it rejects: integers, reduced per wave, one atomic each
-template <bool REC, int R>
-__device__ inline void depth_count_filt(const DepthTable& tab, const CloudGrid& g, const DepthFilter& f, void* buf, unsigned* counters) {
+// LENS: lt is the lens table of the call; a pixel the filter keeps whose camera has a lens takes its ray from the table (entry
+// jv * nu + ju: a kept pixel lies inside the image) and, when it has none, gives no point and is counted neither as kept nor as rejected
+template <bool REC, int R, bool LENS = false>
+__device__ inline void depth_count_filt(const DepthTable& tab, const CloudGrid& g, const DepthFilter& f, void* buf, unsigned* counters,
+                                        const DepthLensTable* lt = nullptr) {
     constexpr int S = filt_stride(R), RH = FILT_TH + 2 * R;
     __shared__ float tile[2][RH * S];
     const DepthCamDev& d = tab.cam[blockIdx.y];
@@ -467,6 +505,13 @@ __device__ inline void depth_count_filt(const DepthTable& tab, const CloudGrid& 
             const float* at = own + j;
             if (!depth_filter_keep(f, R, z, [&](int a, int b) { return at[b * S + a]; })) {
                 ++rejected;
+                continue;
+            }
+            if (LENS && lt->cam[blockIdx.y].ab) {
+                const float2 ray = reinterpret_cast<const float2*>(lt->cam[blockIdx.y].ab)[(long long)(tv0 + ly) * c.nu + tu0 + lx + j];
+                if (ray.x != ray.x) continue;
+                ++kept;
+                cell[j] = depth_ray_cell<REC>(c, g, ray.x, ray.y, z, k[j]);
                 continue;
             }
             ++kept;
@@ -498,6 +543,54 @@ __global__ __launch_bounds__(CLOUD_NT) void k_depth_count(DepthTable tab, CloudG
 }
 __global__ __launch_bounds__(CLOUD_NT) void k_depth_count_rec(DepthTable tab, CloudGrid g, uint4* __restrict__ rec) {
     depth_count<true>(tab, g, rec);
+}
+
+// ---- the lens of a depth camera (depth_lens_def.h) -------------------------------------------------------------------------------------
+// The four counting kernels again, with the lens table of the call by value beside the camera table: launched only when some camera of
+// the call has a lens, so that the kernels above stay the kernels they are.  A camera without a lens (ab == nullptr; the branch is
+// uniform over the workgroup, blockIdx.y being the camera) runs the pinhole arithmetic
+__global__ __launch_bounds__(CLOUD_NT) void k_depth_count_lens(DepthTable tab, DepthLensTable lt, CloudGrid g, unsigned* __restrict__ count) {
+    depth_count<false, true>(tab, g, count, &lt);
+}
+__global__ __launch_bounds__(CLOUD_NT) void k_depth_count_rec_lens(DepthTable tab, DepthLensTable lt, CloudGrid g, uint4* __restrict__ rec) {
+    depth_count<true, true>(tab, g, rec, &lt);
+}
+template <int R>
+__global__ __launch_bounds__(CLOUD_NT) void k_depth_count_filt_lens(DepthTable tab, DepthLensTable lt, CloudGrid g, DepthFilter f,
+                                                                    unsigned* __restrict__ count, unsigned* __restrict__ counters) {
+    depth_count_filt<false, R, true>(tab, g, f, count, counters, &lt);
+}
+template <int R>
+__global__ __launch_bounds__(CLOUD_NT) void k_depth_count_filt_rec_lens(DepthTable tab, DepthLensTable lt, CloudGrid g, DepthFilter f,
+                                                                        uint4* __restrict__ rec, unsigned* __restrict__ counters) {
+    depth_count_filt<true, R, true>(tab, g, f, rec, counters, &lt);
+}
+
+// The ray table of one camera: one lane per visited pixel runs the definition and makes one 8-byte store; a pixel without a ray is
+// (NaN, NaN).  red[0] takes the largest r2 of a valid ray as an integer maximum on the float's bits (non-negative, so the order of the
+// bits is the order of the values), red[1] the pixels without a ray: both reduced per wave, then one integer atomic each.  Every lane
+// reaches the cross-lane steps
+__device__ inline unsigned wave_max(unsigned v) {
+    for (int d = 32; d > 0; d >>= 1) v = max(v, (unsigned)__shfl_xor(v, d, 64));
+    return v;
+}
+__global__ __launch_bounds__(CLOUD_NT) void k_depth_rays(DepthCam c, float fx, float fy, DepthLens l, float2* __restrict__ ab, long long n,
+                                                         unsigned* __restrict__ red) {
+    const long long i = (long long)blockIdx.x * CLOUD_NT + threadIdx.x;
+    unsigned bits = 0u, invalid = 0u;
+    if (i < n) {
+        const int iv = (int)(i / c.nu), iu = (int)(i % c.nu);
+        float a, b;
+        if (depth_lens_ray(c, fx, fy, l, iu * c.step, iv * c.step, &a, &b)) bits = __float_as_uint(depth_lens_r2(a, b));
+        else invalid = 1u;
+        ab[i] = make_float2(a, b);
+    }
+    bits = wave_max(bits);
+    invalid = wave_sum(invalid);
+    if ((threadIdx.x & 63) == 0) {
+        if (bits) atomicMax(red, bits);
+        if (invalid) atomicAdd(red + 1, invalid);
+    }
 }
 
 // ---- the scene memory of the depth route (scene_memory_def.h) ----------------------------------------------------------------------
@@ -542,6 +635,40 @@ __global__ __launch_bounds__(CLOUD_NT) void k_scene_memory(DepthTable tab, Scene
             for (int j = 0; j < CLOUD_ITEMS; ++j) {
                 int what = -1;
                 out[j] = base + j < g.n_cells ? scene_memory_cell(g, sm, cams, ks, n_cams, base + j, n[j], m[j], &what) : 0u;
+                for (int k = 0; k < 4; ++k) tally[k] += what == k ? 1u : 0u;
+            }
+        }
+        *reinterpret_cast<uint4*>(mem_out + base) = make_uint4(out[0], out[1], out[2], out[3]);
+    }
+    for (int k = 0; k < 4; ++k) {
+        const unsigned sum = wave_sum(tally[k]);
+        if ((threadIdx.x & 63) == 0 && sum) atomicAdd(counters + k, sum);
+    }
+}
+
+// ... and its lens form (depth_lens_def.h), launched only when some camera of the call has a lens: the same pass with the lens table by
+// value beside the camera table, the verdicts through scene_memory_cell<true>.  A kernel of its own for the reason above
+template <class N>
+__global__ __launch_bounds__(CLOUD_NT) void k_scene_memory_lens(DepthTable tab, DepthLensTable lt, SceneMemCams ks, int n_cams, CloudGrid g, SceneMem sm,
+                                                                const N* __restrict__ count, const unsigned* __restrict__ mem_in,
+                                                                unsigned* __restrict__ mem_out, int groups, unsigned* __restrict__ counters) {
+    const TableCams cams{tab};
+    unsigned tally[4] = {0u, 0u, 0u, 0u};
+    for (int i = blockIdx.x * CLOUD_NT + threadIdx.x; i < groups; i += gridDim.x * CLOUD_NT) {
+        const int base = i * CLOUD_ITEMS;
+        const uint4 n4 = scene_memory_counts(count, base);
+        const uint4 m4 = mem_in ? *reinterpret_cast<const uint4*>(mem_in + base) : make_uint4(0u, 0u, 0u, 0u);
+        const unsigned n[CLOUD_ITEMS] = {n4.x, n4.y, n4.z, n4.w}, m[CLOUD_ITEMS] = {m4.x, m4.y, m4.z, m4.w};
+        unsigned out[CLOUD_ITEMS];
+        if ((m4.x | m4.y | m4.z | m4.w) == 0u) {
+            for (int j = 0; j < CLOUD_ITEMS; ++j) {
+                out[j] = (base + j < g.n_cells && n[j] >= g.min_points) ? 1u : 0u;
+                tally[SCENE_MEM_SEEN] += out[j];
+            }
+        } else {
+            for (int j = 0; j < CLOUD_ITEMS; ++j) {
+                int what = -1;
+                out[j] = base + j < g.n_cells ? scene_memory_cell<true>(g, sm, cams, ks, n_cams, base + j, n[j], m[j], &what, &lt) : 0u;
                 for (int k = 0; k < 4; ++k) tally[k] += what == k ? 1u : 0u;
             }
         }
@@ -1160,6 +1287,35 @@ void omds_launch_cloud_count(hipStream_t s, DepthTable tab, int n_cams, const Cl
     hipLaunchKernelGGL(k_depth_count_rec, grid, dim3(CLOUD_NT), 0, s, tab, g, rec);
 }
 
+// the lens forms: the same grids, the lens table beside the camera table
+void omds_launch_cloud_count(hipStream_t s, DepthTable tab, const DepthLensTable& lt, int n_cams, const CloudGrid& g, unsigned* count) {
+    const dim3 grid = depth_blocks(tab, n_cams);
+    hipLaunchKernelGGL(k_depth_count_lens, grid, dim3(CLOUD_NT), 0, s, tab, lt, g, count);
+}
+void omds_launch_cloud_count(hipStream_t s, DepthTable tab, const DepthLensTable& lt, int n_cams, const CloudGrid& g, uint4* rec) {
+    const dim3 grid = depth_blocks(tab, n_cams);
+    hipLaunchKernelGGL(k_depth_count_rec_lens, grid, dim3(CLOUD_NT), 0, s, tab, lt, g, rec);
+}
+void omds_launch_cloud_count_filtered(hipStream_t s, DepthTable tab, const DepthLensTable& lt, int n_cams, const CloudGrid& g, const DepthFilter& f,
+                                      unsigned* count, unsigned* counters) {
+    const dim3 grid = depth_filt_blocks(tab, n_cams);
+    with_radius(f.radius, [&](auto R) {
+        hipLaunchKernelGGL((k_depth_count_filt_lens<decltype(R)::value>), grid, dim3(CLOUD_NT), 0, s, tab, lt, g, f, count, counters);
+    });
+}
+void omds_launch_cloud_count_filtered(hipStream_t s, DepthTable tab, const DepthLensTable& lt, int n_cams, const CloudGrid& g, const DepthFilter& f,
+                                      uint4* rec, unsigned* counters) {
+    const dim3 grid = depth_filt_blocks(tab, n_cams);
+    with_radius(f.radius, [&](auto R) {
+        hipLaunchKernelGGL((k_depth_count_filt_rec_lens<decltype(R)::value>), grid, dim3(CLOUD_NT), 0, s, tab, lt, g, f, rec, counters);
+    });
+}
+void omds_launch_depth_rays(hipStream_t s, const DepthCam& c, float fx, float fy, const DepthLens& l, float* ab, unsigned* red) {
+    const long long n = depth_visited(c);
+    hipLaunchKernelGGL(k_depth_rays, dim3((unsigned)((n + CLOUD_NT - 1) / CLOUD_NT)), dim3(CLOUD_NT), 0, s, c, fx, fy, l, reinterpret_cast<float2*>(ab), n,
+                       red);
+}
+
 void omds_launch_cloud_compact_cells(hipStream_t s, const unsigned* count, const CloudGrid& g, float4* out, unsigned* sums) {
     compact(s, CellSrc{count, g, out}, g.n_cells, g.max_spheres, sums);
 }
@@ -1181,6 +1337,20 @@ void omds_launch_scene_memory(hipStream_t s, DepthTable tab, const SceneMemCams&
     const int groups = (int)(cloud_padded_cells(g) / CLOUD_ITEMS);   // a multiple of CLOUD_NT
     const unsigned blocks = std::min((unsigned)(groups / CLOUD_NT), MEM_MAX_BLOCKS);
     hipLaunchKernelGGL(k_scene_memory<uint4>, dim3(blocks), dim3(CLOUD_NT), 0, s, tab, ks, n_cams, g, sm, rec, mem_in, mem_out, groups, counters);
+}
+void omds_launch_scene_memory(hipStream_t s, DepthTable tab, const DepthLensTable& lt, const SceneMemCams& ks, int n_cams, const CloudGrid& g,
+                              const SceneMem& sm, const unsigned* count, const unsigned* mem_in, unsigned* mem_out, unsigned* counters) {
+    const int groups = (int)(cloud_padded_cells(g) / CLOUD_ITEMS);   // a multiple of CLOUD_NT
+    const unsigned blocks = std::min((unsigned)(groups / CLOUD_NT), MEM_MAX_BLOCKS);
+    hipLaunchKernelGGL(k_scene_memory_lens<unsigned>, dim3(blocks), dim3(CLOUD_NT), 0, s, tab, lt, ks, n_cams, g, sm, count, mem_in, mem_out, groups,
+                       counters);
+}
+void omds_launch_scene_memory(hipStream_t s, DepthTable tab, const DepthLensTable& lt, const SceneMemCams& ks, int n_cams, const CloudGrid& g,
+                              const SceneMem& sm, const uint4* rec, const unsigned* mem_in, unsigned* mem_out, unsigned* counters) {
+    const int groups = (int)(cloud_padded_cells(g) / CLOUD_ITEMS);   // a multiple of CLOUD_NT
+    const unsigned blocks = std::min((unsigned)(groups / CLOUD_NT), MEM_MAX_BLOCKS);
+    hipLaunchKernelGGL(k_scene_memory_lens<uint4>, dim3(blocks), dim3(CLOUD_NT), 0, s, tab, lt, ks, n_cams, g, sm, rec, mem_in, mem_out, groups,
+                       counters);
 }
 void omds_launch_cloud_compact_seen(hipStream_t s, const uint4* now, const CloudGrid& g, const int* cells, int n, int* cell, int* idx,
                                     unsigned* sums) {

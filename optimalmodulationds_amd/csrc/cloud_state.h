@@ -73,6 +73,27 @@ struct VelFilterKey {
     void set(const CloudGrid& g, const VelFilter& o) { grid.set(g); f = o; n_cells = g.n_cells; }
 };
 
+// One camera slot of the context's lenses (omds_set_depth_lenses) and the ray table built for it.  The table is a CACHE under a bitwise
+// key of what a ray depends on -- the visited pixels, the intrinsics and the lens, never the pose or the image -- built by the first
+// depth call that needs it and rebuilt only when the key changes; it outlives the lens being turned off and comes back into use when
+// the same camera and lens return
+struct DepthLensSlot {
+    bool on = false;              // camera i of a depth call has this lens
+    DepthLens lens = {};          // behind its checks, while on
+    bool have = false;            // a table is stored, built under the key below
+    int width = 0, height = 0, step = 0;
+    float intr[4] = {0.f, 0.f, 0.f, 0.f};   // fx, fy, cx, cy
+    DepthLens built = {};
+    DevBuf<float> ab;             // [entries][2]
+    int64_t entries = 0;          // nv * nu
+    float r2_max = 0.f;           // ... fetched behind the build
+    int64_t n_invalid = 0;
+    bool same(const DepthCam& c, const float* k, const DepthLens& l) const {
+        return have && width == c.width && height == c.height && step == c.step && std::memcmp(intr, k, 16) == 0 &&
+               std::memcmp(&built, &l, sizeof(l)) == 0;
+    }
+};
+
 // What a context keeps for the obstacle focus (obstacle_focus.hip): omds_ctx::focus.  While `on`, the scene in force is a subset of the
 // MASTER stored here, and idx says which.  Every buffer is allocated at the first focus call and grown with the master.
 struct FocusState {
@@ -139,6 +160,9 @@ struct CloudState {
     DepthFilter filter = {};          // behind its checks, while filter_on
     DevBuf<unsigned> filtCounts;      // [2] pixels the filter kept and rejected in the call under way
     int64_t filter_stats[2] = {0, 0}; // ... of the last depth call that reached its counting pass; 0, 0 when no filter ran
+    // ... the lenses (omds_set_depth_lenses): context state that every depth call consults; no key of anything stored
+    DepthLensSlot lens[OMDS_DEPTH_MAX_CAMERAS];
+    DevBuf<unsigned> lensRed;         // [2] the bits of r2_max and the pixels without a ray of the table being built
     // ... the velocity filter (omds_set_velocity_filter): context state that every velocity route consults, and per cell the record
     // (q_x, q_y, q_z, hits) of velocity_filter_def.h.  One of the two buffers holds the stored state, the other is written; a
     // successful filtered call with a previous frame makes its own the stored one.  A buffer is all zero outside the cells it last

@@ -11,7 +11,7 @@
 //   - "No return" (U16 raw 0) and "outside the image" are both written as z_n = NaN, and an F32 NaN element is one already: NaN fails
 //     the one comparison, which is the whole test for either format.
 #pragma once
-#include "depth_def.h"
+#include "depth_lens_def.h"
 
 // an omds_depth_filter_spec behind its checks: what the kernels take by value
 struct DepthFilter {
@@ -63,8 +63,9 @@ OMDS_CLOUD_FN bool depth_filter_keep(const DepthFilter& f, int radius, float z, 
 }
 
 // Visited pixel (iu, iv) of a host image: 0 = omds_depth_points drops it, 1 = kept (its point in w), 2 = kept there and rejected by the
-// filter (w untouched).  f == nullptr: no filter
-inline int depth_filtered_pixel(const DepthCam& c, const DepthFilter* f, const void* image, int iu, int iv, float* w) {
+// filter (w untouched).  f == nullptr: no filter.  rays (depth_lens_def.h: the table of the camera's lens; nullptr: no lens): the point
+// lies on the pixel's ray, and 3 = kept by both but the pixel has no ray (w untouched)
+inline int depth_filtered_pixel(const DepthCam& c, const DepthFilter* f, const void* image, int iu, int iv, float* w, const float* rays = nullptr) {
     const int u = iu * c.step, v = iv * c.step;
     const float z = depth_filter_z(c, image, (long long)v * c.pitch + u);
     if (!depth_gate(c, z)) return 0;   // NaN: a U16 0 fails here like every other value the gate drops
@@ -75,6 +76,12 @@ inline int depth_filtered_pixel(const DepthCam& c, const DepthFilter* f, const v
             return depth_filter_z(c, image, (long long)y * c.step * c.pitch + (long long)x * c.step);
         });
         if (!keep) return 2;
+    }
+    if (rays) {
+        const float* ab = rays + 2 * ((long long)iv * c.nu + iu);
+        if (ab[0] != ab[0]) return 3;
+        depth_point_ray(c, ab[0], ab[1], z, w);
+        return 1;
     }
     depth_point(c, u, v, z, w);
     return 1;
@@ -107,5 +114,41 @@ inline int depth_points_filtered_host(const omds_depth_camera* cam, const omds_d
         }
     *n_valid_out = valid;
     *n_rejected_out = rejected;
+    return OMDS_OK;
+}
+
+// omds_depth_points_lens without its argument messages: depth_points_filtered_host with xc = a z, yc = b z from the pixel's ray.  A
+// pixel that passes the gate and the filter but has no ray is three NaNs, neither valid nor rejected.  lens == nullptr or model 0:
+// depth_points_filtered_host itself
+inline int depth_points_lens_host(const omds_depth_camera* cam, const omds_depth_lens* lens, const omds_depth_filter_spec* filt, const void* image,
+                                  float* xyz_out, int64_t cap_points, int64_t* n_valid_out, int64_t* n_rejected_out, std::string* err) {
+    auto fail = [&](const char* m) { if (err) *err = m; return (int)OMDS_ERR_INVALID_ARG; };
+    DepthLens l;
+    if (int rc = depth_lens_resolve(lens, &l, err)) return rc;
+    if (l.model == 0) return depth_points_filtered_host(cam, filt, image, xyz_out, cap_points, n_valid_out, n_rejected_out, err);
+    DepthCam c;
+    DepthFilter f;
+    if (int rc = depth_resolve_camera(cam, &c, err)) return rc;
+    if (filt)
+        if (int rc = depth_filter_resolve(filt, &f, err)) return rc;
+    if (!image || !xyz_out || !n_valid_out || (filt && !n_rejected_out))
+        return fail("omds_depth_points_lens: null image, xyz_out or n_valid_out (with a filter: or n_rejected_out)");
+    if (cap_points < depth_visited(c)) return fail("omds_depth_points_lens: cap_points is smaller than the visited pixels, ceil(H / step) * ceil(W / step)");
+    std::vector<float> rays((size_t)depth_visited(c) * 2);
+    float r2_max;
+    int64_t n_invalid;
+    depth_lens_table_host(c, cam->fx, cam->fy, l, rays.data(), &r2_max, &n_invalid);
+    const float nan = std::nanf("");
+    int64_t valid = 0, rejected = 0;
+    float* out = xyz_out;
+    for (int iv = 0; iv < c.nv; ++iv)
+        for (int iu = 0; iu < c.nu; ++iu, out += 3) {
+            const int what = depth_filtered_pixel(c, filt ? &f : nullptr, image, iu, iv, out, rays.data());
+            if (what == 1) { ++valid; continue; }
+            if (what == 2) ++rejected;
+            out[0] = out[1] = out[2] = nan;
+        }
+    *n_valid_out = valid;
+    if (n_rejected_out) *n_rejected_out = rejected;
     return OMDS_OK;
 }

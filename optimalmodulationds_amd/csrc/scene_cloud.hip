@@ -19,6 +19,9 @@
 //             on T, the spheres of the final list whose cell was counted now, carried back to the whole list by one launch
 //   filter  : while the context has a depth filter, the counting pass of every depth call above is the filtered one
 //             (depth_filter_def.h): another kernel in the same place, and two counters fetched behind it
+//   lens    : while the context has lenses (depth_lens_def.h), a depth call in which some camera has one stages that camera's ray table
+//             (a cache of the context, built by k_depth_rays when its key changes) beside the images, and its counting pass and its
+//             memory pass are the lens forms of the same kernels; a call in which no camera has one enqueues what it always did
 //   smoothed: while the context has a velocity filter, every tracked route above blends its velocities against the state kept per
 //             cell (velocity_filter_def.h): one stage between the velocity stages and the install, which run unchanged
 #include "capi_internal.h"
@@ -33,6 +36,8 @@ struct DepthSource {
     int n_cams;
     int on_device;
     const DepthFilter* filt;                // the context's depth filter while it is on, else nullptr
+    float intr[OMDS_DEPTH_MAX_CAMERAS][4];  // fx, fy, cx, cy as the caller gave them (cam keeps 1 / fx and 1 / fy): the key of a ray table
+    bool lensed;                            // some camera of the call has a lens of the context's
 };
 struct PointSource {
     const float* xyz;
@@ -67,7 +72,8 @@ struct CloudCall {
 // What the stages of one call hand on
 struct CloudWork {
     const float* d_xyz = nullptr;   // the points on the device, or
-    DepthTable depth;               // ... the camera table of a depth call
+    DepthTable depth;               // ... the camera table of a depth call,
+    DepthLensTable lens;            // ... and while depth.lensed the lens table beside it
     int occupied = 0;               // cells with min_points points and more
     const float4* d_list = nullptr; // the final list so far: the candidates, behind the self-filter those it keeps
     const int* d_cell = nullptr;    // tracked or memory: the cell of every sphere of d_list, else nullptr
@@ -188,6 +194,32 @@ int reserve_vfilter(omds_ctx* ctx, const CloudCall& c) {
     return OMDS_OK;
 }
 
+// the ray table of a camera under the lens of slot t: built on the context's stream when the slot holds none under this key, and then
+// r2_max and the pixels without a ray fetched behind it (synchronises; a one-off per camera and lens)
+int lens_table(omds_ctx* ctx, const DepthCam& cam, const float* intr, DepthLensSlot& t) {
+    CloudState& s = ctx->cloud;
+    if (t.same(cam, intr, t.lens)) return OMDS_OK;
+    const size_t n = (size_t)depth_visited(cam);
+    if (t.ab.count() < n * 2 || s.lensRed.count() < 2) CK(hipStreamSynchronize(ctx->stream));
+    t.have = false;
+    CK(t.ab.reserve(n * 2));
+    CK(s.lensRed.reserve(2));
+    CK(hipMemsetAsync(s.lensRed, 0, 2 * 4, ctx->stream));
+    omds_launch_depth_rays(ctx->stream, cam, intr[0], intr[1], t.lens, t.ab, s.lensRed);
+    CK(hipGetLastError());
+    unsigned red[2] = {0u, 0u};
+    CK(hipMemcpyAsync(red, s.lensRed, 2 * 4, hipMemcpyDeviceToHost, ctx->stream));
+    CK(hipStreamSynchronize(ctx->stream));
+    std::memcpy(&t.r2_max, &red[0], 4);
+    t.n_invalid = (int64_t)red[1];
+    t.entries = (int64_t)n;
+    t.width = cam.width; t.height = cam.height; t.step = cam.step;
+    std::memcpy(t.intr, intr, 16);
+    t.built = t.lens;
+    t.have = true;
+    return OMDS_OK;
+}
+
 // ---- stage the points: the caller's device memory as it is, host memory through a staging buffer of the context (a host array by
 // one asynchronous copy, host images by one each)
 int stage_points(omds_ctx* ctx, const CloudCall& c, CloudWork& w) {
@@ -224,6 +256,14 @@ int stage_points(omds_ctx* ctx, const CloudCall& c, CloudWork& w) {
         CK(hipMemcpyAsync(s.depthImg.get() + offset[i], src.images[i], bytes[i], hipMemcpyHostToDevice, ctx->stream));
         d.image = s.depthImg.get() + offset[i];
     }
+    if (!src.lensed) return OMDS_OK;
+    std::memset(static_cast<void*>(&w.lens), 0, sizeof(w.lens));   // ab == nullptr: pinhole
+    for (int i = 0; i < src.n_cams; ++i) {
+        DepthLensSlot& t = s.lens[i];
+        if (!t.on) continue;
+        if (int rc = lens_table(ctx, src.cam[i], src.intr[i], t)) return rc;
+        w.lens.cam[i] = DepthLensCam{t.lens, t.r2_max, t.ab.get()};
+    }
     return OMDS_OK;
 }
 
@@ -255,6 +295,8 @@ int count_into(omds_ctx* ctx, const CloudCall& c, CloudWork& w, T* into) {
     CK(hipMemsetAsync(into, 0, cloud_padded_cells(c.g) * sizeof(T), ctx->stream));
     if (c.memory) CK(hipMemsetAsync(s.memCounts, 0, SCENE_MEM_COUNTS * 4, ctx->stream));
     if (!c.images) omds_launch_cloud_count(ctx->stream, w.d_xyz, (long long)c.src.n_points, c.g, into);
+    else if (c.depth.lensed && !c.filter()) omds_launch_cloud_count(ctx->stream, w.depth, w.lens, c.depth.n_cams, c.g, into);
+    else if (c.depth.lensed) omds_launch_cloud_count_filtered(ctx->stream, w.depth, w.lens, c.depth.n_cams, c.g, *c.filter(), into, s.filtCounts);
     else if (!c.filter()) omds_launch_cloud_count(ctx->stream, w.depth, c.depth.n_cams, c.g, into);
     else omds_launch_cloud_count_filtered(ctx->stream, w.depth, c.depth.n_cams, c.g, *c.filter(), into, s.filtCounts);
     if (!c.memory) {
@@ -263,7 +305,8 @@ int count_into(omds_ctx* ctx, const CloudCall& c, CloudWork& w, T* into) {
     }
     w.mem_stored = s.memKey.same(c.g, c.sm) ? s.mem.kept().get() : nullptr;
     if ((rc = prof_begin(ctx))) return rc;   // omds_prof_enable: a memory route's dominant kernel is k_scene_memory
-    omds_launch_scene_memory(ctx->stream, w.depth, c.ks, c.depth.n_cams, c.g, c.sm, into, w.mem_stored, s.mem.next(), s.memCounts);
+    if (c.depth.lensed) omds_launch_scene_memory(ctx->stream, w.depth, w.lens, c.ks, c.depth.n_cams, c.g, c.sm, into, w.mem_stored, s.mem.next(), s.memCounts);
+    else omds_launch_scene_memory(ctx->stream, w.depth, c.ks, c.depth.n_cams, c.g, c.sm, into, w.mem_stored, s.mem.next(), s.memCounts);
     if ((rc = prof_end(ctx, c.g.n_cells, 0.0, "k_scene_memory"))) return rc;
     omds_launch_cloud_compact_cells(ctx->stream, s.mem.next().get(), c.g, s.cand, s.candCell, s.sums);
     return OMDS_OK;
@@ -592,6 +635,12 @@ int scene_from_images(omds_ctx* ctx, CloudCall& c, bool memory, const omds_scene
     c.depth.filt = ctx->cloud.filter_on ? &ctx->cloud.filter : nullptr;
     if (int rc = resolve_depth_source(ctx, c.who, cams, c.depth)) return rc;
     for (int i = 0; memory && i < n_cams; ++i) c.ks.k[i] = scene_memory_camera(cams[i], c.depth.cam[i]);
+    c.depth.lensed = false;
+    for (int i = 0; i < n_cams; ++i) {
+        const float intr[4] = {cams[i].fx, cams[i].fy, cams[i].cx, cams[i].cy};
+        std::memcpy(c.depth.intr[i], intr, 16);
+        if (ctx->cloud.lens[i].on) c.depth.lensed = true;
+    }
     c.q_now = q_now;
     c.out = out;
     return scene_from_cloud(ctx, c);
@@ -627,6 +676,64 @@ int omds_depth_points(const omds_depth_camera* cam, const void* image, float* xy
 int omds_depth_points_filtered(const omds_depth_camera* cam, const omds_depth_filter_spec* filt, const void* image, float* xyz_out,
                                int64_t cap_points, int64_t* n_valid_out, int64_t* n_rejected_out) {
     return depth_points_filtered_host(cam, filt, image, xyz_out, cap_points, n_valid_out, n_rejected_out, &g_create_err);
+}
+
+int omds_depth_lens_rays(const omds_depth_camera* cam, const omds_depth_lens* lens, float* ab_out, float* r2_max_out, int64_t* n_invalid_out) {
+    return depth_lens_rays_host(cam, lens, ab_out, r2_max_out, n_invalid_out, &g_create_err);
+}
+
+int omds_depth_points_lens(const omds_depth_camera* cam, const omds_depth_lens* lens, const omds_depth_filter_spec* filt, const void* image,
+                           float* xyz_out, int64_t cap_points, int64_t* n_valid_out, int64_t* n_rejected_out) {
+    return depth_points_lens_host(cam, lens, filt, image, xyz_out, cap_points, n_valid_out, n_rejected_out, &g_create_err);
+}
+
+int omds_depth_scene_memory_lens(const omds_cloud_spec* spec, const omds_scene_memory_spec* mem_spec, const omds_depth_filter_spec* filt,
+                                 const omds_depth_lens* lenses, const omds_depth_camera* cams, const void* const* images, int32_t n_cams,
+                                 const uint32_t* mem_in, uint32_t* mem_out, int32_t counts_out[4]) {
+    return scene_memory_lens_host(spec, mem_spec, filt, lenses, cams, images, n_cams, mem_in, mem_out, counts_out, &g_create_err);
+}
+
+int omds_depth_scene_memory_flow_lens(const omds_cloud_spec* spec, const omds_scene_memory_spec* mem_spec, const omds_cloud_track_spec* track,
+                                      const omds_cloud_object_spec* obj, const omds_depth_filter_spec* filt, const omds_depth_lens* lenses_prev,
+                                      const omds_depth_camera* cams_prev, const void* const* images_prev, int32_t n_cams_prev,
+                                      const uint8_t* keep_prev, const omds_depth_lens* lenses, const omds_depth_camera* cams,
+                                      const void* const* images, int32_t n_cams, const uint8_t* keep_now, const uint32_t* mem_in, uint32_t* mem_out,
+                                      int32_t counts_out[5], float* xyzr_out, float* vel_out, int32_t* age_out, int32_t* label_out,
+                                      int32_t* object_out, int32_t cap, int32_t* count_out, int32_t* n_matched_out, int32_t* n_objects_out,
+                                      int32_t* n_objects_matched_out) {
+    return scene_memory_flow_host(spec, mem_spec, track, obj, filt, cams_prev, images_prev, n_cams_prev, keep_prev, cams, images, n_cams, keep_now,
+                                  mem_in, mem_out, counts_out, xyzr_out, vel_out, age_out, label_out, object_out, cap, count_out, n_matched_out,
+                                  n_objects_out, n_objects_matched_out, &g_create_err, lenses_prev, lenses);
+}
+
+int omds_set_depth_lenses(omds_ctx* ctx, const omds_depth_lens* lenses, int32_t n) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    CloudState& s = ctx->cloud;
+    REQUIRE(n >= 0 && n <= OMDS_DEPTH_MAX_CAMERAS, OMDS_ERR_INVALID_ARG, "omds_set_depth_lenses: need 0 <= n <= 8");
+    if (!lenses) n = 0;
+    DepthLens l[OMDS_DEPTH_MAX_CAMERAS];
+    for (int i = 0; i < n; ++i)
+        if (int rc = depth_lens_resolve(lenses + i, &l[i], &ctx->err)) return rc;   // the stored lenses stay as they were
+    for (int i = 0; i < OMDS_DEPTH_MAX_CAMERAS; ++i) {
+        s.lens[i].on = i < n && l[i].model != 0;
+        if (s.lens[i].on) s.lens[i].lens = l[i];
+    }
+    return OMDS_OK;
+}
+
+int omds_get_depth_lens_table(omds_ctx* ctx, int32_t i, float* ab_out, float* r2_max_out, int64_t* n_invalid_out, int64_t* n_entries_out) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    REQUIRE(i >= 0 && i < OMDS_DEPTH_MAX_CAMERAS, OMDS_ERR_INVALID_ARG, "omds_get_depth_lens_table: need 0 <= i < 8");
+    const DepthLensSlot& t = ctx->cloud.lens[i];
+    if (n_entries_out) *n_entries_out = t.have ? t.entries : 0;
+    if (r2_max_out) *r2_max_out = t.have ? t.r2_max : 0.f;
+    if (n_invalid_out) *n_invalid_out = t.have ? t.n_invalid : 0;
+    if (ab_out && t.have && t.entries > 0) {
+        CK(hipSetDevice(ctx->dev));
+        CK(hipMemcpyAsync(ab_out, t.ab.get(), (size_t)t.entries * 8, hipMemcpyDeviceToHost, ctx->stream));
+        CK(hipStreamSynchronize(ctx->stream));
+    }
+    return OMDS_OK;
 }
 
 int omds_set_depth_filter(omds_ctx* ctx, const omds_depth_filter_spec* spec) {

@@ -42,7 +42,12 @@ inline SceneMemCam scene_memory_camera(const omds_depth_camera& c, const DepthCa
 // SILENT, the camera cannot tell (out of range, out of the image, no return, or a return at or before lim).  R is taken as orthonormal
 // and applied transposed (camera <- grid frame); it is not checked.  The range gate is NOT applied to the pixel's depth: a return
 // beyond z_max is still a return from behind the cell.
-OMDS_CLOUD_FN bool scene_memory_camera_free(const DepthCam& c, const SceneMemCam& k, const void* image, const SceneMem& sm, const float* p) {
+//   LENS (depth_lens_def.h), and lens->ab != nullptr: the camera has a lens.  The pixel the cell centre falls on comes from the forward
+//   model at (a, b) = (xc iz, yc iz); beyond the field of view of the camera's ray table, !(fmaf(a, a, b * b) <= r2_max), the
+//   polynomial may fold back and the verdict is SILENT, which never clears a cell.  From rintf on everything is the same.
+template <bool LENS = false>
+OMDS_CLOUD_FN bool scene_memory_camera_free(const DepthCam& c, const SceneMemCam& k, const void* image, const SceneMem& sm, const float* p,
+                                            const DepthLensCam* lens = nullptr) {
     const float big = 3.402823466e+38f;
     const float d0 = p[0] - c.pose[3];
     const float d1 = p[1] - c.pose[7];
@@ -57,8 +62,18 @@ OMDS_CLOUD_FN bool scene_memory_camera_free(const DepthCam& c, const SceneMemCam
     const float iz = 1.0f / zc;
     const float xn = xc * iz;
     const float yn = yc * iz;
-    const float uf = fmaf(xn, k.fx, c.cx);
-    const float vf = fmaf(yn, k.fy, c.cy);
+    float uf, vf;
+    if (LENS && lens->ab) {
+        const float r2 = depth_lens_r2(xn, yn);
+        if (!(r2 <= lens->r2_max)) return false;
+        float ad, bd;
+        depth_lens_forward(lens->lens, xn, yn, &ad, &bd);
+        uf = fmaf(ad, k.fx, c.cx);
+        vf = fmaf(bd, k.fy, c.cy);
+    } else {
+        uf = fmaf(xn, k.fx, c.cx);
+        vf = fmaf(yn, k.fy, c.cy);
+    }
     const float us = uf * k.istep;
     const float vs = vf * k.istep;
     const float ju = rintf(us);
@@ -97,16 +112,17 @@ enum { SCENE_MEM_SEEN = 0, SCENE_MEM_REMEMBERED = 1, SCENE_MEM_CLEARED = 2, SCEN
 
 // m' of cell `cell` with n points this call and the stored word m (steps 1 - 5 of omds.h); which of the four counters it adds to
 // goes to *what (-1: none, the cell was and stays empty)
-template <class Cams>   // cams.cam(i): the DepthCam of camera i, cams.image(i): element (0, 0) of its image
+// LENS: lenses->cam[i] is the lens of camera i (ab == nullptr: none)
+template <bool LENS = false, class Cams>   // cams.cam(i): the DepthCam of camera i, cams.image(i): element (0, 0) of its image
 OMDS_CLOUD_FN unsigned scene_memory_cell(const CloudGrid& g, const SceneMem& sm, const Cams& cams, const SceneMemCams& ks, int n_cams, int cell,
-                                         unsigned n, unsigned m, int* what) {
+                                         unsigned n, unsigned m, int* what, const DepthLensTable* lenses = nullptr) {
     if (n >= g.min_points) { *what = SCENE_MEM_SEEN; return 1u; }
     if (m == 0u) { *what = -1; return 0u; }
     float p[4];
     cloud_sphere(g, cell, p);
     bool is_free = false;
     for (int i = 0; i < n_cams; ++i)   // every camera is asked: the index stays uniform over a wave
-        if (scene_memory_camera_free(cams.cam(i), ks.k[i], cams.image(i), sm, p)) is_free = true;
+        if (scene_memory_camera_free<LENS>(cams.cam(i), ks.k[i], cams.image(i), sm, p, LENS ? &lenses->cam[i] : nullptr)) is_free = true;
     if (is_free) { *what = SCENE_MEM_CLEARED; return 0u; }
     const unsigned next = scene_memory_older(sm, m);
     *what = next ? SCENE_MEM_REMEMBERED : SCENE_MEM_EXPIRED;
@@ -115,10 +131,12 @@ OMDS_CLOUD_FN unsigned scene_memory_cell(const CloudGrid& g, const SceneMem& sm,
 
 // omds_depth_scene_memory[_filtered] without its argument messages, the one body of both: the counting pass of the depth route
 // (omds_depth_points[_filtered] + cloud_cell), then steps 1 - 5 per cell.  filt == nullptr: no depth filter.  The filter changes the
-// counts alone: the verdicts of step 3 read the raw images (a flying pixel is still a return).  No self-filter
-inline int scene_memory_host(const omds_cloud_spec* spec, const omds_scene_memory_spec* mem_spec, const omds_depth_filter_spec* filt,
-                             const omds_depth_camera* cams, const void* const* images, int32_t n_cams, const uint32_t* mem_in,
-                             uint32_t* mem_out, int32_t* counts_out, std::string* err) {
+// counts alone: the verdicts of step 3 read the raw images (a flying pixel is still a return).  No self-filter.  lenses [n_cams]
+// (omds_depth_scene_memory_lens; nullptr: none): the counts come from the points on the rays of depth_lens_def.h, and the verdicts of
+// a camera with a lens go through its forward model; a pixel without a ray is still a return for both
+inline int scene_memory_lens_host(const omds_cloud_spec* spec, const omds_scene_memory_spec* mem_spec, const omds_depth_filter_spec* filt,
+                                  const omds_depth_lens* lenses, const omds_depth_camera* cams, const void* const* images, int32_t n_cams,
+                                  const uint32_t* mem_in, uint32_t* mem_out, int32_t* counts_out, std::string* err) {
     auto fail = [&](const char* m) { if (err) *err = m; return (int)OMDS_ERR_INVALID_ARG; };
     CloudGrid g;
     SceneMem sm;
@@ -139,13 +157,27 @@ inline int scene_memory_host(const omds_cloud_spec* spec, const omds_scene_memor
         visited += depth_visited(cam[i]);
     }
     if (visited > OMDS_CLOUD_MAX_POINTS) return fail("omds_depth_scene_memory: more than 16 777 216 visited pixels in all");
+    DepthLensTable lt;
+    std::vector<float> rays[OMDS_DEPTH_MAX_CAMERAS];
+    bool lensed = false;
+    for (int i = 0; i < n_cams; ++i) {
+        lt.cam[i].ab = nullptr;
+        lt.cam[i].r2_max = 0.f;
+        if (int rc = depth_lens_resolve(lenses ? lenses + i : nullptr, &lt.cam[i].lens, err)) return rc;
+        if (lt.cam[i].lens.model == 0) continue;
+        rays[i].resize((size_t)depth_visited(cam[i]) * 2);
+        int64_t n_invalid;
+        depth_lens_table_host(cam[i], cams[i].fx, cams[i].fy, lt.cam[i].lens, rays[i].data(), &lt.cam[i].r2_max, &n_invalid);
+        lt.cam[i].ab = rays[i].data();
+        lensed = true;
+    }
     std::vector<uint32_t> count((size_t)g.n_cells, 0u);
     for (int i = 0; i < n_cams; ++i) {
         const DepthCam& c = cam[i];
         for (int iv = 0; iv < c.nv; ++iv)
             for (int iu = 0; iu < c.nu; ++iu) {
                 float w[3];
-                if (depth_filtered_pixel(c, filt ? &f : nullptr, images[i], iu, iv, w) != 1) continue;
+                if (depth_filtered_pixel(c, filt ? &f : nullptr, images[i], iu, iv, w, lt.cam[i].ab) != 1) continue;
                 const int cell = cloud_cell(g, w[0], w[1], w[2]);
                 if (cell >= 0) count[(size_t)cell]++;
             }
@@ -159,12 +191,19 @@ inline int scene_memory_host(const omds_cloud_spec* spec, const omds_scene_memor
     int32_t counts[4] = {0, 0, 0, 0};
     for (int cell = 0; cell < g.n_cells; ++cell) {
         int what;
-        mem_out[cell] = scene_memory_cell(g, sm, host_cams, ks, n_cams, cell, count[(size_t)cell], mem_in ? mem_in[cell] : 0u, &what);
+        const unsigned n = count[(size_t)cell], m = mem_in ? mem_in[cell] : 0u;
+        mem_out[cell] = lensed ? scene_memory_cell<true>(g, sm, host_cams, ks, n_cams, cell, n, m, &what, &lt)
+                               : scene_memory_cell(g, sm, host_cams, ks, n_cams, cell, n, m, &what);
         if (what >= 0) counts[what]++;
     }
     if (counts_out)
         for (int k = 0; k < 4; ++k) counts_out[k] = counts[k];
     return OMDS_OK;
+}
+inline int scene_memory_host(const omds_cloud_spec* spec, const omds_scene_memory_spec* mem_spec, const omds_depth_filter_spec* filt,
+                             const omds_depth_camera* cams, const void* const* images, int32_t n_cams, const uint32_t* mem_in,
+                             uint32_t* mem_out, int32_t* counts_out, std::string* err) {
+    return scene_memory_lens_host(spec, mem_spec, filt, nullptr, cams, images, n_cams, mem_in, mem_out, counts_out, err);
 }
 inline int scene_memory_host(const omds_cloud_spec* spec, const omds_scene_memory_spec* mem_spec, const omds_depth_camera* cams,
                              const void* const* images, int32_t n_cams, const uint32_t* mem_in, uint32_t* mem_out, int32_t* counts_out,

@@ -17,7 +17,7 @@ OMDS_CLOUD_FN bool scene_memory_flow_still(bool seen_now, unsigned m_stored) { r
 
 // the points of the images of one frame, one after the other (a dropped pixel: three NaNs, which the records drop)
 inline int scene_memory_flow_points(const omds_depth_filter_spec* filt, const omds_depth_camera* cams, const void* const* images, int32_t n_cams,
-                                    std::vector<float>& xyz, std::string* err) {
+                                    std::vector<float>& xyz, std::string* err, const omds_depth_lens* lenses = nullptr) {
     xyz.clear();
     for (int i = 0; i < n_cams; ++i) {
         DepthCam c;
@@ -25,7 +25,8 @@ inline int scene_memory_flow_points(const omds_depth_filter_spec* filt, const om
         const size_t at = xyz.size(), visited = (size_t)depth_visited(c);
         xyz.resize(at + visited * 3);
         int64_t valid = 0, rejected = 0;
-        if (int rc = depth_points_filtered_host(cams + i, filt, images[i], xyz.data() + at, (int64_t)visited, &valid, &rejected, err)) return rc;
+        if (int rc = depth_points_lens_host(cams + i, lenses ? lenses + i : nullptr, filt, images[i], xyz.data() + at, (int64_t)visited, &valid, &rejected, err))
+            return rc;
     }
     return OMDS_OK;
 }
@@ -46,7 +47,8 @@ inline int scene_memory_flow_check_frame(const omds_depth_camera* cams, const vo
     return OMDS_OK;
 }
 
-// omds_depth_scene_memory_flow without its argument messages.  A composition: scene_memory_host for the words, depth_points[_filtered]
+// omds_depth_scene_memory_flow[_lens] without its argument messages (lenses_prev [n_cams_prev], lenses [n_cams]: the lenses of
+// depth_lens_def.h, nullptr: none).  A composition: scene_memory_lens_host for the words, depth_points[_filtered | _lens]
 // for the points of both frames, cloud_objects_host / cloud_flow_cell_host on T, then the rule above per final sphere
 inline int scene_memory_flow_host(const omds_cloud_spec* spec, const omds_scene_memory_spec* mem_spec, const omds_cloud_track_spec* track,
                                   const omds_cloud_object_spec* obj, const omds_depth_filter_spec* filt, const omds_depth_camera* cams_prev,
@@ -54,7 +56,8 @@ inline int scene_memory_flow_host(const omds_cloud_spec* spec, const omds_scene_
                                   const void* const* images, int32_t n_cams, const uint8_t* keep_now, const uint32_t* mem_in, uint32_t* mem_out,
                                   int32_t* counts_out, float* xyzr_out, float* vel_out, int32_t* age_out, int32_t* label_out,
                                   int32_t* object_out, int32_t cap, int32_t* count_out, int32_t* n_matched_out, int32_t* n_objects_out,
-                                  int32_t* n_objects_matched_out, std::string* err) {
+                                  int32_t* n_objects_matched_out, std::string* err, const omds_depth_lens* lenses_prev = nullptr,
+                                  const omds_depth_lens* lenses = nullptr) {
     auto fail = [&](const char* m) { if (err) *err = m; return (int)OMDS_ERR_INVALID_ARG; };
     CloudGrid g;
     SceneMem sm;
@@ -79,7 +82,7 @@ inline int scene_memory_flow_host(const omds_cloud_spec* spec, const omds_scene_
     // 1, 2: the words, into a buffer of this call (mem_out may be mem_in, and a refusal below must leave it alone)
     std::vector<uint32_t> words((size_t)g.n_cells);
     int32_t counts[SCENE_MEM_COUNTS] = {0, 0, 0, 0, 0};
-    if (int rc = scene_memory_host(spec, mem_spec, filt, cams, images, n_cams, mem_in, words.data(), counts, err)) return rc;
+    if (int rc = scene_memory_lens_host(spec, mem_spec, filt, lenses, cams, images, n_cams, mem_in, words.data(), counts, err)) return rc;
     const int64_t candidates = (int64_t)counts[SCENE_MEM_SEEN] + counts[SCENE_MEM_REMEMBERED];
     if (candidates > g.max_spheres || candidates > cap) {
         *count_out = (int32_t)candidates;
@@ -104,9 +107,9 @@ inline int scene_memory_flow_host(const omds_cloud_spec* spec, const omds_scene_
     }
     // 3: T and what the tracked / objects call gives on it
     std::vector<float> xyz_now, xyz_prev;
-    if (int rc = scene_memory_flow_points(filt, cams, images, n_cams, xyz_now, err)) return rc;
+    if (int rc = scene_memory_flow_points(filt, cams, images, n_cams, xyz_now, err, lenses)) return rc;
     if (have_prev)
-        if (int rc = scene_memory_flow_points(filt, cams_prev, images_prev, n_cams_prev, xyz_prev, err)) return rc;
+        if (int rc = scene_memory_flow_points(filt, cams_prev, images_prev, n_cams_prev, xyz_prev, err, lenses_prev)) return rc;
     std::vector<uint32_t> now, prev;
     cloud_records_host(g, xyz_now.data(), (int64_t)(xyz_now.size() / 3), now);
     cloud_records_host(g, xyz_prev.data(), (int64_t)(xyz_prev.size() / 3), prev);

@@ -25,6 +25,7 @@ class Engine:
         self.K = 0
         self.n_obs = 0
         self.depth_filter = None      # the depth filter in force (set_depth_filter), None: off
+        self.depth_lenses = None      # the lenses in force (set_depth_lenses), None: off
         self.velocity_filter = None   # the velocity filter in force (set_velocity_filter), None: off
         self.C = 0
         self.config_version = 0      # bumped by every call that changes params / nominal DS / cost on the context (MPPI._push re-syncs on it)
@@ -217,6 +218,25 @@ class Engine:
         out = (C.c_int64 * 2)()
         self._ck(self.lib.omds_get_depth_filter_stats(self.h, out))
         return int(out[0]), int(out[1])
+
+    # ---- the lenses of the depth cameras (omds.h: THE LENS OF A DEPTH CAMERA) ---------------------------------------------------------
+    def set_depth_lenses(self, lenses):
+        """The context's lenses: a list of ``OmdsDepthLens`` (``depth_lens`` builds one; a coefficient sequence or a dict of its
+        arguments is taken too; None entries: no lens), lens i for camera i of every later depth call, or None to turn them off;
+        ``self.depth_lenses`` holds the list in force (None: off).  While set, every depth route reads unrectified images: every effect
+        is that of the cloud call on ``depth_points(image, cam, filter=, lens=)``.  A refused list raises and leaves the stored one."""
+        table, n = _lens_table(lenses)
+        self._ck(self.lib.omds_set_depth_lenses(self.h, table, n))
+        self.depth_lenses = None if not n else [_lens_of(l) for l in lenses]
+
+    def depth_lens_table(self, i):
+        """(ab [entries, 2], r2_max, n_invalid) of the ray table the context holds for camera slot ``i``, as the last depth call that
+        needed one left it: a pixel without a ray is (NaN, NaN).  No table: an empty array, 0.0, 0."""
+        n, r2, bad = C.c_int64(0), C.c_float(0.0), C.c_int64(0)
+        self._ck(self.lib.omds_get_depth_lens_table(self.h, int(i), None, None, None, C.byref(n)))
+        ab = np.zeros((max(int(n.value), 1), 2), np.float32)
+        self._ck(self.lib.omds_get_depth_lens_table(self.h, int(i), L.fptr(ab), C.addressof(r2), C.byref(bad), C.byref(n)))
+        return ab[:int(n.value)], float(np.float32(r2.value)), int(bad.value)
 
     # ---- the velocity filter (omds.h: THE VELOCITY FILTER) ------------------------------------------------------------------------------
     def set_velocity_filter(self, spec):
@@ -985,6 +1005,61 @@ def depth_filter_spec(radius=1, min_support=4, edge_abs=0.01, edge_rel=0.01):
     return f
 
 
+def depth_lens(k1=0.0, k2=0.0, p1=0.0, p2=0.0, k3=0.0, k4=0.0, k5=0.0, k6=0.0, iters=0, max_residual=0.0):
+    """An ``OmdsDepthLens``: OpenCV's rational Brown-Conrady model (plumb-bob: ``k4`` = ``k5`` = ``k6`` = 0).  ``k1`` may be a sequence of
+    4, 5 or 8 coefficients in OpenCV's order (k1 k2 p1 p2 [k3 [k4 k5 k6]]).  ``iters``: rounds of the fixed-point inverse (< 1: 20; at
+    most 64); ``max_residual``: a pixel whose ray's forward image misses it by more pixels than this gets no ray (<= 0: 0.01)."""
+    if np.ndim(k1) > 0:
+        seq = [float(v) for v in np.asarray(k1, np.float64).reshape(-1)]
+        if len(seq) not in (4, 5, 8):
+            raise ValueError(f"depth_lens: a coefficient sequence must hold 4, 5 or 8 values in OpenCV's order, got {len(seq)}")
+        k = seq + [0.0] * (8 - len(seq))
+    else:
+        k = [k1, k2, p1, p2, k3, k4, k5, k6]
+    l = L.OmdsDepthLens()
+    l.model, l.iters, l.max_residual = 1, int(iters), float(max_residual)
+    l.k[:] = [float(v) for v in k]
+    return l
+
+
+def _lens_of(lens):
+    """None, an ``OmdsDepthLens``, a dict of ``depth_lens``'s arguments or a coefficient sequence -> None or the lens"""
+    if lens is None or isinstance(lens, L.OmdsDepthLens):
+        return lens
+    return depth_lens(**lens) if isinstance(lens, dict) else depth_lens(lens)
+
+
+def _lens_table(lenses, n_cams=None, who="set_depth_lenses"):
+    """(array of ``OmdsDepthLens`` or None, its length) of a list of lenses with None entries (model 0); None or empty: (None, 0).
+    ``n_cams``: the list must have one entry per camera"""
+    if lenses is None:
+        return None, 0
+    lenses = [_lens_of(l) for l in lenses]
+    if n_cams is not None and len(lenses) != n_cams:
+        raise ValueError(f"{who}: {len(lenses)} lenses but {n_cams} cameras")
+    if not lenses:
+        return None, 0
+    table = (L.OmdsDepthLens * len(lenses))()
+    for i, l in enumerate(lenses):
+        if l is not None:
+            C.memmove(C.byref(table[i]), C.byref(l), C.sizeof(L.OmdsDepthLens))
+    return table, len(lenses)
+
+
+def depth_lens_rays(cam, lens):
+    """The ray table of a camera on the host (omds_depth_lens_rays, no GPU): (ab [visited, 2], r2_max, n_invalid) -- the normalised ray
+    of every visited pixel in row-major order, (NaN, NaN) where the inverse did not arrive within ``lens.max_residual`` pixels."""
+    lib = L.load()
+    lens = _lens_of(lens)
+    step = max(int(cam.step), 1)
+    visited = max(-(-int(cam.height) // step), 0) * max(-(-int(cam.width) // step), 0)
+    ab, r2, bad = np.zeros((max(visited, 1), 2), np.float32), C.c_float(0.0), C.c_int64(0)
+    rc = lib.omds_depth_lens_rays(C.byref(cam), None if lens is None else C.byref(lens), L.fptr(ab), C.addressof(r2), C.byref(bad))
+    if rc != 0:
+        raise L.OmdsError(f"omds_depth_lens_rays failed ({rc}): {lib.omds_last_error(None).decode()}")
+    return ab[:visited], float(np.float32(r2.value)), int(bad.value)
+
+
 def velocity_filter_spec(alpha=0.3, alpha_object=0.0, max_jump=0.0):
     """An ``OmdsVelocityFilterSpec``: a new sphere velocity enters the smoothed one with weight max(``alpha``, 1 / frames so far) (a
     running mean first, then an exponential one; ``alpha`` in (0, 1], 1: no smoothing); ``alpha_object`` (<= 0: ``alpha``) is the
@@ -1033,13 +1108,15 @@ def _filter_of(filter):
     return depth_filter_spec(**filter) if isinstance(filter, dict) else filter
 
 
-def depth_scene_memory(images, cams, spec, mem, mem_in=None, filter=None):
+def depth_scene_memory(images, cams, spec, mem, mem_in=None, filter=None, lenses=None):
     """The definition of the scene memory on the host (omds_depth_scene_memory[_filtered], no GPU, no self-filter): the depth images of
     one call and the stored words ``mem_in`` [cells] (uint32; None: all empty) -> (words [cells] uint32, (seen, remembered, cleared,
     expired)).  ``filter`` (an ``OmdsDepthFilterSpec`` or a dict of ``depth_filter_spec``'s arguments): the counts are those of the
-    filtered points."""
+    filtered points.  ``lenses`` (one per camera, entries may be None; omds_depth_scene_memory_lens): the counts are those of the points
+    on the lenses' rays, and the verdicts of a camera with a lens go through its forward model."""
     lib = L.load()
     table, addrs, n, _, keep = _depth_table("depth_scene_memory", images, cams)
+    ltable, _ = _lens_table(lenses, n, "depth_scene_memory")
     cells = max(int(spec.dims[0]), 0) * max(int(spec.dims[1]), 0) * max(int(spec.dims[2]), 0)
     if cells > 1 << 22:
         cells = 0                         # more than the library takes: it refuses the call
@@ -1050,7 +1127,10 @@ def depth_scene_memory(images, cams, spec, mem, mem_in=None, filter=None):
             raise ValueError(f"depth_scene_memory: mem_in must hold {cells} words, got {src.size}")
     out, counts = np.zeros(max(cells, 1), np.uint32), np.zeros(4, np.int32)
     filt = _filter_of(filter)
-    if filt is None:
+    if ltable is not None:
+        rc = lib.omds_depth_scene_memory_lens(C.byref(spec), C.byref(mem), None if filt is None else C.byref(filt), ltable, table, addrs, n,
+                                              None if src is None else src.ctypes.data, out.ctypes.data, L.iptr(counts))
+    elif filt is None:
         rc = lib.omds_depth_scene_memory(C.byref(spec), C.byref(mem), table, addrs, n, None if src is None else src.ctypes.data, out.ctypes.data,
                                          L.iptr(counts))
     else:
@@ -1062,20 +1142,24 @@ def depth_scene_memory(images, cams, spec, mem, mem_in=None, filter=None):
 
 
 def depth_scene_memory_flow(images, cams, spec, mem, track, objects=None, prev=None, mem_in=None, keep_prev=None, keep_now=None, filter=None,
-                            cap=None):
+                            cap=None, lenses=None):
     """The definition of ``Engine.set_obstacles_from_depth_memory_tracked`` on the host (omds_depth_scene_memory_flow, no GPU): the depth
     images of one call, the previous frame ``prev`` = (images, cams) standing for the stored record frame and component table (None: no
     previous frame) and the stored words ``mem_in`` (None: all empty) -> dict(words [cells] uint32, counts (seen, remembered, cleared,
     expired, self-forgotten), spheres [n, 4], vel [n, 3], age [n], label [n], object [n], n_matched, n_objects, n_objects_matched).
     ``keep_prev`` one flag per occupied cell of the previous frame, ``keep_now`` one per candidate cell (the cells with a word that is
     not 0, in cell order) stand for the self-filter; None: keep all.  More candidates than ``spec.max_spheres`` or ``cap`` raises; the
-    error carries ``counts`` and ``n_occupied``."""
+    error carries ``counts`` and ``n_occupied``.  ``lenses`` (one per camera, entries may be None; omds_depth_scene_memory_flow_lens): the
+    lenses of the cameras, of both frames."""
     lib = L.load()
     table, addrs, n, _, keep = _depth_table("depth_scene_memory_flow", images, cams)
+    ltable, _ = _lens_table(lenses, n, "depth_scene_memory_flow")
     if prev is None:
         ptable, paddrs, pn, pkeep = None, None, 0, None
     else:
         ptable, paddrs, pn, _, pkeep = _depth_table("depth_scene_memory_flow", prev[0], prev[1])
+        if ltable is not None and pn != n:
+            raise ValueError(f"depth_scene_memory_flow: lenses need the same cameras in both frames, got {pn} and {n}")
     cells = max(int(spec.dims[0]), 0) * max(int(spec.dims[1]), 0) * max(int(spec.dims[2]), 0)
     if cells > 1 << 22:
         cells = 0                         # more than the library takes: it refuses the call
@@ -1092,12 +1176,15 @@ def depth_scene_memory_flow(images, cams, spec, mem, track, objects=None, prev=N
     age, label, flag = (np.zeros(max(cap, 1), np.int32) for _ in range(3))
     cnt, matched, n_obj, n_acc = (np.zeros(1, np.int32) for _ in range(4))
     filt = _filter_of(filter)
-    rc = lib.omds_depth_scene_memory_flow(C.byref(spec), C.byref(mem), C.byref(track), None if objects is None else C.byref(objects),
-                                          None if filt is None else C.byref(filt), ptable, paddrs, pn,
-                                          None if kp is None or not kp.size else kp.ctypes.data, table, addrs, n,
-                                          None if kn is None or not kn.size else kn.ctypes.data, None if src is None else src.ctypes.data,
-                                          words.ctypes.data, L.iptr(counts), L.fptr(out), L.fptr(vel), L.iptr(age), L.iptr(label), L.iptr(flag),
-                                          cap, L.iptr(cnt), L.iptr(matched), L.iptr(n_obj), L.iptr(n_acc))
+    head = (C.byref(spec), C.byref(mem), C.byref(track), None if objects is None else C.byref(objects), None if filt is None else C.byref(filt))
+    frames = ((ptable, paddrs, pn, None if kp is None or not kp.size else kp.ctypes.data),
+              (table, addrs, n, None if kn is None or not kn.size else kn.ctypes.data))
+    tail = (None if src is None else src.ctypes.data, words.ctypes.data, L.iptr(counts), L.fptr(out), L.fptr(vel), L.iptr(age), L.iptr(label),
+            L.iptr(flag), cap, L.iptr(cnt), L.iptr(matched), L.iptr(n_obj), L.iptr(n_acc))
+    if ltable is None:
+        rc = lib.omds_depth_scene_memory_flow(*head, *frames[0], *frames[1], *tail)
+    else:
+        rc = lib.omds_depth_scene_memory_flow_lens(*head, ltable if prev is not None else None, *frames[0], ltable, *frames[1], *tail)
     if rc != 0:
         e = L.OmdsError(f"omds_depth_scene_memory_flow failed ({rc}): {lib.omds_last_error(None).decode()}")
         e.counts = tuple(int(v) for v in counts)
@@ -1109,11 +1196,13 @@ def depth_scene_memory_flow(images, cams, spec, mem, track, objects=None, prev=N
                 n_objects_matched=int(n_acc[0]))
 
 
-def depth_points(image, cam, filter=None):
+def depth_points(image, cam, filter=None, lens=None):
     """The definition on the host (omds_depth_points, no GPU): one depth image (numpy ``uint16`` / ``float32``) -> (xyz [visited, 3],
     n_valid): the visited pixels in row-major order as points in the frame of the voxel grid, a dropped pixel as three NaNs (which
     the cloud calls drop), and how many were kept.  ``filter`` (an ``OmdsDepthFilterSpec`` or a dict of ``depth_filter_spec``'s
-    arguments; omds_depth_points_filtered): a pixel the depth filter rejects is three NaNs too -> (xyz, n_valid, n_rejected)."""
+    arguments; omds_depth_points_filtered): a pixel the depth filter rejects is three NaNs too -> (xyz, n_valid, n_rejected).
+    ``lens`` (an ``OmdsDepthLens``, a dict of ``depth_lens``'s arguments or a coefficient sequence; omds_depth_points_lens): the points lie
+    on the rays of the lens, and a kept pixel without a ray is three NaNs, counted neither as valid nor as rejected."""
     lib = L.load()
     c = L.OmdsDepthCamera()
     C.memmove(C.byref(c), C.byref(cam), C.sizeof(L.OmdsDepthCamera))
@@ -1124,6 +1213,14 @@ def depth_points(image, cam, filter=None):
     visited = max(-(-int(c.height) // step), 0) * max(-(-int(c.width) // step), 0)
     out, n_valid = np.zeros((max(visited, 1), 3), np.float32), C.c_int64(0)
     filt = _filter_of(filter)
+    lens = _lens_of(lens)
+    if lens is not None:
+        n_rejected = C.c_int64(0)
+        rc = lib.omds_depth_points_lens(C.byref(c), C.byref(lens), None if filt is None else C.byref(filt), addr, L.fptr(out), visited,
+                                        C.byref(n_valid), C.byref(n_rejected))
+        if rc != 0:
+            raise L.OmdsError(f"omds_depth_points_lens failed ({rc}): {lib.omds_last_error(None).decode()}")
+        return (out[:visited], int(n_valid.value)) + (() if filt is None else (int(n_rejected.value),))
     if filt is not None:
         n_rejected = C.c_int64(0)
         rc = lib.omds_depth_points_filtered(C.byref(c), C.byref(filt), addr, L.fptr(out), visited, C.byref(n_valid), C.byref(n_rejected))

@@ -216,11 +216,24 @@ class MPPI:
         ``self.cloud_matched``, ``self.cloud_objects[_matched]`` as there, ``moving_frame`` honoured), remembered spheres and seen
         ones that were occluded at the previous memory call stand still.  Without it, ``memory`` together with ``dt_frame`` /
         ``objects`` is the error it was.
+        ``lenses`` (a list, one ``engine.depth_lens`` per camera, entries may be None): sets the engine's lenses for this call
+        (Engine.set_depth_lenses) -- the images are unrectified, every pixel is deprojected along the ray of its camera's lens, and
+        everything is the cloud call on ``engine.depth_points(image, camera, filter=..., lens=...)``; the engine's lenses are what they
+        were before the call.  None (the default) leaves the call, and whatever lenses the engine has, as it is.  Works with every route.
         ``smooth``: as in ``update_obstacles_from_cloud``; the cloud and depth calls share the one filter and its history.
-        (``memory``, ``filter``, ``memory_motion`` and ``smooth`` are the keywords ``**route`` takes, default None / None / False / None:
-        the named keywords stay those of ``update_obstacles_from_cloud``.)"""
+        (``memory``, ``filter``, ``lenses``, ``memory_motion`` and ``smooth`` are the keywords ``**route`` takes, default None / None /
+        None / False / None: the named keywords stay those of ``update_obstacles_from_cloud``.)"""
         memory, filt, motion = route.pop("memory", None), route.pop("filter", None), bool(route.pop("memory_motion", False))
-        smooth = route.pop("smooth", None)
+        smooth, lenses = route.pop("smooth", None), route.pop("lenses", None)
+        if lenses is not None:
+            before = self._engine.depth_lenses
+            self._engine.set_depth_lenses(lenses)
+            try:
+                return self.update_obstacles_from_depth(images, cameras, voxel, lo, hi, radius, self_margin, min_points, max_spheres, dt_frame,
+                                                        reach, still, moving_frame, objects, link, min_cells, memory=memory, filter=filt,
+                                                        memory_motion=motion, smooth=smooth, **route)
+            finally:
+                self._engine.set_depth_lenses(before)
         if route:
             raise TypeError(f"update_obstacles_from_depth: unexpected keyword arguments {sorted(route)}")
         self._set_smooth("update_obstacles_from_depth", smooth, dt_frame)
