@@ -1,6 +1,7 @@
-// What the host stages of the scene from a point cloud or from depth images (scene_cloud.hip) need of cloud_kernels.hip: the sizes
-// they reserve buffers by, the camera table of the depth counting pass, and the launchers.  A launcher takes a stream and raw
-// pointers, enqueues, and waits for nothing.
+// What the host stages of the scene from a point cloud or from depth images (scene_cloud.hip) need of the cloud kernel files
+// (cloud_kernels.hip, depth_kernels.hip, scene_memory_kernels.hip, cloud_track_kernels.hip, velocity_filter_kernels.hip; what they
+// share on the device: cloud_device.h): the sizes they reserve buffers by, the camera table of the depth counting pass, and the
+// launchers, each defined beside its kernel.  A launcher takes a stream and raw pointers, enqueues, and waits for nothing.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -32,25 +33,17 @@ struct DepthTable {
 };
 
 // The counting pass, from P points xyz [P][3] or from the images of tab.cam[0 .. n_cams), into counts [cells] or into records [cells]
-// (both cleared by the caller)
+// (both cleared by the caller).  lt (depth_lens_def.h): nullptr when no camera of the call has a lens -- the pinhole kernels; else
+// lt->cam[i] beside tab.cam[i], its ab the camera's ray table on the device or nullptr (pinhole arithmetic) -- the lens forms
 void omds_launch_cloud_count(hipStream_t s, const float* xyz, long long P, const CloudGrid& g, unsigned* count);
 void omds_launch_cloud_count(hipStream_t s, const float* xyz, long long P, const CloudGrid& g, uint4* rec);
-void omds_launch_cloud_count(hipStream_t s, DepthTable tab, int n_cams, const CloudGrid& g, unsigned* count);
-void omds_launch_cloud_count(hipStream_t s, DepthTable tab, int n_cams, const CloudGrid& g, uint4* rec);
+void omds_launch_cloud_count(hipStream_t s, DepthTable tab, const DepthLensTable* lt, int n_cams, const CloudGrid& g, unsigned* count);
+void omds_launch_cloud_count(hipStream_t s, DepthTable tab, const DepthLensTable* lt, int n_cams, const CloudGrid& g, uint4* rec);
 // ... from the pixels of the images the depth filter f keeps (depth_filter_def.h); counters [2], cleared by the caller, takes the pixels
 // the filter kept and those it rejected
-void omds_launch_cloud_count_filtered(hipStream_t s, DepthTable tab, int n_cams, const CloudGrid& g, const DepthFilter& f, unsigned* count,
-                                      unsigned* counters);
-void omds_launch_cloud_count_filtered(hipStream_t s, DepthTable tab, int n_cams, const CloudGrid& g, const DepthFilter& f, uint4* rec,
-                                      unsigned* counters);
-
-// ... and the lens forms of the four (depth_lens_def.h), for a call in which some camera has a lens: lt.cam[i] beside tab.cam[i], its ab
-// the camera's ray table on the device or nullptr (pinhole arithmetic)
-void omds_launch_cloud_count(hipStream_t s, DepthTable tab, const DepthLensTable& lt, int n_cams, const CloudGrid& g, unsigned* count);
-void omds_launch_cloud_count(hipStream_t s, DepthTable tab, const DepthLensTable& lt, int n_cams, const CloudGrid& g, uint4* rec);
-void omds_launch_cloud_count_filtered(hipStream_t s, DepthTable tab, const DepthLensTable& lt, int n_cams, const CloudGrid& g, const DepthFilter& f,
+void omds_launch_cloud_count_filtered(hipStream_t s, DepthTable tab, const DepthLensTable* lt, int n_cams, const CloudGrid& g, const DepthFilter& f,
                                       unsigned* count, unsigned* counters);
-void omds_launch_cloud_count_filtered(hipStream_t s, DepthTable tab, const DepthLensTable& lt, int n_cams, const CloudGrid& g, const DepthFilter& f,
+void omds_launch_cloud_count_filtered(hipStream_t s, DepthTable tab, const DepthLensTable* lt, int n_cams, const CloudGrid& g, const DepthFilter& f,
                                       uint4* rec, unsigned* counters);
 // The ray table of camera c (fx, fy: the camera's) under lens l: ab [nv * nu][2]; red [2], cleared by the caller, takes the bits of the
 // largest r2 of a valid ray and the pixels without a ray
@@ -91,16 +84,11 @@ void omds_launch_focus_path_select(hipStream_t s, const unsigned* best, const un
 
 // The scene memory (scene_memory_def.h).  mem_out [cloud_padded_cells]: the words of this call from the counts count and the stored
 // words mem_in (both padded with zeros; mem_in == nullptr: all empty); counters [SCENE_MEM_COUNTS], cleared by the caller, takes the
-// seen, remembered, cleared and expired cells
-void omds_launch_scene_memory(hipStream_t s, DepthTable tab, const SceneMemCams& ks, int n_cams, const CloudGrid& g, const SceneMem& sm,
-                              const unsigned* count, const unsigned* mem_in, unsigned* mem_out, unsigned* counters);
-// ... the same pass with the counts read out of the records rec (the .x of each; padded with zeros like count)
-void omds_launch_scene_memory(hipStream_t s, DepthTable tab, const SceneMemCams& ks, int n_cams, const CloudGrid& g, const SceneMem& sm,
-                              const uint4* rec, const unsigned* mem_in, unsigned* mem_out, unsigned* counters);
-// ... and both with the lens table of the call: the verdicts of a camera with a lens go through its forward model
-void omds_launch_scene_memory(hipStream_t s, DepthTable tab, const DepthLensTable& lt, const SceneMemCams& ks, int n_cams, const CloudGrid& g,
+// seen, remembered, cleared and expired cells.  lt as above: with it the verdicts of a camera with a lens go through its forward model
+void omds_launch_scene_memory(hipStream_t s, DepthTable tab, const DepthLensTable* lt, const SceneMemCams& ks, int n_cams, const CloudGrid& g,
                               const SceneMem& sm, const unsigned* count, const unsigned* mem_in, unsigned* mem_out, unsigned* counters);
-void omds_launch_scene_memory(hipStream_t s, DepthTable tab, const DepthLensTable& lt, const SceneMemCams& ks, int n_cams, const CloudGrid& g,
+// ... the same pass with the counts read out of the records rec (the .x of each; padded with zeros like count)
+void omds_launch_scene_memory(hipStream_t s, DepthTable tab, const DepthLensTable* lt, const SceneMemCams& ks, int n_cams, const CloudGrid& g,
                               const SceneMem& sm, const uint4* rec, const unsigned* mem_in, unsigned* mem_out, unsigned* counters);
 // Memory and velocities in one call (scene_memory_flow_def.h).  One more ordered compaction: of the n spheres of the final list (their
 // cells in cells) those whose cell has min_points points and more in the records now, in list order: the cell to cell, the index in

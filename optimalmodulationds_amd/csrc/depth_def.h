@@ -1,5 +1,5 @@
 // The DEFINITION of the points of a depth image (omds.h: omds_depth_points), stated once for the host entry point, the kernels
-// k_depth_count / k_depth_count_rec of cloud_kernels.hip and the stand-alone host build of tests/depth_host.cpp.  Like
+// k_depth_count / k_depth_count_rec of depth_kernels.hip and the stand-alone host build of tests/depth_host.cpp.  Like
 // point_cloud_def.h, which it builds on and leaves as it is: plain fp32, every operation of omds.h its own statement (one rounding
 // each; the translation units that include this are compiled without contraction across statements), fmaf written out.
 #pragma once

@@ -1,5 +1,5 @@
 // The DEFINITION of the depth filter (omds.h: omds_depth_points_filtered), stated once for the host entry points, the kernels
-// k_depth_count_filt / k_depth_count_filt_rec of cloud_kernels.hip and the stand-alone host build of tests/depth_filter_host.cpp.
+// k_depth_count_filt / k_depth_count_filt_rec of depth_kernels.hip and the stand-alone host build of tests/depth_filter_host.cpp.
 // Like depth_def.h, which it builds on and leaves as it is: plain fp32, every operation of omds.h its own statement (one rounding
 // each; the translation units that include this are compiled without contraction across statements), fmaf written out.
 //   A visited pixel (ju, jv) that omds_depth_points keeps at depth z stays iff at least min_support OTHER pixels of its window of

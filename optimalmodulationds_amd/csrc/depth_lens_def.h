@@ -1,5 +1,5 @@
 // The DEFINITION of the lens of a depth camera (omds.h: omds_depth_lens, omds_depth_lens_rays), stated once for the host entry points,
-// the kernel k_depth_rays and the lens forms of the counting kernels and of k_scene_memory in cloud_kernels.hip, and the stand-alone
+// the kernel k_depth_rays and the lens forms of the counting kernels and of k_scene_memory in depth_kernels.hip and scene_memory_kernels.hip, and the stand-alone
 // host build of tests/depth_lens_host.cpp.  Like depth_def.h, which it builds on and leaves as it is: plain fp32, every operation of
 // omds.h its own statement (one rounding each; the translation units that include this are compiled without contraction across
 // statements), fmaf written out.  The quotients num / den and den / num are the IEEE-rounded ones on both sides, as 1.0f / zc is in

@@ -1,5 +1,5 @@
 // The DEFINITION of the obstacle spheres of a depth point cloud (omds.h: omds_point_cloud_spheres), stated once for the host entry
-// point, the kernels of cloud_kernels.hip and the stand-alone host build of tests/cloud_host.cpp.  Nothing here needs a HIP header:
+// point, the kernels of cloud_kernels.hip and its sister files and the stand-alone host build of tests/cloud_host.cpp.  Nothing here needs a HIP header:
 // every function is plain fp32 arithmetic in which each operation named in omds.h is one rounding (the translation units that
 // include this are compiled without contraction across statements, csrc/Makefile).
 #pragma once

@@ -1,5 +1,5 @@
 // The DEFINITION of the sphere velocities of two successive point clouds (omds.h: omds_point_cloud_flow), stated once for the host
-// entry point, the kernels of cloud_kernels.hip and the stand-alone host build of tests/cloud_flow_host.cpp.  Like point_cloud_def.h,
+// entry point, the kernels of cloud_track_kernels.hip and the stand-alone host build of tests/cloud_flow_host.cpp.  Like point_cloud_def.h,
 // which it builds on and leaves as it is: plain fp32, every operation of omds.h its own statement (one rounding each; the
 // translation units that include this are compiled without contraction across statements), every sum an integer.
 #pragma once

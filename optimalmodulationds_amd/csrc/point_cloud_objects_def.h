@@ -1,5 +1,5 @@
 // The DEFINITION of the object velocities of two successive point clouds (omds.h: omds_point_cloud_object_flow), stated once for the
-// host entry point, the kernels of cloud_kernels.hip and the stand-alone host build of tests/cloud_objects_host.cpp.  It builds on
+// host entry point, the kernels of cloud_track_kernels.hip and the stand-alone host build of tests/cloud_objects_host.cpp.  It builds on
 // point_cloud_flow_def.h (the records, the per-cell fallback, the `still` rule): every sum an integer, the centroids and their
 // distance in fp64 and the velocity in fp32 with every operation of omds.h its own statement (one rounding each; the translation
 // units that include this are compiled without contraction across statements).

@@ -294,19 +294,17 @@ int count_into(omds_ctx* ctx, const CloudCall& c, CloudWork& w, T* into) {
     int rc;
     CK(hipMemsetAsync(into, 0, cloud_padded_cells(c.g) * sizeof(T), ctx->stream));
     if (c.memory) CK(hipMemsetAsync(s.memCounts, 0, SCENE_MEM_COUNTS * 4, ctx->stream));
+    const DepthLensTable* lens = c.depth.lensed ? &w.lens : nullptr;
     if (!c.images) omds_launch_cloud_count(ctx->stream, w.d_xyz, (long long)c.src.n_points, c.g, into);
-    else if (c.depth.lensed && !c.filter()) omds_launch_cloud_count(ctx->stream, w.depth, w.lens, c.depth.n_cams, c.g, into);
-    else if (c.depth.lensed) omds_launch_cloud_count_filtered(ctx->stream, w.depth, w.lens, c.depth.n_cams, c.g, *c.filter(), into, s.filtCounts);
-    else if (!c.filter()) omds_launch_cloud_count(ctx->stream, w.depth, c.depth.n_cams, c.g, into);
-    else omds_launch_cloud_count_filtered(ctx->stream, w.depth, c.depth.n_cams, c.g, *c.filter(), into, s.filtCounts);
+    else if (!c.filter()) omds_launch_cloud_count(ctx->stream, w.depth, lens, c.depth.n_cams, c.g, into);
+    else omds_launch_cloud_count_filtered(ctx->stream, w.depth, lens, c.depth.n_cams, c.g, *c.filter(), into, s.filtCounts);
     if (!c.memory) {
         compact_counted(ctx, c, into);
         return OMDS_OK;
     }
     w.mem_stored = s.memKey.same(c.g, c.sm) ? s.mem.kept().get() : nullptr;
     if ((rc = prof_begin(ctx))) return rc;   // omds_prof_enable: a memory route's dominant kernel is k_scene_memory
-    if (c.depth.lensed) omds_launch_scene_memory(ctx->stream, w.depth, w.lens, c.ks, c.depth.n_cams, c.g, c.sm, into, w.mem_stored, s.mem.next(), s.memCounts);
-    else omds_launch_scene_memory(ctx->stream, w.depth, c.ks, c.depth.n_cams, c.g, c.sm, into, w.mem_stored, s.mem.next(), s.memCounts);
+    omds_launch_scene_memory(ctx->stream, w.depth, lens, c.ks, c.depth.n_cams, c.g, c.sm, into, w.mem_stored, s.mem.next(), s.memCounts);
     if ((rc = prof_end(ctx, c.g.n_cells, 0.0, "k_scene_memory"))) return rc;
     omds_launch_cloud_compact_cells(ctx->stream, s.mem.next().get(), c.g, s.cand, s.candCell, s.sums);
     return OMDS_OK;

@@ -1,5 +1,5 @@
 // The DEFINITION of the scene memory of the depth route (omds.h: omds_depth_scene_memory), stated once for the host entry point, the
-// kernels k_scene_memory / k_scene_memory_forget of cloud_kernels.hip and the stand-alone host build of tests/scene_memory_host.cpp.
+// kernels k_scene_memory / k_scene_memory_forget of scene_memory_kernels.hip and the stand-alone host build of tests/scene_memory_host.cpp.
 // Like depth_def.h, which it builds on and leaves as it is: plain fp32, every operation of omds.h its own statement (one rounding
 // each; the translation units that include this are compiled without contraction across statements), fmaf written out.  The quotient
 // 1.0f / zc is the IEEE-rounded one on both sides: no fast division, no reciprocal intrinsic.

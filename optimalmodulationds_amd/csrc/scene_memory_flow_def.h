@@ -1,5 +1,5 @@
 // The DEFINITION of the depth route that keeps the scene memory AND the sphere velocities in one call (omds.h:
-// omds_depth_scene_memory_flow), stated once for the host entry point, the kernels of cloud_kernels.hip (SeenSrc, k_scene_memory_flow)
+// omds_depth_scene_memory_flow), stated once for the host entry point, the kernels of scene_memory_kernels.hip (SeenSrc, k_scene_memory_flow)
 // and the stand-alone host build of tests/scene_memory_flow_host.cpp.  It builds on scene_memory_def.h (the words), point_cloud_flow_def.h
 // (the records and the per-cell velocities) and point_cloud_objects_def.h (the components and the object velocities) and leaves them
 // as they are: it adds no arithmetic of its own, only which sphere keeps which result.

@@ -1,5 +1,5 @@
 // The DEFINITION of the velocity filter (omds.h: omds_velocity_filter_step), stated once for the host entry point, the kernels
-// k_vel_pred / k_vel_group / k_vel_blend of cloud_kernels.hip and the stand-alone host build of tests/velocity_filter_host.cpp.
+// k_vel_pred / k_vel_group / k_vel_blend of velocity_filter_kernels.hip and the stand-alone host build of tests/velocity_filter_host.cpp.
 // Like point_cloud_flow_def.h, which it builds on and leaves as it is: plain fp32, every operation of omds.h its own statement (one
 // rounding each; the translation units that include this are compiled without contraction across statements), every sum an integer.
 //   THE STATE: per grid cell four int32 (q_x, q_y, q_z, hits); hits == 0: no history; else q the smoothed velocity in 2^-16 m/s and

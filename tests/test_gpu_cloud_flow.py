@@ -1,5 +1,5 @@
 """Sphere velocities from successive point clouds on the device (include/omds.h: omds_set_obstacles_from_cloud_tracked;
-csrc/cloud_kernels.hip: k_cloud_count_rec, the cell indices through both compactions, k_cloud_flow) against the host definition
+csrc/cloud_kernels.hip: k_cloud_count_rec, the cell indices through both compactions; csrc/cloud_track_kernels.hip: k_cloud_flow) against the host definition
 (omds_point_cloud_flow, checked on its own in tests/test_cloud_flow_cpu.py) -- all bit for bit: the records are integer sums, the
 window search is integer, and the fp32 lines are one source for host and kernel.
 

@@ -1,5 +1,5 @@
 """Object velocities from successive point clouds on the device (include/omds.h: omds_set_obstacles_from_cloud_objects;
-csrc/cloud_kernels.hip: k_obj_slot, k_obj_union, k_obj_flatten, k_obj_sums, the component table through the ordered compaction,
+csrc/cloud_track_kernels.hip: k_obj_slot, k_obj_union, k_obj_flatten, k_obj_sums, the component table through the ordered compaction,
 k_obj_match, k_obj_apply) against the host definition (omds_point_cloud_object_flow, checked on its own in
 tests/test_cloud_objects_cpu.py) -- all bit for bit: components and their sums are integers, and the fp64 / fp32 lines are one source
 for host and kernel.

@@ -1,4 +1,4 @@
-"""The scene straight from depth images on the device (include/omds.h: omds_set_obstacles_from_depth; csrc/cloud_kernels.hip:
+"""The scene straight from depth images on the device (include/omds.h: omds_set_obstacles_from_depth; csrc/depth_kernels.hip:
 k_depth_count, k_depth_count_rec in front of the unchanged rest of the cloud calls).  The reference side of every comparison is a
 SECOND Engine that is given engine.depth_points(...) of every image, concatenated in camera order, through the existing cloud calls
 (checked on their own in tests/test_gpu_cloud*.py); the host definition of the points is checked in tests/test_depth_cpu.py.

@@ -1,4 +1,4 @@
-"""The depth filter on the device (include/omds.h: omds_set_depth_filter; csrc/cloud_kernels.hip: k_depth_count_filt,
+"""The depth filter on the device (include/omds.h: omds_set_depth_filter; csrc/depth_kernels.hip: k_depth_count_filt,
 k_depth_count_filt_rec in place of the counting kernels of the depth routes).  The reference side of every comparison is a SECOND
 Engine that is given engine.depth_points(image, cam, filter=...) of every image, concatenated in camera order, through the cloud
 calls -- for the memory route the host definition omds_depth_scene_memory_filtered iterated; the host definition itself is checked

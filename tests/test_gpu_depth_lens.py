@@ -1,5 +1,5 @@
-"""The lens of a depth camera on the device (include/omds.h: omds_set_depth_lenses; csrc/cloud_kernels.hip: k_depth_rays, the lens
-forms of the counting kernels and of k_scene_memory).  The reference side of every comparison is the host definition, which
+"""The lens of a depth camera on the device (include/omds.h: omds_set_depth_lenses; csrc/depth_kernels.hip: k_depth_rays, the lens
+forms of the counting kernels; csrc/scene_memory_kernels.hip: that of k_scene_memory).  The reference side of every comparison is the host definition, which
 tests/test_depth_lens_cpu.py checks: a SECOND Engine is given engine.depth_points(image, cam, filter=, lens=) of every image,
 concatenated in camera order, through the cloud calls; for the memory routes the host definitions omds_depth_scene_memory_lens and
 omds_depth_scene_memory_flow_lens iterated.  Everything is array for array and count for count.
@@ -263,7 +263,60 @@ def test_a_refused_call_leaves_scene_memory_frame_table_and_filters(pair):
     assert got[2] > 0, "the stored frame is frame 0's: frame 1 matches against it"
 
 
-# ---- 6. through the facade ---------------------------------------------------------------------------------------------------------------------
+# ---- 6. the contention extremes of the counting pass under a lens ------------------------------------------------------------------------------
+def contention_case(name):
+    """the three extremes of tests/test_gpu_depth.py (67 x 49 pixels: all in one cell, in two cells, more cells in a wave than the merge
+    has rounds) with the plumb-bob lens on the camera, so that k_depth_count_lens / k_depth_count_rec_lens read a ray table.  On the
+    narrow camera |a|, |b| <= 3.3e-4: the lens leaves every pixel its ray and its cell, so the originals' thresholds hold"""
+    from optimalmodulationds_amd.engine import depth_lens_rays
+    lens = lc.lens_of(lc.PLUMB)
+    if name == "speckle":
+        cam, img = gd.speckle()
+        box = dict(origin=(-1.5, -1.5, 0.5), voxel=0.05, dims=(60, 60, 40), max_spheres=8192)
+    else:
+        cam, img, box = gd.narrow_camera(), gd.one_cell_image() if name == "one-cell" else gd.two_cell_image(), gd.CELL_BOX
+    assert depth_lens_rays(cam, lens)[2] == 0, "the host definition gives every pixel of this camera a ray"
+    return cam, lens, img, box
+
+
+@pytest.mark.parametrize("name", ["one-cell", "two-cell", "speckle"])
+def test_contention_extremes_under_a_lens(pair, name):
+    """the cell counts pinned at n_valid and n_valid + 1 through min_points, as the pinhole tests pin them"""
+    e, ref = pair
+    cam, lens, img, box = contention_case(name)
+    n, near, far = 67 * 49, 1642, 1641           # 3 283 pixels; two cells: the even ones near
+    expect = {"one-cell": ((1, 1), (n, 1), (n + 1, 0)), "two-cell": ((1, 2), (far, 2), (near, 1), (near + 1, 0)),
+              "speckle": ((1, None), (2, None), (3, None))}[name]
+    for min_points, occupied in expect:
+        got = both(e, ref, [img], [cam], [lens], spec_of(**box, min_points=min_points), what=f"{name}, min_points {min_points}")
+        assert lens_points([img], [cam], [lens])[1] == n
+        if occupied is not None:
+            assert got == (occupied, occupied)
+        else:
+            assert got[0] > {1: 300, 2: 300, 3: 100}[min_points]
+    assert e.depth_lens_table(0)[0].shape == (n, 2) and e.depth_lens_table(0)[2] == 0
+
+
+@pytest.mark.parametrize("name", ["one-cell", "two-cell", "speckle"])
+def test_contention_extremes_under_a_lens_tracked(pair, name):
+    """... through the tracked call; the second frame is the first seen from a camera shifted by (10, -5, 15) mm, less than a cell: the
+    velocities come from the sums of the sub-cell offsets and must be the cloud route's bits"""
+    e, ref = pair
+    cam, lens, img, box = contention_case(name)
+    spec = spec_of(**box, min_points=2 if name == "speckle" else 100)
+    moved = dc.cam_of(67, 49, cam.fx, cam.fy, 33.0, 24.0, dc.pose_of(np.eye(3), (0.010, -0.005, 0.015)), U16, 0.001, 0.3, 4.0)
+    track = track_of(1, 0.1)
+    first = both(e, ref, [img], [cam], [lens], spec, track=track, what=name + " frame 1")
+    assert first[2] == -1
+    second = both(e, ref, [img], [moved], [lens], spec, track=track, what=name + " frame 2")
+    vel, have = e.get_obstacle_motion()
+    assert have and second[2] > 0.9 * second[0] > 0
+    if name != "speckle":
+        assert second[2] == second[0] == (1 if name == "one-cell" else 2)
+        assert np.allclose(vel[:second[0]], [0.1, -0.05, 0.15], atol=0.05), "about 10, -5, 15 mm in 0.1 s (offsets count in 1/256 cell)"
+
+
+# ---- 7. through the facade ---------------------------------------------------------------------------------------------------------------------
 def test_facade_takes_lenses_for_one_call():
     """update_obstacles_from_depth(lenses=) on plain, dt_frame= and memory=: what update_obstacles_from_cloud gives on the lens points,
     the memory definition iterated; the keyword is in force for its call only"""

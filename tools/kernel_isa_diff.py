@@ -2,12 +2,13 @@
 """Device assembly of two csrc directories, kernel by kernel (CPU only; hipcc cross-compiles).
 
     python tools/kernel_isa_diff.py PARENT_CSRC CHILD_CSRC [--flags "-DOMDS_TIMELINE"] [--files mlp_kernels tail_kernel]
+                                    [--alias "k_old<int>=k_new<int, bool>"]
 
 Every kernel translation unit of each side (a .hip file with a __global__) is compiled with the Makefile's CXXFLAGS plus
 --cuda-device-only -S into a scratch directory, the assembly is cut per kernel symbol, and each kernel is reported as
 "identical" or with instruction count, resource figures and spill counts of both sides.  Kernels are matched by name over all the
-translation units of a side, so one that moved to another file is compared with itself.  It diffs and counts; it looks for no
-instruction.  Exit status 1 when a kernel differs or exists on one side only.
+translation units of a side, so one that moved to another file is compared with itself; --alias pairs one that was renamed with
+its former name.  It diffs and counts; it looks for no instruction.  Exit status 1 when a kernel differs or exists on one side only.
 """
 import argparse
 import concurrent.futures
@@ -60,11 +61,15 @@ def kernels(asm):
 
 def demangle(sym):
     """k_exact<0, 1> for _Z7k_exactILi0ELi1EEv...; an enumerator prints as its value, so a kernel keeps its name when an int parameter
-    becomes an enum.  Without c++filt the symbol itself."""
+    becomes an enum; "> >" prints as ">>" (c++filt writes either, by how the template's parameters are declared).  Without c++filt the
+    symbol itself."""
     if not shutil.which("c++filt"):
         return sym
     name = subprocess.run(["c++filt", sym], capture_output=True, text=True).stdout.strip().replace("(anonymous namespace)::", "")
-    return re.sub(r"\(\w+\)(?=-?\d)", "", name).split("(")[0].removeprefix("void ")
+    name = re.sub(r"\(\w+\)(?=-?\d)", "", name).split("(")[0].removeprefix("void ")
+    while "> >" in name:
+        name = name.replace("> >", ">>")
+    return name
 
 
 def main():
@@ -75,7 +80,10 @@ def main():
     ap.add_argument("--files", nargs="*", help="translation units by stem (default: every .hip with a __global__)")
     ap.add_argument("--jobs", type=int, default=4)
     ap.add_argument("--scratch", help="keep the assembly in this directory instead of a temporary one")
+    ap.add_argument("--alias", action="append", default=[], metavar="OLD=NEW",
+                    help="pair the parent's kernel OLD with the child's NEW (demangled names): a kernel that was renamed")
     a = ap.parse_args()
+    alias = dict(pair.split("=", 1) for pair in a.alias)
     with tempfile.TemporaryDirectory() as tmp:
         if a.scratch:
             tmp = a.scratch
@@ -90,6 +98,8 @@ def main():
         for _, out, _ in jobs:
             side, stem = out.stem.split("_", 1)
             for sym, entry in kernels(out).items():
+                if side == "parent":
+                    sym = alias.get(sym, sym)
                 (old if side == "parent" else new)[sym] = entry
                 where.setdefault(sym, {})[side] = stem
         same = [s for s in old if s in new and old[s][0] == new[s][0]]

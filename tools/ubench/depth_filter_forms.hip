@@ -1,4 +1,4 @@
-// The two forms of the filtered counting pass of the depth routes (csrc/cloud_kernels.hip: k_depth_count_filt[_rec]) side by side, on
+// The two forms of the filtered counting pass of the depth routes (csrc/depth_kernels.hip: k_depth_count_filt[_rec]) side by side, on
 // one 640 x 480 U16 image in device memory, kernel times by HIP events.  EXPERIMENTS.md R27.
 //   tile   : the library's kernels -- a workgroup stages a tile of 32 x 32 visited pixels and its halo into LDS, the support test reads LDS
 //   direct : the form that was NOT kept, written here only -- today's launch shape (a lane takes a run of 4 pixels of a row, 256
@@ -15,7 +15,7 @@
 #include <cstring>
 #include <vector>
 
-#include "../../optimalmodulationds_amd/csrc/cloud_kernels.hip"
+#include "../../optimalmodulationds_amd/csrc/depth_kernels.hip"
 
 #define HIP_OK(expr)                                                                          \
     do {                                                                                      \
