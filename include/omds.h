@@ -79,6 +79,18 @@ typedef struct {
  * obstacles; not located); for A/B runs and the tests, which run small batches                                                    */
 #define OMDS_FLAG_BLOCK_TILES 64
 #define OMDS_BLOCK_TILES_MIN_PAIRS 131072
+/* THE SCHEDULE OF A PROPAGATE'S FULL STEPS (csrc/propagate_plan_def.h).  The rollouts of a batch do not depend on each
+ * other over the whole horizon, so the dense block-ordered step may run the batch as two halves on two streams, one half's tail and
+ * ordering launches under the other half's pass 1.  Either schedule computes the same bits: a row's chain never depends on its
+ * tile-mates, the tail is local to a rollout, and the key units and the obstacle order are picked on the whole batch either way.
+ * By default omds_propagate runs the two halves where each holds OMDS_BLOCK_TILES_MIN_PAIRS pairs and at least three full steps
+ * follow the shared first one (Franka shelf 1024 x 32: +4.0 %, EXPERIMENTS.md R35).  SERIAL_PROPAGATE keeps every launch of every
+ * step on one stream; PIPELINED_PROPAGATE runs the two halves wherever the dense route's compacting kernel runs and at least two full
+ * steps exist, at any batch size (A/B runs and the tests, which run small batches).  Both set: serial.  omds_get_pipeline_info
+ * reports what the last omds_propagate ran.  While omds_prof_enable is on, a step whose pass 1 is bracketed runs as one whole-batch
+ * launch in either case.                                                                                                          */
+#define OMDS_FLAG_SERIAL_PROPAGATE 128
+#define OMDS_FLAG_PIPELINED_PROPAGATE 256
 
 /* The constants the reference hard-codes inside propagate() (MPPI.py:117-217,277) and
  * LinDS (LinDS.py:9), as parameters; omds_default_params() fills the reference values.   */
@@ -1081,6 +1093,10 @@ OMDS_API int omds_screen_order_stats(omds_ctx* ctx, int64_t* reorders, int32_t* 
  * level L and k-chunks multiplied over it (of 8 positions; the last hidden level: of 16), averaged over the `tiles` tiles since
  * omds_set_mlp (NULL = skip).                                                                                                      */
 OMDS_API int omds_pass1_skip_stats(omds_ctx* ctx, int32_t* active, double* mean_units, double* mean_chunks, int n_levels, int64_t* tiles);
+/* The schedule of the last omds_propagate (OMDS_FLAG_SERIAL_PROPAGATE / OMDS_FLAG_PIPELINED_PROPAGATE above): parts = 2 when its full
+ * steps ran as the rollouts [0, split) on the context's stream and [split, n_traj) on its second stream, else parts = 1 and
+ * split = n_traj.  Either pointer may be NULL.  Before the first propagate: 1 part.                                                */
+OMDS_API int omds_get_pipeline_info(omds_ctx* ctx, int32_t* parts, int32_t* split);
 /* (The two test hooks that damage the screening inputs / force a tile shape are NOT part of this library: they are declared in
  * include/omds_test.h and exported by libomds_hip_test.so only.)                                                           */
 /* Diagnostic: the fp16 screening network alone on q [B,n] -> mindist [B,O] (the values the candidate selection sees). */

@@ -42,7 +42,9 @@ FLAG_DENSE_PASS1 = 8       # k_pass1 multiplies every k-chunk (omds.h: OMDS_FLAG
 FLAG_NATURAL_PASS1 = 16    # first step of a propagate from one state evaluated per rollout (omds.h: OMDS_FLAG_NATURAL_PASS1; same bits)
 FLAG_NATURAL_TILES = 32    # pass-1 tiles over consecutive rows instead of key-ordered rollout x obstacle blocks (omds.h: OMDS_FLAG_NATURAL_TILES; same bits)
 FLAG_BLOCK_TILES = 64      # the block order at every batch size, not only from 131 072 pairs on (omds.h: OMDS_FLAG_BLOCK_TILES; same bits)
-FLAG_TWO_KERNEL_STEP = 2   # keep few-obstacle scenes on k_pass1 + k_tail (omds.h: OMDS_FLAG_TWO_KERNEL_STEP)   # omds_config.flags
+FLAG_SERIAL_PROPAGATE = 128      # every launch of a propagate on one stream (omds.h: OMDS_FLAG_SERIAL_PROPAGATE; same bits)
+FLAG_PIPELINED_PROPAGATE = 256   # the dense step's full steps as two halves of the batch on two streams, at any batch size (omds.h; same bits)
+FLAG_TWO_KERNEL_STEP = 2  # keep few-obstacle scenes on k_pass1 + k_tail (omds.h: OMDS_FLAG_TWO_KERNEL_STEP)   # omds_config.flags
 # omds_params.variant / cost_terms bits (include/omds.h)
 VARIANT_KVAL_TIMES_ACT = 1
 VARIANT_NO_BASE_MASK = 2
@@ -253,6 +255,7 @@ SIGNATURES = {
     "omds_screen_fallback_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "omds_screen_order_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), I32P, C.c_int]),
     "omds_pass1_skip_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int64)]),
+    "omds_get_pipeline_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "omds_set_screening_sweep": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "omds_screen_sweep_hist": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int, C.c_int]),
     "omds_screen_sweep_stats": (C.c_int, [C.c_void_p, I32P, C.POINTER(C.c_int64), F32P]),

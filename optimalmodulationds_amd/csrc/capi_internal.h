@@ -11,6 +11,7 @@
 #include <dlfcn.h>
 
 #include "omds_internal.h"
+#include "propagate_plan_def.h"
 
 // message of a call that has no context to keep it in (omds_last_error(NULL)); defined in context.hip
 extern thread_local std::string g_create_err;
@@ -89,6 +90,10 @@ inline int prof_begin(omds_ctx* ctx) {
     CK(hipEventRecord(p.start[p.used], ctx->stream));
     return OMDS_OK;
 }
+// the next prof_begin will open a bracket / a launch of the dominant kernel that is counted but, by the caller's choice, not bracketed
+// (enqueue_dense: only a step that runs alone on the device is bracketed)
+inline bool prof_due(const omds_ctx* ctx) { return ctx->prof_on && ctx->prof_seen % ctx->prof_stride == 0; }
+inline void prof_pass(omds_ctx* ctx) { if (ctx->prof_on) ctx->prof_seen++; }
 inline int prof_end(omds_ctx* ctx, int64_t rows, double flops = -1.0, const char* kernel = "k_pass1") {
     if (!ctx->prof_on || !ctx->prof_open) return OMDS_OK;
     ctx->prof_open = false;
@@ -212,7 +217,7 @@ int screen_finish_propagate(omds_ctx* ctx, const ScreenPlan& plan);
 int screened_verdict(omds_ctx* ctx, StepArgs& a);
 
 // ---- propagate.hip ------------------------------------------------------------------------------------------------------------
-enum class StepRoute { Unfused, SmallScene, Dense, Emit, ScreenList, ScreenMatrix };
+// (StepRoute: propagate_plan_def.h)
 bool small_step_wanted(omds_ctx* ctx);
 bool fused_step_available(const omds_ctx* ctx);   // the fused tail kernels take this context (else Unfused, never screened)
 StepRoute choose_route(omds_ctx* ctx, bool screen_requested);

@@ -51,6 +51,12 @@ static void free_all(omds_ctx* ctx) {
     if (ctx->ev_in_means) (void)hipEventDestroy(ctx->ev_in_means);
     for (auto e : ctx->prof.start) (void)hipEventDestroy(e);
     for (auto e : ctx->prof.stop) (void)hipEventDestroy(e);
+    for (hipEvent_t* e : {&ctx->ev_fork, &ctx->ev_seed, &ctx->ev_join}) {
+        if (*e) (void)hipEventDestroy(*e);
+        *e = nullptr;
+    }
+    if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
+    ctx->stream2 = nullptr;
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     ctx->stream = nullptr;
 }

@@ -344,8 +344,11 @@ bool omds_pass1_blocks_ok(const MlpDev& m, int N, int O) {
     return m.compact && pass1_size((long long)N * O) != Pass1Size::Tiny && N <= OMDS_ORDER_MAX_ROLLOUTS && O <= OMDS_ORDER_MAX_OBS;
 }
 void omds_launch_pass1_blocks(hipStream_t s, const MlpDev& m, const float* Fq, const float* Fp, const float* radius, int O, int N,
-                              uint32_t ignored, float* Dmin, const int* rperm, const int* operm) {
+                              uint32_t ignored, float* Dmin, const int* rperm, const int* operm, int first) {
     const Pass1BlockGrid g = pass1_block_grid(N, O);
+    // a part of the batch: the kernel addresses Fq and Dmin by the entries of rperm, which count from the part's first rollout
+    Fq += (size_t)first * OMDS_FROW;
+    Dmin += (size_t)first * O;
     launch_lds_kernel<&k_pass1_dyn_blk>(s, g.workgroups(), 512, pass1_dyn_lds_bytes(), pass1_dyn_lds_bytes(), Fq, Fp, radius, Dmin, rperm, operm, N, O, ignored,
                                         (int)g.n_big, g.nrb16, OmdsDivisor::make((unsigned)g.ncb), m);
 }

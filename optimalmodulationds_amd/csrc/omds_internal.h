@@ -182,6 +182,11 @@ struct TileOrderBufs {                         // device buffers of the ordering
 // pick: choose the key units on Fq and Fp and order the obstacles of Fp first (the first full launch of a propagate); then rperm from Fq
 void omds_launch_tile_order(hipStream_t s, const MlpDev& m, const float* Fq, int N, const float* Fp, int O, const TileOrderBufs& b,
                             bool pick);
+// The two halves of that on their own: the pick (key units on Fq and Fp, the obstacles' order), always of the whole batch; and the
+// order of the rollouts [first, first + count) alone -- keys into rkey[first ..), ranks counted from `first` into rperm
+// [omds_order_pad(count)], which is the caller's slice for that part (the two-part propagate, propagate.hip)
+void omds_launch_tile_pick(hipStream_t s, const MlpDev& m, const float* Fq, int N, const float* Fp, int O, const TileOrderBufs& b);
+void omds_launch_rollout_order(hipStream_t s, const TileKeys* keys, const float* Fq, int first, int count, unsigned* rkey, int* rperm);
 
 struct ProfEvents {
     std::vector<hipEvent_t> start, stop;
@@ -353,6 +358,11 @@ struct omds_ctx {
     omds_params prm{};
     int dev = 0;
     hipStream_t stream = nullptr;
+    // the two-part propagate (enqueue_dense, propagate.hip): the second half's stream and the three untimed events that order it
+    // against `stream`, created at the first propagate that runs in two parts; what the last propagate ran (omds_get_pipeline_info)
+    hipStream_t stream2 = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_seed = nullptr, ev_join = nullptr;
+    int pipe_parts = 1, pipe_split = 0;
     std::string err;
     // network
     bool have_mlp = false;
@@ -531,8 +541,10 @@ void omds_launch_pass1(hipStream_t s, const MlpDev& m, const float* Fq, const fl
 // consecutive entries of operm (a 32-row tile: 8 x 4), Dmin stays [N][O] in the caller's obstacle index.  rperm / operm hold
 // omds_order_pad(N) / omds_order_pad(O) entries (tile_order.hip).  Only where omds_pass1_blocks_ok says so.
 bool omds_pass1_blocks_ok(const MlpDev& m, int N, int O);
+// first > 0: the launch of a PART of the batch, N rollouts from `first` on; rperm is then the part's own order, its entries counted
+// from `first` (the launcher moves the bases of Fq and Dmin; the kernel is the same)
 void omds_launch_pass1_blocks(hipStream_t s, const MlpDev& m, const float* Fq, const float* Fp, const float* radius, int O, int N,
-                              uint32_t ignored_links, float* Dmin, const int* rperm, const int* operm);
+                              uint32_t ignored_links, float* Dmin, const int* rperm, const int* operm, int first = 0);
 void omds_launch_topk(hipStream_t s, const float* Dmin, int B, int O, int k, int32_t* idx);
 void omds_launch_pass2(hipStream_t s, const MlpDev& m, const float* Fq, const float* Fp, const float* radius,
                        const float* xyzr, const int32_t* idx, int B, int k, const float* qT, int ldq,
@@ -630,8 +642,11 @@ struct TailScreen {
     unsigned* viol = nullptr;     // ... into *viol (the slack guard)
 };
 // shared_row: Dmin is ONE row [O] that every rollout selects from (the first step of a propagate that starts all rollouts at one state)
+// count >= 0: the tail of a PART of the batch, the rollouts [first, first + count) (ReLU networks; the tile height stays the whole
+// batch's, so a part's step is the whole launch's kernel shape and bits); all tables stay whole-batch tables
 void omds_launch_tail(hipStream_t s, const MlpDev& m, const float* Fp, const float* radius, const float* xyzr,
-                      const float* Dmin, float* Fq, float* dscr, int O, const StepArgs& st, const TailScreen& scr, bool shared_row);
+                      const float* Dmin, float* Fq, float* dscr, int O, const StepArgs& st, const TailScreen& scr, bool shared_row,
+                      int first = 0, int count = -1);
 // screened step's tail: top-k over the candidates k_exact evaluated + pass-2 backward on its masks + the rest of k_tail.  The next
 // step's encoded joint inputs go to Fq.
 bool omds_tail_sel_supported(int n_dof, int k);

@@ -122,7 +122,8 @@ static int enqueue_small_scene(omds_ctx* ctx, StepArgs& a) {
 // The orders of the block-ordered pass 1 (tile_order.hip), allocated at the first launch that uses them and zeroed, so that every
 // entry names a row of the tables whatever happens; a request that failed leaves the step on the natural order.
 static bool acquire_order_buffers(omds_ctx* ctx) {
-    const size_t nr = (size_t)omds_order_pad(ctx->cfg.n_traj), no = (size_t)omds_order_pad(ctx->cfg.max_obs);
+    // rperm: one padded order of the batch, or the padded orders of its two parts behind each other (16 entries more)
+    const size_t nr = (size_t)omds_order_pad(ctx->cfg.n_traj) + 16, no = (size_t)omds_order_pad(ctx->cfg.max_obs);
     const size_t gr = (size_t)omds_share_groups(ctx->cfg.n_traj), go = (size_t)omds_share_groups(ctx->cfg.max_obs);
     if (ctx->d_tileKeys && ctx->d_rperm.count() >= nr && ctx->d_operm.count() >= no && ctx->d_rkey.count() >= (size_t)ctx->cfg.n_traj &&
         ctx->d_okey.count() >= (size_t)ctx->cfg.max_obs && ctx->d_shareSum.count() >= (go + gr) * OMDS_WIDTH && ctx->d_shareCnt.count() >= gr * OMDS_WIDTH)
@@ -144,11 +145,107 @@ static bool acquire_order_buffers(omds_ctx* ctx) {
     return false;
 }
 
+// The second stream and the events of the two-part propagate, at its first use on the context
+static bool acquire_second_stream(omds_ctx* ctx) {
+    if (ctx->stream2) return true;
+    hipStream_t s2 = nullptr;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    bool ok = hipStreamCreateWithFlags(&s2, hipStreamNonBlocking) == hipSuccess;
+    for (int i = 0; ok && i < 3; ++i) ok = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) == hipSuccess;
+    if (!ok) {   // the propagate stays on one stream
+        (void)hipGetLastError();
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        if (s2) (void)hipStreamDestroy(s2);
+        return false;
+    }
+    ctx->stream2 = s2;
+    ctx->ev_fork = ev[0]; ctx->ev_seed = ev[1]; ctx->ev_join = ev[2];
+    return true;
+}
+
+static_assert(PIPE_ORDER_MAX_ROLLOUTS == OMDS_ORDER_MAX_ROLLOUTS && PIPE_ORDER_MAX_OBS == OMDS_ORDER_MAX_OBS, "propagate_plan_def.h restates the order limits");
+
 // Two launches per step: k_pass1 over all (rollout, obstacle) pairs, then the rollout-local tail.
-// (Measured and rejected: independent rollout groups on separate HIP streams for small batches --
-// planar7_1024x32 ran 9.0 M rollout-steps/s on one stream, 7.1 / 3.3 / 2.4 M on 2 / 4 / 8 -- and a two-half
-// ping-pong for large batches with event-chained pass-1 launches so that one half's tail runs under the
-// other half's pass 1: parity-green, but the half-size launches drain twice per step, 1.00 M vs 1.03 M.)
+// Rollouts do not depend on each other, so parts of the batch may run on streams of their own.  Three forms, two of them measured
+// and rejected:
+// (1) independent rollout groups on separate HIP streams for small batches -- planar7_1024x32 ran 9.0 M rollout-steps/s on one
+//     stream, 7.1 / 3.3 / 2.4 M on 2 / 4 / 8;
+// (2) a two-half ping-pong for large batches with EVENT-CHAINED pass-1 launches, so that one half's tail runs under the other half's
+//     pass 1: parity-green, but the half-size launches drain twice per step, 1.00 M vs 1.03 M;
+// (3) TWO HALVES IN ANTI-PHASE (enqueue_dense_halves; the plan: propagate_plan_def.h): the halves' pass-1 launches are free to overlap
+//     each other, so nothing drains, and the phase is seeded ONCE -- the second half's first pass 1 waits for the first half's, and
+//     from then on one half's tail and ordering launches lie under the other half's pass 1.  No event passes between the halves
+//     after the seed until they are joined.  EXPERIMENTS.md R35 has what it measured.
+// The full steps of the batch as the rollouts [0, split) on the context's stream and [split, N) on its second stream.
+static int enqueue_dense_halves(omds_ctx* ctx, StepArgs& a, int split, bool shared) {
+    const int N = a.N, O = ctx->n_obs;
+    int rc;
+    const hipStream_t str[2] = {ctx->stream, ctx->stream2};
+    const int first[2] = {0, split}, count[2] = {split, N - split};
+    int* const rperm[2] = {ctx->d_rperm, ctx->d_rperm + omds_order_pad(split)};   // each part ranks into its own padded order
+    float* const sumO = ctx->d_shareSum;
+    const TileOrderBufs ob{ctx->d_tileKeys, ctx->d_rperm, ctx->d_operm, ctx->d_rkey, ctx->d_okey, sumO,
+                           sumO + (size_t)omds_share_groups(ctx->cfg.max_obs) * OMDS_WIDTH, ctx->d_shareCnt};
+    bool picked = false, forked = false;
+    // the second stream's work becomes part of the context's stream again: everything behind this on ctx->stream sees both halves
+    auto join = [&]() -> int {
+        if (!forked) return OMDS_OK;
+        CK(hipEventRecord(ctx->ev_join, ctx->stream2));
+        CK(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
+        forked = false;
+        return OMDS_OK;
+    };
+    for (int i = 1; i <= a.H; ++i) {
+        const bool one_row = shared && i == 1;
+        const ObsTables t = obstacle_tables(ctx, i);
+        a.step = i;
+        // THE WHOLE BATCH ON ONE STREAM: the shared first step, and every step whose pass 1 the profiling bracket encloses -- the
+        // bracket times ONE launch that has the device to itself (omds_prof_read's rate is per launch), so the halves are joined in front
+        // of it and forked and seeded again behind it.  Launches and rows are counted as the serial propagate counts them.
+        if (one_row || prof_due(ctx)) {
+            if ((rc = join())) return rc;
+            {
+                RoctxRange r1("TAG: evaluate NN_2 (forward pass)");
+                if ((rc = prof_begin(ctx))) return rc;
+                if (one_row) {
+                    omds_launch_pass1(ctx->stream, ctx->mlp, ctx->d_Fq, t.Fp, t.radius, O, 1, ctx->prm.ignored_links, ctx->d_Dmin);
+                } else {
+                    omds_launch_tile_order(ctx->stream, ctx->mlp, ctx->d_Fq, N, obstacle_tables(ctx, 1).Fp, O, ob, !picked);
+                    picked = true;
+                    omds_launch_pass1_blocks(ctx->stream, ctx->mlp, ctx->d_Fq, t.Fp, t.radius, O, N, ctx->prm.ignored_links, ctx->d_Dmin,
+                                             ctx->d_rperm, ctx->d_operm);
+                }
+                if ((rc = prof_end(ctx, (int64_t)(one_row ? 1 : N) * O))) return rc;
+            }
+            RoctxRange r2("TAG: evaluate NN_3-5 + Modulation-propagation");
+            omds_launch_tail(ctx->stream, ctx->mlp, t.Fp, t.radius, t.obs, ctx->d_Dmin, ctx->d_Fq, ctx->d_dscr, O, a, TailScreen{}, one_row);
+            continue;
+        }
+        prof_pass(ctx);
+        // the key units and the obstacles' order are the whole batch's, picked where the serial propagate picks them
+        if (!picked) omds_launch_tile_pick(ctx->stream, ctx->mlp, ctx->d_Fq, N, obstacle_tables(ctx, 1).Fp, O, ob);
+        picked = true;
+        const bool seed = !forked;
+        if (seed) {
+            CK(hipEventRecord(ctx->ev_fork, ctx->stream));
+            CK(hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
+            forked = true;
+        }
+        RoctxRange r1("TAG: evaluate NN_2-5 + Modulation-propagation (two halves)");
+        for (int p = 0; p < 2; ++p) {
+            omds_launch_rollout_order(str[p], ctx->d_tileKeys, ctx->d_Fq, first[p], count[p], ctx->d_rkey, rperm[p]);
+            // THE SEED: the second half's first pass 1 starts behind the first half's, under its tail
+            if (seed && p == 1) CK(hipStreamWaitEvent(ctx->stream2, ctx->ev_seed, 0));
+            omds_launch_pass1_blocks(str[p], ctx->mlp, ctx->d_Fq, t.Fp, t.radius, O, count[p], ctx->prm.ignored_links, ctx->d_Dmin, rperm[p],
+                                     ctx->d_operm, first[p]);
+            if (seed && p == 0) CK(hipEventRecord(ctx->ev_seed, ctx->stream));
+            omds_launch_tail(str[p], ctx->mlp, t.Fp, t.radius, t.obs, ctx->d_Dmin, ctx->d_Fq, ctx->d_dscr, O, a, TailScreen{}, false, first[p],
+                             count[p]);
+        }
+    }
+    return join();
+}
+
 static int enqueue_dense(omds_ctx* ctx, StepArgs& a) {
     const int N = a.N;
     int rc;
@@ -169,6 +266,14 @@ static int enqueue_dense(omds_ctx* ctx, StepArgs& a) {
     // rollouts 0.9 / 3.3 / 3.9 % faster (EXPERIMENTS.md R15).
     const bool blocks = !(ctx->cfg.flags & OMDS_FLAG_NATURAL_TILES) && omds_pass1_blocks_ok(ctx->mlp, N, ctx->n_obs) &&
                         ((ctx->cfg.flags & OMDS_FLAG_BLOCK_TILES) || (long long)N * ctx->n_obs >= OMDS_BLOCK_TILES_MIN_PAIRS) && acquire_order_buffers(ctx);
+    // THE SCHEDULE (propagate_plan_def.h): the full steps as two halves of the batch in anti-phase on two streams, or all on one
+    const bool blocks_may = ctx->mlp.compact && !(ctx->cfg.flags & OMDS_FLAG_NATURAL_TILES);
+    const PipelinePlan plan = omds_pipeline_plan(N, ctx->n_obs, a.H, shared, StepRoute::Dense, (unsigned)ctx->cfg.flags, blocks_may);
+    if (plan.parts == 2 && acquire_order_buffers(ctx) && acquire_second_stream(ctx)) {
+        ctx->pipe_parts = 2;
+        ctx->pipe_split = plan.split;
+        return enqueue_dense_halves(ctx, a, plan.split, shared);
+    }
     bool picked = false;
     for (int i = 1; i <= a.H; ++i) {
         const bool one_row = shared && i == 1;
@@ -295,6 +400,8 @@ int omds_propagate(omds_ctx* ctx, const float* q_cur, int per_rollout) {
     if ((rc = prepare_obstacle_horizon(ctx))) return rc;
     const int N = ctx->cfg.n_traj, H = ctx->cfg.horizon, n = ctx->cfg.n_dof;
     ctx->shared_start = per_rollout == 0;
+    ctx->pipe_parts = 1;
+    ctx->pipe_split = N;
     // all_traj[:, 0, :] = q_cur  (MPPI.py:99)
     if (per_rollout) {
         CK(hipMemcpyAsync(ctx->d_stage, q_cur, (size_t)N * n * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -338,6 +445,13 @@ int omds_propagate(omds_ctx* ctx, const float* q_cur, int per_rollout) {
     CK(hipStreamSynchronize(ctx->stream));
     ctx->have_rollouts = true;
     if (screen && (rc = screened_verdict(ctx, a))) return rc;
+    return OMDS_OK;
+}
+
+int omds_get_pipeline_info(omds_ctx* ctx, int32_t* parts, int32_t* split) {
+    if (!ctx) return OMDS_ERR_INVALID_ARG;
+    if (parts) *parts = ctx->pipe_parts;
+    if (split) *split = ctx->pipe_parts == 2 ? ctx->pipe_split : ctx->cfg.n_traj;
     return OMDS_OK;
 }
 
@@ -407,6 +521,7 @@ int omds_get_rollout_rows(omds_ctx* ctx, const int32_t* t, int count, float* all
 int omds_test_tile_orders(omds_ctx* ctx, int32_t* rperm, int32_t* operm) {
     if (!ctx) return OMDS_ERR_INVALID_ARG;
     REQUIRE(ctx->d_rperm && ctx->d_operm, OMDS_ERR_NOT_INITIALISED, "omds_test_tile_orders: no block-ordered launch has run on this context");
+    REQUIRE(ctx->pipe_parts == 1, OMDS_ERR_UNSUPPORTED, "omds_test_tile_orders: the last propagate ran in two parts, each with an order of its own (OMDS_FLAG_SERIAL_PROPAGATE)");
     CK(hipSetDevice(ctx->dev));
     CK(hipStreamSynchronize(ctx->stream));
     if (rperm) CK(hipMemcpy(rperm, ctx->d_rperm, (size_t)ctx->cfg.n_traj * 4, hipMemcpyDeviceToHost));
@@ -417,6 +532,7 @@ int omds_test_tile_state(omds_ctx* ctx, uint32_t* rkey, uint32_t* okey, int32_t*
     if (!ctx) return OMDS_ERR_INVALID_ARG;
     REQUIRE(rkey && okey && rperm && operm && unit && W && cR && cO, OMDS_ERR_INVALID_ARG, "omds_test_tile_state: NULL output");
     REQUIRE(ctx->d_rperm && ctx->d_operm && ctx->d_tileKeys, OMDS_ERR_NOT_INITIALISED, "omds_test_tile_state: no block-ordered launch has run on this context");
+    REQUIRE(ctx->pipe_parts == 1, OMDS_ERR_UNSUPPORTED, "omds_test_tile_state: the last propagate ran in two parts, each with an order of its own (OMDS_FLAG_SERIAL_PROPAGATE)");
     CK(hipSetDevice(ctx->dev));
     CK(hipStreamSynchronize(ctx->stream));
     TileKeys k;

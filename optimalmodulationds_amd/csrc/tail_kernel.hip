@@ -11,6 +11,7 @@
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 
 #include "pass2_device.h"
 #include "timeline_device.h"
@@ -43,6 +44,11 @@ struct TailArgs {
     ExactOut ex;
     StepArgs st;
 };
+// ... of the launch of one half of a two-part propagate: the rollouts [t0, t_end) of the batch
+struct TailPartArgs : TailArgs {
+    int t0, t_end;
+};
+template <bool PART> using TailArgsOf = std::conditional_t<PART, TailPartArgs, TailArgs>;
 
 // The two tails' pointers into their dynamic LDS block.  Where the blocks lie and how large the launch is, is TailLdsPlan
 // (tail_plan_def.h); every pointer is formed from the block's start and its offset there (k_tail does not read sel).
@@ -66,9 +72,11 @@ struct TailLds {
 };
 
 // FRAME: the modulation runs in the moving obstacle's frame (step_device.h); its own instantiation, so that the kernel of every
-// other propagate is the code it was
-template <int ND, int ACT, int ROWS, bool FRAME = false>
-__global__ __launch_bounds__(P2_NT) void k_tail(TailArgs a) {
+// other propagate is the code it was.  PART, likewise: the launch of one half of a two-part propagate (enqueue_dense), which owns the
+// rollouts [a.t0, a.t_end) -- workgroup b starts at a.t0 + b RW and stops at a.t_end -- while N stays the row stride of every table.
+// ReLU networks only: the tanh scratch is laid out by workgroup, and two launches at once would share it.
+template <int ND, int ACT, int ROWS, bool FRAME = false, bool PART = false>
+__global__ __launch_bounds__(P2_NT) void k_tail(TailArgsOf<PART> a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const MlpDev& m = a.m;
     TailLds L(smem, m.nhh + 1);
@@ -78,21 +86,23 @@ __global__ __launch_bounds__(P2_NT) void k_tail(TailArgs a) {
     const int N = a.st.N, k = a.st.k, O = a.O;
     // ROWS = 4: forward and backward on 4-row groups (pass2_body_g4): 4 G4_NG = 20 network rows per workgroup
     static_assert(ACT == OMDS_ACT_RELU || ROWS != 4, "the 4-row-group pass 2 works on ReLU masks");
+    static_assert(ACT == OMDS_ACT_RELU || !PART, "the tanh scratch is one launch's");
     constexpr int G4_NG = 5, TROWS = ROWS == 4 ? 4 * G4_NG : ROWS;
     const int RW = TROWS / k;                 // rollouts per workgroup
-    const int t_base = blockIdx.x * RW;
+    int t_base = blockIdx.x * RW, T1 = N;     // the launch's rollouts start at workgroup 0's t_base and end in front of T1
+    if constexpr (PART) { t_base += a.t0; T1 = a.t_end; }
 
     OMDS_TL_STAMP(0);
     OMDS_TL_STAMP(1);
     P2G4Pre pre;   // (ROWS = 4) everything of pass 2 that does not wait for the top-k is requested in front of it
     if constexpr (ROWS == 4)
-        pass2_g4_prefetch(m, a.Fq, [&](int r) { const int rl = r / k; return (rl < RW && t_base + rl < N) ? t_base + rl : -1; }, pre);
+        pass2_g4_prefetch(m, a.Fq, [&](int r) { const int rl = r / k; return (rl < RW && t_base + rl < T1) ? t_base + rl : -1; }, pre);
     // ---- top-k of each rollout's min-distance row (ascending, ties by lower obstacle index) -------
     if (tid < P2_MT) { sm.rowT[tid] = -1; sm.rowO[tid] = 0; }
     __syncthreads();
     for (int rl = wave; rl < RW; rl += 8) {
         const int t = t_base + rl;
-        if (t >= N) break;
+        if (t >= T1) break;
         topk_row(a.Dmin + (size_t)t * a.ldD, O, k, lane, [&](int j, int bi) {
             sm.rowT[rl * k + j] = t;
             sm.rowO[rl * k + j] = bi;
@@ -108,19 +118,19 @@ __global__ __launch_bounds__(P2_NT) void k_tail(TailArgs a) {
     // ---- forward + backward on the selected rows; gradients and distances stay in LDS ------------
     const float* qT = a.st.trajT + (size_t)(a.st.step - 1) * ND * N;
     if constexpr (ROWS == 4)
-        pass2_body_g4<G4_NG>(m, sm, pre, a.Fp, a.radius, a.xyzr, t_base * k, N * k, qT, N, gx, dr, 0);
+        pass2_body_g4<G4_NG>(m, sm, pre, a.Fp, a.radius, a.xyzr, t_base * k, T1 * k, qT, N, gx, dr, 0);
     else
-        pass2_body<ACT, ROWS>(m, sm, a.Fq, a.Fp, a.radius, a.xyzr, t_base * k, N * k, qT, N, gx, dr, 0, nullptr, nullptr,
+        pass2_body<ACT, ROWS>(m, sm, a.Fq, a.Fp, a.radius, a.xyzr, t_base * k, T1 * k, qT, N, gx, dr, 0, nullptr, nullptr,
                               a.dscr, (size_t)a.n_slots * ROWS * OMDS_WIDTH, (int)blockIdx.x * ROWS);
     __syncthreads();
     OMDS_TL_STAMP(9);
 
     // ---- modulation / policy / Euler step: 16 lanes per rollout; then the encoded joint inputs of the next step -------------
-    step_advance<ND, FRAME>(a.st, m, qT, N, N, t_base, RW, k, gx, dr, sm.rowO, feat, a.FqH, a.ldF);
+    step_advance<ND, FRAME>(a.st, m, qT, N, T1, t_base, RW, k, gx, dr, sm.rowO, feat, a.FqH, a.ldF);
     OMDS_TL_STAMP(10);
     if (a.st.step >= a.st.H) return;   // last step: nothing is integrated, no next network evaluation
     __syncthreads();
-    step_write_next_rows<ND, P2_NT>(a.FqOut, feat, m.d, N, t_base, RW);
+    step_write_next_rows<ND, P2_NT>(a.FqOut, feat, m.d, T1, t_base, RW);
     OMDS_TL_STAMP(11);
     OMDS_TL_STAMP(19);
 }
@@ -328,6 +338,29 @@ using TailLauncher = void (*)(hipStream_t, const TailArgs&);
 static const TailLauncher TAIL_LAUNCHERS[TAIL_N_KEYS] = {OMDS_TAIL_KEYS(OMDS_TAIL_LAUNCHER)};
 static const TailLauncher TAIL_SEL_LAUNCHERS[TAIL_N_KEYS] = {OMDS_TAIL_KEYS(OMDS_TAIL_SEL_LAUNCHER)};
 
+// k_tail<.., PART>: the ReLU keys of the table again, entry i beside TAIL_KEYS[i] (nullptr: a tanh key, which has no such form)
+using TailPartLauncher = void (*)(hipStream_t, const TailArgs&, int, int);
+template <int ND, int ACT, int ROWS, bool FRAME>
+static void launch_tail_part_k(hipStream_t s, const TailArgs& a, int t0, int t_end) {
+    static std::atomic<uint64_t> configured{0};
+    if (omds_first_use_on_device(configured)) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_tail<ND, ACT, ROWS, FRAME, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)TailLdsPlan::bytes(OMDS_MAX_HIDDEN + 1, false));
+    }
+    TailPartArgs pa;
+    static_cast<TailArgs&>(pa) = a;
+    pa.t0 = t0; pa.t_end = t_end;
+    hipLaunchKernelGGL((k_tail<ND, ACT, ROWS, FRAME, true>), dim3(tail_workgroups(t_end - t0, ROWS, a.st.k)), dim3(P2_NT),
+                       TailLdsPlan::bytes(a.m.nhh + 1, false), s, pa);
+}
+template <int ND, int ACT, int ROWS, bool FRAME>
+constexpr TailPartLauncher tail_part_launcher() {
+    if constexpr (ACT == OMDS_ACT_RELU) return launch_tail_part_k<ND, ACT, ROWS, FRAME>;
+    else return nullptr;
+}
+#define OMDS_TAIL_PART_LAUNCHER(ND, ACT, ROWS, FRAME) tail_part_launcher<ND, ACT, ROWS, FRAME>(),
+static const TailPartLauncher TAIL_PART_LAUNCHERS[TAIL_N_KEYS] = {OMDS_TAIL_KEYS(OMDS_TAIL_PART_LAUNCHER)};
+
 static void launch_tail_key(const TailLauncher* launchers, const TailKey& key, hipStream_t s, const TailArgs& a) {
     const int i = tail_key_index(key);
     // A miss cannot happen: omds_tail_supported / omds_tail_sel_supported (the routes ask them, propagate.hip) admit n_dof 7 and 2 only,
@@ -375,7 +408,8 @@ bool omds_tail_supported(int n_dof, int k) { return (n_dof == 7 || n_dof == 2) &
 int omds_pass2_rows(int N, int k) { return omds_tail_rows(N, k, false, omds_cu_count(), OMDS_FORCED_ROWS(g_force_tail_rows)); }
 
 void omds_launch_tail(hipStream_t s, const MlpDev& m, const float* Fp, const float* radius, const float* xyzr,
-                      const float* Dmin, float* Fq, float* dscr, int O, const StepArgs& st, const TailScreen& scr, bool shared_row) {
+                      const float* Dmin, float* Fq, float* dscr, int O, const StepArgs& st, const TailScreen& scr, bool shared_row,
+                      int first, int count) {
     TailArgs a;
     a.ldD = shared_row ? 0 : O;
     a.FqH = reinterpret_cast<_Float16*>(scr.FqH);
@@ -385,5 +419,15 @@ void omds_launch_tail(hipStream_t s, const MlpDev& m, const float* Fp, const flo
     a.n_slots = tail_workgroups(st.N, key.rows, st.k);
     a.rowlist = nullptr; a.range = scr.range; a.ex = ExactOut{}; a.e_bound = scr.e_bound; a.viol = scr.viol;
     a.m = m; a.Fp = Fp; a.radius = radius; a.xyzr = xyzr; a.Dmin = Dmin; a.Fq = Fq; a.FqOut = scr.FqOut ? scr.FqOut : Fq; a.dscr = dscr; a.O = O; a.st = st;
-    launch_tail_key(TAIL_LAUNCHERS, key, s, a);
+    if (count < 0) {
+        launch_tail_key(TAIL_LAUNCHERS, key, s, a);
+        return;
+    }
+    // a part of the batch: the key above is the whole batch's, so the part runs the tile shape its rollouts have in the whole launch
+    const int i = tail_key_index(key);
+    if (i < 0 || !TAIL_PART_LAUNCHERS[i]) {   // cannot happen: the plan parts the propagate of a compacting (ReLU) network only
+        fprintf(stderr, "omds: no part tail kernel is instantiated for n_dof %d, activation %d, %d rows, frame %d\n", key.n_dof, key.act, key.rows, (int)key.frame);
+        abort();
+    }
+    TAIL_PART_LAUNCHERS[i](s, a, first, first + count);
 }

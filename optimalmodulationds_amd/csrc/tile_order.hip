@@ -164,14 +164,21 @@ static void launch_order(hipStream_t s, const TileKeys* keys, const float* c, co
     hipLaunchKernelGGL(k_order_rank, dim3((n + OMDS_RANK_ENTRIES - 1) / OMDS_RANK_ENTRIES), dim3(256), lds, s, key, n, perm, omds_order_pad(n));
 }
 
+void omds_launch_tile_pick(hipStream_t s, const MlpDev& m, const float* Fq, int N, const float* Fp, int O, const TileOrderBufs& b) {
+    const int gO = omds_share_groups(O), gR = omds_share_groups(N), F = 3 * m.d;
+    hipLaunchKernelGGL(k_share_stats, dim3(gO), dim3(OMDS_WIDTH), 0, s, m.W1t, F, Fp, O, m.b1, nullptr, 0, 1, b.sumO, nullptr);
+    hipLaunchKernelGGL(k_share_stats, dim3(gR), dim3(OMDS_WIDTH), 0, s, m.W1t, F, Fq, N, m.b1, b.sumO, gO, O, b.sumR, b.cntR);
+    hipLaunchKernelGGL(k_tile_pick, dim3(1), dim3(OMDS_WIDTH), 0, s, m.W1t, m.b1, F, b.sumO, gO, O, b.sumR, b.cntR, gR, N, b.keys);
+    launch_order(s, b.keys, b.keys->cO, Fp, O, b.okey, b.operm);
+}
+
+// the kernels see a table of `count` rows that starts at the part's first row: the same two launches as for a whole batch
+void omds_launch_rollout_order(hipStream_t s, const TileKeys* keys, const float* Fq, int first, int count, unsigned* rkey, int* rperm) {
+    launch_order(s, keys, keys->cR, Fq + (size_t)first * OMDS_FROW, count, rkey + first, rperm);
+}
+
 void omds_launch_tile_order(hipStream_t s, const MlpDev& m, const float* Fq, int N, const float* Fp, int O, const TileOrderBufs& b,
                             bool pick) {
-    if (pick) {
-        const int gO = omds_share_groups(O), gR = omds_share_groups(N), F = 3 * m.d;
-        hipLaunchKernelGGL(k_share_stats, dim3(gO), dim3(OMDS_WIDTH), 0, s, m.W1t, F, Fp, O, m.b1, nullptr, 0, 1, b.sumO, nullptr);
-        hipLaunchKernelGGL(k_share_stats, dim3(gR), dim3(OMDS_WIDTH), 0, s, m.W1t, F, Fq, N, m.b1, b.sumO, gO, O, b.sumR, b.cntR);
-        hipLaunchKernelGGL(k_tile_pick, dim3(1), dim3(OMDS_WIDTH), 0, s, m.W1t, m.b1, F, b.sumO, gO, O, b.sumR, b.cntR, gR, N, b.keys);
-        launch_order(s, b.keys, b.keys->cO, Fp, O, b.okey, b.operm);
-    }
-    launch_order(s, b.keys, b.keys->cR, Fq, N, b.rkey, b.rperm);
+    if (pick) omds_launch_tile_pick(s, m, Fq, N, Fp, O, b);
+    omds_launch_rollout_order(s, b.keys, Fq, 0, N, b.rkey, b.rperm);
 }

@@ -780,6 +780,13 @@ class Engine:
         nl = getattr(self, "n_hidden_levels", 9)
         return dict(active=bool(act.value), units=[float(u) for u in un][:nl], chunks=[float(c) for c in ch][:nl], tiles=int(tiles.value))
 
+    def pipeline_info(self):
+        """omds_get_pipeline_info: (parts, split) of the last propagate -- (2, split) when its full steps ran as the rollouts [0, split)
+        and [split, N) on two streams, else (1, N)."""
+        parts, split = C.c_int32(), C.c_int32()
+        self._ck(self.lib.omds_get_pipeline_info(self.h, C.byref(parts), C.byref(split)))
+        return int(parts.value), int(split.value)
+
     def sync(self):
         """Waits for everything enqueued on the context's stream (omds_sync)."""
         self._ck(self.lib.omds_sync(self.h))

@@ -1,6 +1,8 @@
 """Feasibility probe: does the all-fp32 propagate of 1024 rollouts run faster as TWO independent halves on two streams?
 Two Engine contexts of 512 rollouts driven by two host threads (ctypes releases the GIL inside omds_propagate) against one context of
-1024: while one half sits in its latency-bound k_tail the other half's k_pass1 has the GPU.  usage: python tools/studies/two_halves_probe.py"""
+1024: while one half sits in its latency-bound k_tail the other half's k_pass1 has the GPU.
+Superseded by the two-part propagate inside one context (csrc/propagate.hip: enqueue_dense_halves, EXPERIMENTS.md R35), which seeds the
+phase the free-running halves here lack; kept as the record of the +1.5 .. 3.4 % of R6.12.  usage: python tools/studies/two_halves_probe.py"""
 import os
 import sys
 import threading
